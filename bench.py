@@ -13,13 +13,21 @@ starts; weights are the seeded synthetic SDXL-base architecture (no checkpoint c
 rank renders its own prompt (weak scaling, no collective in the loop) after ONE RCCL broadcast of the packed weight arena
 from rank 0 over xGMI; value = total images of all ranks / max-over-ranks wall time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps images and prints the JSON line (value, ms_per_step, unet_step_ms_p50, ...).
+--dump-outputs DIR also writes what the last timed image returned to its caller (the latent, the u8 image as float32) as
+DIR/<name>.npy, for comparing two builds output for output.  --full adds the measurements below, each of which takes runs
+of its own; without it their objects are null on the line.
+
+Extra objects on the JSON line (--full):
+  decode_ms     latent_to_image timed on its own, 3 calls after the timed region.
   roofline      live hipEvent measurement of the dominant kernel (the implicit-GEMM conv/linear kernel, which carries
                 ~94% of the algorithmic FLOPs): achieved = sum of its algorithmic FLOPs (2*M*N*K per launch, unpadded) /
                 sum of its launch durations over one UNet forward of the timed configuration; peak = 2500 TFLOP/s
                 (dense fp16 MFMA, MI355X_MICROARCH.md).
   cpu_baseline  the oracle (torch-CPU fp32 restatement of the reference graph; the reference's burn-ndarray path cannot
                 be built here) timed on this box's host cores on a bounded sample, rank 0 / N=1 only.
+  parity        the committed parity report under profiles/ and, for config 2 at 1024^2 on one GPU, parity measured in
+                this run against tests/golden/ fixtures; strict_f32 = the fp32-class engines timed on the same trajectory.
 """
 from __future__ import annotations
 
@@ -132,6 +140,23 @@ def barrier():
 def prompt_seed(rank: int, step: int) -> int:
     """prompt i -> GPU i mod N: every (rank, step) pair is an independent synthetic prompt"""
     return 1000 + 97 * rank + step
+
+
+DUMP_BUDGET_BYTES = 60 << 20         # --dump-outputs: all arrays together stay under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """writes each tensor as out_dir/<name>.npy in float32.  When together they exceed `budget`, each is replaced by the same
+    share of its flattened elements, drawn once with a fixed seed (identical indices on every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > budget:
+            k = max(1, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -501,6 +526,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed images per GPU")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: decode_ms, roofline, cpu_baseline, parity / strict_f32 "
+                         "(off: those objects are null on the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed image's outputs (latent, u8 image) as DIR/<name>.npy in float32")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configs index + 1 (2 = the metric's)")
     ap.add_argument("--res", type=int, default=None)
     ap.add_argument("--n-steps", type=int, default=None, help="--n-diffusion-steps of the reference CLI (30 -> 31 iterations)")
@@ -519,10 +549,10 @@ def main():
     ap.add_argument("--pipeline-decode", action="store_true",
                     help="decode image i on a second HIP stream under the sampling of image i+1 (measured +0.3 %% only: both legs "
                          "are chip-filling MFMA work; off by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--no-live-parity", action="store_true",
-                    help="skip the parity block measured in this run (config 2 only: 1024^2 forward / decode / the 31-step trajectory "
-                         "on the fixture inputs, and the strict-fp32 engine timed on it, ~10 s)")
+                    help="with --full: skip the parity block measured in this run (config 2 only: 1024^2 forward / decode / the 31-step "
+                         "trajectory on the fixture inputs, and the strict-fp32 engine timed on it, ~10 s)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--prompts-per-call", type=int, default=1, choices=[1, 2, 4],
                     help="serving-shape extra (config 2 only): n independent prompts per sample_latent call = UNet batch 2n; "
@@ -533,6 +563,8 @@ def main():
                     help="run the CFG pair as two concurrent batch-1 chains (measured -2.6 %% step time; off by default so "
                          "the timed launches are the ones the roofline object and the rocprofv3 summary describe)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     C = CONFIGS[args.config]
     res = args.res or C["res"]
     n_steps = args.n_steps or C["n_steps"]
@@ -718,15 +750,9 @@ def main():
     finite = bool(torch.isfinite(latent).all().item())
     n_images = sum_over_ranks(float(args.steps * npc), dev)
 
-    # decode leg on its own (outside the timed region): ms per latent_to_image at this resolution and VAE precision
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(3):
-        decoder.latent_to_image(latent)
-    e1.record()
-    torch.cuda.synchronize()
-    decode_ms = e0.elapsed_time(e1) / 3 / npc      # per image
+    # what the last timed image returned to its caller, written after the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": latent, "image": last.buffer})
 
     sc = (res / 1024.0) ** 2
     # SURVEY section 8(d) gives exact counts at 1024^2 and 512^2 (attention is quadratic in the pixel count); other sizes scale by area
@@ -739,77 +765,90 @@ def main():
         tflop_image += dec_tf                            # encoder ~ mirror of the decoder
     value = n_images / elapsed
 
-    # --- roofline of the dominant kernel, measured live with hipEvents on the timed configuration (B=2 CFG pair)
-    prof = diffuser.diffusion.profile(2 * npc, lat, lat)
-    # The eager profile brackets every launch with two hipEvents, so its class times carry the events' own cost.  `frac` is computed from
-    # those RAW times (a lower bound of the kernel's rate).  The overhead is calibrated DIRECTLY (round 6): the same eager chain is
-    # timed once more without the per-launch events (one event pair around the whole forward, sdxl_unet_eager_forward_ms); (class sum - that) /
-    # launches is what a bracketed launch carries, independent of what the captured graph gains elsewhere (warming workgroups, no host
-    # launches).  The class times with that overhead removed are reported next to the raw ones as DERIVED figures; they sum to the un-bracketed
-    # eager forward, not -- by construction -- to the graph-replayed step (r5 booked the whole eager-vs-graph gap as event overhead).
-    p50_all = statistics.median(step_ms) if step_ms else None
-    raw_ms = {k: float(v[0]) for k, v in prof.items()}
-    n_launch = {k: int(v[1]) for k, v in prof.items()}
-    class_sum = sum(raw_ms.values())
-    eager_plain_ms = diffuser.diffusion.eager_forward_ms(2 * npc, lat, lat)
-    ev_over_ms = 0.0
-    if class_sum > eager_plain_ms > 0 and sum(n_launch.values()) > 0:
-        ev_over_ms = (class_sum - eager_plain_ms) / sum(n_launch.values())
-    adj_ms = {k: max(raw_ms[k] - n_launch[k] * ev_over_ms, 0.0) for k in raw_ms}
-    ig_ms, ig_n, ig_fl = raw_ms["igemm"], prof["igemm"][1], prof["igemm"][2]
-    # f32: exact-fp32 MFMA peak; f32_split: three f16 MFMAs per product -> a third of the f16 matrix peak in algorithmic FLOPs; the mixed modes run
-    # one (f16 classes), two (split-operand classes on f16-representable weights) or three MFMAs per product: priced against the split peak for
-    # f32_split_mix and against the full f16 peak for f32_split_mix_f16w (most of its FLOPs are single-MFMA classes) -- `peak_note` says so
-    peak = PEAK_F32_TFLOPS if args.dtype == "f32" else (PEAK_F16_TFLOPS / 3.0 if args.dtype in ("f32_split", "f32_split_mix") else
-                                                        PEAK_F16_TFLOPS / 2.0 if args.dtype == "f32_split_f16w" else PEAK_F16_TFLOPS)
-    achieved = ig_fl / 1e12 / (ig_ms / 1e3) if ig_ms > 0 else 0.0
-    achieved_adj = ig_fl / 1e12 / (adj_ms["igemm"] / 1e3) if adj_ms["igemm"] > 0 else 0.0
-    # HBM-side traffic of the same launches: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/profile_step.py,
-    # summarised by tools/pmc_traffic.py (gfx950 correction applied there); null when no committed summary exists
-    traffic, traffic_src = None, None
-    for tname in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if os.path.exists(tpath) and args.dtype == "f16" and res == 1024:
-            try:
-                with open(tpath) as fh:
-                    traffic = round(json.load(fh)["igemm_total"]["bytes_per_launch"])
-                traffic_src = f"profiles/{tname} (bytes per implicit-GEMM launch, averaged over one UNet step)"
-                break
-            except Exception:
-                traffic = None
-    roofline = {"bound": "mfma", "kernel": "igemm_{pipe,glds}_kernel (NHWC implicit-GEMM conv3x3/1x1/linear, direct-to-LDS f16)",
-                "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                "traffic": traffic, "traffic_source": traffic_src,
-                "peak_note": {"f32": "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) dense peak", "f32_split": "f16 dense MFMA peak / 3 (three MFMAs per product)",
-                              "f32_split_mix": "f16 dense MFMA peak / 3 (split-operand classes: three MFMAs per product; two classes run one)",
-                              "f32_split_mix_f16w": "f16 dense MFMA peak; the eight f16 classes run one MFMA per product, the split-operand classes two on "
-                                                    "f16-representable weights -- algorithmic TFLOP/s understate the matrix work of this mode",
-                              "f32_split_mix_f16w_geglu2": "f16 dense MFMA peak; as f32_split_mix_f16w with the GEGLU projection at two MFMAs per product",
-                              "f32_split_f16w": "f16 dense MFMA peak / 2 (two MFMAs per product on f16-representable weights)"}.get(args.dtype, "f16 dense MFMA peak (MI355X_MICROARCH.md)"),
-                "launches_per_unet_step": ig_n, "avg_launch_us": round(1e3 * ig_ms / max(ig_n, 1), 2),
-                "algorithmic_tflop_per_unet_step": round(ig_fl / 1e12, 3),
-                # headline class times = the RAW event-bracketed ones (frac / achieved follow them); derived: the same with the calibrated event overhead removed
-                "class_ms_per_unet_step": {k: round(v, 3) for k, v in raw_ms.items()},
-                "class_sum_ms": round(class_sum, 3),
-                "eager_forward_ms_without_events": round(eager_plain_ms, 3),
-                "event_overhead_us_per_launch": round(1e3 * ev_over_ms, 3),
-                "class_ms_event_overhead_removed": {k: round(v, 3) for k, v in adj_ms.items()},
-                "frac_event_overhead_removed": round(achieved_adj / peak, 4),
-                "class_method": "eager pass with hipEvents around every launch (raw: frac / achieved / class_ms_per_unet_step); event overhead per launch = "
-                                "(raw class sum - the same eager chain timed WITHOUT per-launch events) / launches, removed in the *_event_overhead_removed figures; "
-                                "the graph-replayed step (unet_step_ms_p50) additionally gains from weight-warming workgroups and the absence of host launches",
-                # the whole CFG step against the peak (2 UNet forwards = SURVEY 8d's 13.52 TFLOP at 1024^2 over the graph-replayed step p50): attention, norms
-                # and every launch boundary included -- next to the GEMM-class fraction above
-                "whole_step_tflops": None if not p50_all else round(2 * npc * fwd_tf / (p50_all / 1e3), 1),
-                "whole_step_frac_of_peak": None if not p50_all else round(2 * npc * fwd_tf / (p50_all / 1e3) / peak, 4),
-                "whole_job_tflops": round(tflop_image * value, 1),
-                "whole_job_frac_of_peak": round(tflop_image * value / (peak * max(world, 1)), 4),
-                "flop_accounting": "tflop_per_image is the REFERENCE's count (SURVEY 8d); the engine hoists the cross-attention K/V "
-                                   "projections out of the step (constant context), ~0.8 % fewer FLOPs executed than credited"}
+    # --full: measurements that take runs of their own (null on the line of a plain run)
+    decode_ms, roofline = None, None
+    if args.full:
+        # decode leg on its own (outside the timed region): ms per latent_to_image at this resolution and VAE precision
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(3):
+            decoder.latent_to_image(latent)
+        e1.record()
+        torch.cuda.synchronize()
+        decode_ms = e0.elapsed_time(e1) / 3 / npc      # per image
+
+        # --- roofline of the dominant kernel, measured live with hipEvents on the timed configuration (B=2 CFG pair)
+        prof = diffuser.diffusion.profile(2 * npc, lat, lat)
+        # The eager profile brackets every launch with two hipEvents, so its class times carry the events' own cost.  `frac` is computed from
+        # those RAW times (a lower bound of the kernel's rate).  The overhead is calibrated DIRECTLY (round 6): the same eager chain is
+        # timed once more without the per-launch events (one event pair around the whole forward, sdxl_unet_eager_forward_ms); (class sum - that) /
+        # launches is what a bracketed launch carries, independent of what the captured graph gains elsewhere (warming workgroups, no host
+        # launches).  The class times with that overhead removed are reported next to the raw ones as DERIVED figures; they sum to the un-bracketed
+        # eager forward, not -- by construction -- to the graph-replayed step (r5 booked the whole eager-vs-graph gap as event overhead).
+        p50_all = statistics.median(step_ms) if step_ms else None
+        raw_ms = {k: float(v[0]) for k, v in prof.items()}
+        n_launch = {k: int(v[1]) for k, v in prof.items()}
+        class_sum = sum(raw_ms.values())
+        eager_plain_ms = diffuser.diffusion.eager_forward_ms(2 * npc, lat, lat)
+        ev_over_ms = 0.0
+        if class_sum > eager_plain_ms > 0 and sum(n_launch.values()) > 0:
+            ev_over_ms = (class_sum - eager_plain_ms) / sum(n_launch.values())
+        adj_ms = {k: max(raw_ms[k] - n_launch[k] * ev_over_ms, 0.0) for k in raw_ms}
+        ig_ms, ig_n, ig_fl = raw_ms["igemm"], prof["igemm"][1], prof["igemm"][2]
+        # f32: exact-fp32 MFMA peak; f32_split: three f16 MFMAs per product -> a third of the f16 matrix peak in algorithmic FLOPs; the mixed modes run
+        # one (f16 classes), two (split-operand classes on f16-representable weights) or three MFMAs per product: priced against the split peak for
+        # f32_split_mix and against the full f16 peak for f32_split_mix_f16w (most of its FLOPs are single-MFMA classes) -- `peak_note` says so
+        peak = PEAK_F32_TFLOPS if args.dtype == "f32" else (PEAK_F16_TFLOPS / 3.0 if args.dtype in ("f32_split", "f32_split_mix") else
+                                                            PEAK_F16_TFLOPS / 2.0 if args.dtype == "f32_split_f16w" else PEAK_F16_TFLOPS)
+        achieved = ig_fl / 1e12 / (ig_ms / 1e3) if ig_ms > 0 else 0.0
+        achieved_adj = ig_fl / 1e12 / (adj_ms["igemm"] / 1e3) if adj_ms["igemm"] > 0 else 0.0
+        # HBM-side traffic of the same launches: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/profile_step.py,
+        # summarised by tools/pmc_traffic.py (gfx950 correction applied there); null when no committed summary exists
+        traffic, traffic_src = None, None
+        for tname in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", tname)
+            if os.path.exists(tpath) and args.dtype == "f16" and res == 1024:
+                try:
+                    with open(tpath) as fh:
+                        traffic = round(json.load(fh)["igemm_total"]["bytes_per_launch"])
+                    traffic_src = f"profiles/{tname} (bytes per implicit-GEMM launch, averaged over one UNet step)"
+                    break
+                except Exception:
+                    traffic = None
+        roofline = {"bound": "mfma", "kernel": "igemm_{pipe,glds}_kernel (NHWC implicit-GEMM conv3x3/1x1/linear, direct-to-LDS f16)",
+                    "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "peak_note": {"f32": "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) dense peak", "f32_split": "f16 dense MFMA peak / 3 (three MFMAs per product)",
+                                  "f32_split_mix": "f16 dense MFMA peak / 3 (split-operand classes: three MFMAs per product; two classes run one)",
+                                  "f32_split_mix_f16w": "f16 dense MFMA peak; the eight f16 classes run one MFMA per product, the split-operand classes two on "
+                                                        "f16-representable weights -- algorithmic TFLOP/s understate the matrix work of this mode",
+                                  "f32_split_mix_f16w_geglu2": "f16 dense MFMA peak; as f32_split_mix_f16w with the GEGLU projection at two MFMAs per product",
+                                  "f32_split_f16w": "f16 dense MFMA peak / 2 (two MFMAs per product on f16-representable weights)"}.get(args.dtype, "f16 dense MFMA peak of the MI355X"),
+                    "launches_per_unet_step": ig_n, "avg_launch_us": round(1e3 * ig_ms / max(ig_n, 1), 2),
+                    "algorithmic_tflop_per_unet_step": round(ig_fl / 1e12, 3),
+                    # headline class times = the RAW event-bracketed ones (frac / achieved follow them); derived: the same with the calibrated event overhead removed
+                    "class_ms_per_unet_step": {k: round(v, 3) for k, v in raw_ms.items()},
+                    "class_sum_ms": round(class_sum, 3),
+                    "eager_forward_ms_without_events": round(eager_plain_ms, 3),
+                    "event_overhead_us_per_launch": round(1e3 * ev_over_ms, 3),
+                    "class_ms_event_overhead_removed": {k: round(v, 3) for k, v in adj_ms.items()},
+                    "frac_event_overhead_removed": round(achieved_adj / peak, 4),
+                    "class_method": "eager pass with hipEvents around every launch (raw: frac / achieved / class_ms_per_unet_step); event overhead per launch = "
+                                    "(raw class sum - the same eager chain timed WITHOUT per-launch events) / launches, removed in the *_event_overhead_removed figures; "
+                                    "the graph-replayed step (unet_step_ms_p50) additionally gains from weight-warming workgroups and the absence of host launches",
+                    # the whole CFG step against the peak (2 UNet forwards = SURVEY 8d's 13.52 TFLOP at 1024^2 over the graph-replayed step p50): attention, norms
+                    # and every launch boundary included -- next to the GEMM-class fraction above
+                    "whole_step_tflops": None if not p50_all else round(2 * npc * fwd_tf / (p50_all / 1e3), 1),
+                    "whole_step_frac_of_peak": None if not p50_all else round(2 * npc * fwd_tf / (p50_all / 1e3) / peak, 4),
+                    "whole_job_tflops": round(tflop_image * value, 1),
+                    "whole_job_frac_of_peak": round(tflop_image * value / (peak * max(world, 1)), 4),
+                    "flop_accounting": "tflop_per_image is the REFERENCE's count (SURVEY 8d); the engine hoists the cross-attention K/V "
+                                       "projections out of the step (constant context), ~0.8 % fewer FLOPs executed than credited"}
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.config == 1:
                 cpu, _ = cpu_oracle_config1()
             else:
@@ -820,9 +859,9 @@ def main():
         p50 = statistics.median(step_ms) if step_ms else None
         # `live` (and `strict_f32`) are measured in THIS run; `committed_report` is the static summary of the parity tests' last
         # recorded run under profiles/ -- context, not a measurement of this run
-        committed, strict = load_parity(), None
+        committed, strict = (load_parity() if args.full else None), None
         parity = {"committed_report": committed} if committed else None
-        if args.config == 2 and res == 1024 and world == 1 and npc == 1 and not args.no_live_parity:
+        if args.full and args.config == 2 and res == 1024 and world == 1 and npc == 1 and not args.no_live_parity:
             try:
                 live, strict = live_parity(pkg, ctx, diffuser, decoder, args.dtype, args.vae_dtype, args.weights)
                 parity = dict(parity or {}, **{"live": live})
@@ -846,12 +885,12 @@ def main():
                        "mix_classes": mix_classes,
                        "parallelism": f"replica x{world}, 1 prompt per GPU, weights broadcast once over RCCL",
                        "hipgraph": not args.no_graph, "split_cfg": bool(args.split_cfg), "fused_xattn": not args.unfused_xattn,
-                       "pipelined_decode": bool(pipelined), "prompts_per_call": npc,
+                       "pipelined_decode": bool(pipelined), "prompts_per_call": npc, "full": bool(args.full),
                        # which build of the engine ran (SDXL_LIB_PATH / SDXL_MEASURE_LIB swap it: tools only) and the A/B knobs in force
                        "library": os.path.relpath(pkg.LIB_PATH, ROOT), "debug_set": os.environ.get("SDXL_DEBUG_SET", "")},
             "images_per_sec_per_gpu": round(value / world, 4),
             "unet_step_ms_p50": None if p50 is None else round(p50, 3),
-            "vae_dtype": args.vae_dtype, "decode_ms": round(decode_ms, 2),
+            "vae_dtype": args.vae_dtype, "decode_ms": None if decode_ms is None else round(decode_ms, 2),
             "tflop_per_image": round(tflop_image, 1),
             "outputs_finite": finite,
             "setup_s": {"build_weights": round(t_build, 2), "broadcast": round(t_bcast, 2), "broadcast_path": bcast_path},

@@ -13,7 +13,20 @@ import torch.nn.functional as F
 from oracle import config as OC, model as OM, pipeline as OP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+TOKENIZER_GOLDEN = os.path.join(ROOT, "tests", "golden", "tokenizer")
+
+
+@pytest.fixture(scope="module")
+def tokdir(tmp_path_factory):
+    """the reference's tokenizer/ assets, unpacked from the gzipped copies under tests/golden/tokenizer/ into the same layout
+    (clip/bpe_simple_vocab_16e6.txt -- the header and the 48894 merges ClipTokenizer reads --, open_clip/{merges,vocab}.txt, tokenizer.json)"""
+    import gzip
+    d = tmp_path_factory.mktemp("tokenizer")
+    for rel in ("clip/bpe_simple_vocab_16e6.txt", "open_clip/merges.txt", "open_clip/vocab.txt", "tokenizer.json"):
+        (d / rel).parent.mkdir(parents=True, exist_ok=True)
+        with gzip.open(os.path.join(TOKENIZER_GOLDEN, rel + ".gz"), "rb") as fh:
+            (d / rel).write_bytes(fh.read())
+    return str(d)
 
 
 # ------------------------------------------------------------------ oracle primitives vs libtorch (the reference's real backend)
@@ -121,11 +134,10 @@ def test_block_plan_matches_reference_comment():
     assert mid["depth"] == 10 and mid["n_head"] == 20
 
 
-@pytest.mark.skipif(not os.path.exists(REF + "/tokenizer/tokenizer.json"), reason="reference checkout not present")
-def test_tokenizer_known_answer_vector():
+def test_tokenizer_known_answer_vector(tokdir):
     # the ONE golden vector the reference holds (src/token/clip.rs:236-248), reproduced from its own tokenizer.json
     tokenizers = pytest.importorskip("tokenizers")
-    tok = tokenizers.Tokenizer.from_file(REF + "/tokenizer/tokenizer.json")
+    tok = tokenizers.Tokenizer.from_file(tokdir + "/tokenizer.json")
     ids = tok.encode("Hello world! <|startoftext|>asdf<|startoftext|>", add_special_tokens=False).ids
     assert ids == [3306, 1002, 256, 49406, 587, 10468, 49406]
 
@@ -370,21 +382,15 @@ def test_product_path_never_imports_oracle():
 
 
 # ------------------------------------------------------------------ Embedder: tokenizers (host string code) + CLIP oracle
-_TOKDIR = REF + "/tokenizer"
-_need_assets = pytest.mark.skipif(not os.path.exists(_TOKDIR + "/clip/bpe_simple_vocab_16e6.txt"),
-                                  reason="tokenizer assets (reference checkout) not present")
-
-
 @pytest.fixture(scope="module")
 def tok(pkg):
     import importlib
     return importlib.import_module(pkg.__name__ + ".tokenizer")
 
 
-@_need_assets
-def test_clip_tokenizer_known_answer(tok):
+def test_clip_tokenizer_known_answer(tok, tokdir):
     # src/token/clip.rs:236-248 -- the reference's only expected-value test on this path
-    t = tok.ClipTokenizer(_TOKDIR)
+    t = tok.ClipTokenizer(tokdir)
     text = "Hello world! <|startoftext|>asdf<|startoftext|>"
     ids = t.encode(text, False, False)
     assert ids == [3306, 1002, 256, 49406, 587, 10468, 49406]
@@ -392,12 +398,11 @@ def test_clip_tokenizer_known_answer(tok):
     assert (t.start_of_text_token(), t.end_of_text_token(), t.padding_token()) == (49406, 49407, 49407)
 
 
-@_need_assets
-def test_tokenizers_agree_with_hf_tokenizer_json(tok):
+def test_tokenizers_agree_with_hf_tokenizer_json(tok, tokdir):
     # the reference ships the HF tokenizer.json of the same vocabulary: an independent implementation to pin against
     tokenizers = pytest.importorskip("tokenizers")
-    hf = tokenizers.Tokenizer.from_file(_TOKDIR + "/tokenizer.json")
-    clip, oc = tok.ClipTokenizer(_TOKDIR), tok.OpenClipTokenizer(_TOKDIR)
+    hf = tokenizers.Tokenizer.from_file(tokdir + "/tokenizer.json")
+    clip, oc = tok.ClipTokenizer(tokdir), tok.OpenClipTokenizer(tokdir)
     texts = ["a photo of an astronaut riding a horse on mars", "An elegant bright-colored bird, ultra-detailed 8k!!",
              "  multiple   spaces\tand\nnewlines ", "it's the cat's 1234 toys", "naïve café — déjà vu", "日本語のテキスト", ""]
     for s in texts:
@@ -407,9 +412,8 @@ def test_tokenizers_agree_with_hf_tokenizer_json(tok):
     assert oc.padding_token() == 0
 
 
-@_need_assets
-def test_tokenize_text_pads_and_truncates(tok):
-    clip, oc = tok.ClipTokenizer(_TOKDIR), tok.OpenClipTokenizer(_TOKDIR)
+def test_tokenize_text_pads_and_truncates(tok, tokdir):
+    clip, oc = tok.ClipTokenizer(tokdir), tok.OpenClipTokenizer(tokdir)
     a = tok.tokenize_text("a cat", clip, 77)
     b = tok.tokenize_text("a cat", oc, 77)
     assert len(a) == len(b) == 77 and a[0] == b[0] == 49406
@@ -569,14 +573,13 @@ def test_c_host_example_builds(built, tmp_path):
     assert r.returncode == 0, r.stderr
 
 
-@_need_assets
-def test_tokenizers_agree_with_hf_on_random_text(tok):
+def test_tokenizers_agree_with_hf_on_random_text(tok, tokdir):
     # 300 seeded pseudo-random strings (words, digits, punctuation runs, accents, CJK, emoji, odd spacing) through both
     # tokenizers and the HF tokenizer.json the reference ships
     tokenizers = pytest.importorskip("tokenizers")
     import random
-    hf = tokenizers.Tokenizer.from_file(_TOKDIR + "/tokenizer.json")
-    clip, oc = tok.ClipTokenizer(_TOKDIR), tok.OpenClipTokenizer(_TOKDIR)
+    hf = tokenizers.Tokenizer.from_file(tokdir + "/tokenizer.json")
+    clip, oc = tok.ClipTokenizer(tokdir), tok.OpenClipTokenizer(tokdir)
     rng = random.Random(1234)
     words = ["a", "photo", "of", "an", "astronaut", "riding", "horse", "Mars", "ultra-detailed", "8k", "it's", "they'll", "we've",
              "I'm", "don't", "café", "naïve", "über", "日本語", "猫", "🙂", "🚀", "1234", "3.14", "...", "!!!", "?!", "(", ")", "#tag", "@me",
@@ -592,11 +595,10 @@ def test_tokenizers_agree_with_hf_on_random_text(tok):
         assert oc.encode(s, False, False) == want, repr(s)
 
 
-@_need_assets
-def test_special_token_literal_follows_the_reference_regex(tok):
+def test_special_token_literal_follows_the_reference_regex(tok, tokdir):
     # src/token/clip.rs:110: the alternation is tried left to right at each position, so a punctuation run that starts
     # BEFORE "<|startoftext|>" takes the "<|" with it (OpenAI's original behaves the same; HF's added-token pass does not)
-    t = tok.ClipTokenizer(_TOKDIR)
+    t = tok.ClipTokenizer(tokdir)
     assert t.encode("a <|startoftext|>", False, False) == [320, 49406]
     ids = t.encode("-<|startoftext|>", False, False)
     assert 49406 not in ids and t.decode(ids).replace(" ", "") == "-<|startoftext|>"

@@ -10,16 +10,16 @@ for p in $PARTS; do
   case $p in
     tests) timeout 2400 python -m pytest tests -m gpu -q -s --maxfail=12 > $OUT/tests.log 2>&1; echo "tests rc=$?" >> $OUT/tests.log; grep -E "passed|failed|error" $OUT/tests.log | tail -5;;
     smoke) timeout 600 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log;;
-    bench) SDXL_PROFILE_DUMP=$OUT/step_launches.csv timeout 900 python bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; line $OUT/bench.json f16; python -c "import json; d=json.load(open('$OUT/bench.json')); [print(' strict', k, v.get('images_per_sec'), v.get('unet_step_ms'), v.get('config2_final_latent_max_abs_vs_oracle'), v.get('inside_lat_bound_scaled')) for k, v in (d.get('strict_f32') or {}).items()]";;
-    benchf16w) SDXL_PROFILE_DUMP=$OUT/step_launches_f16w.csv timeout 900 python bench.py --dtype f32_split_mix_f16w --weights f16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_f16w.json 2> $OUT/bench_f16w.err; line $OUT/bench_f16w.json f16w; python -c "import json; d=json.load(open('$OUT/bench_f16w.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
-    benchg2) timeout 900 python bench.py --dtype f32_split_mix_f16w_geglu2 --weights f16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_geglu2.json 2> $OUT/bench_geglu2.err; line $OUT/bench_geglu2.json f16w-geglu2; python -c "import json; d=json.load(open('$OUT/bench_geglu2.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
-    bench7) timeout 900 python bench.py --dtype f32_split_f16w --weights f16 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_f32_split_f16w.json 2> $OUT/bench_f32_split_f16w.err; line $OUT/bench_f32_split_f16w.json f32_split_f16w; python -c "import json; d=json.load(open('$OUT/bench_f32_split_f16w.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
-    benchmix) timeout 900 python bench.py --dtype f32_split_mix --steps 3 --warmup 1 --no-cpu-baseline --no-live-parity > $OUT/bench_mix.json 2> $OUT/bench_mix.err; line $OUT/bench_mix.json f32_split_mix;;
-    cfg1) timeout 900 python bench.py --config 1 --steps 3 --warmup 1 > $OUT/bench_cfg1.json 2> $OUT/bench_cfg1.err; line $OUT/bench_cfg1.json cfg1;;
-    cfg4) timeout 900 python bench.py --config 4 --steps 2 --warmup 1 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err; line $OUT/bench_cfg4.json cfg4;;
-    cfg5) timeout 900 python bench.py --config 5 --steps 1 --warmup 1 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err; line $OUT/bench_cfg5.json cfg5;;
-    cfg4f16w) timeout 900 python bench.py --config 4 --dtype f32_split_mix_f16w --weights f16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg4_f16w.json 2> $OUT/bench_cfg4_f16w.err; line $OUT/bench_cfg4_f16w.json cfg4-f16w;;
-    cfg5f16w) timeout 900 python bench.py --config 5 --dtype f32_split_mix_f16w --weights f16 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_f16w.json 2> $OUT/bench_cfg5_f16w.err; line $OUT/bench_cfg5_f16w.json cfg5-f16w;;
+    bench) SDXL_PROFILE_DUMP=$OUT/step_launches.csv timeout 900 python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; line $OUT/bench.json f16; python -c "import json; d=json.load(open('$OUT/bench.json')); [print(' strict', k, v.get('images_per_sec'), v.get('unet_step_ms'), v.get('config2_final_latent_max_abs_vs_oracle'), v.get('inside_lat_bound_scaled')) for k, v in (d.get('strict_f32') or {}).items()]";;
+    benchf16w) SDXL_PROFILE_DUMP=$OUT/step_launches_f16w.csv timeout 900 python bench.py --full --dtype f32_split_mix_f16w --weights f16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_f16w.json 2> $OUT/bench_f16w.err; line $OUT/bench_f16w.json f16w; python -c "import json; d=json.load(open('$OUT/bench_f16w.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
+    benchg2) timeout 900 python bench.py --full --dtype f32_split_mix_f16w_geglu2 --weights f16 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_geglu2.json 2> $OUT/bench_geglu2.err; line $OUT/bench_geglu2.json f16w-geglu2; python -c "import json; d=json.load(open('$OUT/bench_geglu2.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
+    bench7) timeout 900 python bench.py --full --dtype f32_split_f16w --weights f16 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_f32_split_f16w.json 2> $OUT/bench_f32_split_f16w.err; line $OUT/bench_f32_split_f16w.json f32_split_f16w; python -c "import json; d=json.load(open('$OUT/bench_f32_split_f16w.json')); print(' timed engine parity', d['parity']['live'].get('timed_engine'))";;
+    benchmix) timeout 900 python bench.py --full --dtype f32_split_mix --steps 3 --warmup 1 --no-cpu-baseline --no-live-parity > $OUT/bench_mix.json 2> $OUT/bench_mix.err; line $OUT/bench_mix.json f32_split_mix;;
+    cfg1) timeout 900 python bench.py --full --config 1 --steps 3 --warmup 1 > $OUT/bench_cfg1.json 2> $OUT/bench_cfg1.err; line $OUT/bench_cfg1.json cfg1;;
+    cfg4) timeout 900 python bench.py --full --config 4 --steps 2 --warmup 1 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err; line $OUT/bench_cfg4.json cfg4;;
+    cfg5) timeout 900 python bench.py --full --config 5 --steps 1 --warmup 1 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err; line $OUT/bench_cfg5.json cfg5;;
+    cfg4f16w) timeout 900 python bench.py --full --config 4 --dtype f32_split_mix_f16w --weights f16 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg4_f16w.json 2> $OUT/bench_cfg4_f16w.err; line $OUT/bench_cfg4_f16w.json cfg4-f16w;;
+    cfg5f16w) timeout 900 python bench.py --full --config 5 --dtype f32_split_mix_f16w --weights f16 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_f16w.json 2> $OUT/bench_cfg5_f16w.err; line $OUT/bench_cfg5_f16w.json cfg5-f16w;;
     trace) rm -rf /tmp/kt; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o k -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-live-parity > /dev/null 2>&1)
       f=$(find /tmp/kt -name '*kernel_trace*' | head -1)
       python tools/trace_step_summary.py $f > $OUT/step_kernels.txt 2>&1; python tools/trace_gaps.py $f $OUT/trace_gaps.json > /dev/null 2>&1; head -24 $OUT/step_kernels.txt;;
