@@ -245,15 +245,15 @@ enum MixClass {
   MIX_OUT2_F16 = 32,    // cross-attention out-projection (the split-operand attention rounds its fp32 result to f16 once, in its store)
   MIX_XATTN_F16 = 64,   // with OUT2: cross-attention + its query projection as the f16 engine's fused launch -- a knob, in no mode
   MIX_Q2_F16 = 128,     // cross-attention QUERY projection alone on f16 operands (HL16 output: the split-operand attention behind it keeps an fp32-class q)
-  MIX_XATTN_SPLIT = 512, // with MIX_Q2_F16: the 77-key cross-attention at SPLIT precision inside the f16 query projection's epilogue (IgemmParams::xa_k_lo) -- the
+  MIX_XATTN_SPLIT = 512, // with MIX_Q2_F16 + MIX_OUT2_F16, or MIX_LINEAR_F16X2: the 77-key cross-attention at SPLIT precision inside the f16 query projection's epilogue (IgemmParams::xa_k_lo) -- the
                         // arithmetic of the stand-alone split-operand attention without its launch
   MIX_GEGLU_HILO = 1024, // with MIX_GEGLU_F16 (and without the shadow form): the GEGLU weights as (hi, lo) f16 pairs along a doubled K against [a | a 2^-8] -- the f16 wide-tile
                         // kernel at twice the depth, two MFMAs per product: activation rounding only on ANY weights.  SDXL_DTYPE_F32_SPLIT_MIX
-  MIX_GEGLU_AHILO = 2048, // a knob, in no mode (f16-representable weights): the GEGLU projection's ACTIVATIONS as (hi, lo) f16 pairs along a doubled K against (w | w 2^-8) --
-                        // the class that carries 70 % of the F16W mode's error variance at two MFMAs per product on the f16 kernel
+  MIX_GEGLU_AHILO = 2048, // with MIX_GEGLU_F16 (f16-representable weights): the GEGLU projection's ACTIVATIONS as (hi, lo) f16 pairs along a doubled K against (w | w 2^-8) --
+                        // the class that carries 70 % of the F16W mode's error variance at two MFMAs per product on the f16 kernel.  SDXL_DTYPE_F32_SPLIT_MIX_F16W_GEGLU2
   MIX_LINEAR_F16X2 = 4096, // (f16-representable weights) transformer linears whose A operand is an un-scaled HL16 tensor run on the F16 kernels: an HL16 row of C channels is an f16 row of 2 C
                         // columns, the weight is packed twice in the same interleave -- two MFMAs per product on the weights-in-registers / wide / pipe kernels
-  MIX_LN_SHADOW = 256   // the LayerNorms in front of the f16 projections (QKV, GEGLU, the query projection with MIX_Q2_F16) folded into them: the producers of
+  MIX_LN_SHADOW = 256   // the LayerNorms in front of the f16 projections (QKV, GEGLU, the query projection; f16 or MIX_LINEAR_F16X2) folded into them: the producers of
                         // the fp32 stream leave an f16 shadow f16(x o gamma) + row statistics (IgemmParams::shadow), no LayerNorm launch
 };
 enum DemoteClass { DM_QKV = 1, DM_ATTN = 2, DM_OUT = 4, DM_XATTN = 8, DM_GEGLU = 16, DM_FF = 32, DM_CONV_RES = 64, DM_CONV_SKIP = 128,
@@ -296,7 +296,25 @@ void run_layernorm(Exec& ex, const NormW& n, const Act& x, int rows, const Act& 
 struct ResBlockW { NormW norm_in, norm_out; Lin conv_in, conv_out, skip; bool has_skip = false; int emb_off = 0, cin = 0, cout = 0; };
 struct TBlockW { NormW n1, n2, n3; Lin qkv, out1, q2, kv2, out2, geglu, ff;
                  Lin qkv_sh, q2_sh, geglu_sh; };   // *_sh: shadow forms (MIX_LN_SHADOW; .cs set) sharing the packed matrix of their plain twin
-struct STW { NormW norm; Lin proj_in, proj_out; std::vector<TBlockW> blocks; int C = 0, heads = 0; };
+// Form of a transformer projection on a split-operand model (StPlan): what it packs and which operand it reads
+enum LinForm {
+  LF_NATIVE,      // split-operand (HL16) weights, fp32-class (fp32 where K % 32 != 0)
+  LF_F16,         // plain f16 weights x f16 operand
+  LF_F16_WHILO,   // (hi | lo 2^8) weight halves along a doubled K against [a | a 2^-8] (MIX_GEGLU_HILO; k_form 1)
+  LF_F16_AHILO,   // (w | w 2^-8) against (hi | lo 2^8) activation halves (MIX_GEGLU_AHILO; k_form 1)
+  LF_X2           // the weight twice in the HL16 interleave against an HL16 operand read as f16 (MIX_LINEAR_F16X2; k_form 2)
+};
+inline bool packs_f16_values(LinForm f) { return f == LF_F16 || f == LF_F16_AHILO || f == LF_X2; }   // the packed weights are the parameter rounded to f16
+enum XattnForm { XA_LAUNCH, XA_F16, XA_SPLIT };   // cross-attention: its own launch / in the query projection's epilogue on f16 (the f16 engines'
+                                                  // fused launch; MIX_XATTN_F16) / there at split precision (MIX_XATTN_SPLIT)
+// how one spatial transformer runs (UNet plan_transformer): the only reading of the MixClass bits besides the fallback and mix_classes()
+struct StPlan {
+  LinForm qkv = LF_NATIVE, out1 = LF_NATIVE, q2 = LF_NATIVE, out2 = LF_NATIVE, geglu = LF_NATIVE, ff = LF_NATIVE;
+  bool qkv_sh = false, q2_sh = false, geglu_sh = false;   // LayerNorm-shadow twins (MIX_LN_SHADOW)
+  bool attn_f16 = false;                                   // self-attention on the f16 flash kernels
+  XattnForm xattn = XA_LAUNCH;                             // (where the forward's shapes and the context images allow it)
+};
+struct STW { NormW norm; Lin proj_in, proj_out; std::vector<TBlockW> blocks; int C = 0, heads = 0; StPlan plan; };
 struct BlockW { BlockDesc d; ResBlockW res; STW st; Lin conv; };
 
 class UNet {
@@ -347,6 +365,7 @@ class UNet {
   int cdt_, sdt_;
   int mix_ = 0;                          // MixClass bits (split-operand engine): classes on plain f16 operands
   bool mix_knob_ = false;                // the bits came from sdxl_debug_set "mix_classes" (no f16-exactness fallback)
+  bool attn16_ = false;                  // some transformer runs its self-attention on the f16 kernels (key-split workspace)
   DeviceArena warena_;
   std::vector<BlockW> inp_, out_;
   BlockW mid_res1_, mid_res2_;   // middle_block: res1 -> transformer (in mid_res1_.st) -> res2

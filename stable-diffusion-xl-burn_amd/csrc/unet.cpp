@@ -37,69 +37,97 @@ ResBlockW load_res(WeightBuilder& wb, const std::string& p, int cin, int cout, s
   emb_off += cout;
   return r;
 }
-bool spec_k_ok(WeightBuilder& wb, const std::string& name) { return wb.spec(name + ".weight").shape[0] % 32 == 0; }
-STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth, bool fuse_ln, int mix = 0) {
-  const bool geglu_f16 = (mix & MIX_GEGLU_F16) != 0, qkv_f16 = (mix & MIX_QKV_F16) != 0, ff_f16 = (mix & MIX_FF_F16) != 0, out1_f16 = (mix & MIX_OUT1_F16) != 0,
-             out2_f16 = (mix & MIX_OUT2_F16) != 0, q2_fused = out2_f16 && (mix & MIX_XATTN_F16) != 0, q2_f16 = q2_fused || (mix & MIX_Q2_F16) != 0,
-             ln_sh = (mix & MIX_LN_SHADOW) != 0, x2 = (mix & MIX_LINEAR_F16X2) != 0;
+// parameter names of a transformer block's projections (suffixes of "<transformer>.blocks.<j>")
+const std::vector<std::string> kQkv = {".attn1.query", ".attn1.key", ".attn1.value"};
+const char* const kOut1 = ".attn1.out", *const kQ2 = ".attn2.query", *const kOut2 = ".attn2.out", *const kGeglu = ".mlp.geglu.proj", *const kFf = ".mlp.lin";
+
+// the forms of transformer `p`'s projections for MixClass bits `mix` on compute dtype `cdt` (all blocks of a transformer share their shapes)
+StPlan plan_transformer(int mix, int cdt, const std::vector<ParamSpec>& specs, const std::string& p) {
+  StPlan s;
+  if (cdt == DT_F16) s.xattn = XA_F16;
+  auto shape = [&](const char* proj) -> const std::vector<int>* {
+    const std::string n = p + ".blocks.0" + proj + ".weight";
+    for (const ParamSpec& ps : specs) if (ps.name == n) return &ps.shape;
+    return nullptr;
+  };
+  if (cdt != DT_HL || !shape(kQ2)) return s;
+  auto fits = [&](const char* proj, int k, int n) { const std::vector<int>& sh = *shape(proj); return sh[0] % k == 0 && sh[1] % n == 0; };
+  const bool ln_sh = (mix & MIX_LN_SHADOW) != 0, x2 = (mix & MIX_LINEAR_F16X2) != 0;
+  const bool xattn_f16 = (mix & MIX_OUT2_F16) && (mix & MIX_XATTN_F16);
+  // MIX_LINEAR_F16X2: a projection that stays fp32-class (its A operand an HL16 tensor) runs on the f16 kernels over the weight packed twice in the HL16 interleave
+  auto x2_ok = [&](const char* proj) { return x2 && fits(proj, 32, 128); };
+  // MIX_LN_SHADOW: the projections behind a LayerNorm also exist in the shadow form (same packed matrix, cs = gamma W, b = beta W + bias): where the
+  // producer of the stream left the shadow f16(x o gamma) and the row statistics, the LayerNorm launch is skipped (spatial_transformer)
+  if (mix & MIX_QKV_F16) { s.qkv = LF_F16; s.qkv_sh = ln_sh; }
+  else if (ln_sh && x2 && fits(kQkv[0].c_str(), 64, 128)) { s.qkv = LF_X2; s.qkv_sh = true; }     // (the plain twin reads the LayerNorm launch's HL16 output)
+  s.out1 = (mix & MIX_OUT1_F16) ? LF_F16 : x2_ok(kOut1) ? LF_X2 : LF_NATIVE;
+  if ((mix & MIX_Q2_F16) || xattn_f16) { s.q2 = LF_F16; s.q2_sh = ln_sh && !xattn_f16; }
+  else if (x2_ok(kQ2)) { s.q2 = LF_X2; s.q2_sh = ln_sh && fits(kQ2, 64, 1); }
+  s.out2 = (mix & MIX_OUT2_F16) ? LF_F16 : x2_ok(kOut2) ? LF_X2 : LF_NATIVE;
+  if (mix & MIX_GEGLU_F16) {
+    const bool k32 = fits(kGeglu, 32, 1);
+    if ((mix & MIX_GEGLU_AHILO) && k32) { s.geglu = LF_F16_AHILO; s.geglu_sh = ln_sh && fits(kGeglu, 64, 1); }   // (the shadow carries both halves)
+    else if (ln_sh) { s.geglu = LF_F16; s.geglu_sh = true; }
+    else s.geglu = (mix & MIX_GEGLU_HILO) && k32 ? LF_F16_WHILO : LF_F16;
+  } else if (x2 && fits(kGeglu, 32, 640)) { s.geglu = LF_X2; s.geglu_sh = ln_sh && fits(kGeglu, 64, 1); }    // (K = 2 C on the f16 wide-tile kernel)
+  s.ff = (mix & MIX_FF_F16) ? LF_F16 : x2_ok(kFf) ? LF_X2 : LF_NATIVE;
+  s.attn_f16 = ((mix & MIX_ATTN_F16) || s.qkv == LF_F16) && shape(kQ2)->at(0) % 16 == 0;
+  SDXL_REQUIRE(s.out1 != LF_F16 || s.attn_f16, "mixed mode: an f16 out-projection reads the f16 self-attention's output");
+  // the split-precision epilogue writes the out-projection's operand: f16 rows for an f16 one, HL16 rows behind the X2 query projection
+  if (xattn_f16) s.xattn = XA_F16;
+  else if ((mix & MIX_XATTN_SPLIT) && ((s.q2 == LF_F16 && s.out2 == LF_F16) || (s.q2 == LF_X2 && s.out2 != LF_F16))) s.xattn = XA_SPLIT;
+  return s;
+}
+// the weights of block `q` that plan `s` packs as f16 values (what the create-time guard checks)
+void f16_valued_weights(const StPlan& s, const std::string& q, std::vector<std::string>& names) {
+  auto add = [&](LinForm f, const char* proj) { if (packs_f16_values(f)) names.push_back(q + proj + ".weight"); };
+  for (const std::string& n : kQkv) add(s.qkv, n.c_str());
+  add(s.out1, kOut1); add(s.q2, kQ2); add(s.out2, kOut2); add(s.geglu, kGeglu); add(s.ff, kFf);
+}
+// projection `names` packed in form f; with `sh` also its shadow twin (behind LayerNorm `norm`), which shares the packed matrix
+Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh = nullptr, const std::string& norm = "") {
+  Lin l;
+  if (sh) { *sh = wb.fold_ln(names, norm, geglu, DT_F16, true, &l, f == LF_F16_AHILO, f == LF_X2); return l; }
+  switch (f) {
+    case LF_F16: return names.size() > 1 ? wb.fused_linear(names, DT_F16) : wb.linear(names[0], geglu, DT_F16);
+    case LF_F16_WHILO: return wb.linear_hilo(names[0], geglu);
+    case LF_F16_AHILO: return wb.linear_hilo(names[0], geglu, true);
+    case LF_X2: return wb.linear_hilo(names[0], geglu, false, true);
+    default: return names.size() > 1 ? wb.fused_linear(names) : wb.linear(names[0], geglu);
+  }
+}
+STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth, bool fuse_ln, const StPlan& plan) {
   STW s;
-  s.C = C; s.heads = heads;
+  s.C = C; s.heads = heads; s.plan = plan;
   s.norm = wb.norm(p + ".norm");
   s.proj_in = wb.linear(p + ".proj_in");
   for (int j = 0; j < depth; ++j) {
     const std::string q = p + ".blocks." + std::to_string(j);
+    const std::vector<std::string> qkv = {q + kQkv[0], q + kQkv[1], q + kQkv[2]};
     TBlockW t;
     if (fuse_ln) {
       // the three LayerNorms of TransformerBlock::forward (unet/mod.rs:885-891) are folded into the projections that
       // consume them; their row statistics come out of the epilogue of the GEMM that produced the residual stream
-      t.qkv = wb.fused_linear_ln({q + ".attn1.query", q + ".attn1.key", q + ".attn1.value"}, q + ".norm1");
-      t.out1 = wb.linear(q + ".attn1.out");
-      t.q2 = wb.linear_ln(q + ".attn2.query", false, q + ".norm2");
+      t.qkv = wb.fused_linear_ln(qkv, q + ".norm1");
+      t.out1 = wb.linear(q + kOut1);
+      t.q2 = wb.linear_ln(q + kQ2, false, q + ".norm2");
       t.kv2 = wb.fused_linear({q + ".attn2.key", q + ".attn2.value"});
-      t.out2 = wb.linear(q + ".attn2.out");
-      t.geglu = wb.linear_ln(q + ".mlp.geglu.proj", true, q + ".norm3");
-      t.ff = wb.linear(q + ".mlp.lin");
+      t.out2 = wb.linear(q + kOut2);
+      t.geglu = wb.linear_ln(q + kGeglu, true, q + ".norm3");
+      t.ff = wb.linear(q + kFf);
       s.blocks.push_back(t);
       continue;
     }
     t.n1 = wb.norm(q + ".norm1");
-    // MIX_LN_SHADOW: the f16 projections behind a LayerNorm also exist in the shadow form (same packed matrix, cs = gamma W, b = beta W + bias): where the
-    // producer of the stream left the f16 shadow f16(x o gamma) and the row statistics, the LayerNorm launch is skipped (spatial_transformer)
-    if (ln_sh && qkv_f16) t.qkv_sh = wb.fold_ln({q + ".attn1.query", q + ".attn1.key", q + ".attn1.value"}, q + ".norm1", false, DT_F16, true, &t.qkv);
-    else if (ln_sh && !qkv_f16 && x2 && wb.spec(q + ".attn1.query.weight").shape[0] % 64 == 0 && wb.spec(q + ".attn1.query.weight").shape[1] % 128 == 0)
-      // MIX_LINEAR_F16X2 + MIX_LN_SHADOW: fp32-class projection on the f16 kernels over an HL16 shadow (k_form 2); the plain twin reads the LayerNorm launch's HL16 output
-      t.qkv_sh = wb.fold_ln({q + ".attn1.query", q + ".attn1.key", q + ".attn1.value"}, q + ".norm1", false, DT_F16, true, &t.qkv, false, true);
-    else
-    t.qkv = wb.fused_linear({q + ".attn1.query", q + ".attn1.key", q + ".attn1.value"}, qkv_f16 ? (int)DT_F16 : -1);
-    // MIX_LINEAR_F16X2: a projection that stays fp32-class (its A operand an HL16 tensor) runs on the f16 kernels over the weight packed twice in the HL16 interleave
-    auto x2_ok = [&](const std::string& nm) { return x2 && wb.spec(nm + ".weight").shape[0] % 32 == 0 && wb.spec(nm + ".weight").shape[1] % 128 == 0; };
-    t.out1 = !out1_f16 && x2_ok(q + ".attn1.out") ? wb.linear_hilo(q + ".attn1.out", false, false, true) : wb.linear(q + ".attn1.out", false, out1_f16 ? (int)DT_F16 : -1);
+    t.qkv = pack_proj(wb, plan.qkv, qkv, false, plan.qkv_sh ? &t.qkv_sh : nullptr, q + ".norm1");
+    t.out1 = pack_proj(wb, plan.out1, {q + kOut1}, false);
     t.n2 = wb.norm(q + ".norm2");
-    if (ln_sh && q2_f16 && !q2_fused) t.q2_sh = wb.fold_ln({q + ".attn2.query"}, q + ".norm2", false, DT_F16, true, &t.q2);
-    else if (!q2_f16 && ln_sh && x2_ok(q + ".attn2.query") && wb.spec(q + ".attn2.query.weight").shape[0] % 64 == 0)
-      t.q2_sh = wb.fold_ln({q + ".attn2.query"}, q + ".norm2", false, DT_F16, true, &t.q2, false, true);
-    else if (!q2_f16 && x2_ok(q + ".attn2.query")) t.q2 = wb.linear_hilo(q + ".attn2.query", false, false, true);
-    else
-    t.q2 = wb.linear(q + ".attn2.query", false, q2_f16 ? (int)DT_F16 : -1);
+    t.q2 = pack_proj(wb, plan.q2, {q + kQ2}, false, plan.q2_sh ? &t.q2_sh : nullptr, q + ".norm2");
     t.kv2 = wb.fused_linear({q + ".attn2.key", q + ".attn2.value"});
-    t.out2 = !out2_f16 && x2_ok(q + ".attn2.out") ? wb.linear_hilo(q + ".attn2.out", false, false, true) : wb.linear(q + ".attn2.out", false, out2_f16 ? (int)DT_F16 : -1);
+    t.out2 = pack_proj(wb, plan.out2, {q + kOut2}, false);
     t.n3 = wb.norm(q + ".norm3");
-    // (mixed mode: the GEGLU projection of a split-operand model packed as plain f16 -- it runs on the f16 wide-tile kernel)
-    if (geglu_f16 && (mix & MIX_GEGLU_AHILO) && spec_k_ok(wb, q + ".mlp.geglu.proj")) {
-      // activations as (hi | lo 2^8) along a doubled K against (w | w 2^-8); with MIX_LN_SHADOW the producer's shadow carries both halves
-      if (ln_sh && wb.spec(q + ".mlp.geglu.proj.weight").shape[0] % 64 == 0) t.geglu_sh = wb.fold_ln({q + ".mlp.geglu.proj"}, q + ".norm3", true, DT_F16, true, &t.geglu, true);
-      else t.geglu = wb.linear_hilo(q + ".mlp.geglu.proj", true, true);
-    }
-    else if (ln_sh && geglu_f16) t.geglu_sh = wb.fold_ln({q + ".mlp.geglu.proj"}, q + ".norm3", true, DT_F16, true, &t.geglu);
-    else if (geglu_f16 && (mix & MIX_GEGLU_HILO) && spec_k_ok(wb, q + ".mlp.geglu.proj")) t.geglu = wb.linear_hilo(q + ".mlp.geglu.proj", true);
-    else if (!geglu_f16 && x2 && wb.spec(q + ".mlp.geglu.proj.weight").shape[0] % 32 == 0 && wb.spec(q + ".mlp.geglu.proj.weight").shape[1] % 640 == 0) {
-      // fp32-class GEGLU on the f16 wide-tile kernel (HL16 operand read as f16, K = 2 C); with MIX_LN_SHADOW also in the shadow form
-      if (ln_sh && wb.spec(q + ".mlp.geglu.proj.weight").shape[0] % 64 == 0) t.geglu_sh = wb.fold_ln({q + ".mlp.geglu.proj"}, q + ".norm3", true, DT_F16, true, &t.geglu, false, true);
-      else t.geglu = wb.linear_hilo(q + ".mlp.geglu.proj", true, false, true);
-    }
-    else
-    t.geglu = wb.linear(q + ".mlp.geglu.proj", true, geglu_f16 ? (int)DT_F16 : -1);
-    t.ff = !ff_f16 && x2_ok(q + ".mlp.lin") ? wb.linear_hilo(q + ".mlp.lin", false, false, true) : wb.linear(q + ".mlp.lin", false, ff_f16 ? (int)DT_F16 : -1);
+    t.geglu = pack_proj(wb, plan.geglu, {q + kGeglu}, true, plan.geglu_sh ? &t.geglu_sh : nullptr, q + ".norm3");
+    t.ff = pack_proj(wb, plan.ff, {q + kFf}, false);
     s.blocks.push_back(t);
   }
   s.proj_out = wb.linear(p + ".proj_out");
@@ -218,40 +246,54 @@ UNet::~UNet() {
 
 void UNet::build_weights(WeightSource& src, hipStream_t st) {
   const std::vector<ParamSpec> specs = unet_param_specs(cfg_);
-  size_t bound = WeightBuilder::arena_bound(specs, cdt_);
-  if (cdt_ == DT_HL && (mix_ & MIX_LINEAR_F16X2))      // f16 x 2 K images carry a fragment-order twin the split-operand bound does not count
-    for (const ParamSpec& ps : specs) if (ps.kind == PK_LINEAR_W) bound += round_up(ps.shape[1], 128) * round_up((size_t)ps.shape[0], 64) * 4 + 256;
-  warena_.reserve(bound);
+  std::vector<BlockDesc> inp, out; BlockDesc mid;
+  unet_block_plan(cfg_, inp, mid, out);
+  // the spatial transformers in build order (parameter prefix, depth) and their plans
+  std::vector<std::pair<std::string, int>> sts;
+  auto has_st = [](const BlockDesc& d) { return d.kind == BK_REST || d.kind == BK_RESTU; };
+  for (size_t i = 0; i < inp.size(); ++i) if (has_st(inp[i])) sts.push_back({"input_blocks." + std::to_string(i) + ".transformer", inp[i].depth});
+  sts.push_back({"middle_block.transformer", mid.depth});
+  for (size_t i = 0; i < out.size(); ++i) if (has_st(out[i])) sts.push_back({"output_blocks." + std::to_string(i) + ".transformer", out[i].depth});
+  std::vector<StPlan> plans;
+  std::vector<std::string> f16_names;      // weights the plans pack as f16 values
+  auto plan_all = [&]() {
+    plans.clear(); f16_names.clear();
+    for (const auto& t : sts) {
+      plans.push_back(plan_transformer(mix_, cdt_, specs, t.first));
+      for (int j = 0; j < t.second; ++j) f16_valued_weights(plans.back(), t.first + ".blocks." + std::to_string(j), f16_names);
+    }
+  };
+  plan_all();
   WeightBuilder wb(specs, src, warena_, cdt_, st);
-  // SDXL_DTYPE_F32_SPLIT_MIX_F16W moves classes to plain f16 operands whose WEIGHTS must be f16 values (the reference's records are,
-  // src/bin/sample/main.rs:37): on other parameters that would round the weights as well and leave the mode's error bound (0.029 against
-  // 0.0212).  Checked here on the tensors themselves; a model that does not qualify falls back to F32_SPLIT_MIX's two classes (mix_classes() tells).
+  // A form that packs a parameter's values as f16 (StPlan) must get f16 values (the reference's records are, src/bin/sample/main.rs:37): on other
+  // parameters it would round the weights as well and leave the mode's error bound (0.029 against 0.0212).  Checked here on exactly those
+  // tensors; a model that does not qualify falls back to F32_SPLIT_MIX's classes (capi.hip mix_of) -- plain F32_SPLIT for a mode without f16-OPERAND classes,
+  // SDXL_DTYPE_F32_SPLIT_F16W -- and mix_classes() tells.
   // Not applied to the A/B knob "mix_classes" (the frontier tools run those maps on fp32 weights on purpose) nor on replicas built from an empty
   // source (they receive rank 0's arena: the caller compares rank 0's mix_classes() with the mode before the broadcast, bench.py does).
-  constexpr int kNeedExact = MIX_QKV_F16 | MIX_FF_F16 | MIX_OUT1_F16 | MIX_OUT2_F16 | MIX_XATTN_F16 | MIX_Q2_F16 | MIX_GEGLU_AHILO | MIX_LINEAR_F16X2;
-  if (cdt_ == DT_HL && (mix_ & kNeedExact) && !mix_knob_ && !src.empty()) {
-    std::vector<std::string> names;
-    auto ends = [](const std::string& n, const char* suf) { const size_t l = std::strlen(suf); return n.size() >= l && n.compare(n.size() - l, l, suf) == 0; };
-    for (const ParamSpec& ps : specs) {
-      const std::string& n = ps.name;
-      if (n.find(".transformer.blocks.") == std::string::npos) continue;
-      if (((mix_ & MIX_QKV_F16) && (ends(n, ".attn1.query.weight") || ends(n, ".attn1.key.weight") || ends(n, ".attn1.value.weight"))) ||
-          ((mix_ & MIX_OUT1_F16) && ends(n, ".attn1.out.weight")) || ((mix_ & MIX_OUT2_F16) && ends(n, ".attn2.out.weight")) ||
-          ((mix_ & (MIX_FF_F16 | MIX_LINEAR_F16X2)) && ends(n, ".mlp.lin.weight")) || ((mix_ & MIX_LINEAR_F16X2) && (ends(n, ".attn1.out.weight") || ends(n, ".attn2.out.weight"))) || ((mix_ & (MIX_GEGLU_AHILO | MIX_LINEAR_F16X2)) && ends(n, ".mlp.geglu.proj.weight")) || ((mix_ & (MIX_XATTN_F16 | MIX_Q2_F16 | MIX_LINEAR_F16X2)) && ends(n, ".attn2.query.weight")))
-        names.push_back(n);
-    }
-    if (!wb.all_f16_exact(names))      // = SDXL_DTYPE_F32_SPLIT_MIX (capi.hip mix_of); a mode without f16-OPERAND classes (SDXL_DTYPE_F32_SPLIT_F16W) falls back to plain F32_SPLIT
-      mix_ = (mix_ & (MIX_ATTN_F16 | MIX_GEGLU_F16)) ? (MIX_ATTN_F16 | MIX_GEGLU_F16 | MIX_GEGLU_HILO) : 0;
+  if (!mix_knob_ && !wb.all_f16_exact(f16_names)) {
+    mix_ = (mix_ & (MIX_ATTN_F16 | MIX_GEGLU_F16)) ? (MIX_ATTN_F16 | MIX_GEGLU_F16 | MIX_GEGLU_HILO) : 0;
+    plan_all();
+    SDXL_REQUIRE(f16_names.empty(), "the fallback classes pack no parameter as f16 values");
   }
+  bool x2 = false;
+  attn16_ = cdt_ == DT_F16;
+  for (const StPlan& pl : plans) {
+    x2 = x2 || pl.qkv == LF_X2 || pl.out1 == LF_X2 || pl.q2 == LF_X2 || pl.out2 == LF_X2 || pl.geglu == LF_X2 || pl.ff == LF_X2;
+    attn16_ = attn16_ || pl.attn_f16;
+  }
+  size_t bound = WeightBuilder::arena_bound(specs, cdt_);
+  if (x2)      // f16 x 2 K images carry a fragment-order twin the split-operand bound does not count
+    for (const ParamSpec& ps : specs) if (ps.kind == PK_LINEAR_W) bound += round_up(ps.shape[1], 128) * round_up((size_t)ps.shape[0], 64) * 4 + 256;
+  warena_.reserve(bound);
   const int gv = cdt_ == DT_HL ? DT_F32 : -1;     // the M <= 8 GEMV weights of a split-operand model are packed fp32
   lin1_t_ = wb.linear("lin1_time_embed", false, gv);
   lin2_t_ = wb.linear("lin2_time_embed", false, gv);
   lin1_l_ = wb.linear("lin1_label_embed", false, gv);
   lin2_l_ = wb.linear("lin2_label_embed", false, gv);
-  std::vector<BlockDesc> inp, out; BlockDesc mid;
-  unet_block_plan(cfg_, inp, mid, out);
   std::vector<std::string> emb_names;
   int emb_off = 0;
+  size_t sti = 0;
   auto load_block = [&](const std::string& p, const BlockDesc& d) {
     BlockW b; b.d = d;
     switch (d.kind) {
@@ -259,7 +301,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
       case BK_RES: b.res = load_res(wb, p, d.c_in, d.c_out, emb_names, emb_off); break;
       default:
         b.res = load_res(wb, p + ".res", d.c_in, d.c_out, emb_names, emb_off);
-        if (d.kind == BK_REST || d.kind == BK_RESTU) b.st = load_st(wb, p + ".transformer", d.c_out, d.n_head, d.depth, fuse_ln_, mix_);
+        if (d.kind == BK_REST || d.kind == BK_RESTU) b.st = load_st(wb, p + ".transformer", d.c_out, d.n_head, d.depth, fuse_ln_, plans[sti++]);
         if (d.kind == BK_RESTU || d.kind == BK_RESU) b.conv = wb.conv(p + ".upsample.conv");
     }
     return b;
@@ -267,7 +309,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
   for (size_t i = 0; i < inp.size(); ++i) inp_.push_back(load_block("input_blocks." + std::to_string(i), inp[i]));
   mid_res1_.d = mid;
   mid_res1_.res = load_res(wb, "middle_block.res1", mid.c_in, mid.c_out, emb_names, emb_off);
-  mid_res1_.st = load_st(wb, "middle_block.transformer", mid.c_out, mid.n_head, mid.depth, fuse_ln_, mix_);
+  mid_res1_.st = load_st(wb, "middle_block.transformer", mid.c_out, mid.n_head, mid.depth, fuse_ln_, plans[sti++]);
   mid_res2_.d = mid;
   mid_res2_.res = load_res(wb, "middle_block.res2", mid.c_in, mid.c_out, emb_names, emb_off);
   for (size_t i = 0; i < out.size(); ++i) out_.push_back(load_block("output_blocks." + std::to_string(i), out[i]));
@@ -288,8 +330,9 @@ void UNet::set_context(const float* context, int n_ctx, const float* label, int 
   const int vt_ld = (int)round_up(n_ctx, 64);
   // operand-order copies for the fused cross-attention epilogue (f16 engines; the split-operand engine when that class runs on f16: MIX_XATTN_F16)
   // (MIX_XATTN_SPLIT: TWO images -- the hi and the lo halves of the fp32-class projection -- for the split-precision form of that epilogue)
-  const bool pack_xs = cdt_ == DT_HL && (mix_ & MIX_XATTN_SPLIT) && (mix_ & (MIX_Q2_F16 | MIX_LINEAR_F16X2)) && !(mix_ & MIX_XATTN_F16) && n_ctx <= 96;
-  const bool pack_xa = (cdt_ == DT_F16 || (cdt_ == DT_HL && (mix_ & MIX_XATTN_F16) && (mix_ & MIX_OUT2_F16)) || pack_xs) && n_ctx <= 96;
+  bool pack_xs = false, pack_xa = false;
+  for (const STW* st : st_list_) { pack_xs = pack_xs || st->plan.xattn == XA_SPLIT; pack_xa = pack_xa || st->plan.xattn != XA_LAUNCH; }
+  pack_xs = pack_xs && n_ctx <= 96; pack_xa = pack_xa && n_ctx <= 96;
   const int kvdt = attn_dt();                           // dtype of the K / V^T caches (fp32 in the split-operand mode)
   const int emb = 4 * cfg_.model_channels;
   {   // precision-frontier instrument: the demoted classes take effect from here (weights now, activations in every forward after)
@@ -459,78 +502,74 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   if (npad != HW && !ex.dry) launch_fill_zero(vt, (size_t)B * C * npad * dt_size(adt), ex.s);
   // split-operand mode: the attention kernel takes K and V^T in HL16 (same bytes as fp32); q and the output stay fp32
   const bool hl_attn = ex.cdt == DT_HL;
-  // mixed mode (SDXL_DTYPE_F32_SPLIT_MIX; classes chosen on the measured precision frontier, profiles/r05_precision_frontier.json):
-  //   * self-attention on the f16 flash kernels: the (split-operand) QKV projection writes q | k and V^T as f16, the attention output is
-  //     handed to the out-projection as HL16 with zero lo halves (an f16 value is its own hi half);
-  //   * GEGLU projection on f16 operands (f16 LayerNorm output x f16-packed weights, the f16 wide-tile kernel) -- its output leaves the
-  //     epilogue as HL16 (fp32-class), so FF-out's operand is not rounded a second time.
-  const bool mix_qkv = hl_attn && !w.blocks.empty() && w.blocks[0].qkv.dt == DT_F16 && w.blocks[0].qkv.k_form == 0;     // (f16-packed at build: the only path those weights can take; k_form 2 = fp32-class, MIX_LINEAR_F16X2)
-  const bool mix_ff = hl_attn && !w.blocks.empty() && w.blocks[0].ff.dt == DT_F16 && w.blocks[0].ff.k_form == 0;      // (K = 2 x: the MIX_LINEAR_F16X2 form, an fp32-class projection)
-  const bool mix_out1 = hl_attn && !w.blocks.empty() && w.blocks[0].out1.dt == DT_F16 && w.blocks[0].out1.k_form == 0;
-  const bool mix_out2 = hl_attn && !w.blocks.empty() && w.blocks[0].out2.dt == DT_F16 && w.blocks[0].out2.k_form == 0;
+  // forms of the projections (plan_transformer; mixed modes SDXL_DTYPE_F32_SPLIT_MIX*: classes chosen on the measured precision frontier,
+  // profiles/r05_precision_frontier.json):
+  //   * self-attention on the f16 flash kernels: the QKV projection writes q | k and V^T as f16, the attention output is handed to the
+  //     out-projection as HL16 with zero lo halves (an f16 value is its own hi half) -- or as it is to an f16 one;
+  //   * f16 projections read an f16 LayerNorm output; an f16 GEGLU projection's output leaves the epilogue as HL16 (fp32-class), so FF-out's
+  //     operand is not rounded a second time (an f16 FF-out reads it as f16).
+  const StPlan& pl = w.plan;
+  auto f16_in = [](LinForm f) { return f == LF_F16 || f == LF_F16_WHILO || f == LF_F16_AHILO; };   // the projection reads f16 activations
   Act ao2_16;      // operand of an f16 cross-attention out-projection: the split-operand attention rounds its fp32 result once, in its own store (AttnParams::o_dt)
-  if (mix_out2) ao2_16 = ex.alloc(M, C, DT_F16);
-  const bool mix_attn = hl_attn && ((mix_ & MIX_ATTN_F16) || mix_qkv) && C % 16 == 0;
-  SDXL_REQUIRE(!mix_qkv || mix_attn, "mixed mode: an f16 QKV projection feeds the f16 self-attention");
-  SDXL_REQUIRE(!mix_out1 || mix_attn, "mixed mode: an f16 out-projection reads the f16 self-attention's output");
-  // (the GEGLU weights of a mixed-mode model are PACKED f16 at build: the f16 path is the only one they can take, whatever the token count)
-  const bool mix_geglu = hl_attn && !w.blocks.empty() && w.blocks[0].geglu.dt == DT_F16 && w.blocks[0].geglu.k_form != 2;      // (k_form 2: an fp32-class projection on the f16 kernel, MIX_LINEAR_F16X2)
+  if (pl.out2 == LF_F16) ao2_16 = ex.alloc(M, C, DT_F16);
+  const Act ao2 = pl.out2 == LF_F16 ? ao2_16 : ao;      // what the cross-attention writes: the out-projection's operand
   Act qk16, ao16, ln16; void* vt16 = nullptr;
-  if (mix_attn) {
+  if (pl.attn_f16) {
     qk16 = ex.alloc(M, 2 * C, DT_F16); ao16 = ex.alloc(M, C, DT_F16);
     vt16 = ex.act->alloc((size_t)B * C * npad * 2);
     if (npad != HW && !ex.dry) launch_fill_zero(vt16, (size_t)B * C * npad * 2, ex.s);
   }
-  // cross-attention of the mixed mode on f16 (MIX_XATTN_F16): the f16 engine's fused launch -- query projection and the 77-key attention in one kernel on
-  // the f16 LayerNorm output and the packed f16 context; shapes that launch does not take (tiny nets) widen the f16 query for the split-operand attention
-  const bool mix_q2 = hl_attn && !w.blocks.empty() && w.blocks[0].q2.dt == DT_F16 && w.blocks[0].q2.k_form == 0;
-  const bool x2_q2 = hl_attn && !w.blocks.empty() && w.blocks[0].q2.k_form == 2;      // fp32-class query projection on the f16 kernels (MIX_LINEAR_F16X2)
-  // the f16 engine's fused launch (MIX_XATTN_F16: the set_context of such a model packed the f16 context, kv.xa) -- otherwise an f16 query projection
-  // (MIX_Q2_F16) writes an fp32 q for the split-operand attention
-  const bool mix_xa = mix_q2 && mix_out2 && (mix_ & MIX_XATTN_F16) && plan_xattn_ && !kv_.empty() && kv_[si][0].xa && igemm_xattn_ok(DT_F16, DT_F16, (int)M, C, C, HW, n_ctx_);
-  const bool mix_q2_widen = mix_q2 && (mix_ & MIX_XATTN_F16) && mix_out2;     // round 5's form of the knob on shapes the fused launch does not take: f16 q, widened
-  if (mix_geglu || mix_qkv || mix_q2) ln16 = ex.alloc(M, C, DT_F16);
-  // MIX_GEGLU_HILO: the GEGLU projection's weights are (hi | lo 2^8) halves along a doubled K (WeightBuilder::linear_hilo): its A operand is [a | a 2^-8]
-  const bool gg_hilo = mix_geglu && !w.blocks.empty() && w.blocks[0].geglu.k_form == 1;      // (the LayerNorm-launch path; the shadow form of such a projection reads sh16g)
+  if (f16_in(pl.geglu) || pl.qkv == LF_F16 || pl.q2 == LF_F16) ln16 = ex.alloc(M, C, DT_F16);
+  // (hi | lo) GEGLU forms: the LayerNorm launch writes [a | a 2^-8] or [a_hi | a_lo 2^8] along a doubled K
   Act ln16x2;
-  if (gg_hilo) ln16x2 = ex.alloc(M, 2 * C, DT_F16);
-  // MIX_LN_SHADOW: f16 shadow of the stream + the fp32 rows' statistics, left by the weights-in-registers producers (out-projections, FF-out) for the f16
+  if (pl.geglu == LF_F16_WHILO || pl.geglu == LF_F16_AHILO) ln16x2 = ex.alloc(M, 2 * C, DT_F16);
+  // MIX_LN_SHADOW: f16 shadow of the stream + the fp32 rows' statistics, left by the weights-in-registers producers (out-projections, FF-out) for the
   // projection behind the next LayerNorm; `have_sh` says whether the last producer wrote them (else: LayerNorm launch + the plain form of the projection)
-  const bool any_sh = hl_attn && !w.blocks.empty() && (w.blocks[0].qkv_sh.cs || w.blocks[0].q2_sh.cs || w.blocks[0].geglu_sh.cs);
   Act sh16; float* shst = nullptr; bool have_sh = false;
-  if (any_sh) { sh16 = ex.alloc(M, C, DT_F16); shst = (float*)ex.act->alloc(M * (size_t)((C + 63) / 64) * 2 * sizeof(float)); }
-  Act sh16g;       // (hi | lo 2^8) shadow for a GEGLU projection packed (w | w 2^-8) along a doubled K (MIX_GEGLU_AHILO with MIX_LN_SHADOW)
-  const bool sh_g2 = any_sh && w.blocks[0].geglu_sh.cs && w.blocks[0].geglu_sh.k_form == 1;
-  if (sh_g2) sh16g = ex.alloc(M, 2 * C, DT_F16);
-  // MIX_LINEAR_F16X2 with MIX_LN_SHADOW: the shadow is the HL16 image of x o gamma (what the LayerNorm launch would hand the k_form-2 projection, minus the
-  // normalisation the consumer's epilogue applies from the row statistics)
+  if (pl.qkv_sh || pl.q2_sh || pl.geglu_sh) { sh16 = ex.alloc(M, C, DT_F16); shst = (float*)ex.act->alloc(M * (size_t)((C + 63) / 64) * 2 * sizeof(float)); }
+  Act sh16g;       // (hi | lo 2^8) shadow for a GEGLU projection packed (w | w 2^-8) along a doubled K
+  if (pl.geglu_sh && pl.geglu == LF_F16_AHILO) sh16g = ex.alloc(M, 2 * C, DT_F16);
+  // X2 shadow: the HL16 image of x o gamma (what the LayerNorm launch would hand the projection, minus the normalisation the consumer's epilogue
+  // applies from the row statistics)
   Act shhl;
-  if (any_sh && (w.blocks[0].qkv_sh.k_form == 2 || w.blocks[0].q2_sh.k_form == 2 || w.blocks[0].geglu_sh.k_form == 2)) shhl = ex.alloc(M, C, DT_HL);
-  Act q32;     // MIX_Q2_F16: fp32 q of the cross-attention (the f16 projection's fp32 accumulators, never rounded to f16)
-  if (mix_q2 && !mix_q2_widen) q32 = ex.alloc(M, C, DT_F32);
-  // MIX_XATTN_SPLIT: the split-precision attention runs inside that projection's epilogue on q's accumulators (hi / lo context images of set_context), and its
-  // f16 rows are the out-projection's operand: q never reaches memory, no attention launch
-  const bool mix_xs = mix_q2 && !mix_q2_widen && mix_out2 && plan_xattn_ && !kv_.empty() && kv_[si][0].xa_lo && igemm_xattn_ok(DT_F16, DT_F16, (int)M, C, C, HW, n_ctx_);
-  // ... and in the MIX_LINEAR_F16X2 form of the query projection (K = 2 C, HL16 rows out: the out-projection's fp32-class operand)
-  const bool x2_xs = x2_q2 && plan_xattn_ && !kv_.empty() && kv_[si][0].xa_lo && ao.dt == DT_HL && igemm_xattn_ok(DT_F16, DT_HL, (int)M, C, 2 * C, HW, n_ctx_);
-  // MIX_LINEAR_F16X2: an un-scaled HL16 operand of C logical channels handed to an f16 GEMM whose weight is packed twice in the HL16 interleave (K = 2 C)
-  auto x2op = [&](const Lin& l, const Act& a, int Cl) { return (l.dt == DT_F16 && l.k_form == 2 && l.K == 2 * Cl && a.dt == DT_HL && !a.a_scale) ? Act(a.p, 2 * a.ld, DT_F16) : a; };
-  auto want_shadow = [&](Epi& e, const Lin& consumer_sh, const NormW& n) {     // ask producer `e` for the shadow the consumer behind LayerNorm n reads
+  if ((pl.qkv_sh && pl.qkv == LF_X2) || (pl.q2_sh && pl.q2 == LF_X2) || (pl.geglu_sh && pl.geglu == LF_X2)) shhl = ex.alloc(M, C, DT_HL);
+  // the knob's f16 fused cross-attention on shapes its launch does not take: f16 q, widened for the split-operand attention
+  const bool q2_widen = hl_attn && pl.xattn == XA_F16;
+  Act q32;     // f16 query projection: fp32 q for the split-operand attention (the projection's fp32 accumulators, never rounded to f16)
+  if (pl.q2 == LF_F16 && !q2_widen) q32 = ex.alloc(M, C, DT_F32);
+  // cross-attention inside the query projection's epilogue (the context images of set_context): q never reaches memory, no attention launch
+  const bool xa_fused = pl.xattn != XA_LAUNCH && plan_xattn_ && !w.blocks.empty() && (pl.xattn == XA_SPLIT ? kv_[si][0].xa_lo : kv_[si][0].xa) &&
+                        igemm_xattn_ok(DT_F16, ao2.dt, (int)M, C, pl.q2 == LF_X2 ? 2 * C : C, HW, n_ctx_);
+  // X2: an un-scaled HL16 operand of C logical channels handed to an f16 GEMM whose weight is packed twice in the HL16 interleave (K = 2 C)
+  auto x2op = [](LinForm f, const Act& a) { return f == LF_X2 ? Act(a.p, 2 * a.ld, DT_F16) : a; };
+  auto want_shadow = [&](Epi& e, bool sh, LinForm f, const NormW& n) {     // ask producer `e` for the shadow the consumer (form f) behind LayerNorm n reads
     have_sh = false;
-    if (!consumer_sh.cs || C % 64 != 0) return;
+    if (!sh || C % 64 != 0) return;
     e.shadow = sh16.p; e.shadow_ld = sh16.ld; e.shadow_gamma = n.gamma; e.stat_out = shst; e.shadow_done = &have_sh;
-    if (consumer_sh.k_form == 1) { e.shadow = sh16g.p; e.shadow_ld = sh16g.ld; e.shadow_lo_scale = kHiLoScale; }      // (hi | lo) halves: the consumer's K is doubled
-    if (consumer_sh.k_form == 2) { e.shadow = shhl.p; e.shadow_ld = shhl.ld; e.shadow_lo_scale = -1.f; }      // HL16 rows
+    if (f == LF_F16_AHILO) { e.shadow = sh16g.p; e.shadow_ld = sh16g.ld; e.shadow_lo_scale = kHiLoScale; }      // (hi | lo) halves: the consumer's K is doubled
+    if (f == LF_X2) { e.shadow = shhl.p; e.shadow_ld = shhl.ld; e.shadow_lo_scale = -1.f; }      // HL16 rows
   };
-  auto sh_of = [&](const Lin& consumer_sh) { return consumer_sh.k_form == 2 ? Act(shhl.p, 2 * shhl.ld, DT_F16) : consumer_sh.k_form == 1 ? sh16g : sh16; };
-  // producers of the shadow: the projections that run the f16 kernels (f16 class or MIX_LINEAR_F16X2), where the selection picks the weights-in-registers kernel
-  auto sh_prod = [&](const Lin& l) { return hl_attn && l.dt == DT_F16; };
+  // the projection behind LayerNorm n: its shadow twin on the shadow the producer left (no LayerNorm launch), or its plain form on a LayerNorm launch
+  // into the operand the form reads.  -> (weights, operand, row statistics of the shadow)
+  struct LnIn { const Lin* w; Act a; const float* stat; };
+  auto ln_in = [&](const Lin& plain, const Lin& sh, LinForm f, const NormW& n, int cls) {
+    const bool from_sh = have_sh;
+    have_sh = false;
+    if (from_sh) return LnIn{&sh, f == LF_X2 ? Act(shhl.p, 2 * shhl.ld, DT_F16) : f == LF_F16_AHILO ? sh16g : sh16, shst};
+    if (f == LF_F16_WHILO || f == LF_F16_AHILO) {
+      run_layernorm(ex, n, t, (int)M, ln16x2, f == LF_F16_AHILO ? -kHiLoScale : 1.0f / kHiLoScale);
+      return LnIn{&plain, ln16x2, nullptr};
+    }
+    run_layernorm(ex, n, t, (int)M, f == LF_F16 ? ln16 : ln);
+    demote_lo(ex, cls, ln, M, C);
+    return LnIn{&plain, f == LF_F16 ? ln16 : x2op(f, ln), nullptr};
+  };
   // the f16 GEGLU kernels store an HL16 output through the LDS-staged epilogue of the wide / pipelined tiles -- the kernels every SDXL shape runs on
   // (M = 2048 ... 32768).  Small token counts (tiny test nets: M < 256) run on other tiles; they take the form the F16_F32RES engine
   // runs at every size -- f16 output -- and widen it.
   const bool gg_direct = M >= 256;
   Act gg16;
-  if ((mix_geglu && !gg_direct) || mix_ff) gg16 = ex.alloc(M, 4 * C, DT_F16);      // (an f16 FF-out reads the GEGLU output as f16, whichever kernel wrote it)
+  if ((f16_in(pl.geglu) && !gg_direct) || pl.ff == LF_F16) gg16 = ex.alloc(M, 4 * C, DT_F16);      // (an f16 FF-out reads the GEGLU output as f16, whichever kernel wrote it)
   void* kh = hl_attn && !hl_direct ? ex.act->alloc(M * (size_t)C * 4) : nullptr;
   void* vth = hl_attn && !hl_direct ? ex.act->alloc((size_t)B * C * npad * 4) : nullptr;
   if (fuse_ln_) {
@@ -565,19 +604,12 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   } else
   for (size_t j = 0; j < w.blocks.size(); ++j) {
     const TBlockW& b = w.blocks[j];
-    Epi eq; eq.n_split = 2 * C; eq.Ct = mix_attn ? vt16 : vt; eq.ct_rows = C; eq.ct_ld = npad; eq.rpb = HW; eq.cls = DM_QKV;
-    if (have_sh && b.qkv_sh.cs) {      // the previous block's FF-out left f16(t o gamma1) and the row statistics: no LayerNorm launch
-      eq.ln_stat = shst;
-      run_linear(ex, b.qkv_sh, sh_of(b.qkv_sh), (int)M, mix_attn ? qk16 : qk, eq);
-    } else {
-    run_layernorm(ex, b.n1, t, (int)M, mix_qkv ? ln16 : ln);
-    demote_lo(ex, DM_QKV, ln, M, C);
-    run_linear(ex, b.qkv, mix_qkv ? ln16 : x2op(b.qkv, ln, C), (int)M, mix_attn ? qk16 : qk, eq);
-    }
-    have_sh = false;
-    if (mix_attn) {
+    const LnIn iq = ln_in(b.qkv, b.qkv_sh, pl.qkv, b.n1, DM_QKV);
+    Epi eq; eq.n_split = 2 * C; eq.Ct = pl.attn_f16 ? vt16 : vt; eq.ct_rows = C; eq.ct_ld = npad; eq.rpb = HW; eq.cls = DM_QKV; eq.ln_stat = iq.stat;
+    run_linear(ex, *iq.w, iq.a, (int)M, pl.attn_f16 ? qk16 : qk, eq);
+    if (pl.attn_f16) {
       attention(ex, qk16, qk16.cols(C), vt16, npad, ao16, B, w.heads, HW, HW);
-      if (!ex.dry && !mix_out1) launch_f16_to_hl(ao16.p, ao16.ld, ao.p, ao.ld, M, C, ex.s);
+      if (!ex.dry && pl.out1 != LF_F16) launch_f16_to_hl(ao16.p, ao16.ld, ao.p, ao.ld, M, C, ex.s);
     }
     else if (hl_attn && hl_direct) {     // q | k and V^T are HL16; the attention writes the out-projection's operand
       demote_lo(ex, DM_ATTN, qk, M, 2 * C);
@@ -594,85 +626,40 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
     else attention(ex, qk, qk.cols(C), vt, npad, ao, B, w.heads, HW, HW);
     Epi er; er.R = t; er.rpb = HW; er.cls = DM_OUT;
     demote_lo(ex, DM_OUT, ao, M, C);
-    { Epi e1 = er; if (sh_prod(b.out1)) want_shadow(e1, b.q2_sh, b.n2); run_linear(ex, b.out1, mix_out1 ? ao16 : x2op(b.out1, ao, C), (int)M, t, e1); }
-    if (have_sh && b.q2_sh.cs) {       // f16 query projection on the shadow the out-projection left; fp32 q for the split-operand attention
-      Epi e2q; e2q.cls = DM_XATTN; e2q.rpb = HW; e2q.ln_stat = shst;
-      if (mix_xs || x2_xs) {
-        e2q.xa_k = kv_xa(si, j); e2q.xa_k_lo = kv_xa_lo(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
-        run_linear(ex, b.q2_sh, sh_of(b.q2_sh), (int)M, mix_xs ? ao2_16 : ao, e2q);
-      } else {
-      const Act& qo = x2_q2 ? q : q32;
-      run_linear(ex, b.q2_sh, sh_of(b.q2_sh), (int)M, qo, e2q);
-      attention_hl(ex, qo, kv_k(si, j), C, kv_vt(si, j), vt_ld_ctx_, mix_out2 ? ao2_16 : ao, B, w.heads, HW, n_ctx_, DM_XATTN);
-      }
+    // (producers of the shadow: the projections that run the f16 kernels -- f16 or X2 -- where the selection picks the weights-in-registers kernel)
+    { Epi e1 = er; if (pl.out1 != LF_NATIVE) want_shadow(e1, pl.q2_sh, pl.q2, b.n2); run_linear(ex, b.out1, pl.out1 == LF_F16 ? ao16 : x2op(pl.out1, ao), (int)M, t, e1); }
+    // cross-attention
+    const LnIn i2 = ln_in(b.q2, b.q2_sh, pl.q2, b.n2, DM_XATTN);
+    Epi e2q; e2q.cls = DM_XATTN; e2q.ln_stat = i2.stat;
+    if (xa_fused) {      // the projection's waves run the 77-key attention on their own q tiles (hi / lo context images at split precision)
+      e2q.rpb = HW; e2q.xa_k = kv_xa(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
+      if (pl.xattn == XA_SPLIT) e2q.xa_k_lo = kv_xa_lo(si, j);
+      run_linear(ex, *i2.w, i2.a, (int)M, ao2, e2q);
     } else {
-    run_layernorm(ex, b.n2, t, (int)M, mix_q2 ? ln16 : ln);
-    demote_lo(ex, DM_XATTN, ln, M, C);
-    if (mix_q2 && !mix_xa && !mix_q2_widen) {
-      if (mix_xs) {
-        Epi e2q; e2q.cls = DM_XATTN; e2q.rpb = HW;
-        e2q.xa_k = kv_xa(si, j); e2q.xa_k_lo = kv_xa_lo(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
-        run_linear(ex, b.q2, ln16, (int)M, ao2_16, e2q);
-      } else {
-      { Epi e2q; e2q.cls = DM_XATTN; e2q.rpb = HW; run_linear(ex, b.q2, ln16, (int)M, q32, e2q); }
-      attention_hl(ex, q32, kv_k(si, j), C, kv_vt(si, j), vt_ld_ctx_, mix_out2 ? ao2_16 : ao, B, w.heads, HW, n_ctx_, DM_XATTN);
-      }
-    } else
-    if (mix_xa) {
-      Epi e2q; e2q.rpb = HW; e2q.cls = DM_XATTN;
-      e2q.xa_k = kv_xa(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
-      run_linear(ex, b.q2, ln16, (int)M, ao2_16, e2q);
-    } else if (mix_q2) {
-      { Epi e2q; e2q.cls = DM_XATTN; run_linear(ex, b.q2, ln16, (int)M, ao2_16, e2q); }
-      if (!ex.dry) {
+      const bool to_q32 = pl.q2 == LF_F16 && !q2_widen;
+      const Act& qo = to_q32 ? q32 : q;
+      if (i2.stat || to_q32) e2q.rpb = HW;      // (the other forms' launches select their kernel on the whole batch's rows)
+      run_linear(ex, *i2.w, i2.a, (int)M, q2_widen ? ao2_16 : qo, e2q);
+      if (q2_widen && !ex.dry) {
         if (q.dt == DT_HL) launch_f16_to_hl(ao2_16.p, ao2_16.ld, q.p, q.ld, M, C, ex.s);
         else launch_copy_rows(ao2_16.p, DT_F16, ao2_16.ld, q.p, q.dt, q.ld, (int)M, C, ex.s);
       }
-      attention_hl(ex, q, kv_k(si, j), C, kv_vt(si, j), vt_ld_ctx_, ao2_16, B, w.heads, HW, n_ctx_, DM_XATTN);
-    } else if (xattn) {
-      Epi e2q; e2q.rpb = HW; e2q.cls = DM_XATTN;
-      e2q.xa_k = kv_xa(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
-      run_linear(ex, b.q2, ln, (int)M, ao, e2q);
-    } else if (x2_xs) {     // fp32-class projection on the f16 kernel (HL16 operand read as f16) with the split-precision attention in its epilogue: HL16 rows for the out-projection
-      Epi e2q; e2q.rpb = HW; e2q.cls = DM_XATTN;
-      e2q.xa_k = kv_xa(si, j); e2q.xa_k_lo = kv_xa_lo(si, j); e2q.xa_nctx = n_ctx_; e2q.xa_scale = 0.125f;
-      run_linear(ex, b.q2, x2op(b.q2, ln, C), (int)M, ao, e2q);
-    } else {
-      { Epi e2q; e2q.cls = DM_XATTN; run_linear(ex, b.q2, x2op(b.q2, ln, C), (int)M, q, e2q); }
-      demote_lo(ex, DM_XATTN, q, M, C);
-      if (hl_attn) attention_hl(ex, q, kv_k(si, j), C, kv_vt(si, j), vt_ld_ctx_, mix_out2 ? ao2_16 : ao, B, w.heads, HW, n_ctx_, DM_XATTN);   // caches are HL16 (set_context)
-      else attention(ex, q, Act(kv_k(si, j), C, adt), kv_vt(si, j), vt_ld_ctx_, ao, B, w.heads, HW, n_ctx_);
+      if (!i2.stat && pl.q2 != LF_F16) demote_lo(ex, DM_XATTN, q, M, C);
+      if (hl_attn) attention_hl(ex, qo, kv_k(si, j), C, kv_vt(si, j), vt_ld_ctx_, ao2, B, w.heads, HW, n_ctx_, DM_XATTN);   // caches are HL16 (set_context)
+      else attention(ex, qo, Act(kv_k(si, j), C, adt), kv_vt(si, j), vt_ld_ctx_, ao, B, w.heads, HW, n_ctx_);
     }
-    }
-    have_sh = false;
     demote_lo(ex, DM_OUT, ao, M, C);
-    { Epi e2 = er; if (sh_prod(b.out2)) want_shadow(e2, b.geglu_sh, b.n3); run_linear(ex, b.out2, mix_out2 ? ao2_16 : x2op(b.out2, ao, C), (int)M, t, e2); }
-    Epi eg; eg.act = 1; eg.cls = DM_GEGLU;
-    const bool gg_sh = have_sh && b.geglu_sh.cs;      // GEGLU projection on the shadow the cross-attention's out-projection left: no LayerNorm launch
-    if (gg_sh) eg.ln_stat = shst;
-    else if (gg_hilo) run_layernorm(ex, b.n3, t, (int)M, ln16x2, (mix_ & MIX_GEGLU_AHILO) ? -kHiLoScale : 1.0f / kHiLoScale);
-    else {
-    run_layernorm(ex, b.n3, t, (int)M, mix_geglu ? ln16 : ln);
-    demote_lo(ex, DM_GEGLU, ln, M, C);
-    }
-    have_sh = false;
-    if (gg_sh) {
-      eg.rpb = HW;
-      const Act shg = sh_of(b.geglu_sh);
-      if (mix_ff) run_linear(ex, b.geglu_sh, shg, (int)M, gg16, eg);
-      else if (!gg_direct) { run_linear(ex, b.geglu_sh, shg, (int)M, gg16, eg); if (!ex.dry) launch_f16_to_hl(gg16.p, gg16.ld, gg.p, gg.ld, M, 4 * C, ex.s); }
-      else run_linear(ex, b.geglu_sh, shg, (int)M, gg, eg);
-    } else
-    if (mix_ff) {
-      run_linear(ex, b.geglu, gg_hilo ? ln16x2 : mix_geglu ? ln16 : ln, (int)M, gg16, eg);         // f16 output for the f16 FF-out (f16 or split-operand GEGLU compute)
-    } else if (mix_geglu && !gg_direct) {
-      run_linear(ex, b.geglu, gg_hilo ? ln16x2 : ln16, (int)M, gg16, eg);
-      if (!ex.dry) launch_f16_to_hl(gg16.p, gg16.ld, gg.p, gg.ld, M, 4 * C, ex.s);
-    } else
-    run_linear(ex, b.geglu, gg_hilo ? ln16x2 : mix_geglu ? ln16 : x2op(b.geglu, ln, C), (int)M, gg, eg);
+    { Epi e2 = er; if (pl.out2 != LF_NATIVE) want_shadow(e2, pl.geglu_sh, pl.geglu, b.n3); run_linear(ex, b.out2, pl.out2 == LF_F16 ? ao2_16 : x2op(pl.out2, ao), (int)M, t, e2); }
+    // feed-forward
+    const LnIn ig = ln_in(b.geglu, b.geglu_sh, pl.geglu, b.n3, DM_GEGLU);
+    Epi eg; eg.act = 1; eg.cls = DM_GEGLU; eg.ln_stat = ig.stat;
+    if (ig.stat) eg.rpb = HW;
+    const bool gg_widen = pl.ff != LF_F16 && !gg_direct && (ig.stat || f16_in(pl.geglu));
+    run_linear(ex, *ig.w, ig.a, (int)M, pl.ff == LF_F16 || gg_widen ? gg16 : gg, eg);
+    if (gg_widen && !ex.dry) launch_f16_to_hl(gg16.p, gg16.ld, gg.p, gg.ld, M, 4 * C, ex.s);
     demote_lo(ex, DM_FF, gg, M, 4 * C);
     er.cls = DM_FF;
-    { Epi ef = er; if (sh_prod(b.ff) && j + 1 < w.blocks.size()) want_shadow(ef, w.blocks[j + 1].qkv_sh, w.blocks[j + 1].n1); run_linear(ex, b.ff, mix_ff ? gg16 : x2op(b.ff, gg, 4 * C), (int)M, t, ef); }
+    { Epi ef = er; if (pl.ff != LF_NATIVE && j + 1 < w.blocks.size()) want_shadow(ef, pl.qkv_sh, pl.qkv, w.blocks[j + 1].n1); run_linear(ex, b.ff, pl.ff == LF_F16 ? gg16 : x2op(pl.ff, gg), (int)M, t, ef); }
   }
   Epi eo; eo.R = x; eo.rpb = HW; eo.cls = DM_CONV_PROJ;
   run_linear(ex, w.proj_out, hl_op(ex, w.proj_out, t, M, C, DM_CONV_PROJ, B), (int)M, x, eo);
@@ -815,7 +802,7 @@ void UNet::ensure_plan(int B, int H, int W) {
     ebias_ = (float*)act_.alloc((size_t)B * emb_total_ * sizeof(float));
     gn_partial_ = (float*)act_.alloc(groupnorm_workspace_floats(B, 32) * sizeof(float));
     tconv_ = (float*)act_.alloc(8 * sizeof(float));
-    if (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16)) {   // cross-workgroup key split of the (f16) self-attention: workspace + tickets per chain, sized for the largest level
+    if (attn16_) {   // cross-workgroup key split of the (f16) self-attention: workspace + tickets per chain, sized for the largest level
       size_t wsb = 0, cnt = 0;
       { int h = H, w = W;
         for (size_t lv = 0; lv < cfg_.channel_mults.size(); ++lv) {
@@ -877,7 +864,7 @@ void UNet::ensure_plan(int B, int H, int W) {
   act_.off = 0; act_.peak = 0;
   persist();
   for (int c = 0; c < 2; ++c) if (skcnt_[c]) SDXL_HIP(hipMemset(skcnt_[c], 0, kSplitkCounters * sizeof(unsigned)));   // armed once
-  for (int c = 0; c < (split ? 2 : 1); ++c) if (attn_xcnt_[c] && (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16))) SDXL_HIP(hipMemset(attn_xcnt_[c], 0, attn_xcnt_bytes_));
+  for (int c = 0; c < (split ? 2 : 1); ++c) if (attn_xcnt_[c] && attn16_) SDXL_HIP(hipMemset(attn_xcnt_[c], 0, attn_xcnt_bytes_));
 }
 
 void* UNet::unet_in(int B, int H, int W) { ensure_plan(B, H, W); return in_; }
@@ -887,7 +874,7 @@ void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStr
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before forward");
   Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.demote = demote_mask_;
   ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
-  if (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16)) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
+  if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
   // weight warming (f16 engine, batched chain): the plan's first forward records the GEMM sequence, every later one replays it
   const bool warming = cdt_ == DT_F16 && !plan_split_ && igemm_warm_enabled();
   if (warming) { ex.warm = &warm_; if (!warm_.ready) { warm_.seq.clear(); warm_.recording = true; } }
@@ -898,7 +885,7 @@ void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStr
     if (!plan_split_) { run(ex, t_dev, t_stride, 0, B); if (warm_.recording) warm_.finish(); return; }
     Exec e2; e2.s = s2_; e2.cdt = cdt_; e2.sdt = sdt_; e2.act = &act2_; e2.demote = demote_mask_;
     e2.splitk_ws = skws_[1]; e2.splitk_ws_bytes = skws_bytes_; e2.splitk_cnt = skcnt_[1];
-    if (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16)) { e2.attn_xws = attn_xws_[1]; e2.attn_xcnt = attn_xcnt_[1]; }
+    if (attn16_) { e2.attn_xws = attn_xws_[1]; e2.attn_xcnt = attn_xcnt_[1]; }
     act2_.off = 0;
     ex.fork_ev = ev_fork_; ex.fork_after = split_offset_; ex.launches = 0;
     if (ex.fork_after <= 0) SDXL_HIP(hipEventRecord(ev_fork_, s));
@@ -949,7 +936,7 @@ void UNet::profile(int B, int H, int W, float ms[Profiler::NCLS], int launches[P
   Profiler prof;
   Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.prof = &prof; ex.demote = demote_mask_;
   ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
-  if (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16)) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
+  if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
   const size_t m = act_.mark();
   run(ex, tconv_, 1, 0, B);   // always the batched chain: per-launch events need one stream
   act_.reset(m);
@@ -970,7 +957,7 @@ float UNet::eager_ms(int B, int H, int W, hipStream_t s) {
   for (int rep = 0; rep < 3; ++rep) {
     Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.demote = demote_mask_;
     ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
-    if (cdt_ == DT_F16 || (mix_ & MIX_ATTN_F16)) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
+    if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
     const size_t m = act_.mark();
     SDXL_HIP(hipEventRecord(a, s));
     run(ex, tconv_, 1, 0, B);

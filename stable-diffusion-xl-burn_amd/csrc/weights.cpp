@@ -436,20 +436,24 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
   p.stat_out = e.stat_out; p.stat_slots = w.N / 64;
   p.splitk_ws = ex.splitk_ws; p.splitk_ws_bytes = ex.splitk_ws_bytes; p.splitk_cnt = ex.splitk_cnt; p.splitk = 0;
   p.xa_k = e.xa_k; p.xa_nctx = e.xa_nctx; p.xa_scale = e.xa_scale; p.xa_k_lo = e.xa_k_lo;
+  p.acc_scale = w.acc_scale;
+  p.a_scale = (w.dt >= 0 ? w.dt : ex.cdt) == DT_HL ? a.a_scale : nullptr;
+  p.a_scale_rpb = (p.a_scale && a.a_scale_n > 1) ? p.M / a.a_scale_n : 0;      // (M = entries x output rows per entry)
+  // GroupNorm statistics of the output from this GEMM's epilogue -- only when the kernel the selection picks anyway can do it
+  p.gn_part = nullptr;
+  {
+    const int wdt_ = w.dt >= 0 ? w.dt : ex.cdt;      // (f16 engines; round 6: the split-operand convolutions that run the 256x128 split-K kernel)
+    if (e.gn_part && (wdt_ == DT_F16 || wdt_ == DT_HL) && wdt_ == ex.cdt) { p.gn_part = e.gn_part; if (!igemm_gn_part_ok(p)) p.gn_part = nullptr; }
+  }
   // f16 shadow of an fp32 output (+ its row statistics) for the GEMM behind the next LayerNorm: only where the selection picks the
-  // weights-in-registers kernel anyway; otherwise neither is written and the caller runs the LayerNorm launch
+  // weights-in-registers kernel anyway; otherwise neither is written and the caller runs the LayerNorm launch.  (Decided on the filled
+  // parameters: the selection looks at the scales and gn_part too.)
   if (e.shadow_done) *e.shadow_done = false;
   if (e.shadow) {
     p.shadow = e.shadow; p.shadow_ld = e.shadow_ld; p.shadow_gamma = e.shadow_gamma; p.shadow_lo_scale = e.shadow_lo_scale;
     const bool ok = (w.dt >= 0 ? w.dt : ex.cdt) == DT_F16 && igemm_wreg_selected(p);
     if (!ok) { p.shadow = nullptr; p.shadow_gamma = nullptr; p.stat_out = nullptr; p.shadow_lo_scale = 0.f; }
     if (e.shadow_done) *e.shadow_done = ok;
-  }
-  // GroupNorm statistics of the output from this GEMM's epilogue -- only when the kernel the selection picks anyway can do it
-  p.gn_part = nullptr;
-  {
-    const int wdt_ = w.dt >= 0 ? w.dt : ex.cdt;      // (f16 engines; round 6: the split-operand convolutions that run the 256x128 split-K kernel)
-    if (e.gn_part && (wdt_ == DT_F16 || wdt_ == DT_HL) && wdt_ == ex.cdt) { p.gn_part = e.gn_part; if (!igemm_gn_part_ok(p)) p.gn_part = nullptr; }
   }
   SDXL_REQUIRE(!e.xa_k || igemm_xattn_ok(a.dt, out.dt, p.M, p.N, p.K, p.rpb, e.xa_nctx), "fused cross-attention: unsupported shape");
   SDXL_REQUIRE(!e.ln_stat || (w.ln_k ? w.ln_k : w.K) % 64 == 0, "LayerNorm-folded GEMM needs K % 64 == 0");
@@ -458,9 +462,6 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
   SDXL_REQUIRE(!w.cs || e.ln_stat, "LayerNorm-folded weight used without row statistics");
   SDXL_REQUIRE(!((w.dt >= 0 ? w.dt : ex.cdt) == DT_F32 && a.dt != DT_F32), "f32 compute needs f32 activations");
   if (ex.prof) ex.prof->begin(Profiler::IGEMM, 2.0 * p.M * (double)p.N * p.K, ex.s, p.M, p.N, p.K, p.ksize, e.cls);
-  p.acc_scale = w.acc_scale;
-  p.a_scale = (w.dt >= 0 ? w.dt : ex.cdt) == DT_HL ? a.a_scale : nullptr;
-  p.a_scale_rpb = (p.a_scale && a.a_scale_n > 1) ? p.M / a.a_scale_n : 0;      // (M = entries x output rows per entry)
   if (ex.warm && (w.dt >= 0 ? w.dt : ex.cdt) == DT_F16) {
     // weight warming: the plan's first forward records which weights every launch reads and whether its kernel has idle CUs to host
     // warming workgroups; later forwards hand launch i the weights of a later launch (WarmSeq::finish)

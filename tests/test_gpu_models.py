@@ -345,9 +345,18 @@ def test_f16w_mode_falls_back_on_parameters_that_are_not_f16_values(pkg, ctx):
     specs = pkg.unet_param_specs(cfg)
     W16 = {k: (v if k.endswith(".eps") else v.half().float()).numpy().copy() for k, v in unet_weights(ocfg).items()}
     assert pkg.UNet(ctx, cfg, 5, weights=pkg.flatten_weights(specs, W16)).mix_classes() == F16W_CLASSES
-    name = next(k for k in W16 if k.endswith(".mlp.lin.weight"))
-    W16[name].flat[3] = np.float32(W16[name].flat[3]) * np.float32(1.0 + 2.0 ** -16)      # one value that is not an f16
-    assert pkg.UNet(ctx, cfg, 5, weights=pkg.flatten_weights(specs, W16)).mix_classes() == MIX_CLASSES
+    def perturbed(suffix):      # the f16 weights with one value of the first `suffix` tensor that is not an f16
+        W = {k: v.copy() for k, v in W16.items()}
+        name = next(k for k in W if k.endswith(suffix))
+        W[name].flat[3] = np.float32(W[name].flat[3]) * np.float32(1.0 + 2.0 ** -16)
+        return pkg.flatten_weights(specs, W)
+    assert pkg.UNet(ctx, cfg, 5, weights=perturbed(".mlp.lin.weight")).mix_classes() == MIX_CLASSES
+    # the guard checks what the planned forms round: attn1 Q/K/V are f16 values under dtype 5 (f16 QKV) and under dtype 7 (their HL16-interleaved
+    # shadow form: the tiny net's C = 256 / 512 qualifies), which then falls back to plain F32_SPLIT
+    assert pkg.UNet(ctx, cfg, 5, weights=perturbed(".attn1.query.weight")).mix_classes() == MIX_CLASSES
+    u7, u3 = pkg.UNet(ctx, cfg, 7, weights=perturbed(".attn1.query.weight")), pkg.UNet(ctx, cfg, 3, weights=perturbed(".attn1.query.weight"))
+    assert u7.mix_classes() == 0
+    assert torch.equal(u7.forward(x, t, c, y), u3.forward(x, t, c, y))
     for dt in (0, 1, 2, 3):
         assert pkg.UNet(ctx, cfg, dt, seed=0).mix_classes() == 0
 
