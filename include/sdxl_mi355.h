@@ -345,6 +345,25 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
                                   const float* wq, const float* k, const float* v, int B, int Nq, int Nk, int C, int fused,
                                   float* out);
 
+/* forms of a transformer projection on the split-operand UNet (SDXL_DTYPE_F32_SPLIT_MIX* / _F16W): NATIVE = (hi, lo) operands, three MFMAs
+ * per product; F16 = f16 activations x f16 weights; F16_WHILO = f16 activations x (hi | lo) weight halves along a doubled K; F16_AHILO = (hi | lo)
+ * activation halves x f16 weights; X2 = HL16 activations x the f16 weight packed twice in the HL16 interleave */
+enum { SDXL_FORM_NATIVE = 0, SDXL_FORM_F16 = 1, SDXL_FORM_F16_WHILO = 2, SDXL_FORM_F16_AHILO = 3, SDXL_FORM_X2 = 4 };
+/* the LayerNorm-fed projections of a transformer block: attn1 QKV (fused along N), attn2 query, the GEGLU projection */
+enum { SDXL_PROJ_QKV = 0, SDXL_PROJ_QUERY = 1, SDXL_PROJ_GEGLU = 2 };
+/* One LayerNorm-fed projection of a split-operand UNet transformer block in a given form, run by the UNet's own code.  B entries of rows_per_entry rows
+ * (M = B x rows_per_entry), C channels; fp32 device tensors.
+ *   producer (producer_form >= 0: SDXL_FORM_NATIVE, _F16 or _X2): t = r + a[M,Kp] @ wp[Kp,C] + bp, the out-projection / FF-out that writes the residual
+ *   stream; producer_form < 0: t = r (a, wp, bp unused).
+ *   consumer: LayerNorm(t; gamma, beta, eps) @ w[C,N] + b (b may be NULL), GEGLU for SDXL_PROJ_GEGLU (out [M, N/2], else [M, N]).
+ *   shadow != 0: the producer is asked for the LayerNorm shadow (MIX_LN_SHADOW) and the consumer runs its shadow twin where the producer's kernel left
+ *   it, otherwise the LayerNorm launch and the plain form.  *shadow_taken (may be NULL): whether the shadow was taken.  t_out (may be NULL): t.
+ * Arguments outside what the form supports (C or N % 32 != 0, X2 with N % 128 != 0, AHILO / X2 on weights that are not f16 values, a shadow with
+ * C % 64 != 0 or without an F16 / X2 producer, ...) return SDXL_ERR_INVALID. */
+int sdxl_transformer_projection(sdxl_ctx* ctx, void* stream, int B, int rows_per_entry, int C, const float* a, const float* wp, const float* bp,
+                                const float* r, int Kp, int producer_form, const float* gamma, const float* beta, float eps, const float* w,
+                                const float* b, int N, int proj, int form, int shadow, float* t_out, float* out, int* shadow_taken);
+
 /* conv3x3 (pad 1, optional residual) -> GroupNorm (+SiLU): the conv -> norm pairs of ResBlock::forward (src/model/unet/mod.rs:
  * 1082-1106) and of the SpatialTransformer entry (:820-845), f16 engine arithmetic.  x [B,Cin,H,W], weight [Cout,Cin,3,3],
  * residual / out [B,Cout,H,W]; fp32 device tensors.  fused != 0: the convolution's epilogue leaves the GroupNorm statistics

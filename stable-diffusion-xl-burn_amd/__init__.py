@@ -84,6 +84,7 @@ ABI_SYMBOLS = [
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
     "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule",
     "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
+    "sdxl_transformer_projection",
     "sdxl_clip_config_clip_l", "sdxl_clip_config_open_clip_bigg", "sdxl_clip_param_count", "sdxl_clip_param_spec",
     "sdxl_clip_create", "sdxl_clip_create_synthetic", "sdxl_clip_destroy", "sdxl_clip_forward_hidden",
     "sdxl_clip_forward_hidden_pooled", "sdxl_conditioning_embedding", "sdxl_clip_weight_arena",
@@ -912,6 +913,52 @@ def conv2d_group_norm(ctx: Context, x, weight, bias, gamma, beta, eps: float = 1
                                        int(W), Cout, int(n_group), int(silu), int(fused), ctypes.byref(took),
                                        ctypes.c_void_p(out.data_ptr())))
     return out, bool(took.value)
+
+
+FORM_NATIVE, FORM_F16, FORM_F16_WHILO, FORM_F16_AHILO, FORM_X2 = 0, 1, 2, 3, 4   # include/sdxl_mi355.h SDXL_FORM_*
+PROJ_QKV, PROJ_QUERY, PROJ_GEGLU = 0, 1, 2                                      # include/sdxl_mi355.h SDXL_PROJ_*
+
+
+class InvalidArgument(EngineError):
+    """SDXL_ERR_INVALID: arguments outside what the entry supports"""
+
+
+def transformer_projection(ctx: Context, r, gamma, beta, weight, bias, proj: int, form: int, eps: float = 1e-5, shadow: bool = False,
+                           producer=None, batch: int = 1):
+    """One LayerNorm-fed projection of a split-operand UNet's transformer block in form `form` (FORM_*), through the UNet's own code
+    (sdxl_transformer_projection).  r [M, C] fp32 (M = batch x rows per entry); producer = (a [M, Kp], wp [Kp, C], bp [C] or None, form) adds
+    a @ wp + bp to r the way an out-projection / FF-out writes the residual stream t; shadow=True asks that producer for the LayerNorm shadow.
+    Returns (out [M, N] or [M, N/2] for PROJ_GEGLU, t [M, C], shadow_taken).  Unsupported arguments raise InvalidArgument."""
+    torch = _torch()
+    r, pr = _dev(r)
+    gamma, pg = _dev(gamma)
+    beta, pbeta = _dev(beta)
+    weight, pw = _dev(weight)
+    pb = None
+    if bias is not None:
+        bias, pb = _dev(bias)
+    M, C = r.shape
+    N = int(weight.shape[1])
+    pa = pwp = pbp = None
+    Kp, pform = 0, -1
+    if producer is not None:
+        a, wp, bp, pform = producer
+        a, pa = _dev(a)
+        wp, pwp = _dev(wp)
+        if bp is not None:
+            bp, pbp = _dev(bp)
+        Kp = int(wp.shape[0])
+    assert M % batch == 0
+    out = torch.empty((M, N // 2 if proj == PROJ_GEGLU else N), device=r.device, dtype=torch.float32)
+    t = torch.empty((M, C), device=r.device, dtype=torch.float32)
+    took = ctypes.c_int(0)
+    rc = lib().sdxl_transformer_projection(ctx.h, _stream(), int(batch), int(M // batch), int(C), pa, pwp, pbp, pr, Kp, int(pform), pg, pbeta,
+                                           ctypes.c_float(eps), pw, pb, N, int(proj), int(form), int(shadow), ctypes.c_void_p(t.data_ptr()),
+                                           ctypes.c_void_p(out.data_ptr()), ctypes.byref(took))
+    if rc == 1:
+        raise InvalidArgument(lib().sdxl_last_error().decode())
+    _check(rc)
+    return out, t, bool(took.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------- multi-GPU

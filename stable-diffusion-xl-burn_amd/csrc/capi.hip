@@ -1260,6 +1260,128 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
   API_END
 }
 
+int sdxl_transformer_projection(sdxl_ctx* ctx, void* stream, int B, int rows_per_entry, int C, const float* a, const float* wp, const float* bp,
+                                const float* r, int Kp, int producer_form, const float* gamma, const float* beta, float eps, const float* w,
+                                const float* b, int N, int proj, int form, int shadow, float* t_out, float* out, int* shadow_taken) {
+  // one LayerNorm-fed projection of a split-operand UNet's transformer block in a named form (plan_transformer), through the code
+  // UNet::spatial_transformer runs: pack_proj, alloc_ln_operands, want_ln_shadow, ln_input.  The producer (an out-projection / FF-out) adds into the
+  // fp32 stream t in place and, with `shadow`, is asked for the shadow of LayerNorm(t) exactly as the UNet asks it.
+  API_BEGIN
+  SDXL_REQUIRE(ctx && r && gamma && beta && w && out, "null argument");
+  if (B < 1 || rows_per_entry < 1 || C < 32 || C % 32 != 0 || N < 1) return fail(SDXL_ERR_INVALID, "transformer projection: B, rows >= 1, C % 32 == 0");
+  if (proj < SDXL_PROJ_QKV || proj > SDXL_PROJ_GEGLU || form < SDXL_FORM_NATIVE || form > SDXL_FORM_X2 || producer_form > SDXL_FORM_X2)
+    return fail(SDXL_ERR_INVALID, "transformer projection: unknown projection or form");
+  const LinForm f = (LinForm)form, pf = producer_form < 0 ? LF_NATIVE : (LinForm)producer_form;
+  const bool geglu = proj == SDXL_PROJ_GEGLU, has_p = producer_form >= 0;
+  const int parts = proj == SDXL_PROJ_QKV ? 3 : 1;
+  // what plan_transformer lets each form take (anything else would compute wrong numbers, not fail)
+  if (N % (32 * parts) != 0) return fail(SDXL_ERR_INVALID, "transformer projection: N % 32 == 0 per projection");
+  if ((f == LF_F16_WHILO || f == LF_F16_AHILO) && !geglu) return fail(SDXL_ERR_INVALID, "transformer projection: the (hi | lo) forms are GEGLU forms");
+  if (f == LF_X2 && (N / parts % 128 != 0 || (geglu && N % 640 != 0))) return fail(SDXL_ERR_INVALID, "transformer projection: X2 needs N % 128 == 0 (GEGLU: N % 640 == 0)");
+  if (f == LF_X2 && proj == SDXL_PROJ_QKV && !shadow) return fail(SDXL_ERR_INVALID, "transformer projection: the X2 QKV projection exists only as a shadow-form pair");
+  if (has_p && (!a || !wp || Kp < 32 || Kp % 32 != 0)) return fail(SDXL_ERR_INVALID, "transformer projection: a producer needs its operand, its weight and K % 32 == 0");
+  if (has_p && pf == LF_X2 && (Kp % 32 != 0 || C % 128 != 0)) return fail(SDXL_ERR_INVALID, "transformer projection: an X2 producer needs K % 32 == 0 and C % 128 == 0");
+  if (has_p && (pf == LF_F16_WHILO || pf == LF_F16_AHILO)) return fail(SDXL_ERR_INVALID, "transformer projection: producers run NATIVE, F16 or X2");
+  if (shadow && (!has_p || pf == LF_NATIVE || C % 64 != 0 || !(f == LF_F16 || f == LF_F16_AHILO || f == LF_X2)))
+    return fail(SDXL_ERR_INVALID, "transformer projection: a shadow needs an F16 / X2 producer, C % 64 == 0 and an F16, AHILO or X2 consumer");
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  const size_t M = (size_t)B * rows_per_entry;
+  const int Np = N / parts;
+  // parameters: producer, LayerNorm, consumer (QKV: three projections fused along N, as the UNet packs attn1.query / key / value)
+  std::vector<ParamSpec> specs;
+  auto add = [&](const std::string& n, std::vector<int> shape, int kind) { ParamSpec p; p.name = n; p.shape = shape; p.kind = kind; specs.push_back(p); };
+  if (has_p) { add("prod.weight", {Kp, C}, PK_LINEAR_W); add("prod.bias", {C}, PK_BIAS); }
+  add("norm.gamma", {C}, PK_GAMMA); add("norm.beta", {C}, PK_BETA); add("norm.eps", {1}, PK_EPS);
+  std::vector<std::string> names;
+  for (int i = 0; i < parts; ++i) {
+    names.push_back("p" + std::to_string(i));
+    add(names.back() + ".weight", {C, Np}, PK_LINEAR_W); add(names.back() + ".bias", {Np}, PK_BIAS);
+  }
+  Tmp tmp;
+  size_t nflat = 0;
+  for (const ParamSpec& p : specs) nflat += p.numel();
+  float* flat = (float*)tmp.get(nflat * sizeof(float));
+  {
+    float* d = flat;
+    auto put = [&](const float* src, size_t n) {
+      if (src) SDXL_HIP(hipMemcpyAsync(d, src, n * sizeof(float), hipMemcpyDefault, s)); else SDXL_HIP(hipMemsetAsync(d, 0, n * sizeof(float), s));
+      d += n;
+    };
+    if (has_p) { put(wp, (size_t)Kp * C); put(bp, C); }
+    put(gamma, C); put(beta, C);
+    SDXL_HIP(hipMemcpyAsync(d, &eps, sizeof(float), hipMemcpyHostToDevice, s)); d += 1;
+    for (int i = 0; i < parts; ++i) {      // columns [i Np, (i + 1) Np) of w
+      SDXL_HIP(hipMemcpy2DAsync(d, (size_t)Np * sizeof(float), w + (size_t)i * Np, (size_t)N * sizeof(float), (size_t)Np * sizeof(float), C, hipMemcpyDefault, s));
+      d += (size_t)C * Np;
+      put(b ? b + (size_t)i * Np : nullptr, Np);
+    }
+  }
+  SDXL_HIP(hipStreamSynchronize(s));
+  FlatSource src(flat, specs);
+  DeviceArena arena;
+  arena.reserve(2 * WeightBuilder::arena_bound(specs, DT_HL) + (1 << 20));
+  WeightBuilder wb(specs, src, arena, DT_HL, s);
+  // the forms that pack the parameter's values as f16 need f16 values (the UNet's create-time guard); LF_F16 rounds them -- that is its class
+  std::vector<std::string> wnames;
+  for (const std::string& nm : names) wnames.push_back(nm + ".weight");
+  if ((f == LF_F16_AHILO || f == LF_X2) && !wb.all_f16_exact(wnames)) return fail(SDXL_ERR_INVALID, "transformer projection: AHILO / X2 need f16-valued weights");
+  if (has_p && pf == LF_X2 && !wb.all_f16_exact({"prod.weight"})) return fail(SDXL_ERR_INVALID, "transformer projection: an X2 producer needs f16-valued weights");
+  const NormW n = wb.norm("norm");
+  Lin plain, sh;
+  plain = pack_proj(wb, f, names, geglu, shadow ? &sh : nullptr, "norm");
+  const Lin lp = has_p ? pack_proj(wb, pf, {"prod"}, false) : Lin();
+  // the UNet's plan for this one projection: its form (+ shadow twin) in its slot
+  StPlan pl;
+  LinForm& slot = proj == SDXL_PROJ_QKV ? pl.qkv : proj == SDXL_PROJ_QUERY ? pl.q2 : pl.geglu;
+  bool& slot_sh = proj == SDXL_PROJ_QKV ? pl.qkv_sh : proj == SDXL_PROJ_QUERY ? pl.q2_sh : pl.geglu_sh;
+  slot = f; slot_sh = shadow != 0;
+  DeviceArena act;
+  act.reserve(M * (size_t)C * 40 + M * (size_t)N * 8 + (size_t)(has_p ? M * Kp * 4 : 0) + (1 << 20));
+  Exec ex; ex.s = s; ex.cdt = DT_HL; ex.sdt = DT_F32; ex.act = &act;
+  ex.splitk_ws_bytes = igemm_splitk_ws_bytes(B, std::max(rows_per_entry, 1024), std::max(N, 1536));
+  ex.splitk_ws = (float*)tmp.get(ex.splitk_ws_bytes);
+  ex.splitk_cnt = (unsigned*)tmp.get(kSplitkCounters * sizeof(unsigned));
+  SDXL_HIP(hipMemsetAsync(ex.splitk_cnt, 0, kSplitkCounters * sizeof(unsigned), s));
+  const Act t = ex.alloc(M, C, DT_F32);
+  launch_copy_rows(r, DT_F32, C, t.p, DT_F32, C, (int)M, C, s);
+  const Act ln = ex.alloc(M, C, DT_HL);
+  LnOperands lo;
+  alloc_ln_operands(ex, pl, M, C, ln, lo);
+  const int cls = proj == SDXL_PROJ_QKV ? DM_QKV : proj == SDXL_PROJ_QUERY ? DM_XATTN : DM_GEGLU;
+  if (has_p) {
+    // the producer's operand as spatial_transformer hands it over: f16 rows (an f16 out-projection), or the un-scaled HL16 rows the attention writes
+    Act pa = ex.alloc(M, Kp, pf == LF_F16 ? DT_F16 : DT_HL);
+    if (pf == LF_F16) launch_copy_rows(a, DT_F32, Kp, pa.p, DT_F16, Kp, (int)M, Kp, s);
+    else launch_f32_to_hl(a, Kp, pa.p, Kp, M, Kp, s);
+    Epi e; e.R = t; e.rpb = rows_per_entry; e.cls = proj == SDXL_PROJ_QKV ? DM_FF : DM_OUT;
+    if (pf != LF_NATIVE) want_ln_shadow(lo, e, shadow != 0, f, n);
+    run_linear(ex, lp, x2_operand(pf, pa), (int)M, t, e);
+  }
+  const LnIn in = ln_input(ex, lo, plain, sh, f, n, t, cls);
+  if (shadow_taken) *shadow_taken = in.stat ? 1 : 0;
+  // the consumer's output rows as the UNet stores them: the GEGLU output HL16 (f16, widened, on small token counts); an f16 QKV projection
+  // writes f16 for the f16 self-attention, an f16 query projection fp32 q; the others HL16 where the attention takes it (else fp32).
+  // (The QKV projection's V^T transposition is not modelled: all 3 C columns are stored as rows.)
+  const int No = geglu ? N / 2 : N;
+  const bool hl_direct = rows_per_entry % 8 == 0 && (2 * C) % 128 == 0;
+  const bool widen = geglu && geglu_widened(f, in, M);
+  const int odt = geglu ? (widen ? DT_F16 : DT_HL) : f == LF_F16 ? (proj == SDXL_PROJ_QKV ? DT_F16 : DT_F32) : hl_direct ? DT_HL : DT_F32;
+  Act o = ex.alloc(M, No, odt);
+  Epi e; e.act = geglu ? 1 : 0; e.ln_stat = in.stat; e.cls = cls;
+  if (proj == SDXL_PROJ_QKV || in.stat || (proj == SDXL_PROJ_QUERY && f == LF_F16)) e.rpb = rows_per_entry;     // (as the UNet's launches select their kernel)
+  run_linear(ex, *in.w, in.a, (int)M, o, e);
+  if (widen) {
+    const Act o2 = ex.alloc(M, No, DT_HL);
+    launch_f16_to_hl(o.p, o.ld, o2.p, o2.ld, M, No, s);
+    o = o2;
+  }
+  launch_copy_rows(o.p, o.dt, o.ld, out, DT_F32, No, (int)M, No, s);
+  if (t_out) launch_copy_rows(t.p, DT_F32, C, t_out, DT_F32, C, (int)M, C, s);
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
+
 int sdxl_conv2d_group_norm(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, const float* residual,
                            const float* gamma, const float* beta, float eps, int B, int Cin, int H, int W, int Cout, int n_group,
                            int silu, int fused, int* fused_taken, float* out) {

@@ -315,6 +315,37 @@ struct StPlan {
   XattnForm xattn = XA_LAUNCH;                             // (where the forward's shapes and the context images allow it)
 };
 struct STW { NormW norm; Lin proj_in, proj_out; std::vector<TBlockW> blocks; int C = 0, heads = 0; StPlan plan; };
+// The LayerNorm-fed projections of a transformer block, shared by UNet::spatial_transformer and the op entry that runs one of them
+// (sdxl_transformer_projection), so that both go through the same packing, operands and shadow hand-off.
+// projection `names` packed in form f; with `sh` also its shadow twin (behind LayerNorm `norm`), which shares the packed matrix
+Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh = nullptr, const std::string& norm = "");
+inline bool reads_f16(LinForm f) { return f == LF_F16 || f == LF_F16_WHILO || f == LF_F16_AHILO; }   // the projection reads f16 activations
+// X2: an un-scaled HL16 operand of C logical channels handed to an f16 GEMM whose weight is packed twice in the HL16 interleave (K = 2 C)
+inline Act x2_operand(LinForm f, const Act& a) { return f == LF_X2 ? Act(a.p, 2 * a.ld, DT_F16) : a; }
+// the operands a LayerNorm launch writes for the forms of plan `pl`, and the shadow the weights-in-registers producers of the stream (out-projections,
+// FF-out) leave for the projection behind the next LayerNorm (MIX_LN_SHADOW); `have_sh`: the last producer wrote it (else: LayerNorm launch + the
+// plain form of the projection)
+struct LnOperands {
+  Act ln;                           // LayerNorm output in the compute dtype (NATIVE; X2 reads it as f16 rows of 2 C)
+  Act ln16;                         // f16 LayerNorm output (LF_F16)
+  Act ln16x2;                       // [a | a 2^-8] (WHILO) or [a_hi | a_lo 2^8] (AHILO) along a doubled K
+  Act sh16; float* shst = nullptr;  // f16 shadow f16(x o gamma) + the fp32 rows' statistics
+  Act sh16g;                        // (hi | lo 2^8) shadow for a GEGLU projection packed (w | w 2^-8) along a doubled K
+  Act shhl;                         // X2 shadow: the HL16 image of x o gamma (the LayerNorm launch's operand minus the normalisation the consumer applies)
+  bool have_sh = false;
+  size_t M = 0; int C = 0;
+};
+void alloc_ln_operands(Exec& ex, const StPlan& pl, size_t M, int C, const Act& ln, LnOperands& o);   // ln: the compute-dtype LayerNorm output (allocated by the caller)
+void want_ln_shadow(LnOperands& o, Epi& e, bool sh, LinForm f, const NormW& n);     // ask producer `e` for the shadow the consumer (form f) behind LayerNorm n reads
+// the projection behind LayerNorm n: its shadow twin on the shadow the producer left (no LayerNorm launch), or its plain form on a LayerNorm launch
+// of stream t into the operand the form reads.  -> (weights, operand, row statistics of the shadow)
+struct LnIn { const Lin* w; Act a; const float* stat; };
+LnIn ln_input(Exec& ex, LnOperands& o, const Lin& plain, const Lin& sh, LinForm f, const NormW& n, const Act& t, int cls);
+// the f16 GEGLU kernels store an HL16 output through the LDS-staged epilogue of the wide / pipelined tiles -- the kernels every SDXL shape runs on
+// (M = 2048 ... 32768).  Small token counts (tiny test nets: M < 256) run on other tiles; they take the form the F16_F32RES engine runs at every
+// size -- f16 output -- and widen it.  true: the GEGLU projection `in` of form f writes f16 rows that are widened afterwards
+constexpr size_t kGegluDirectRows = 256;
+inline bool geglu_widened(LinForm f, const LnIn& in, size_t M) { return M < kGegluDirectRows && (in.stat || reads_f16(f)); }
 struct BlockW { BlockDesc d; ResBlockW res; STW st; Lin conv; };
 
 class UNet {

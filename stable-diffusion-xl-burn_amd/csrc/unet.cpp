@@ -84,8 +84,8 @@ void f16_valued_weights(const StPlan& s, const std::string& q, std::vector<std::
   for (const std::string& n : kQkv) add(s.qkv, n.c_str());
   add(s.out1, kOut1); add(s.q2, kQ2); add(s.out2, kOut2); add(s.geglu, kGeglu); add(s.ff, kFf);
 }
-// projection `names` packed in form f; with `sh` also its shadow twin (behind LayerNorm `norm`), which shares the packed matrix
-Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh = nullptr, const std::string& norm = "") {
+}  // namespace
+Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh, const std::string& norm) {
   Lin l;
   if (sh) { *sh = wb.fold_ln(names, norm, geglu, DT_F16, true, &l, f == LF_F16_AHILO, f == LF_X2); return l; }
   switch (f) {
@@ -96,6 +96,7 @@ Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& name
     default: return names.size() > 1 ? wb.fused_linear(names) : wb.linear(names[0], geglu);
   }
 }
+namespace {
 STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth, bool fuse_ln, const StPlan& plan) {
   STW s;
   s.C = C; s.heads = heads; s.plan = plan;
@@ -189,6 +190,35 @@ void attention_hl(Exec& ex, const Act& q, const void* kh, int ldk, const void* v
   if (ex.prof) ex.prof->end(ex.s);
 }
 }  // namespace
+
+void alloc_ln_operands(Exec& ex, const StPlan& pl, size_t M, int C, const Act& ln, LnOperands& o) {
+  o.M = M; o.C = C; o.ln = ln; o.have_sh = false;
+  if (reads_f16(pl.geglu) || pl.qkv == LF_F16 || pl.q2 == LF_F16) o.ln16 = ex.alloc(M, C, DT_F16);
+  // (hi | lo) GEGLU forms: the LayerNorm launch writes [a | a 2^-8] or [a_hi | a_lo 2^8] along a doubled K
+  if (pl.geglu == LF_F16_WHILO || pl.geglu == LF_F16_AHILO) o.ln16x2 = ex.alloc(M, 2 * C, DT_F16);
+  if (pl.qkv_sh || pl.q2_sh || pl.geglu_sh) { o.sh16 = ex.alloc(M, C, DT_F16); o.shst = (float*)ex.act->alloc(M * (size_t)((C + 63) / 64) * 2 * sizeof(float)); }
+  if (pl.geglu_sh && pl.geglu == LF_F16_AHILO) o.sh16g = ex.alloc(M, 2 * C, DT_F16);
+  if ((pl.qkv_sh && pl.qkv == LF_X2) || (pl.q2_sh && pl.q2 == LF_X2) || (pl.geglu_sh && pl.geglu == LF_X2)) o.shhl = ex.alloc(M, C, DT_HL);
+}
+void want_ln_shadow(LnOperands& o, Epi& e, bool sh, LinForm f, const NormW& n) {
+  o.have_sh = false;
+  if (!sh || o.C % 64 != 0) return;
+  e.shadow = o.sh16.p; e.shadow_ld = o.sh16.ld; e.shadow_gamma = n.gamma; e.stat_out = o.shst; e.shadow_done = &o.have_sh;
+  if (f == LF_F16_AHILO) { e.shadow = o.sh16g.p; e.shadow_ld = o.sh16g.ld; e.shadow_lo_scale = kHiLoScale; }      // (hi | lo) halves: the consumer's K is doubled
+  if (f == LF_X2) { e.shadow = o.shhl.p; e.shadow_ld = o.shhl.ld; e.shadow_lo_scale = -1.f; }      // HL16 rows
+}
+LnIn ln_input(Exec& ex, LnOperands& o, const Lin& plain, const Lin& sh, LinForm f, const NormW& n, const Act& t, int cls) {
+  const bool from_sh = o.have_sh;
+  o.have_sh = false;
+  if (from_sh) return LnIn{&sh, f == LF_X2 ? Act(o.shhl.p, 2 * o.shhl.ld, DT_F16) : f == LF_F16_AHILO ? o.sh16g : o.sh16, o.shst};
+  if (f == LF_F16_WHILO || f == LF_F16_AHILO) {
+    run_layernorm(ex, n, t, (int)o.M, o.ln16x2, f == LF_F16_AHILO ? -kHiLoScale : 1.0f / kHiLoScale);
+    return LnIn{&plain, o.ln16x2, nullptr};
+  }
+  run_layernorm(ex, n, t, (int)o.M, f == LF_F16 ? o.ln16 : o.ln);
+  demote_lo(ex, cls, o.ln, o.M, o.C);
+  return LnIn{&plain, f == LF_F16 ? o.ln16 : x2_operand(f, o.ln), nullptr};
+}
 
 static std::atomic<int> g_mix_classes{-1};     // A/B / debugging knob (sdxl_debug_set "mix_classes"): overrides the MixClass bits of SDXL_DTYPE_F32_SPLIT_MIX models built afterwards (-1 = the mode's own)
 void unet_set_mix_classes(int v) { g_mix_classes = v; }
@@ -509,30 +539,18 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   //   * f16 projections read an f16 LayerNorm output; an f16 GEGLU projection's output leaves the epilogue as HL16 (fp32-class), so FF-out's
   //     operand is not rounded a second time (an f16 FF-out reads it as f16).
   const StPlan& pl = w.plan;
-  auto f16_in = [](LinForm f) { return f == LF_F16 || f == LF_F16_WHILO || f == LF_F16_AHILO; };   // the projection reads f16 activations
   Act ao2_16;      // operand of an f16 cross-attention out-projection: the split-operand attention rounds its fp32 result once, in its own store (AttnParams::o_dt)
   if (pl.out2 == LF_F16) ao2_16 = ex.alloc(M, C, DT_F16);
   const Act ao2 = pl.out2 == LF_F16 ? ao2_16 : ao;      // what the cross-attention writes: the out-projection's operand
-  Act qk16, ao16, ln16; void* vt16 = nullptr;
+  Act qk16, ao16; void* vt16 = nullptr;
   if (pl.attn_f16) {
     qk16 = ex.alloc(M, 2 * C, DT_F16); ao16 = ex.alloc(M, C, DT_F16);
     vt16 = ex.act->alloc((size_t)B * C * npad * 2);
     if (npad != HW && !ex.dry) launch_fill_zero(vt16, (size_t)B * C * npad * 2, ex.s);
   }
-  if (f16_in(pl.geglu) || pl.qkv == LF_F16 || pl.q2 == LF_F16) ln16 = ex.alloc(M, C, DT_F16);
-  // (hi | lo) GEGLU forms: the LayerNorm launch writes [a | a 2^-8] or [a_hi | a_lo 2^8] along a doubled K
-  Act ln16x2;
-  if (pl.geglu == LF_F16_WHILO || pl.geglu == LF_F16_AHILO) ln16x2 = ex.alloc(M, 2 * C, DT_F16);
-  // MIX_LN_SHADOW: f16 shadow of the stream + the fp32 rows' statistics, left by the weights-in-registers producers (out-projections, FF-out) for the
-  // projection behind the next LayerNorm; `have_sh` says whether the last producer wrote them (else: LayerNorm launch + the plain form of the projection)
-  Act sh16; float* shst = nullptr; bool have_sh = false;
-  if (pl.qkv_sh || pl.q2_sh || pl.geglu_sh) { sh16 = ex.alloc(M, C, DT_F16); shst = (float*)ex.act->alloc(M * (size_t)((C + 63) / 64) * 2 * sizeof(float)); }
-  Act sh16g;       // (hi | lo 2^8) shadow for a GEGLU projection packed (w | w 2^-8) along a doubled K
-  if (pl.geglu_sh && pl.geglu == LF_F16_AHILO) sh16g = ex.alloc(M, 2 * C, DT_F16);
-  // X2 shadow: the HL16 image of x o gamma (what the LayerNorm launch would hand the projection, minus the normalisation the consumer's epilogue
-  // applies from the row statistics)
-  Act shhl;
-  if ((pl.qkv_sh && pl.qkv == LF_X2) || (pl.q2_sh && pl.q2 == LF_X2) || (pl.geglu_sh && pl.geglu == LF_X2)) shhl = ex.alloc(M, C, DT_HL);
+  // the LayerNorm outputs of the forms and the shadow the producers leave (LnOperands)
+  LnOperands lo;
+  alloc_ln_operands(ex, pl, M, C, ln, lo);
   // the knob's f16 fused cross-attention on shapes its launch does not take: f16 q, widened for the split-operand attention
   const bool q2_widen = hl_attn && pl.xattn == XA_F16;
   Act q32;     // f16 query projection: fp32 q for the split-operand attention (the projection's fp32 accumulators, never rounded to f16)
@@ -540,36 +558,11 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   // cross-attention inside the query projection's epilogue (the context images of set_context): q never reaches memory, no attention launch
   const bool xa_fused = pl.xattn != XA_LAUNCH && plan_xattn_ && !w.blocks.empty() && (pl.xattn == XA_SPLIT ? kv_[si][0].xa_lo : kv_[si][0].xa) &&
                         igemm_xattn_ok(DT_F16, ao2.dt, (int)M, C, pl.q2 == LF_X2 ? 2 * C : C, HW, n_ctx_);
-  // X2: an un-scaled HL16 operand of C logical channels handed to an f16 GEMM whose weight is packed twice in the HL16 interleave (K = 2 C)
-  auto x2op = [](LinForm f, const Act& a) { return f == LF_X2 ? Act(a.p, 2 * a.ld, DT_F16) : a; };
-  auto want_shadow = [&](Epi& e, bool sh, LinForm f, const NormW& n) {     // ask producer `e` for the shadow the consumer (form f) behind LayerNorm n reads
-    have_sh = false;
-    if (!sh || C % 64 != 0) return;
-    e.shadow = sh16.p; e.shadow_ld = sh16.ld; e.shadow_gamma = n.gamma; e.stat_out = shst; e.shadow_done = &have_sh;
-    if (f == LF_F16_AHILO) { e.shadow = sh16g.p; e.shadow_ld = sh16g.ld; e.shadow_lo_scale = kHiLoScale; }      // (hi | lo) halves: the consumer's K is doubled
-    if (f == LF_X2) { e.shadow = shhl.p; e.shadow_ld = shhl.ld; e.shadow_lo_scale = -1.f; }      // HL16 rows
-  };
-  // the projection behind LayerNorm n: its shadow twin on the shadow the producer left (no LayerNorm launch), or its plain form on a LayerNorm launch
-  // into the operand the form reads.  -> (weights, operand, row statistics of the shadow)
-  struct LnIn { const Lin* w; Act a; const float* stat; };
-  auto ln_in = [&](const Lin& plain, const Lin& sh, LinForm f, const NormW& n, int cls) {
-    const bool from_sh = have_sh;
-    have_sh = false;
-    if (from_sh) return LnIn{&sh, f == LF_X2 ? Act(shhl.p, 2 * shhl.ld, DT_F16) : f == LF_F16_AHILO ? sh16g : sh16, shst};
-    if (f == LF_F16_WHILO || f == LF_F16_AHILO) {
-      run_layernorm(ex, n, t, (int)M, ln16x2, f == LF_F16_AHILO ? -kHiLoScale : 1.0f / kHiLoScale);
-      return LnIn{&plain, ln16x2, nullptr};
-    }
-    run_layernorm(ex, n, t, (int)M, f == LF_F16 ? ln16 : ln);
-    demote_lo(ex, cls, ln, M, C);
-    return LnIn{&plain, f == LF_F16 ? ln16 : x2op(f, ln), nullptr};
-  };
-  // the f16 GEGLU kernels store an HL16 output through the LDS-staged epilogue of the wide / pipelined tiles -- the kernels every SDXL shape runs on
-  // (M = 2048 ... 32768).  Small token counts (tiny test nets: M < 256) run on other tiles; they take the form the F16_F32RES engine
-  // runs at every size -- f16 output -- and widen it.
-  const bool gg_direct = M >= 256;
+  auto want_shadow = [&](Epi& e, bool sh, LinForm f, const NormW& n) { want_ln_shadow(lo, e, sh, f, n); };
+  auto ln_in = [&](const Lin& plain, const Lin& sh, LinForm f, const NormW& n, int cls) { return ln_input(ex, lo, plain, sh, f, n, t, cls); };
+  const auto x2op = x2_operand;
   Act gg16;
-  if ((f16_in(pl.geglu) && !gg_direct) || pl.ff == LF_F16) gg16 = ex.alloc(M, 4 * C, DT_F16);      // (an f16 FF-out reads the GEGLU output as f16, whichever kernel wrote it)
+  if ((reads_f16(pl.geglu) && M < kGegluDirectRows) || pl.ff == LF_F16) gg16 = ex.alloc(M, 4 * C, DT_F16);     // (an f16 FF-out reads the GEGLU output as f16, whichever kernel wrote it)
   void* kh = hl_attn && !hl_direct ? ex.act->alloc(M * (size_t)C * 4) : nullptr;
   void* vth = hl_attn && !hl_direct ? ex.act->alloc((size_t)B * C * npad * 4) : nullptr;
   if (fuse_ln_) {
@@ -654,7 +647,7 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
     const LnIn ig = ln_in(b.geglu, b.geglu_sh, pl.geglu, b.n3, DM_GEGLU);
     Epi eg; eg.act = 1; eg.cls = DM_GEGLU; eg.ln_stat = ig.stat;
     if (ig.stat) eg.rpb = HW;
-    const bool gg_widen = pl.ff != LF_F16 && !gg_direct && (ig.stat || f16_in(pl.geglu));
+    const bool gg_widen = pl.ff != LF_F16 && geglu_widened(pl.geglu, ig, M);
     run_linear(ex, *ig.w, ig.a, (int)M, pl.ff == LF_F16 || gg_widen ? gg16 : gg, eg);
     if (gg_widen && !ex.dry) launch_f16_to_hl(gg16.p, gg16.ld, gg.p, gg.ld, M, 4 * C, ex.s);
     demote_lo(ex, DM_FF, gg, M, 4 * C);
