@@ -255,6 +255,8 @@ def test_linear_asymmetric_identity(pkg, ctx, dtype):
     w = (torch.arange(n * n, dtype=torch.float32).reshape(n, n) % 251) / 251.0
     out = pkg.linear(ctx, x.cuda(), w.cuda(), None, False, dtype)
     assert rel_err(out, w) < TOL[dtype]
+    if dtype in (1, 2):      # the packed weights are RNE f16(w) and I w is exact: bit for bit (test_gpu_f16_kernels, conversions)
+        assert torch.equal(out.cpu(), w.half().float())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

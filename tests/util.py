@@ -1,6 +1,7 @@
 """shared helpers of the parity tests"""
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from oracle import config as OC, model as OM
 
@@ -31,3 +32,33 @@ def to_pkg_vcfg(pkg, v):
 
 def unet_weights(ocfg, seed=0):
     return OM.to_torch(OC.synth_weights(OC.unet_param_specs(ocfg), seed))
+
+
+def f16v(x):
+    return x.half().float()
+
+
+def ulp16(v):
+    """spacing of the f16 numbers at |v| (subnormals: 2^-24)"""
+    return torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -14))) - 10.0)
+
+
+def rounding_slack(x, d):
+    """(f16(x) as fp64, per element: one f16 spacing where x lies within d of a rounding midpoint -- the kernel rounds an fp32 value that
+    may sit on the other side -- else 0)"""
+    h = x.half().double()
+    gap = (x - h).abs()
+    u1, u2 = ulp16(x), ulp16(h)
+    near = ((gap - u1 / 2).abs() <= d) | ((gap - u2 / 2).abs() <= d)
+    return h, torch.where(near, torch.maximum(u1, u2), torch.zeros_like(x))
+
+
+def geglu(y, dy=None):
+    """GEGLU (unet/mod.rs:942-956: value half * gelu(gate half)) in fp64; with dy: + the propagated per-element bound"""
+    n = y.shape[1] // 2
+    v, g = y[:, :n], y[:, n:]
+    out = v * F.gelu(g)
+    if dy is None:
+        return out, None
+    dv, dg = dy[:, :n], dy[:, n:]
+    return out, F.gelu(g).abs() * dv + (v.abs() + dv) * 1.13 * dg
