@@ -195,6 +195,27 @@ int sdxl_sample_latent_with_inpainting(sdxl_diffuser* d, void* stream, const sdx
 int sdxl_refine_latent(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond,
                        double unconditional_guidance_scale, int step_start, int n_steps, const float* noise,
                        float* out_latent);
+/* ---- seeded noise: the same three calls with gen_noise() played by a counter-based generator on the device.
+ * Philox4x32-10, key = (low, high) 32 bits of the batch entry's seed, counter = (hw, draw, 0, 0) with hw the row-major pixel
+ * index of the h/8 x w/8 latent: one counter yields the four channel values of that pixel (two Box-Muller pairs).  The same
+ * seed gives the same bits for the same entry, resolution and library build, whatever the batch size and the entry's place
+ * in the batch.  `draw` numbers the tensors of one trajectory: */
+#define SDXL_DRAW_INITIAL 0u                     /* noise0 of sampling, the re-noise of refine_latent */
+#define SDXL_DRAW_BLEND(i) (1u + 2u * (i))       /* inpainting blend in front of iteration i (:463) */
+#define SDXL_DRAW_SIGMA(i) (2u + 2u * (i))       /* the gen_noise() * sigma term of iteration i (:427) */
+/* gen_noise (:378-388) with a seed: out [n,4,h,w] fp32 (device); seeds: host array [n], one per batch entry */
+int sdxl_gen_noise(sdxl_ctx* ctx, void* stream, const uint64_t* seeds, uint32_t draw, int n, int h, int w, float* out);
+/* eta in [0, 1] scales sigma of :423-427 (the reference pins it to 0): sigma_t = eta sqrt((1-ap)/(1-a)) sqrt(1-a/ap) and
+ * x = x0 sqrt(ap) + e sqrt(1-ap-sigma^2) + z sigma.  The blend and sigma noise are drawn inside the per-step kernel and never
+ * stored.  seeds == NULL or eta outside [0, 1] (NaN included): SDXL_ERR_INVALID. */
+int sdxl_sample_latent_seeded(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double unconditional_guidance_scale,
+                              int n_steps, const uint64_t* seeds, double eta, float* out_latent);
+int sdxl_sample_latent_with_inpainting_seeded(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond,
+                                              double unconditional_guidance_scale, int n_steps, const float* reference,
+                                              const uint8_t* mask, const uint64_t* seeds, double eta, float* out_latent);
+int sdxl_refine_latent_seeded(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond,
+                              double unconditional_guidance_scale, int step_start, int n_steps, const uint64_t* seeds,
+                              double eta, float* out_latent);
 /* number of UNet evaluations of `(0..n_train-step_start).rev().step_by(n_train/n_steps)` (:400-406): 30 -> 31 */
 int sdxl_step_count(int n_steps, int step_start, int n_train_steps);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */

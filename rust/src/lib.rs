@@ -16,7 +16,8 @@
 //! The reference draws its noise from an unseeded generator inside `sample_latent` (`gen_noise`, `:378-388`); the engine
 //! takes noise as an argument so results are reproducible.  The reference-shaped methods therefore draw
 //! `Tensor::random(Normal(0,1))` exactly where the reference does and forward to `*_with_noise` companions, which are the
-//! ones parity tests use.
+//! ones parity tests use.  `Diffuser::set_seed` switches them to the `*_seeded` companions: every noise tensor is then drawn
+//! on the device from one 64-bit seed per batch entry (`sdxl_gen_noise`, `sdxl_*_seeded`), the same bits as from C or Python.
 //!
 //! Tensors cross the boundary as fp32 device buffers in the reference's own layouts.  `bridge` is the generic path for ANY
 //! burn backend (host hop, like the reference's own `DefaultBackendConverter`, `src/backend_converter.rs:25-39`); the
@@ -269,7 +270,7 @@ impl DiffuserConfig {
             ffi::sdxl_diffuser_create(ctx.raw, &cfg, precision as c_int, weights_flat.as_ptr(), alphas_cumprod.as_ptr(),
                                       alphas_cumprod.len() as c_int, &mut raw)
         })?;
-        Ok(Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, _b: std::marker::PhantomData })
+        Ok(Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, seed: std::cell::Cell::new(None), _b: std::marker::PhantomData })
     }
     /// seeded synthetic weights generated on the device (no checkpoint): what the parity tests and `bench.py` run
     pub fn init_synthetic<B: BurnBackend>(&self, ctx: &Mi355Context, precision: Precision, seed: u64, alphas_cumprod: &[f32]) -> Diffuser<B> {
@@ -279,7 +280,7 @@ impl DiffuserConfig {
             ffi::sdxl_diffuser_create_synthetic(ctx.raw, &cfg, precision as c_int, seed, alphas_cumprod.as_ptr(),
                                                 alphas_cumprod.len() as c_int, &mut raw)
         });
-        Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, _b: std::marker::PhantomData }
+        Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, seed: std::cell::Cell::new(None), _b: std::marker::PhantomData }
     }
 }
 fn param_numel(cfg: &ffi::sdxl_unet_config) -> usize {
@@ -312,7 +313,17 @@ pub struct Diffuser<B: BurnBackend> {
     raw: *mut ffi::sdxl_diffuser,
     n_steps: usize,
     is_refiner: bool,
+    /// `set_seed`: (seed of batch entry 0, eta) for the reference-shaped methods; `None` = unseeded `Tensor::random`
+    seed: std::cell::Cell<Option<(u64, f64)>>,
     _b: std::marker::PhantomData<B>,
+}
+/// draw numbers of the seeded noise (`SDXL_DRAW_*` of the header; bindgen does not translate function-like macros)
+pub const DRAW_INITIAL: u32 = 0;
+pub const fn draw_blend(i: u32) -> u32 {
+    1 + 2 * i
+}
+pub const fn draw_sigma(i: u32) -> u32 {
+    2 + 2 * i
 }
 impl<B: BurnBackend> Drop for Diffuser<B> {
     fn drop(&mut self) {
@@ -322,6 +333,10 @@ impl<B: BurnBackend> Drop for Diffuser<B> {
 impl<B: BurnBackend> Diffuser<B> {
     /// reference signature (`:317-322`); noise = `gen_noise` (`:378-388`)
     pub fn sample_latent(&self, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize) -> Tensor<B, 4> {
+        if let Some((seed, eta)) = self.seed.get() {
+            let seeds = Self::entry_seeds(seed, &conditioning);
+            return self.sample_latent_seeded(conditioning, unconditional_guidance_scale, n_steps, &seeds, eta);
+        }
         let noise = Self::gen_noise(&conditioning);
         self.sample_latent_with_noise(conditioning, unconditional_guidance_scale, n_steps, noise)
     }
@@ -341,6 +356,10 @@ impl<B: BurnBackend> Diffuser<B> {
     /// of the reference (`:463`) is drawn here, one `gen_noise` per iteration
     pub fn sample_latent_with_inpainting(&self, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize,
                                          reference: Tensor<B, 4>, mask: Tensor<B, 4, Bool>) -> Tensor<B, 4> {
+        if let Some((seed, eta)) = self.seed.get() {
+            let seeds = Self::entry_seeds(seed, &conditioning);
+            return self.sample_latent_with_inpainting_seeded(conditioning, unconditional_guidance_scale, n_steps, reference, mask, &seeds, eta);
+        }
         let iters = unsafe { ffi::sdxl_step_count(n_steps as c_int, 0, self.n_steps as c_int) } as usize;
         let noise0 = Self::gen_noise(&conditioning);
         let step_noise: Vec<Tensor<B, 4>> = (0..iters).map(|_| Self::gen_noise(&conditioning)).collect();
@@ -366,6 +385,10 @@ impl<B: BurnBackend> Diffuser<B> {
     /// reference signature (`:355-362`)
     pub fn refine_latent(&self, latent: Tensor<B, 4>, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, step_start: usize,
                          n_steps: usize) -> Tensor<B, 4> {
+        if let Some((seed, eta)) = self.seed.get() {
+            let seeds = Self::entry_seeds(seed, &conditioning);
+            return self.refine_latent_seeded(latent, conditioning, unconditional_guidance_scale, step_start, n_steps, &seeds, eta);
+        }
         let noise = Self::gen_noise(&conditioning);
         self.refine_latent_with_noise(latent, conditioning, unconditional_guidance_scale, step_start, n_steps, noise)
     }
@@ -379,6 +402,73 @@ impl<B: BurnBackend> Diffuser<B> {
         check(unsafe {
             ffi::sdxl_refine_latent(self.raw, ptr::null_mut(), d_lat.f32_ptr(), &dc.c, unconditional_guidance_scale, step_start as c_int,
                                     n_steps as c_int, d_noise.f32_ptr(), out.f32_mut())
+        });
+        bridge::download(&out, dims, &device)
+    }
+    /// From now on the reference-shaped methods draw their noise on the device: batch entry `b` uses `seed + b` (wrapping),
+    /// `eta` in [0, 1] scales the `gen_noise() * sigma` term of `:427` (0.0 = the reference's update).  `None` restores the
+    /// unseeded `Tensor::random` path.
+    pub fn set_seed(&self, seed: Option<u64>, eta: f64) {
+        self.seed.set(seed.map(|s| (s, eta)));
+    }
+    fn entry_seeds(seed: u64, conditioning: &Conditioning<B>) -> Vec<u64> {
+        let [n, _, _] = conditioning.context_full.dims();
+        (0..n as u64).map(|b| seed.wrapping_add(b)).collect()
+    }
+    /// `gen_noise` (`:378-388`) with one seed per batch entry: `[seeds.len(), 4, height / 8, width / 8]` (`sdxl_gen_noise`)
+    pub fn gen_noise_seeded(ctx: &Mi355Context, seeds: &[u64], draw: u32, resolution: [usize; 2], device: &B::Device) -> Tensor<B, 4> {
+        let dims = [seeds.len(), 4, resolution[0] / 8, resolution[1] / 8];
+        let out = DeviceBuf::new(dims.iter().product::<usize>() * 4);
+        check(unsafe {
+            ffi::sdxl_gen_noise(ctx.raw, ptr::null_mut(), seeds.as_ptr(), draw, dims[0] as c_int, dims[2] as c_int, dims[3] as c_int, out.f32_mut())
+        });
+        bridge::download(&out, dims, device)
+    }
+    /// `sample_latent` with `gen_noise` played by the device generator (`sdxl_sample_latent_seeded`): one seed per batch entry
+    pub fn sample_latent_seeded(&self, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize, seeds: &[u64],
+                                eta: f64) -> Tensor<B, 4> {
+        let device = conditioning.context_full.device();
+        let [n, _, _] = conditioning.context_full.dims();
+        assert_eq!(seeds.len(), n, "one seed per batch entry");
+        let dims = [n, 4, conditioning.resolution[0] / 8, conditioning.resolution[1] / 8];
+        let dc = to_c_conditioning(&conditioning);
+        let out = DeviceBuf::new(dims.iter().product::<usize>() * 4);
+        check(unsafe {
+            ffi::sdxl_sample_latent_seeded(self.raw, ptr::null_mut(), &dc.c, unconditional_guidance_scale, n_steps as c_int, seeds.as_ptr(), eta,
+                                           out.f32_mut())
+        });
+        bridge::download(&out, dims, &device)
+    }
+    /// inpainting without noise tensors: the blend noise of `:463` is drawn inside the per-step kernel
+    #[allow(clippy::too_many_arguments)]
+    pub fn sample_latent_with_inpainting_seeded(&self, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize,
+                                                reference: Tensor<B, 4>, mask: Tensor<B, 4, Bool>, seeds: &[u64], eta: f64) -> Tensor<B, 4> {
+        let device = conditioning.context_full.device();
+        let dims = reference.dims();
+        assert_eq!(seeds.len(), dims[0], "one seed per batch entry");
+        let dc = to_c_conditioning(&conditioning);
+        let mask_u8: Vec<u8> = mask.into_data().value.iter().map(|&m| m as u8).collect();
+        let (d_ref, d_mask) = (bridge::upload(reference), DeviceBuf::from_u8(&mask_u8));
+        let out = DeviceBuf::new(dims.iter().product::<usize>() * 4);
+        check(unsafe {
+            ffi::sdxl_sample_latent_with_inpainting_seeded(self.raw, ptr::null_mut(), &dc.c, unconditional_guidance_scale, n_steps as c_int,
+                                                           d_ref.f32_ptr(), d_mask.ptr as *const u8, seeds.as_ptr(), eta, out.f32_mut())
+        });
+        bridge::download(&out, dims, &device)
+    }
+    /// `refine_latent` with the re-noise tensor drawn on the device (`sdxl_refine_latent_seeded`)
+    #[allow(clippy::too_many_arguments)]
+    pub fn refine_latent_seeded(&self, latent: Tensor<B, 4>, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, step_start: usize,
+                                n_steps: usize, seeds: &[u64], eta: f64) -> Tensor<B, 4> {
+        let device = conditioning.context_full.device();
+        let dims = latent.dims();
+        assert_eq!(seeds.len(), dims[0], "one seed per batch entry");
+        let dc = to_c_conditioning(&conditioning);
+        let d_lat = bridge::upload(latent);
+        let out = DeviceBuf::new(dims.iter().product::<usize>() * 4);
+        check(unsafe {
+            ffi::sdxl_refine_latent_seeded(self.raw, ptr::null_mut(), d_lat.f32_ptr(), &dc.c, unconditional_guidance_scale, step_start as c_int,
+                                           n_steps as c_int, seeds.as_ptr(), eta, out.f32_mut())
         });
         bridge::download(&out, dims, &device)
     }

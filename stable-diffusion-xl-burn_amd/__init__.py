@@ -79,6 +79,7 @@ ABI_SYMBOLS = [
     "sdxl_diffuser_create", "sdxl_diffuser_create_synthetic", "sdxl_diffuser_destroy", "sdxl_diffuser_unet",
     "sdxl_sample_latent", "sdxl_sample_latent_with_inpainting", "sdxl_refine_latent", "sdxl_step_count",
     "sdxl_diffuser_enable_step_timing", "sdxl_diffuser_step_times", "sdxl_diffuser_set_trace",
+    "sdxl_gen_noise", "sdxl_sample_latent_seeded", "sdxl_sample_latent_with_inpainting_seeded", "sdxl_refine_latent_seeded",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -584,6 +585,44 @@ def default_alphas_cumprod(n: int = 1000) -> np.ndarray:
     return np.cumprod(1.0 - betas).astype(np.float32)
 
 
+DRAW_INITIAL = 0        # SDXL_DRAW_INITIAL: noise0 of sampling, the re-noise of refine_latent
+
+
+def draw_blend(i: int) -> int:
+    """SDXL_DRAW_BLEND(i): the inpainting blend in front of iteration i (:463)"""
+    return 1 + 2 * i
+
+
+def draw_sigma(i: int) -> int:
+    """SDXL_DRAW_SIGMA(i): the gen_noise() * sigma term of iteration i (:427)"""
+    return 2 + 2 * i
+
+
+def _seeds(seeds, n: int):
+    """host uint64 array [n] (None stays NULL: the engine reports it)"""
+    if seeds is None:
+        return None
+    a = [int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds]
+    if len(a) != n:
+        raise EngineError(f"expected {n} seeds (one per batch entry), got {len(a)}")
+    return (ctypes.c_uint64 * n)(*a)
+
+
+def _explicit_eta(eta: float):
+    if eta != 0.0:
+        raise EngineError("eta needs seeds=: the explicit-noise calls carry no noise for the sigma term")
+
+
+def gen_noise(ctx: Context, seeds, draw: int, n: int, h: int, w: int):
+    """gen_noise (:378-388) with a seed: float32 CUDA tensor [n, 4, h, w] (h, w in latent pixels), entry b from seeds[b];
+    the values the seeded trajectories draw for (seed, pixel, draw)"""
+    torch = _torch()
+    out = torch.empty((max(n, 0), 4, max(h, 0), max(w, 0)), dtype=torch.float32, device="cuda")
+    _check(lib().sdxl_gen_noise(ctx.h, _stream(), None if seeds is None else _seeds(seeds, n), ctypes.c_uint32(draw), n, h, w,
+                               ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 class Diffuser:
     """reference Diffuser<B> (src/model/stablediffusion/mod.rs:308-542)"""
 
@@ -614,10 +653,19 @@ class Diffuser:
         n = int((cond.context_full if cond.context_full is not None else cond.context_open_clip).shape[0])
         return (n, 4, cond.resolution[0] // 8, cond.resolution[1] // 8)
 
-    def sample_latent(self, conditioning: Conditioning, unconditional_guidance_scale: float, n_steps: int, noise0):
-        """Diffuser::sample_latent (:317-332); noise0 plays gen_noise()"""
+    def sample_latent(self, conditioning: Conditioning, unconditional_guidance_scale: float, n_steps: int, noise0=None, *,
+                      seeds=None, eta: float = 0.0):
+        """Diffuser::sample_latent (:317-332); noise0 plays gen_noise(), or seeds= (one per batch entry) draws it on the
+        device, with eta scaling the sigma term of :427"""
         torch = _torch()
         c, keep = conditioning.to_c()
+        if seeds is not None or noise0 is None:
+            out = torch.empty(self._latent_shape(conditioning), dtype=torch.float32, device="cuda")
+            _check(lib().sdxl_sample_latent_seeded(self.h, _stream(), ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+                                                  n_steps, _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
+                                                  ctypes.c_void_p(out.data_ptr())))
+            return out
+        _explicit_eta(eta)
         noise0, pn = _dev(noise0)
         assert tuple(noise0.shape) == self._latent_shape(conditioning)
         out = torch.empty_like(noise0)
@@ -625,11 +673,22 @@ class Diffuser:
                                        n_steps, pn, ctypes.c_void_p(out.data_ptr())))
         return out
 
-    def sample_latent_with_inpainting(self, conditioning, unconditional_guidance_scale, n_steps, reference, mask, noise0,
-                                      step_noise):
-        """Diffuser::sample_latent_with_inpainting (:334-353); mask True = keep generated; step_noise [iters,n,4,h,w]"""
+    def sample_latent_with_inpainting(self, conditioning, unconditional_guidance_scale, n_steps, reference, mask, noise0=None,
+                                      step_noise=None, *, seeds=None, eta: float = 0.0):
+        """Diffuser::sample_latent_with_inpainting (:334-353); mask True = keep generated; step_noise [iters,n,4,h,w], or
+        seeds= (one per batch entry): no noise tensor exists, every draw happens inside the per-step kernel"""
         torch = _torch()
         c, keep = conditioning.to_c()
+        if seeds is not None or noise0 is None:
+            reference, pr = _dev(reference)
+            mask, pm = _dev(mask, torch.uint8)
+            out = torch.empty_like(reference)
+            _check(lib().sdxl_sample_latent_with_inpainting_seeded(self.h, _stream(), ctypes.byref(c),
+                                                                  ctypes.c_double(unconditional_guidance_scale), n_steps, pr, pm,
+                                                                  _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
+                                                                  ctypes.c_void_p(out.data_ptr())))
+            return out
+        _explicit_eta(eta)
         noise0, pn = _dev(noise0)
         reference, pr = _dev(reference)
         mask, pm = _dev(mask, torch.uint8)
@@ -640,11 +699,19 @@ class Diffuser:
                                                        ps, ctypes.c_void_p(out.data_ptr())))
         return out
 
-    def refine_latent(self, latent, conditioning, unconditional_guidance_scale, step_start, n_steps, noise):
-        """Diffuser::refine_latent (:355-376)"""
+    def refine_latent(self, latent, conditioning, unconditional_guidance_scale, step_start, n_steps, noise=None, *, seeds=None,
+                      eta: float = 0.0):
+        """Diffuser::refine_latent (:355-376); noise is the re-noise tensor, or seeds= draws it on the device"""
         torch = _torch()
         c, keep = conditioning.to_c()
         latent, pl = _dev(latent)
+        if seeds is not None or noise is None:
+            out = torch.empty_like(latent)
+            _check(lib().sdxl_refine_latent_seeded(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+                                                  step_start, n_steps, _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
+                                                  ctypes.c_void_p(out.data_ptr())))
+            return out
+        _explicit_eta(eta)
         noise, pn = _dev(noise)
         out = torch.empty_like(latent)
         _check(lib().sdxl_refine_latent(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),

@@ -795,6 +795,49 @@ int sdxl_refine_latent(sdxl_diffuser* d, void* stream, const float* latent, cons
   d->d->refine_latent(latent, to_cond(cond), cfg, step_start, n_steps, noise, out, pick(d->ctx, stream));
   API_END
 }
+// seeded forms: argument errors are SDXL_ERR_INVALID (nothing was launched, the handle is untouched)
+static const char* seeded_args_error(const uint64_t* seeds, double eta) {
+  if (!seeds) return "seeds is NULL: one 64-bit seed per batch entry";
+  if (!(eta >= 0.0 && eta <= 1.0)) return "eta must be a finite value in [0, 1]";
+  return nullptr;
+}
+int sdxl_gen_noise(sdxl_ctx* ctx, void* stream, const uint64_t* seeds, uint32_t draw, int n, int h, int w, float* out) {
+  if (!ctx || !out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (!seeds) return fail(SDXL_ERR_INVALID, "seeds is NULL: one 64-bit seed per batch entry");
+  if (n < 1 || h < 1 || w < 1 || (int64_t)h * w > (int64_t)1 << 30) return fail(SDXL_ERR_INVALID, "gen_noise: n, h, w out of range");
+  API_BEGIN
+  use(ctx);
+  launch_seeded_noise(out, seeds, draw, n, h * w, pick(ctx, stream));
+  API_END
+}
+int sdxl_sample_latent_seeded(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double cfg, int n_steps,
+                              const uint64_t* seeds, double eta, float* out) {
+  if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  SDXL_REQUIRE(d && out, "null argument");
+  use(d->ctx);
+  d->d->sample_latent_seeded(to_cond(cond), cfg, n_steps, seeds, eta, out, pick(d->ctx, stream));
+  API_END
+}
+int sdxl_sample_latent_with_inpainting_seeded(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double cfg, int n_steps,
+                                              const float* reference, const uint8_t* mask, const uint64_t* seeds, double eta,
+                                              float* out) {
+  if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  SDXL_REQUIRE(d && out, "null argument");
+  use(d->ctx);
+  d->d->sample_latent_inpaint_seeded(to_cond(cond), cfg, n_steps, reference, mask, seeds, eta, out, pick(d->ctx, stream));
+  API_END
+}
+int sdxl_refine_latent_seeded(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond, double cfg,
+                              int step_start, int n_steps, const uint64_t* seeds, double eta, float* out) {
+  if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  SDXL_REQUIRE(d && latent && out, "null argument");
+  use(d->ctx);
+  d->d->refine_latent_seeded(latent, to_cond(cond), cfg, step_start, n_steps, seeds, eta, out, pick(d->ctx, stream));
+  API_END
+}
 int sdxl_step_count(int n_steps, int step_start, int n_train) {
   try { return (int)Diffuser::step_schedule(n_steps, step_start, n_train).size(); }
   catch (const std::exception& e) { g_err = e.what(); return -1; }

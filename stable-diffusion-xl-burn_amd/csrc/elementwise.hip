@@ -510,9 +510,70 @@ void launch_causal_mask(float* out, int n, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// CFG combine + DDIM (eta = 0) update + inpaint blend + next-UNet-input refresh, one thread per latent pixel.
+// Seeded noise: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC11), key = the batch entry's
+// 64-bit seed (low, high), counter = (hw, draw, 0, 0).  One call is the four channel values of one latent pixel: two
+// Box-Muller pairs from the four output words.  Both uniforms are 24-bit fractions, exact in fp32; ua is in (0, 1] so the
+// logarithm is finite and |z| <= sqrt(48 ln 2).  Contraction is off so the stand-alone fill and the in-register draw of
+// ddim_kernel round every product alike.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ void seeded_normal4(uint64_t seed, uint32_t hw, uint32_t draw, float z[4]) {
+#pragma clang fp contract(off)
+  uint32_t x[4];
+  philox4x32_10(hw, draw, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float ua = (float)((x[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f;   // * 2^-24, exact, (0, 1]
+    const float ub = (float)(x[2 * p + 1] >> 8) * 5.9604644775390625e-08f;      // exact, [0, 1)
+    const float r = sqrtf(-2.0f * logf(ua));
+    const float theta = 6.283185307179586f * ub;
+    float sn, cs;
+    sincosf(theta, &sn, &cs);
+    z[2 * p] = r * cs;
+    z[2 * p + 1] = r * sn;
+  }
+}
+__global__ void seeded_noise_kernel(float* out, DdimSeeds seeds, uint32_t draw, int n, int HW) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n * HW) return;
+  const int b = i / HW;
+  const int hw = i - (size_t)b * HW;
+  float z[4];
+  seeded_normal4(seeds.v[b], (uint32_t)hw, draw, z);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) out[((size_t)b * 4 + c) * HW + hw] = z[c];
+}
+void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n, int HW, hipStream_t s) {
+  for (int b0 = 0; b0 < n; b0 += kMaxSeeds) {
+    const int nb = std::min(kMaxSeeds, n - b0);
+    DdimSeeds k{};
+    for (int b = 0; b < nb; ++b) k.v[b] = seeds[b0 + b];
+    const size_t total = (size_t)nb * HW;
+    hipLaunchKernelGGL(seeded_noise_kernel, dim3((total + 255) / 256), dim3(256), 0, s, out + (size_t)b0 * 4 * HW, k, draw, nb, HW);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// CFG combine + DDIM update + inpaint blend + next-UNet-input refresh, one thread per latent pixel.
 // stablediffusion/mod.rs:423-428 (update), :539-540 (CFG), :463-465 (mask_where blend).
+// SEEDED = false: explicit noise, eta = 0 (step_noise tensor, sigma never read).  SEEDED = true: the blend noise of :463 and the
+// gen_noise() * sigma term of :427 are drawn in registers from the entry's seed; z is drawn only where sigma != 0.
+// Every rounding is written out (contraction off, fmaf where a product is fused) so that both instantiations round alike and the
+// explicit one keeps the bits the committed fixtures were produced with: e = fma(ec - eu, cfg, eu), x0 = fma(-e, sqrt_1ma, x) / sqrt_a,
+// then x = x0 sqrt_ap + e sqrt_1map with the first product fused into the sum on channels 2 and 3 only (channels 0 and 1 round both
+// products: that is how the update was first compiled, and a trajectory amplifies a last-bit change); the blend rounds both products.
+template <bool SEEDED>
 __global__ void ddim_kernel(const DdimParams p, int do_update) {
+#pragma clang fp contract(off)
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)p.n * p.HW) return;
   const int b = i / p.HW;
@@ -530,18 +591,33 @@ __global__ void ddim_kernel(const DdimParams p, int do_update) {
       float e = ec;
       if (p.use_cfg) {
         const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-        e = eu + (ec - eu) * k.cfg;
+        e = __builtin_fmaf(ec - eu, k.cfg, eu);
       }
-      const float x0 = (x[c] - e * k.sqrt_1ma) / k.sqrt_a;
-      x[c] = x0 * k.sqrt_ap + e * k.sqrt_1map;
+      const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
+      const float en = e * k.sqrt_1map;
+      x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
+    }
+    if constexpr (SEEDED) {
+      if (k.sigma != 0.f) {
+        float z[4];
+        seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], k.sigma, x[c]);
+      }
     }
   }
   if (p.mask && next < p.n_steps_total) {
     const StepCoef kn = p.table[next];
+    float z[4];
+    if constexpr (SEEDED) seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_blend((uint32_t)next), z);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const size_t e = ((size_t)b * 4 + c) * p.HW + hw;
-      if (!p.mask[e]) x[c] = p.ref[e] * kn.sqrt_a + p.step_noise[(size_t)next * p.n * 4 * p.HW + e] * kn.sqrt_1ma;
+      if (!p.mask[e]) {
+        float zn;
+        if constexpr (SEEDED) zn = z[c]; else zn = p.step_noise[(size_t)next * p.n * 4 * p.HW + e];
+        x[c] = p.ref[e] * kn.sqrt_a + zn * kn.sqrt_1ma;
+      }
     }
   }
 #pragma unroll
@@ -557,7 +633,8 @@ __global__ void ddim_advance_kernel(const StepCoef* table, int* step_idx, float*
 }
 void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s) {
   const size_t total = (size_t)p.n * p.HW;
-  hipLaunchKernelGGL(ddim_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p, do_update);
+  if (p.seeded) hipLaunchKernelGGL(ddim_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, s, p, do_update);
+  else hipLaunchKernelGGL(ddim_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, p, do_update);
   hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, do_update);
 }
 __global__ void axpby_kernel(float* dst, const float* a, float sa, const float* b, float sb, size_t n) {

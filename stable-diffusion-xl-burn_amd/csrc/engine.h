@@ -556,6 +556,14 @@ class Diffuser {
   // Diffuser::refine_latent (:355-376)
   void refine_latent(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                      const float* noise, float* out, hipStream_t s);
+  // the same three calls with the noise drawn on the device from one 64-bit seed per batch entry (host array [n]) and the
+  // gen_noise() * sigma term of :427 live: sigma_t = eta sqrt((1 - ap) / (1 - a)) sqrt(1 - a / ap), eta in [0, 1]
+  void sample_latent_seeded(const Conditioning& c, double cfg_scale, int n_steps, const uint64_t* seeds, double eta, float* out,
+                            hipStream_t s);
+  void sample_latent_inpaint_seeded(const Conditioning& c, double cfg_scale, int n_steps, const float* reference,
+                                    const unsigned char* mask, const uint64_t* seeds, double eta, float* out, hipStream_t s);
+  void refine_latent_seeded(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
+                            const uint64_t* seeds, double eta, float* out, hipStream_t s);
   static std::vector<int> step_schedule(int n_steps, int step_start, int n_train);
   std::vector<float> step_ms;   // per-iteration GPU time of the last trajectory (hipEvent), for "UNet step ms p50"
   bool time_steps = false;
@@ -565,13 +573,14 @@ class Diffuser {
 
  private:
   void diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale, const float* reference,
-               const unsigned char* mask, const float* step_noise, hipStream_t s);
+               const unsigned char* mask, const float* step_noise, hipStream_t s, const uint64_t* seeds = nullptr, double eta = 0.0);
   std::unique_ptr<UNet> unet_;
   std::vector<double> alphas_;
   int n_train_;
   bool is_refiner_;
   // device state
   float* latent_ = nullptr; size_t latent_cap_ = 0;
+  float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
   StepCoef* table_ = nullptr; int table_cap_ = 0;
   int* step_idx_ = nullptr; float* t_dev_ = nullptr;
   float* ctx_buf_ = nullptr; size_t ctx_cap_ = 0;     // [2n][77][ctx] cond then uncond

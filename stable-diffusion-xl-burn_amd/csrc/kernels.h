@@ -267,7 +267,14 @@ void launch_causal_mask(float* out, int n, hipStream_t s);
 void launch_conditioning_embedding(const float* pooled, int E, const int* vals, int w, int dim, float* out, int n, hipStream_t s);
 
 // DDIM step table entry (host f64 -> f32): stablediffusion/mod.rs:407-428
-struct StepCoef { float t; float sqrt_a; float sqrt_1ma; float sqrt_ap; float sqrt_1map; float cfg; float pad0, pad1; };
+// sigma: the DDIM eta term of :427 (0 on every explicit-noise trajectory; then sqrt_1map = sqrt(1 - ap), else sqrt(1 - ap - sigma^2))
+struct StepCoef { float t; float sqrt_a; float sqrt_1ma; float sqrt_ap; float sqrt_1map; float cfg; float sigma; float pad1; };
+// draw numbers of the seeded noise (counter word 1 of the generator); the public header carries the same values as SDXL_DRAW_*
+constexpr uint32_t kDrawInitial = 0;
+constexpr uint32_t draw_blend(uint32_t i) { return 1u + 2u * i; }
+constexpr uint32_t draw_sigma(uint32_t i) { return 2u + 2u * i; }
+constexpr int kMaxSeeds = 8;   // batch entries of one trajectory (Diffuser::diffuse: B <= 8)
+struct DdimSeeds { uint64_t v[kMaxSeeds]; };   // per-entry seeds, passed by value in the kernel arguments
 // eps = u + (c-u)*cfg (or c when !use_cfg); x0 = (x - eps*sqrt_1ma)/sqrt_a; x = x0*sqrt_ap + eps*sqrt_1map
 // eps_nhwc: UNet output [Bu][HW][4] fp32-or-T rows; latent NCHW fp32 [n][4][HW].  Also refreshes the UNet input
 // (NHWC, replicated for cond/uncond) and advances *step_idx.
@@ -278,12 +285,18 @@ struct DdimParams {
   int n, HW; int use_cfg;
   // inpainting (optional): before the *next* UNet call latent = mask ? latent : ref*sqrt_a(next)+noise*sqrt_1ma(next)
   const float* ref; const unsigned char* mask; const float* step_noise; int n_steps_total;
+  // seeded mode: the blend noise (draw_blend(next)) and the sigma noise (draw_sigma(idx)) are drawn in the thread from
+  // seeds[b]; step_noise is not read.  seeded = 0 is the explicit-noise kernel, which never looks at sigma.
+  int seeded; DdimSeeds seeds;
   void* unet_in; int in_dt; int in_ld; int in_rep;   // next UNet input NHWC [in_rep*n][HW][4]
   float* t_out;              // device scalar(s): timestep for the next UNet call
 };
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
 // input and timestep.  do_update=1: DDIM update with table[*step_idx], blend for the next step, then advances.
 void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s);
+// gen_noise (:378-388) with a seed: out [n][4][HW] fp32, entry b from seeds[b] (host array, n <= kMaxSeeds per launch), the
+// same values the seeded ddim kernel draws in registers for (seed, hw, draw)
+void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n, int HW, hipStream_t s);
 // noised = latent*sa + noise*sb   (refine_latent :363-367)
 void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb, size_t n, hipStream_t s);
 // image post-process (stablediffusion/mod.rs:210-230): u8 = trunc(clamp(((x+1)/2)*255, 0, 255)), NHWC rows of 3

@@ -7,10 +7,12 @@
 //   * alpha lookups (:407-412, two blocking device->host scalar reads per step in the reference) become a per-trajectory
 //     coefficient table computed on the host in f64 and uploaded once; the step index lives on the device, so every
 //     iteration is the same captured graph + one fused CFG/DDIM/inpaint kernel, with no host sync inside the loop.
-//   * noise is an explicit input (the reference's generator is unseeded, gen_noise :378-388); sigma = 0 so the per-step
-//     gen_noise()*sigma term (:427) contributes nothing and is not drawn.
+//   * noise is an explicit input (the reference's generator is unseeded, gen_noise :378-388) with sigma = 0, or, in the
+//     *_seeded calls, drawn on the device from one seed per batch entry: the initial latent by a fill kernel, the inpainting
+//     blend (:463) and the gen_noise()*sigma term (:427, sigma from eta) in the registers of the per-step kernel.
 #include "engine.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace sdxl {
@@ -34,7 +36,7 @@ Diffuser::Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSour
   SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
 }
 Diffuser::~Diffuser() {
-  for (void* p : {(void*)latent_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_})
+  for (void* p : {(void*)latent_, (void*)noise_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_})
     if (p) (void)hipFree(p);
 }
 
@@ -45,13 +47,15 @@ static constexpr bool g_debug_no_cfg = false;
 #endif
 
 void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale,
-                       const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s) {
+                       const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s,
+                       const uint64_t* seeds, double eta) {
   // diffuse_latent :390-432 / diffuse_latent_with_inpainting :434-483
   UNet& u = *unet_;
   const UNetCfg& uc = u.cfg();
   const bool single = is_refiner_ || g_debug_no_cfg;   // debug knob: conditional branch only (concurrency experiments)
   const int n = c.n, B = single ? n : 2 * n;
   SDXL_REQUIRE(n >= 1 && B <= 8, "batch out of range");
+  static_assert(kMaxSeeds >= 8, "one seed per batch entry");
   const int h = c.height / 8, w = c.width / 8, HW = h * w;
   const int ctx_dim = uc.context_dim, adm = uc.adm_in_channels;
   // --- contexts of the batched CFG pair (forward_diffuser :506-537)
@@ -96,7 +100,10 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
     k.sqrt_a = (float)std::sqrt(a);
     k.sqrt_1ma = (float)std::sqrt(1.0 - a);
     k.sqrt_ap = (float)std::sqrt(ap);
-    k.sqrt_1map = (float)std::sqrt(1.0 - ap - 0.0);
+    // sigma (:423 pins it to 0.0): standard DDIM eta; ap = 1 on the last iteration, so nothing is drawn there
+    const double sigma = eta == 0.0 ? 0.0 : eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - a / ap);
+    k.sqrt_1map = (float)std::sqrt(std::max(1.0 - ap - sigma * sigma, 0.0));
+    k.sigma = (float)sigma;
     k.cfg = (float)cfg_scale;
     tab[i] = k;
   }
@@ -117,6 +124,10 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   p.ref = reference; p.mask = mask; p.step_noise = step_noise; p.n_steps_total = iters;
   p.unet_in = unet_in; p.in_dt = u.input_dt(); p.in_ld = uc.in_channels; p.in_rep = single ? 1 : 2;
   p.t_out = t_dev_;
+  if (seeds) {
+    p.seeded = 1;
+    for (int b = 0; b < n; ++b) p.seeds.v[b] = seeds[b];
+  }
   launch_ddim_step(p, 0, s);
 
   std::vector<hipEvent_t> ev;
@@ -177,6 +188,46 @@ void Diffuser::refine_latent(const float* latent, const Conditioning& c, double 
   const double a = alphas_[n_train_ - step_start];
   launch_axpby(latent_, latent, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
   diffuse(latent_, c, step_start, n_steps, cfg_scale, nullptr, nullptr, nullptr, s);
+  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+// The seeded forms: same trajectories, noise from launch_seeded_noise / the seeded per-step kernel.
+void Diffuser::sample_latent_seeded(const Conditioning& c, double cfg_scale, int n_steps, const uint64_t* seeds, double eta,
+                                    float* out, hipStream_t s) {
+  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
+  const int HW = (c.height / 8) * (c.width / 8);
+  const size_t elems = (size_t)c.n * 4 * HW;
+  ensure_latent(latent_, latent_cap_, elems);
+  launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
+  diffuse(latent_, c, 0, n_steps, cfg_scale, nullptr, nullptr, nullptr, s, seeds, eta);
+  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+void Diffuser::sample_latent_inpaint_seeded(const Conditioning& c, double cfg_scale, int n_steps, const float* reference,
+                                            const unsigned char* mask, const uint64_t* seeds, double eta, float* out,
+                                            hipStream_t s) {
+  SDXL_REQUIRE(reference && mask, "inpainting needs reference and mask");
+  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
+  const int HW = (c.height / 8) * (c.width / 8);
+  const size_t elems = (size_t)c.n * 4 * HW;
+  ensure_latent(latent_, latent_cap_, elems);
+  launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
+  diffuse(latent_, c, 0, n_steps, cfg_scale, reference, mask, nullptr, s, seeds, eta);
+  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+void Diffuser::refine_latent_seeded(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
+                                    const uint64_t* seeds, double eta, float* out, hipStream_t s) {
+  SDXL_REQUIRE(step_start >= 1 && step_start <= n_train_, "step_start out of range");
+  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
+  const int HW = (c.height / 8) * (c.width / 8);
+  const size_t elems = (size_t)c.n * 4 * HW;
+  ensure_latent(latent_, latent_cap_, elems);
+  ensure_latent(noise_, noise_cap_, elems);
+  launch_seeded_noise(noise_, seeds, kDrawInitial, c.n, HW, s);
+  const double a = alphas_[n_train_ - step_start];
+  launch_axpby(latent_, latent, (float)std::sqrt(a), noise_, (float)std::sqrt(1.0 - a), elems, s);
+  diffuse(latent_, c, step_start, n_steps, cfg_scale, nullptr, nullptr, nullptr, s, seeds, eta);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
