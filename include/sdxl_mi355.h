@@ -218,6 +218,32 @@ int sdxl_refine_latent_seeded(sdxl_diffuser* d, void* stream, const float* laten
                               double eta, float* out_latent);
 /* number of UNet evaluations of `(0..n_train-step_start).rev().step_by(n_train/n_steps)` (:400-406): 30 -> 31 */
 int sdxl_step_count(int n_steps, int step_start, int n_train_steps);
+/* ---- solver: the update behind every UNet evaluation, a per-handle option all six trajectory calls above honour.
+ * SDXL_SOLVER_DDIM (default) is the reference's loop.  SDXL_SOLVER_DPMPP_2M is DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2;
+ * eta > 0: its SDE form, k-diffusion's dpmpp_2m_sde with the midpoint rule, in alpha / sigma terms) on the SAME schedule: one
+ * UNet evaluation per iteration, second-order accurate, so it needs about half of DDIM's iterations.  With a = alphas[t_i],
+ * ap = alphas[t_i - step] (1 on the last iteration), alpha = sqrt(a), sigma = sqrt(1-a), lambda = ln(alpha / sigma), primes
+ * for ap, h = lambda' - lambda, r = h_prev / h, e the CFG-combined noise prediction, x0 = (x - sigma e) / alpha, x0p the x0 of
+ * the previous iteration and z a unit normal:
+ *     x' = c_x x + c_0 x0 + c_1 x0p + c_z z
+ *     A   = -expm1(-(1 + eta) h)      c_x = (sigma' / sigma) exp(-eta h)      c_z = sigma' sqrt(-expm1(-2 eta h))
+ *     second order:  c_0 = alpha' A (1 + 1/(2r)),  c_1 = -alpha' A / (2r)
+ *     first order:   c_0 = alpha' A,               c_1 = 0
+ * First order on iteration 0 of a trajectory (refine_latent's included: no history) and where ap == 1 (h infinite: the row is
+ * (0, 1, 0, 0), the iteration returns x0); second order everywhere else.  At eta = 0 a first-order row equals DDIM's.  The
+ * draw numbers do not change: SDXL_DRAW_SIGMA(i) is the z of iteration i for both solvers, drawn where c_z != 0; with explicit
+ * noise eta is 0.  Inpainting keeps its blend in front of every iteration; x0p is the x0 computed from the blended state. */
+enum { SDXL_SOLVER_DDIM = 0, SDXL_SOLVER_DPMPP_2M = 1 };
+/* unknown value: SDXL_ERR_INVALID ("solver" in sdxl_last_error), the handle keeps its solver */
+int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver);
+int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out);
+/* host logic only, no device needed: (c_x, c_0, c_1, c_z) as f64 per iteration, out[4*i ..], for i < sdxl_step_count(n_steps,
+ * step_start, n_train_steps) <= capacity_steps -- the numbers the sampler rounds to fp32 for its DPM-Solver++(2M) table.  For
+ * SDXL_SOLVER_DDIM the same four numbers of the DDIM update: (sqrt(1-ap-sigma_t^2) / sigma, sqrt(ap) - sqrt(1-ap-sigma_t^2)
+ * alpha / sigma, 0, sigma_t).  eta outside [0, 1] (NaN included), n_steps outside 1..n_train_steps, step_start outside
+ * 0..n_train_steps-1, capacity_steps too small, an unknown solver, alphas outside (0, 1): SDXL_ERR_INVALID, out untouched. */
+int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver,
+                             double eta, double* out, int capacity_steps);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

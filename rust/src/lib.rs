@@ -325,6 +325,14 @@ pub const fn draw_blend(i: u32) -> u32 {
 pub const fn draw_sigma(i: u32) -> u32 {
     2 + 2 * i
 }
+/// the update behind every UNet evaluation (`SDXL_SOLVER_*`): a per-handle option all trajectory methods honour
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Solver {
+    /// the reference's DDIM loop (`:390-432`), the default
+    Ddim = ffi::SDXL_SOLVER_DDIM as isize,
+    /// DPM-Solver++(2M) on the same schedule, with `eta > 0` its SDE form: second order at one UNet evaluation per iteration
+    Dpmpp2M = ffi::SDXL_SOLVER_DPMPP_2M as isize,
+}
 impl<B: BurnBackend> Drop for Diffuser<B> {
     fn drop(&mut self) {
         unsafe { ffi::sdxl_diffuser_destroy(self.raw) };
@@ -410,6 +418,15 @@ impl<B: BurnBackend> Diffuser<B> {
     /// unseeded `Tensor::random` path.
     pub fn set_seed(&self, seed: Option<u64>, eta: f64) {
         self.seed.set(seed.map(|s| (s, eta)));
+    }
+    /// every following trajectory of this handle runs `solver` (`sdxl_diffuser_set_solver`)
+    pub fn set_solver(&self, solver: Solver) {
+        check(unsafe { ffi::sdxl_diffuser_set_solver(self.raw, solver as c_int) });
+    }
+    pub fn solver(&self) -> Solver {
+        let mut v: c_int = 0;
+        check(unsafe { ffi::sdxl_diffuser_get_solver(self.raw, &mut v) });
+        if v == Solver::Dpmpp2M as c_int { Solver::Dpmpp2M } else { Solver::Ddim }
     }
     fn entry_seeds(seed: u64, conditioning: &Conditioning<B>) -> Vec<u64> {
         let [n, _, _] = conditioning.context_full.dims();

@@ -80,6 +80,7 @@ ABI_SYMBOLS = [
     "sdxl_sample_latent", "sdxl_sample_latent_with_inpainting", "sdxl_refine_latent", "sdxl_step_count",
     "sdxl_diffuser_enable_step_timing", "sdxl_diffuser_step_times", "sdxl_diffuser_set_trace",
     "sdxl_gen_noise", "sdxl_sample_latent_seeded", "sdxl_sample_latent_with_inpainting_seeded", "sdxl_refine_latent_seeded",
+    "sdxl_diffuser_set_solver", "sdxl_diffuser_get_solver", "sdxl_solver_coefficients",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -120,6 +121,11 @@ def lib() -> ctypes.CDLL:
                      "sdxl_comm_destroy"):
             getattr(l, name).restype = None
             getattr(l, name).argtypes = [ctypes.c_void_p]
+        if hasattr(l, "sdxl_solver_coefficients"):   # SDXL_LIB_PATH may name an older build (tools/): it fails at the call, not at the load
+            l.sdxl_diffuser_set_solver.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_diffuser_get_solver.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+            l.sdxl_solver_coefficients.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                   ctypes.c_void_p, ctypes.c_int]
         _lib = l
     return _lib
 
@@ -598,6 +604,31 @@ def draw_sigma(i: int) -> int:
     return 2 + 2 * i
 
 
+SOLVER_DDIM = 0         # SDXL_SOLVER_DDIM: the reference's loop (default)
+SOLVER_DPMPP_2M = 1     # SDXL_SOLVER_DPMPP_2M: DPM-Solver++(2M), with eta > 0 its SDE form
+_SOLVER_NAMES = {"ddim": SOLVER_DDIM, "dpmpp_2m": SOLVER_DPMPP_2M}
+
+
+def _solver(solver) -> int:
+    """a name of _SOLVER_NAMES or an SDXL_SOLVER_* value (an unknown value travels on: the engine reports it)"""
+    if isinstance(solver, str):
+        if solver not in _SOLVER_NAMES:
+            raise EngineError(f"unknown solver {solver!r}: one of {sorted(_SOLVER_NAMES)}")
+        return _SOLVER_NAMES[solver]
+    return int(solver)
+
+
+def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp_2m", eta: float = 0.0) -> np.ndarray:
+    """sdxl_solver_coefficients: float64 [iterations, 4] rows (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z, the
+    table the sampler runs (host logic: no GPU needed)"""
+    a = np.ascontiguousarray(alphas, dtype=np.float32)
+    iters = max(step_count(n_steps, step_start, int(a.shape[0])), 0) if n_steps >= 1 else 0
+    out = np.zeros((iters, 4), dtype=np.float64)
+    _check(lib().sdxl_solver_coefficients(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), n_steps, step_start, _solver(solver),
+                                         float(eta), out.ctypes.data_as(ctypes.c_void_p), iters))
+    return out
+
+
 def _seeds(seeds, n: int):
     """host uint64 array [n] (None stays NULL: the engine reports it)"""
     if seeds is None:
@@ -717,6 +748,16 @@ class Diffuser:
         _check(lib().sdxl_refine_latent(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
                                        step_start, n_steps, pn, ctypes.c_void_p(out.data_ptr())))
         return out
+
+    def set_solver(self, solver):
+        """"ddim" (default) or "dpmpp_2m" (or the SOLVER_* value): the update every following trajectory of this handle runs"""
+        _check(lib().sdxl_diffuser_set_solver(self.h, _solver(solver)))
+
+    @property
+    def solver(self) -> str:
+        v = ctypes.c_int(-1)
+        _check(lib().sdxl_diffuser_get_solver(self.h, ctypes.byref(v)))
+        return {v: k for k, v in _SOLVER_NAMES.items()}[v.value]
 
     def enable_step_timing(self, enabled: bool = True):
         _check(lib().sdxl_diffuser_enable_step_timing(self.h, int(enabled)))

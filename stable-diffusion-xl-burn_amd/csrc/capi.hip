@@ -842,6 +842,38 @@ int sdxl_step_count(int n_steps, int step_start, int n_train) {
   try { return (int)Diffuser::step_schedule(n_steps, step_start, n_train).size(); }
   catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+// solver: a per-handle option; an unknown value is an argument error and leaves the handle as it was
+int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return fail(SDXL_ERR_INVALID, "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)");
+  API_BEGIN
+  d->d->set_solver(solver);
+  API_END
+}
+int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out) {
+  if (!d || !solver_out) return fail(SDXL_ERR_INVALID, "null argument");
+  *solver_out = d->d->solver();
+  return SDXL_OK;
+}
+// host logic of the sampler's coefficient table -- no device needed; the function Diffuser::diffuse fills its DPM-Solver++(2M) table from
+int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta,
+                             double* out, int capacity_steps) {
+  if (!alphas_cumprod_host || !out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return fail(SDXL_ERR_INVALID, "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)");
+  if (!(eta >= 0.0 && eta <= 1.0)) return fail(SDXL_ERR_INVALID, "eta must be a finite value in [0, 1]");
+  if (n_train_steps < 1 || n_steps < 1 || n_steps > n_train_steps) return fail(SDXL_ERR_INVALID, "n_steps out of range (1..n_train_steps)");
+  if (step_start < 0 || step_start >= n_train_steps) return fail(SDXL_ERR_INVALID, "step_start out of range (0..n_train_steps-1)");
+  const int iters = (int)Diffuser::step_schedule(n_steps, step_start, n_train_steps).size();
+  if (capacity_steps < iters) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than sdxl_step_count");
+  for (int i = 0; i < n_train_steps; ++i)
+    if (!(alphas_cumprod_host[i] > 0.f && alphas_cumprod_host[i] < 1.f)) return fail(SDXL_ERR_INVALID, "alphas_cumprod outside (0, 1)");
+  API_BEGIN
+  std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
+  std::vector<double> rows((size_t)4 * iters);
+  Diffuser::solver_coefficients(alphas.data(), n_train_steps, n_steps, step_start, solver, eta, rows.data());
+  std::copy(rows.begin(), rows.end(), out);
+  API_END
+}
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled) {
   API_BEGIN
   SDXL_REQUIRE(d != nullptr, "null argument");

@@ -626,6 +626,77 @@ __global__ void ddim_kernel(const DdimParams p, int do_update) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) st_f(p.unet_in, ((size_t)(r * p.n + b) * p.HW + hw) * p.in_ld + c, p.in_dt, x[c]);
 }
+// DPM-Solver++(2M) (SDE form where c_z != 0) in the same place: the table holds the 2M layout of StepCoef, p.hist the data prediction of the
+// previous iteration.  e and x0 exactly as in ddim_kernel; x0 is what the history keeps -- with inpainting the one computed from the blended
+// state.  The update, the same on all four channels, one rounding per line:
+//     acc = c_1 * x0p                (x0p read only where c_1 != 0: a first-order row never looks at the history, whatever it holds)
+//     acc = fma(x0, c_0, acc)
+//     acc = fma(x,  c_x, acc)
+//     acc = fma(z,  c_z, acc)        (SEEDED and c_z != 0 only; z = seeded_normal4(seed, hw, draw_sigma(idx)), never stored)
+// The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.  Load, CFG, blend and store restate ddim_kernel's lines
+// instead of sharing them through a helper: ddim_kernel stays the text it was compiled from when the fixtures were produced.
+template <bool SEEDED>
+__global__ void dpmpp2m_kernel(const DdimParams p, int do_update) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)p.n * p.HW) return;
+  const int b = i / p.HW;
+  const int hw = i - (size_t)b * p.HW;
+  const int idx = *p.step_idx;
+  const int next = do_update ? idx + 1 : 0;
+  float x[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = p.latent[((size_t)b * 4 + c) * p.HW + hw];
+  if (do_update) {
+    const StepCoef k = p.table[idx];
+    float x0p[4] = {0.f, 0.f, 0.f, 0.f};
+    if (k.c_1 != 0.f) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
+      float e = ec;
+      if (p.use_cfg) {
+        const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
+        e = __builtin_fmaf(ec - eu, k.cfg, eu);
+      }
+      const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
+      p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
+      float acc = k.c_1 * x0p[c];
+      acc = __builtin_fmaf(x0, k.c_0, acc);
+      x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+    }
+    if constexpr (SEEDED) {
+      if (k.c_z != 0.f) {
+        float z[4];
+        seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], k.c_z, x[c]);
+      }
+    }
+  }
+  if (p.mask && next < p.n_steps_total) {
+    const StepCoef kn = p.table[next];
+    float z[4];
+    if constexpr (SEEDED) seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_blend((uint32_t)next), z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const size_t e = ((size_t)b * 4 + c) * p.HW + hw;
+      if (!p.mask[e]) {
+        float zn;
+        if constexpr (SEEDED) zn = z[c]; else zn = p.step_noise[(size_t)next * p.n * 4 * p.HW + e];
+        x[c] = p.ref[e] * kn.sqrt_a + zn * kn.sqrt_1ma;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) p.latent[((size_t)b * 4 + c) * p.HW + hw] = x[c];
+  for (int r = 0; r < p.in_rep; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) st_f(p.unet_in, ((size_t)(r * p.n + b) * p.HW + hw) * p.in_ld + c, p.in_dt, x[c]);
+}
 __global__ void ddim_advance_kernel(const StepCoef* table, int* step_idx, float* t_out, int do_update) {
   const int next = do_update ? *step_idx + 1 : 0;
   *step_idx = next;
@@ -633,8 +704,14 @@ __global__ void ddim_advance_kernel(const StepCoef* table, int* step_idx, float*
 }
 void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s) {
   const size_t total = (size_t)p.n * p.HW;
-  if (p.seeded) hipLaunchKernelGGL(ddim_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, s, p, do_update);
-  else hipLaunchKernelGGL(ddim_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, p, do_update);
+  const dim3 grid((total + 255) / 256), block(256);
+  if (p.solver == kSolverDpmpp2M) {
+    if (p.seeded) hipLaunchKernelGGL(dpmpp2m_kernel<true>, grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL(dpmpp2m_kernel<false>, grid, block, 0, s, p, do_update);
+  } else {
+    if (p.seeded) hipLaunchKernelGGL(ddim_kernel<true>, grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL(ddim_kernel<false>, grid, block, 0, s, p, do_update);
+  }
   hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, do_update);
 }
 __global__ void axpby_kernel(float* dst, const float* a, float sa, const float* b, float sb, size_t n) {

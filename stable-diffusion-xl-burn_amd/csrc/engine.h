@@ -565,6 +565,13 @@ class Diffuser {
   void refine_latent_seeded(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                             const uint64_t* seeds, double eta, float* out, hipStream_t s);
   static std::vector<int> step_schedule(int n_steps, int step_start, int n_train);
+  // (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z per iteration of step_schedule, f64, out[4 * i ..] (host logic only;
+  // formulas in include/sdxl_mi355.h, sdxl_solver_coefficients).  kSolverDpmpp2M: what diffuse() rounds into its table.  kSolverDdim: the
+  // DDIM update folded into the same four numbers.  alphas: n_train values in (0, 1).
+  static void solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out);
+  // kSolverDdim (default) or kSolverDpmpp2M: the update every following trajectory of this handle runs
+  void set_solver(int solver);
+  int solver() const { return solver_; }
   std::vector<float> step_ms;   // per-iteration GPU time of the last trajectory (hipEvent), for "UNet step ms p50"
   bool time_steps = false;
   // parity instrumentation: after DDIM iteration i the latent [n,4,h,w] is copied to trace + i * numel (device, caller-owned)
@@ -572,6 +579,7 @@ class Diffuser {
   float* trace = nullptr; int trace_cap = 0;
 
  private:
+  void ensure_state(size_t elems);   // latent_ (and hist_ under kSolverDpmpp2M) hold a trajectory of `elems` values
   void diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale, const float* reference,
                const unsigned char* mask, const float* step_noise, hipStream_t s, const uint64_t* seeds = nullptr, double eta = 0.0);
   std::unique_ptr<UNet> unet_;
@@ -581,6 +589,8 @@ class Diffuser {
   // device state
   float* latent_ = nullptr; size_t latent_cap_ = 0;
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
+  float* hist_ = nullptr; size_t hist_cap_ = 0;       // kSolverDpmpp2M: x0 of the previous iteration [n,4,h,w], allocated with the latent
+  int solver_ = kSolverDdim;
   StepCoef* table_ = nullptr; int table_cap_ = 0;
   int* step_idx_ = nullptr; float* t_dev_ = nullptr;
   float* ctx_buf_ = nullptr; size_t ctx_cap_ = 0;     // [2n][77][ctx] cond then uncond

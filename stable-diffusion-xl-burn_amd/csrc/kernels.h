@@ -268,7 +268,19 @@ void launch_conditioning_embedding(const float* pooled, int E, const int* vals, 
 
 // DDIM step table entry (host f64 -> f32): stablediffusion/mod.rs:407-428
 // sigma: the DDIM eta term of :427 (0 on every explicit-noise trajectory; then sqrt_1map = sqrt(1 - ap), else sqrt(1 - ap - sigma^2))
-struct StepCoef { float t; float sqrt_a; float sqrt_1ma; float sqrt_ap; float sqrt_1map; float cfg; float sigma; float pad1; };
+// The DPM-Solver++(2M) table (kSolverDpmpp2M) is the second layout of the same 32 bytes: t, sqrt_a, sqrt_1ma and cfg as in the DDIM one
+// (x0, the inpainting blend and ddim_advance_kernel read them alike), and the four coefficients of x' = c_x x + c_0 x0 + c_1 x0p + c_z z
+// (include/sdxl_mi355.h, sdxl_solver_coefficients) where the DDIM layout keeps its three update terms and its padding.
+struct StepCoef {
+  float t; float sqrt_a; float sqrt_1ma;
+  union { float sqrt_ap; float c_0; };
+  union { float sqrt_1map; float c_x; };
+  float cfg;
+  union { float sigma; float c_z; };
+  float c_1;     // padding of the DDIM layout (0)
+};
+static_assert(sizeof(StepCoef) == 32, "one table entry is eight floats in both layouts");
+constexpr int kSolverDdim = 0, kSolverDpmpp2M = 1;   // SDXL_SOLVER_* of the public header
 // draw numbers of the seeded noise (counter word 1 of the generator); the public header carries the same values as SDXL_DRAW_*
 constexpr uint32_t kDrawInitial = 0;
 constexpr uint32_t draw_blend(uint32_t i) { return 1u + 2u * i; }
@@ -290,9 +302,12 @@ struct DdimParams {
   int seeded; DdimSeeds seeds;
   void* unet_in; int in_dt; int in_ld; int in_rep;   // next UNet input NHWC [in_rep*n][HW][4]
   float* t_out;              // device scalar(s): timestep for the next UNet call
+  // kSolverDpmpp2M: table holds the 2M layout and hist [n][4][HW] fp32 the x0 of the previous iteration (read where c_1 != 0, written by
+  // every update); kSolverDdim reads neither
+  int solver; float* hist;
 };
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
-// input and timestep.  do_update=1: DDIM update with table[*step_idx], blend for the next step, then advances.
+// input and timestep.  do_update=1: DDIM (or, p.solver, DPM-Solver++(2M)) update with table[*step_idx], blend for the next step, then advances.
 void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s);
 // gen_noise (:378-388) with a seed: out [n][4][HW] fp32, entry b from seeds[b] (host array, n <= kMaxSeeds per launch), the
 // same values the seeded ddim kernel draws in registers for (seed, hw, draw)

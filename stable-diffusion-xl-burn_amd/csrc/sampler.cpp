@@ -10,6 +10,8 @@
 //   * noise is an explicit input (the reference's generator is unseeded, gen_noise :378-388) with sigma = 0, or, in the
 //     *_seeded calls, drawn on the device from one seed per batch entry: the initial latent by a fill kernel, the inpainting
 //     blend (:463) and the gen_noise()*sigma term (:427, sigma from eta) in the registers of the per-step kernel.
+//   * the update itself is a per-handle choice (set_solver): the reference's DDIM, or DPM-Solver++(2M) on the same schedule, same table
+//     mechanism and same fused kernel position, with one more latent-sized buffer for the previous data prediction.
 #include "engine.h"
 
 #include <algorithm>
@@ -36,8 +38,62 @@ Diffuser::Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSour
   SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
 }
 Diffuser::~Diffuser() {
-  for (void* p : {(void*)latent_, (void*)noise_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_})
+  for (void* p : {(void*)latent_, (void*)noise_, (void*)hist_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_})
     if (p) (void)hipFree(p);
+}
+
+// sigma (:423 pins it to 0.0): standard DDIM eta; ap = 1 on the last iteration, so nothing is drawn there
+static void ddim_terms(double a, double ap, double eta, double& sqrt_ap, double& sqrt_1map, double& sigma) {
+  sigma = eta == 0.0 ? 0.0 : eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - a / ap);
+  sqrt_ap = std::sqrt(ap);
+  sqrt_1map = std::sqrt(std::max(1.0 - ap - sigma * sigma, 0.0));
+}
+
+void Diffuser::set_solver(int solver) {
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
+  solver_ = solver;
+}
+
+void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out) {
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
+  const std::vector<int> ts = step_schedule(n_steps, step_start, n_train);
+  const int step_size = n_train / n_steps;
+  double h_prev = 0.0;
+  bool have_prev = false;       // false on iteration 0: no history, first order
+  for (size_t i = 0; i < ts.size(); ++i) {
+    const int t = ts[i];
+    const double a = alphas[t];
+    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+    SDXL_REQUIRE(a > 0.0 && a < 1.0 && ap > 0.0 && ap <= 1.0, "alphas_cumprod outside (0, 1)");
+    const double alpha = std::sqrt(a), sigma = std::sqrt(1.0 - a);
+    double* c = out + 4 * i;     // c_x, c_0, c_1, c_z
+    if (solver == kSolverDdim) {
+      double sqrt_ap, sqrt_1map, sigma_t;
+      ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma_t);
+      c[0] = sqrt_1map / sigma; c[1] = sqrt_ap - sqrt_1map * alpha / sigma; c[2] = 0.0; c[3] = sigma_t;
+      continue;
+    }
+    if (ap == 1.0) {             // h is infinite: the step lands on the data prediction
+      c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[3] = 0.0;
+      have_prev = false;
+      continue;
+    }
+    const double alpha_p = std::sqrt(ap), sigma_p = std::sqrt(1.0 - ap);
+    const double h = std::log(alpha_p / sigma_p) - std::log(alpha / sigma);
+    const double A = -std::expm1(-(1.0 + eta) * h);
+    c[0] = (sigma_p / sigma) * std::exp(-eta * h);
+    c[3] = sigma_p * std::sqrt(-std::expm1(-2.0 * eta * h));
+    if (have_prev) {
+      const double r = h_prev / h;
+      c[1] = alpha_p * A * (1.0 + 1.0 / (2.0 * r));
+      c[2] = -alpha_p * A / (2.0 * r);
+    } else {
+      c[1] = alpha_p * A;
+      c[2] = 0.0;
+    }
+    h_prev = h;
+    have_prev = true;
+  }
 }
 
 #ifdef SDXL_MEASURE
@@ -91,6 +147,11 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   const int iters = (int)ts.size();
   const int step_size = n_train_ / n_steps;
   std::vector<StepCoef> tab(iters + 1);
+  std::vector<double> c2m;
+  if (solver_ == kSolverDpmpp2M) {
+    c2m.resize((size_t)4 * iters);
+    solver_coefficients(alphas_.data(), n_train_, n_steps, step_start, solver_, eta, c2m.data());
+  }
   for (int i = 0; i < iters; ++i) {
     const int t = ts[i];
     const double a = alphas_[t];
@@ -99,12 +160,16 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
     k.t = (float)t;
     k.sqrt_a = (float)std::sqrt(a);
     k.sqrt_1ma = (float)std::sqrt(1.0 - a);
-    k.sqrt_ap = (float)std::sqrt(ap);
-    // sigma (:423 pins it to 0.0): standard DDIM eta; ap = 1 on the last iteration, so nothing is drawn there
-    const double sigma = eta == 0.0 ? 0.0 : eta * std::sqrt((1.0 - ap) / (1.0 - a)) * std::sqrt(1.0 - a / ap);
-    k.sqrt_1map = (float)std::sqrt(std::max(1.0 - ap - sigma * sigma, 0.0));
-    k.sigma = (float)sigma;
     k.cfg = (float)cfg_scale;
+    if (solver_ == kSolverDpmpp2M) {
+      k.c_x = (float)c2m[4 * i]; k.c_0 = (float)c2m[4 * i + 1]; k.c_1 = (float)c2m[4 * i + 2]; k.c_z = (float)c2m[4 * i + 3];
+    } else {
+      double sqrt_ap, sqrt_1map, sigma;
+      ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma);
+      k.sqrt_ap = (float)sqrt_ap;
+      k.sqrt_1map = (float)sqrt_1map;
+      k.sigma = (float)sigma;
+    }
     tab[i] = k;
   }
   tab[iters] = StepCoef{};
@@ -124,6 +189,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   p.ref = reference; p.mask = mask; p.step_noise = step_noise; p.n_steps_total = iters;
   p.unet_in = unet_in; p.in_dt = u.input_dt(); p.in_ld = uc.in_channels; p.in_rep = single ? 1 : 2;
   p.t_out = t_dev_;
+  p.solver = solver_; p.hist = hist_;
   if (seeds) {
     p.seeded = 1;
     for (int b = 0; b < n; ++b) p.seeds.v[b] = seeds[b];
@@ -158,11 +224,15 @@ static void ensure_latent(float*& buf, size_t& cap, size_t elems) {
     cap = elems;
   }
 }
+void Diffuser::ensure_state(size_t elems) {
+  ensure_latent(latent_, latent_cap_, elems);
+  if (solver_ == kSolverDpmpp2M) ensure_latent(hist_, hist_cap_, elems);
+}
 
 void Diffuser::sample_latent(const Conditioning& c, double cfg_scale, int n_steps, const float* noise0, float* out,
                              hipStream_t s) {
   const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   SDXL_HIP(hipMemcpyAsync(latent_, noise0, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
   diffuse(latent_, c, 0, n_steps, cfg_scale, nullptr, nullptr, nullptr, s);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -173,7 +243,7 @@ void Diffuser::sample_latent_inpaint(const Conditioning& c, double cfg_scale, in
                                      hipStream_t s) {
   SDXL_REQUIRE(reference && mask && step_noise, "inpainting needs reference, mask and per-step noise");
   const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   SDXL_HIP(hipMemcpyAsync(latent_, noise0, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
   diffuse(latent_, c, 0, n_steps, cfg_scale, reference, mask, step_noise, s);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -184,7 +254,7 @@ void Diffuser::refine_latent(const float* latent, const Conditioning& c, double 
   // :355-376: re-noise the finished latent to t = n_train - step_start, then denoise from there
   SDXL_REQUIRE(step_start >= 1 && step_start <= n_train_, "step_start out of range");
   const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   const double a = alphas_[n_train_ - step_start];
   launch_axpby(latent_, latent, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
   diffuse(latent_, c, step_start, n_steps, cfg_scale, nullptr, nullptr, nullptr, s);
@@ -197,7 +267,7 @@ void Diffuser::sample_latent_seeded(const Conditioning& c, double cfg_scale, int
   SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
   diffuse(latent_, c, 0, n_steps, cfg_scale, nullptr, nullptr, nullptr, s, seeds, eta);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -210,7 +280,7 @@ void Diffuser::sample_latent_inpaint_seeded(const Conditioning& c, double cfg_sc
   SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
   diffuse(latent_, c, 0, n_steps, cfg_scale, reference, mask, nullptr, s, seeds, eta);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -222,7 +292,7 @@ void Diffuser::refine_latent_seeded(const float* latent, const Conditioning& c, 
   SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_latent(latent_, latent_cap_, elems);
+  ensure_state(elems);
   ensure_latent(noise_, noise_cap_, elems);
   launch_seeded_noise(noise_, seeds, kDrawInitial, c.n, HW, s);
   const double a = alphas_[n_train_ - step_start];
