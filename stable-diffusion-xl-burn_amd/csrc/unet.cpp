@@ -297,7 +297,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
   WeightBuilder wb(specs, src, warena_, cdt_, st);
   // A form that packs a parameter's values as f16 (StPlan) must get f16 values (the reference's records are, src/bin/sample/main.rs:37): on other
   // parameters it would round the weights as well and leave the mode's error bound (0.029 against 0.0212).  Checked here on exactly those
-  // tensors; a model that does not qualify falls back to F32_SPLIT_MIX's classes (capi.hip mix_of) -- plain F32_SPLIT for a mode without f16-OPERAND classes,
+  // tensors; a model that does not qualify falls back to F32_SPLIT_MIX's classes (capi_internal.h mix_of) -- plain F32_SPLIT for a mode without f16-OPERAND classes,
   // SDXL_DTYPE_F32_SPLIT_F16W -- and mix_classes() tells.
   // Not applied to the A/B knob "mix_classes" (the frontier tools run those maps on fp32 weights on purpose) nor on replicas built from an empty
   // source (they receive rank 0's arena: the caller compares rank 0's mix_classes() with the mode before the broadcast, bench.py does).

@@ -13,8 +13,8 @@ rounding the kernels perform is emulated or bounded per element (DESIGN 5.1 list
     epilogue forms rstd (x W') - rstd mu cs + b' (igemm_common.h:211-219) with (mu, rstd) of the f16 rows (the identity GEMM's stat_out).
     Emulated exactly in fp64 (W' bit-exact on the host).
   * GELU: gelu_erf2 (igemm_common.h:65-74), A&S 7.1.26, |d erf| <= 1.5e-7 -> |d gelu(g)| <= 0.75e-7 |g|.
-  * f16-stored outputs: the norm outputs (norm.hip), the conv output h of conv2d_group_norm (capi.hip:1421, igemm_common.h:510-520),
-    attention O (attention.hip:674, :1186, :1608), the projected q of the unfused cross-attention (capi.hip:1252).
+  * f16-stored outputs: the norm outputs (norm.hip), the conv output h of conv2d_group_norm (capi_ops.hip sdxl_conv2d_group_norm: Act h, igemm_common.h:510-520),
+    attention O (attention.hip:674, :1186, :1608), the projected q of the unfused cross-attention (capi_ops.hip sdxl_ln_query_cross_attention: qd).
   * the GroupNorm statistics of conv2d_group_norm: the fused path takes them from the STORED f16 values (igemm_common.h:506-509, rr =
     (float)(half_t)v), the statistics pass reads the stored f16 h: both describe the same data, so both paths share one bar.
   * Q pre-scale: (half_t)((float)q * sc), sc = fp32(scale * log2 e) (attention.hip:506-517 and its siblings): emulated BIT-EXACTLY on the
