@@ -340,6 +340,9 @@ int sdxl_bench_attention(sdxl_ctx* ctx, void* stream, int B, int H, int Nq, int 
  * "igemm_wreg": 0 = the auto selection never picks the weights-in-registers GEMM (csrc/igemm_wreg.hip; A/B, default 1), forced by
  * "igemm_variant" 60 / 62 (96 / 64 rows per tile); "igemm_epilogue_staged", "hl_weights_exact": A/B knobs of the epilogue form / the
  * two-MFMA loop of exact-f16 split-operand weights;
+ * "wreg_xattn": 0 = the fused query projection + cross-attention of the f16 engine stays on the pipe kernels instead of the weights-in-registers
+ *   GEMM with the attention behind its partial-sum exchange (csrc/igemm_wreg.hip, XA instantiation; A/B, default 1; the two sum k in different
+ *   orders, so the results differ at rounding level; a UNet picks it up on its next forward, its weight-warming schedule when it is next recorded);
  * "igemm_warm": 0 = no weight-warming workgroups (spare workgroups of a weights-in-registers launch read a later GEMM's weights into the
  * Infinity Cache; results unchanged; A/B, default 1; a UNet picks it up on its next forward);
  * "attn_xsplit": 0 = the self-attention of the 32^2 level never runs 1/5 of its heads as two half-key blocks per 64 queries merged across

@@ -114,6 +114,7 @@ int sdxl_debug_set(const char* key, int value) {
   else if (std::strcmp(key, "igemm_epilogue_staged") == 0) igemm_set_epilogue_staged(value);
   else if (std::strcmp(key, "hl_weights_exact") == 0) igemm_set_hl_weights_exact(value);
   else if (std::strcmp(key, "igemm_wreg") == 0) igemm_set_wreg(value);
+  else if (std::strcmp(key, "wreg_xattn") == 0) igemm_set_wreg_xattn(value);
   else if (std::strcmp(key, "igemm_tsw") == 0) igemm_set_tsw(value);
   else if (std::strcmp(key, "igemm_warm") == 0) igemm_set_warm(value);
   else if (std::strcmp(key, "attn_xsplit") == 0) attention_set_xsplit(value);

@@ -449,7 +449,7 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
   Tmp tmp;
   Exec ex; ex.s = s; ex.cdt = DT_F16; ex.sdt = DT_F16;
   // beta W is folded into the packed bias; attn2.query has none of its own, so fold with beta as given (zero beta -> no bias)
-  const Lin l = pk.wb.linear_ln("lin", false, "norm");
+  const Lin l = pk.wb.linear_ln("lin", false, "norm", true);
   const F16Stream xs = identity_producer(ex, tmp, x, M, C, s);
   const Act xi(xs.rows, C, DT_F16);
   void* od = tmp.get((size_t)M * C * 2);

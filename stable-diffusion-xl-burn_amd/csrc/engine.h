@@ -156,7 +156,8 @@ struct WeightBuilder {
       // f16 GEMM on (hi | lo * kHiLoScale) weight halves along a doubled K: un-rounded weights (MIX_GEGLU_HILO)
   float hl_scale(Lin& l, const std::vector<std::string>& weight_names);     // DT_HL packing: power-of-two factor, inverse into the arena
   // the same with the preceding LayerNorm(gamma, beta) folded into weight / bias / column sums
-  Lin linear_ln(const std::string& name, bool geglu, const std::string& norm);
+  // xattn_query: the attn2 query projection -- also packed in fragment order, for the weights-in-registers form of the fused cross-attention
+  Lin linear_ln(const std::string& name, bool geglu, const std::string& norm, bool xattn_query = false);
   Lin fused_linear_ln(const std::vector<std::string>& names, const std::string& norm);
   // dt_override / shadow / plain: the SHADOW form (round 6, split-operand models): the weights are packed UN-folded in dt_override (f16) -- gamma rides on
   // the A operand, an f16 shadow  f16(x o gamma)  the producer of the fp32 stream leaves (IgemmParams::shadow) -- with cs = gamma W over the packed values
@@ -167,7 +168,7 @@ struct WeightBuilder {
   bool all_f16_exact(const std::vector<std::string>& names);
   float* tmp2 = nullptr; size_t tmp2_numel = 0;   // scratch for folded biases (device)
   Lin conv(const std::string& name);                                        // name.weight [Cout,Cin,k,k] + bias
-  void attach_wfrag(Lin& l, bool fill);    // second image of a plain f16 linear / 1x1 weight in fragment order (arena; no-op for other layers)
+  void attach_wfrag(Lin& l, bool fill, bool folded = false);    // second image of a plain f16 linear / 1x1 weight in fragment order (arena; no-op for other layers)
   NormW norm(const std::string& name);
 };
 

@@ -1057,6 +1057,56 @@ __device__ __forceinline__ void xattn_inplace(const IgemmParams& p, f32x16 (&acc
   }
 }
 
+// One (32 queries x one head) unit of the same attention for a kernel whose q tile does NOT sit in one wave's accumulators (the
+// weights-in-registers GEMM: igemm_wreg.hip hands the finished q over through LDS).  qf = the head's four k-steps of q as B fragments,
+// already affine-transformed, scaled and rounded exactly like xattn_inplace's (one f16 rounding of (a acc + c cs + b) * scale); from
+// there on this IS xattn_inplace's arithmetic -- S MFMAs in k-step order, mask, exp2 softmax, f16 P, O MFMAs in key order, one
+// multiply by 1 / l.  o[dt][r] = O^T[d = 32 dt + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)][query lane & 31], fp32.
+__device__ __forceinline__ void xattn_unit(const half8 (&qf)[4], const half8 (&kf)[3][4], const half8 (&vf)[2][6], int nctx, int fh, f32x16 (&o)[2]) {
+  f32x16 sv[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sv[t][r] = 0.f;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) sv[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t][s4], qf[s4], sv[t], 0, 0, 0);
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (32 * t + 8 * (r >> 2) + 4 * fh + (r & 3) >= nctx) sv[t][r] = -INFINITY;
+      mx = fmaxf(mx, sv[t][r]);
+    }
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  float l = 0.f;
+  half8 pf[6];
+#pragma unroll
+  for (int s6 = 0; s6 < 6; ++s6) {
+    float ls = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float pe = __builtin_amdgcn_exp2f(sv[s6 >> 1][8 * (s6 & 1) + e] - mx);
+      ls += pe;
+      pf[s6][e] = (half_t)pe;
+    }
+    l += ls;
+  }
+  l += __shfl_xor(l, 32);
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    f32x16 a;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+#pragma unroll
+    for (int s6 = 0; s6 < 6; ++s6) a = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[dt][s6], pf[s6], a, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = a[r] * inv;
+  }
+}
+
 // ---- the same fusion at split precision (IgemmParams::xa_k_lo; round 6): q stays what the projection's fp32 accumulators hold -- it is split into
 // (hi, lo) f16 pairs here, like the probabilities (times 2^11, so that the lo halves of small probabilities stay out of the f16 subnormals), and meets
 // context keys / values that were split once per prompt: three MFMAs per product, fp32 accumulation, fp32 softmax -- the arithmetic of the stand-alone

@@ -1233,6 +1233,7 @@ void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, i
 }
 
 bool launch_igemm_wreg(const IgemmParams& p, int variant, hipStream_t s);   // igemm_wreg.hip
+bool launch_igemm_wreg_xattn(const IgemmParams& p, int variant, hipStream_t s);   // igemm_wreg.hip
 bool launch_igemm_glds(const IgemmParams& p, int variant, hipStream_t s) {
   if (!g_zero_pages[current_device()]) return false;
   if (p.act > 1) return false;   // GELU / QuickGELU epilogues (CLIP MLP, once per prompt) live in the generic kernel
@@ -1260,6 +1261,9 @@ bool launch_igemm_glds(const IgemmParams& p, int variant, hipStream_t s) {
       return true;
     }
     int v = variant;
+    // the f16 form of a layer whose weights also exist in fragment order: the weights-in-registers kernel with the attention behind its
+    // partial-sum exchange (igemm_wreg.hip, XA instantiation; static rule per layer, knob "wreg_xattn").  Forced pipe tiles stay forced.
+    if (v != 35 && v != 36 && v != 44 && v != 45 && launch_igemm_wreg_xattn(psk, v, s)) return true;
     if (v != 35 && v != 36 && v != 44 && v != 45) {
       const double c256 = tile_cost(p.M, p.N, nk, 256, 128, 1.0), c128 = tile_cost(p.M, p.N, nk, 128, 128, 1.0), c96 = tile_cost(p.M, p.N, nk, 96, 128, 1.0);
       v = c256 <= c128 && c256 <= c96 ? 35 : (c96 < c128 ? 45 : (nk >= 40 ? 44 : 36));

@@ -25,6 +25,8 @@
 //     iteration j - 1 (activations) and the last MFMAs of iteration j - 1 (weights) have freed.
 //   * one s_barrier per iteration, between the third and the fourth kk-step: before it the wave's own pieces of tile j + 1 have
 //     landed and all its reads of tile j are complete (lgkmcnt(0)).
+//   * the XA instantiation (fused cross-attention, further down) leaves this queue as it is: everything it adds is issued behind the k-loop's
+//     last counted wait and is waited for by the compiler.
 // tools/asm_lint.py checks the asm-load rule (no instruction touches the destination of a pending asm global_load before a
 // counted vmcnt wait covers it) on the device assembly of this file.
 #include "igemm_common.h"
@@ -224,6 +226,113 @@ __device__ __forceinline__ void wreg_epilogue(const IgemmParams& p, const f32x16
   }
 }
 
+// ---- cross-attention behind the query projection (XA instantiation; the pipe kernels' form: igemm_common.h xattn_inplace) ----
+// A wave of this kernel never holds a whole 64-column head (its accumulators are BM rows x 32 columns, half of them final per k-group),
+// so q crosses LDS once more -- in a form that costs no shuffles: behind the partial-sum exchange wave w of group g holds the final
+// values of columns n0 + 32 w + 16 g .. + 15 in accumulator groups q = 2g, 2g + 1, a lane row lane & 31 and the columns
+// 8 (e >> 2) + 4 (lane >> 5) + (e & 3), e = 0 .. 7 -- exactly the B-operand image of ONE 16-deep k-step of S = K q^T, k-step
+// 2 (w & 1) + g of head w >> 1, in the k-order xattn_pack_kernel gives the K fragments.  So each (w, g) applies the folded-LayerNorm
+// affine, the bias and the softmax scale to its 16 columns, rounds to f16 (the roundings of xattn_inplace) and parks TM fragments of
+// 1 KiB; head h's fragments fill slot L of ring h ([row block][k-step][lane], TM x 4 KiB = one slot), dead behind the exchange
+// rendezvous.  One more rendezvous, then wave u < 2 TM runs the attention of unit (row block u >> 1, head u & 1) = 32 queries x one
+// head -- the wave tile of the 96x128 pipe kernel -- and stores its rows (permlane32 half swap, 16-byte stores).  The unit's 24
+// K / V^T fragments, the tile's LayerNorm statistics (LnCoop over 4 BM threads; the (a, c) pairs wait in BM x 8 bytes of LDS behind
+// the rings) and the wave's column vectors are requested BEFORE the exchange, like the plain epilogue's residual rows; all of it is
+// compiler-counted VMEM / SMEM behind the k-loop's last counted wait, so the hand-kept VMEM queue above is unchanged.
+// A 32-row block lies in one batch entry (rpb % 64 == 0); a 96-row tile may straddle two, so the entry is looked up per unit.
+template <int BM> struct WregXaOperands {
+  LnCoop<BM, 4 * BM> ln;
+  half8 kf[3][4], vf[2][6];
+  f32x4 cz[2], bz[2];
+  bool unit;
+};
+template <int BM>
+__device__ __forceinline__ void wreg_xattn_request(const IgemmParams& p, int m0, int n0, int lane, int wave, const void* zeros, WregXaOperands<BM>& op) {
+  constexpr int TM = BM / 32;
+  static_assert((4 * BM) % 64 == 0 && 4 * BM <= 512 && LnCoop<BM, 4 * BM>::OK, "four statistics threads per tile row, whole waves");
+  const int g = wave >> 2, w = wave & 3, fh = lane >> 5;
+  if (wave < 4 * BM / 64) op.ln.load(p, m0, wave * 64 + lane);
+  const int mu = m0 + 32 * (wave >> 1);
+  op.unit = wave < 2 * TM && mu < p.M;
+  if (op.unit) {
+    const int b = __builtin_amdgcn_readfirstlane(mu / p.rpb);
+    const half8* fx = reinterpret_cast<const half8*>(p.xa_k) + ((size_t)b * (p.N >> 6) + ((n0 >> 6) + (wave & 1))) * (24 * 64) + lane;
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) op.kf[t][s4] = fx[(t * 4 + s4) * 64];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int s6 = 0; s6 < 6; ++s6) op.vf[dt][s6] = fx[(12 + dt * 6 + s6) * 64];
+  }
+  const int nb = n0 + 32 * w + 16 * g;      // the wave's 16 final columns: wave-uniform, through the scalar cache
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    op.cz[q] = col_vec4(p.ln_cs, p.ln_stat != nullptr, nb + 8 * q, fh, zeros);
+    op.bz[q] = col_vec4(p.bias, p.bias != nullptr, nb + 8 * q, fh, zeros);
+  }
+}
+// the tile's BM (a, c) pairs into LDS (in front of the exchange rendezvous, which publishes them).  More than 24 statistics slots
+// (K > 1536): one thread per row evaluates ln_row_coef -- the same canonical order, so the same bits.
+template <int BM>
+__device__ __forceinline__ void wreg_xattn_coef(const IgemmParams& p, int m0, int lane, int wave, WregXaOperands<BM>& op, float* coef) {
+  const int tid = wave * 64 + lane;
+  if (p.ln_stat != nullptr && p.ln_slots <= 24) {
+    if (wave < 4 * BM / 64) op.ln.finish(p, m0, coef);
+  } else if (tid < BM) {
+    float a, c;
+    ln_row_coef(p, m0 + tid, a, c);
+    coef[tid * 2] = a; coef[tid * 2 + 1] = c;
+  }
+}
+template <int BM, int L>
+__device__ __forceinline__ void wreg_xattn_tail(const IgemmParams& p, const f32x16 (&acc)[BM / 32], int m0, int n0, int lane, int wave, char* smem,
+                                                const float* coef, const WregXaOperands<BM>& op) {
+  constexpr int TM = BM / 32, SLOT = BM * 128, RING = (L + 1) * SLOT;
+  static_assert(TM * 4 * 1024 == SLOT, "a head's q fragments fill one ring slot");
+  const int fr = lane & 31, fh = lane >> 5, g = wave >> 2, w = wave & 3;
+  const float sc = p.xa_scale * 1.44269504088896340736f;             // p = exp2(s - m)
+  half8* qx = reinterpret_cast<half8*>(smem + (w >> 1) * RING + L * SLOT) + (2 * (w & 1) + g) * 64 + lane;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const float lna = coef[(i * 32 + fr) * 2], lnc = coef[(i * 32 + fr) * 2 + 1];
+    half8 qf;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float a = g ? acc[i][8 + e] : acc[i][e];                   // (wave-uniform g: a select, not an index)
+      qf[e] = (half_t)((lna * a + lnc * op.cz[e >> 2][e & 3] + op.bz[e >> 2][e & 3]) * sc);
+    }
+    qx[i * 256] = qf;
+  }
+  wait_lgkmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  if (!op.unit) return;
+  const int ui = wave >> 1, uh = wave & 1;
+  const half8* qr = reinterpret_cast<const half8*>(smem + uh * RING + L * SLOT) + ui * 256 + lane;
+  half8 qf[4];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) qf[s4] = qr[s4 * 64];
+  f32x16 o[2];
+  xattn_unit(qf, op.kf, op.vf, p.xa_nctx, fh, o);
+  const int m = m0 + 32 * ui + fr;
+  half_t* crow = reinterpret_cast<half_t*>(p.C) + (size_t)(m < p.M ? m : 0) * p.ldc + n0 + 64 * uh + 8 * fh;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      half8 h;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {                                    // accumulator groups 2t / 2t + 1 -> 8 consecutive columns per lane (wreg_epilogue)
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(o[dt][8 * t + r]), __float_as_uint(o[dt][8 * t + 4 + r]), false, false);
+        h[r] = (half_t)__uint_as_float(sw[0]);
+        h[4 + r] = (half_t)__uint_as_float(sw[1]);
+      }
+      if (m < p.M) *reinterpret_cast<half8*>(crow + 32 * dt + 16 * t) = h;
+    }
+}
+
 #ifdef SDXL_MEASURE
 // coarse s_memtime stamps (tools/wreg_timeline.py): [workgroup][wave][8] = entry, prologue issued, tile 0 landed, k-loop done, partial
 // sums exchanged, epilogue issued, stores drained; word 7 = shader cycles per 100 MHz tick x 100 (clock) is derived by the tool from
@@ -247,7 +356,8 @@ void igemm_set_wreg_timeline(void* buf) {
 constexpr int wreg_mode_flags(int m) {
   return m >= 16 ? m : m == 1 ? 16 : m == 2 ? 32 : m == 3 ? 64 : m == 4 ? 128 : m == 5 ? 256 : m == 6 ? 512 : m == 7 ? 1024 : m == 8 ? 2048 : 0;
 }
-template <int BM, int L, int MODE = 0>
+// XA: the query projection of a cross-attention with the attention behind it (IgemmParams::xa_k, f16 form; block comment above)
+template <int BM, int L, int MODE = 0, bool XA = false>
 __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, const void* zeros) {
 #ifdef SDXL_MEASURE
   unsigned wtl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -494,7 +604,10 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
   // groups q = 2t, 2t + 1), so it parks the other half for its partner (lane-linear 16-byte pieces) and adds the partner's half
   // to its own: even k-tiles + odd k-tiles whichever group does the add (fp32 addition commutes bit for bit)
   WregEpiOperands<TM> eop;
-  wreg_epilogue_request<TM>(p, m0, n0 + w * 32, lane, g, zeros, eop);
+  WregXaOperands<XA ? BM : 64> xop;
+  float* const xa_coef = reinterpret_cast<float*>(smem + NG * RING);      // XA: the tile's LayerNorm (a, c) pairs, behind the rings
+  if constexpr (XA) { static_assert(MODE == 0, "production arithmetic only"); wreg_xattn_request<BM>(p, m0, n0, lane, wave, zeros, xop); }
+  else wreg_epilogue_request<TM>(p, m0, n0 + w * 32, lane, g, zeros, eop);
   static_assert(4 * TM * 2 * 64 * 16 <= L * SLOT, "a group's four exchange pieces must fit its dead slots 0 .. L - 1");
   f32x4* xw = reinterpret_cast<f32x4*>(smem + g * RING) + (size_t)w * (TM * 2 * 64) + lane;                    // written by (g, w): own group's slots 0 ..
   const f32x4* xo = reinterpret_cast<const f32x4*>(smem + (1 - g) * RING) + (size_t)w * (TM * 2 * 64) + lane;  // partner's
@@ -507,6 +620,7 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
       for (int r = 0; r < 4; ++r) v[r] = g ? acc[i][4 * qq + r] : acc[i][8 + 4 * qq + r];     // group 1 parks q = 0, 1; group 0 parks q = 2, 3
       xw[(i * 2 + qq) * 64] = v;
     }
+  if constexpr (XA) wreg_xattn_coef<BM>(p, m0, lane, wave, xop, xa_coef);
   wait_lgkmcnt<0>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -524,7 +638,8 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
   WREG_STAMP(4);
   static_assert((2 * BM + 6 * 2 * BM) * 4 <= SLOT, "statistics exchange must fit one slot");
   float* xch = reinterpret_cast<float*>(smem + L * SLOT);           // statistics exchange: slot L of ring 0 (dead behind the exchange rendezvous)
-  wreg_epilogue<TM>(p, acc, m0, n0 + w * 32, lane, w, g, xch, eop);
+  if constexpr (XA) wreg_xattn_tail<BM, L>(p, acc, m0, n0, lane, wave, smem, xa_coef, xop);
+  else wreg_epilogue<TM>(p, acc, m0, n0 + w * 32, lane, w, g, xch, eop);
 #ifdef SDXL_MEASURE
   WREG_STAMP(5);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -547,14 +662,14 @@ static int wreg_warm_groups(const IgemmParams& p, int ntiles) {
   const int spare = (ntiles <= 256 ? 256 : 512) - ntiles;
   return spare < 8 ? 0 : spare > 64 ? 64 : spare;
 }
-template <int BM, int L, int MODE = 0>
+template <int BM, int L, int MODE = 0, bool XA = false>
 static void launch_wreg_t(const IgemmParams& p, hipStream_t s) {
-  constexpr size_t lds = (size_t)2 * (L + 1) * BM * 128;
+  constexpr size_t lds = (size_t)2 * (L + 1) * BM * 128 + (XA ? BM * 8 : 0);      // (XA: + the tile's LayerNorm coefficients)
   static_assert(lds >= (size_t)8 * (BM / 32) * 2048 + (size_t)(2 * BM + 6 * 2 * BM) * 4, "exchange areas must fit the dead rings");
   static bool attr_set[kIgemmMaxDev] = {};
   const int dev = igemm_current_device();
   if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wreg_kernel<BM, L, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wreg_kernel<BM, L, MODE, XA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       throw std::runtime_error("igemm_wreg: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
     attr_set[dev] = true;
   }
@@ -562,7 +677,7 @@ static void launch_wreg_t(const IgemmParams& p, hipStream_t s) {
   const int ntiles = tilesM * tilesN;
   IgemmParams q = p;
   q.wreg_xcd2d = g_wreg_xcd2d.load();
-  hipLaunchKernelGGL((igemm_wreg_kernel<BM, L, MODE>), dim3(ntiles + wreg_warm_groups(p, ntiles)), dim3(512), lds, s, q, igemm_zero_page());
+  hipLaunchKernelGGL((igemm_wreg_kernel<BM, L, MODE, XA>), dim3(ntiles + wreg_warm_groups(p, ntiles)), dim3(512), lds, s, q, igemm_zero_page());
 }
 
 // shapes this kernel takes: plain f16 linear layers / 1x1 convolutions whose weights were also packed in fragment order
@@ -629,6 +744,42 @@ bool launch_igemm_wreg(const IgemmParams& p, int variant, hipStream_t s) {
   }
   if (bm == 64) launch_wreg_t<64, 2>(p, s);
   else launch_wreg_t<96, 2>(p, s);
+  return true;
+}
+
+// ---- the fused query projection + cross-attention (f16 form) on this kernel: the XA instantiation
+static std::atomic<int> g_wreg_xattn{1};
+void igemm_set_wreg_xattn(int v) { g_wreg_xattn = v; }
+// what the XA instantiation takes: a plain f16 linear layer with fragment-order weights whose epilogue is the f16 cross-attention
+// (with or without a folded LayerNorm in front) and nothing else.  The caller has checked igemm_xattn_ok (rpb % 64 == 0, <= 96 keys).
+static bool wreg_xattn_ok(const IgemmParams& p) {
+  if (!p.xa_k || p.xa_k_lo || !p.Wf || !igemm_zero_page()) return false;
+  if (p.a_dt != DT_F16 || p.c_dt != DT_F16) return false;
+  if (p.ksize != 1 || p.stride != 1 || p.up != 0 || p.pad != 0 || p.Hin != p.Hout || p.Win != p.Wout) return false;
+  if (p.N % 128 != 0 || p.Cin != p.K || p.K != p.Kpad || p.Kpad % 64 != 0 || p.Kpad < 128) return false;
+  if (p.act != 0 || p.n_split < p.N || p.gn_part || p.acc_scale || p.stat_out || p.R || p.ebias || p.shadow) return false;
+  if (p.rpb <= 0 || p.rpb % 64 != 0 || p.M % p.rpb != 0 || p.xa_nctx < 1 || p.xa_nctx > 96) return false;
+  if ((p.lda & 7) != 0 || (reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
+  if ((p.ldc & 7) != 0 || (reinterpret_cast<uintptr_t>(p.C) & 15) != 0) return false;
+  return true;
+}
+// the static rule of igemm_wreg_selected -- the CFG pair's grid (2 entries of rpb rows), never the actual batch: this kernel and the
+// pipe kernels sum k in different orders, and an entry must come out bit-identical alone or batched
+bool igemm_wreg_xattn_selected(const IgemmParams& p) {
+  if (!wreg_xattn_ok(p) || !g_wreg_enable.load() || !g_wreg_xattn.load()) return false;
+  const long rows = 2L * p.rpb;
+  return ((rows + 95) / 96) * (long)(p.N / 128) <= 512;
+}
+// variant 60 / 62: 96 / 64 rows per tile (the result does not depend on it); anything else: the rule of launch_igemm_wreg
+bool launch_igemm_wreg_xattn(const IgemmParams& p, int variant, hipStream_t s) {
+  if (!igemm_wreg_xattn_selected(p)) return false;
+  int bm = variant == 60 ? 96 : variant == 62 ? 64 : 0;
+  if (!bm) {
+    const long t64 = (long)((p.M + 63) / 64) * (p.N / 128);
+    bm = t64 <= 256 ? 64 : 96;
+  }
+  if (bm == 64) launch_wreg_t<64, 2, 0, true>(p, s);
+  else launch_wreg_t<96, 2, 0, true>(p, s);
   return true;
 }
 

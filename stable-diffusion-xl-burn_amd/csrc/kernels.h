@@ -104,6 +104,8 @@ void launch_repack_wfrag(const void* w, void* wf, int Npad, int Kpad, hipStream_
 bool igemm_wreg_ok(const IgemmParams& p);   // shapes the weights-in-registers kernel takes (plain f16 linear / 1x1, N % 128 == 0, Wf set)
 void igemm_set_tsw(int v);       // A/B knob (sdxl_debug_set "igemm_tsw"): 0 = no operand-swapped k-loop for the transposed part of a fused QKV projection
 bool igemm_wreg_selected(const IgemmParams& p);   // the auto selection (variant 0) would run this launch on the weights-in-registers kernel
+bool igemm_wreg_xattn_selected(const IgemmParams& p);   // a fused query projection + cross-attention (xa_k, f16 form) would run on the weights-in-registers kernel
+void igemm_set_wreg_xattn(int v);   // A/B knob (sdxl_debug_set "wreg_xattn"): 0 = the fused cross-attention stays on the pipe kernels
 void igemm_set_warm(int v);      // A/B knob (sdxl_debug_set "igemm_warm"): 0 = no weight warming workgroups; read when a UNet plan records its GEMM sequence
 int igemm_warm_enabled();
 void igemm_set_splitk_wt(int v);

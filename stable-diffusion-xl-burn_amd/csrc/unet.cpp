@@ -111,7 +111,7 @@ STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth
       // consume them; their row statistics come out of the epilogue of the GEMM that produced the residual stream
       t.qkv = wb.fused_linear_ln(qkv, q + ".norm1");
       t.out1 = wb.linear(q + kOut1);
-      t.q2 = wb.linear_ln(q + kQ2, false, q + ".norm2");
+      t.q2 = wb.linear_ln(q + kQ2, false, q + ".norm2", true);
       t.kv2 = wb.fused_linear({q + ".attn2.key", q + ".attn2.value"});
       t.out2 = wb.linear(q + kOut2);
       t.geglu = wb.linear_ln(q + kGeglu, true, q + ".norm3");

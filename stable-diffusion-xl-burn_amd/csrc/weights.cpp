@@ -177,10 +177,12 @@ float WeightBuilder::hl_scale(Lin& l, const std::vector<std::string>& weight_nam
 // Plain f16 linear layers / 1x1 convolutions whose width is a multiple of 128 keep a second image of the packed weights in MFMA
 // fragment order: the weights-in-registers GEMM (igemm_wreg.hip) streams it straight into VGPRs.  Same bytes, same arena (so a
 // replica receives it with the weight broadcast); allocated on empty replicas too (identical arena layout).
-void WeightBuilder::attach_wfrag(Lin& l, bool fill) {
+// (folded: a LayerNorm-folded weight -- only the attn2 query projection asks for it: the weights-in-registers kernel applies the folded
+// affine in its fused cross-attention form alone, every other LayerNorm-fed linear stays on the pipe kernels.)
+void WeightBuilder::attach_wfrag(Lin& l, bool fill, bool folded) {
   const int wdt = l.dt >= 0 ? l.dt : dt;
   if (!wfrag) return;
-  if (wdt != DT_F16 || l.ksize != 1 || l.N % 128 != 0 || l.K != l.Kpad || l.Kpad % 64 != 0 || l.Kpad < 128 || l.cs || l.acc_scale) return;
+  if (wdt != DT_F16 || l.ksize != 1 || l.N % 128 != 0 || l.K != l.Kpad || l.Kpad % 64 != 0 || l.Kpad < 128 || (l.cs && !folded) || l.acc_scale) return;
   void* wf = arena.alloc((size_t)l.Npad * l.Kpad * 2);
   l.wf = wf;
   if (fill) launch_repack_wfrag(l.w, wf, l.Npad, l.Kpad, st);
@@ -264,8 +266,11 @@ Lin WeightBuilder::fused_linear(const std::vector<std::string>& names, int dt_ov
 // LayerNorm(gamma, beta) followed by Linear(W, b):  LN(x) W + b = rstd (x - mu) (diag(gamma) W) + (beta W + b)
 //   = rstd * (x W') - rstd * mu * colsum(W') + b'   -- W' is packed (rounded to the compute dtype) FIRST and the column sums
 // are taken over the rounded values, so the identity holds exactly for what the MFMA multiplies.
-Lin WeightBuilder::linear_ln(const std::string& name, bool geglu, const std::string& norm) {
-  return fold_ln({name}, norm, geglu);
+Lin WeightBuilder::linear_ln(const std::string& name, bool geglu, const std::string& norm, bool xattn_query) {
+  Lin l = fold_ln({name}, norm, geglu);
+  // (after everything fold_ln allocates, filled or not: replicas keep the arena layout)
+  if (xattn_query && !geglu && !l.k_form) attach_wfrag(l, !src.empty(), true);
+  return l;
 }
 Lin WeightBuilder::fused_linear_ln(const std::vector<std::string>& names, const std::string& norm) {
   return fold_ln(names, norm, false);
@@ -468,7 +473,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     WarmSeq& ws = *ex.warm;
     // the region the launch reads cold: its weights and the per-column vectors next to them in the arena (allocation order: packed
     // weights, bias, [column sums, eps of a folded LayerNorm], [fragment-order image])
-    const bool host = igemm_wreg_selected(p);
+    const bool host = igemm_wreg_selected(p) || igemm_wreg_xattn_selected(p);
     const size_t wbytes = (size_t)w.Npad * w.Kpad * 2;
     const char* lo; const char* hi;
     if (host) {
