@@ -335,7 +335,7 @@ int sdxl_bench_igemm(sdxl_ctx* ctx, void* stream, int B, int H, int W, int Cin, 
 /* times the fused attention kernel alone (head dim 64, f16) on seeded random data: B*H heads, Nq queries, Nk keys */
 int sdxl_bench_attention(sdxl_ctx* ctx, void* stream, int B, int H, int Nq, int Nk, int iters, float* avg_ms);
 /* benchmarking / debugging knobs.  "igemm_variant": -1 generic kernel only, 0 auto, > 0 forced fast-path tile / pipeline
- * (list in csrc/igemm_glds.hip); "attn_variant": -1 generic, 0 auto, 1/2/4/6 forced f16 kernels, 7/8 forced mixed block sizes,
+ * (table in csrc/select.cpp); "attn_variant": -1 generic, 0 auto, 1/2/4/6 forced f16 kernels, 7/8 forced mixed block sizes,
  * 9 = auto without them (csrc/attention.hip);
  * "igemm_wreg": 0 = the auto selection never picks the weights-in-registers GEMM (csrc/igemm_wreg.hip; A/B, default 1), forced by
  * "igemm_variant" 60 / 62 (96 / 64 rows per tile); "igemm_epilogue_staged", "hl_weights_exact": A/B knobs of the epilogue form / the
@@ -365,6 +365,34 @@ int sdxl_debug_set(const char* key, int value);
 /* host logic of the weight-warming schedule on a synthetic launch sequence (no device needed; tests): bytes[j] / host[j] = what entry j reads and
  * whether its kernel can carry warming workgroups; warmed_by[j] receives the index of the entry that warms j, -1 if nobody does */
 int sdxl_debug_warm_schedule(int n, const unsigned* bytes, const unsigned char* host, int* warmed_by);
+/* the kernel selection on a described launch (no device needed, no process-wide state read or written; tests): which kernel instantiation, grid and LDS
+ * bytes a GEMM / a head-dim-64 attention call with these integer fields, optional operands and knob values would launch.  Optional operands are named by
+ * the SDXL_SEL_* bits of `present`; `misaligned` != 0 puts every operand 8 bytes off a 16-byte boundary.  A status != 0 (text in sdxl_last_error())
+ * reports a launch the selection refuses.  dtypes: 0 fp32, 1 f16, 2 split-operand HL16 (engine-internal numbering). */
+enum {
+  SDXL_SEL_WF = 1 << 0, SDXL_SEL_R = 1 << 1, SDXL_SEL_EBIAS = 1 << 2, SDXL_SEL_STAT_OUT = 1 << 3, SDXL_SEL_LN_STAT = 1 << 4, SDXL_SEL_GN_PART = 1 << 5,
+  SDXL_SEL_SHADOW = 1 << 6, SDXL_SEL_XA_K = 1 << 7, SDXL_SEL_XA_K_LO = 1 << 8, SDXL_SEL_ACC_SCALE = 1 << 9, SDXL_SEL_SPLITK_WS = 1 << 10,
+  SDXL_SEL_XSPLIT_WS = 1 << 11, SDXL_SEL_MASK = 1 << 12, SDXL_SEL_WARM = 1 << 13
+};
+typedef struct sdxl_select_knobs {      /* the sdxl_debug_set keys of the same names; zero_page: the device's zero page exists (after sdxl_ctx_create) */
+  int igemm_variant, igemm_wreg, wreg_xattn, hl_tile96, igemm_tsw, igemm_unrolled, wide_db, attn_variant, attn_xsplit, zero_page;
+} sdxl_select_knobs;
+typedef struct sdxl_igemm_case {
+  int batch, rows_per_entry;            /* M = batch * rows_per_entry output rows (rows_per_entry = Hout * Wout, square) */
+  int N, cin, ksize, stride, up;        /* K = ksize^2 * cin (Kpad: up to the k-tile); pad = ksize / 2 */
+  int act, n_split;                     /* n_split < 0: none */
+  int a_dt, c_dt, compute_dt;
+  int xa_nctx, shadow_lo_sign;          /* sign of the shadow's lo scale (-1, 0, 1) */
+  unsigned present; int misaligned;
+} sdxl_igemm_case;
+typedef struct sdxl_igemm_choice {      /* csrc/kernels.h IgemmChoice */
+  int family, bm, bn, ns, wgm, nw, elem, a_elem, xa, xh, tsw, s2, splitk, mode, db, measure, grid, block, lds;
+  int gn_part_ok, wreg_selected, wreg_xattn_selected;      /* what the predicates of the same rules answer for this launch */
+} sdxl_igemm_choice;
+int sdxl_debug_igemm_select(const sdxl_igemm_case* c, const sdxl_select_knobs* knobs, sdxl_igemm_choice* out);
+typedef struct sdxl_attn_case { int B, H, Nq, Nk, dt; unsigned present; int misaligned; } sdxl_attn_case;
+typedef struct sdxl_attn_choice { int kernel, mix, big_heads, ns, elem, ko, grid_x, grid_y, block, lds; } sdxl_attn_choice;      /* csrc/kernels.h AttnChoice */
+int sdxl_debug_attn_select(const sdxl_attn_case* c, const sdxl_select_knobs* knobs, sdxl_attn_choice* out);
 
 /* ---- single-op entry points used by the parity tests (same kernels the models run) */
 /* GroupNorm::forward (groupnorm/mod.rs:52-73) on NCHW fp32 [B,C,H,W]; silu!=0 fuses SILU::forward (silu.rs:14-16) */

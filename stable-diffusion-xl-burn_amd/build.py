@@ -20,7 +20,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsdxl_mi355.so")
 ARCH = "gfx950"
 SOURCES = ["igemm.hip", "igemm_glds.hip", "igemm_wreg.hip", "igemm_measure.hip", "norm.hip", "attention.hip", "elementwise.hip", "capi.hip", "capi_ops.hip",
-           "specs.cpp", "weights.cpp", "unet.cpp", "vae.cpp", "sampler.cpp", "clip.cpp", "comm.cpp"]
+           "select.cpp", "specs.cpp", "weights.cpp", "unet.cpp", "vae.cpp", "sampler.cpp", "clip.cpp", "comm.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result"]
 
@@ -50,7 +50,7 @@ def _flags() -> list:
 
 def _deps_hash(src: str) -> str:
     h = hashlib.sha256()
-    for f in [src] + [os.path.join(CSRC, x) for x in ("kernels.h", "engine.h", "igemm_common.h", "capi_internal.h")] + \
+    for f in [src] + [os.path.join(CSRC, x) for x in ("kernels.h", "engine.h", "igemm_common.h", "capi_internal.h", "select_debug.h")] + \
             [os.path.join(HERE, "..", "include", "sdxl_mi355.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())

@@ -1611,11 +1611,9 @@ __global__ __launch_bounds__(256, 1) void attn_hd_kernel(const AttnParams p, con
   }
 }
 
-// per-DEVICE zero page (key-tail / padded rows of the DMA-staged kernels) and dynamic-LDS attribute flags
-constexpr int kMaxDev = 64;
+// per-DEVICE zero page (key-tail / padded rows of the DMA-staged kernels)
+constexpr int kMaxDev = kMaxDevices;
 static const void* g_attn_zeros[kMaxDev] = {};
-static std::atomic<int> g_attn_variant{0};   // test hook (sdxl_debug_set "attn_variant"): -1 generic kernel only, 0 auto
-void attention_set_variant(int v) { g_attn_variant = v; }
 static int attn_device() {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) throw std::runtime_error("attention: no current HIP device");
@@ -1630,111 +1628,55 @@ void attention_init() {
   g_attn_zeros[d] = z;
 }
 
-// cross-workgroup key halves (attn_d64_mix_kernel level 2): 1/5 of the heads run as two half-key blocks per 64 queries, so that the CFG
-// pair at the 32^2 level is 512 whole + 256 half blocks = two whole and one half block on every CU (2.5 units of work each) instead of
-// three blocks on one half of the CUs and two on the other
-static std::atomic<int> g_attn_xsplit{1};
-void attention_set_xsplit(int v) { g_attn_xsplit = v; }
-static int xsplit_heads(int H) { return H - std::max(1, H * 4 / 5); }
-size_t attention_xsplit_counters(int B, int H, int Nq) { return (size_t)B * xsplit_heads(H) * ((Nq + 63) / 64) * 2; }
-size_t attention_xsplit_ws_bytes(int B, int H, int Nq) { return attention_xsplit_counters(B, H, Nq) * 2 * (9 * 64 * 4 * sizeof(float)); }
-
+// snapshot the knobs, select (attn_select, select.cpp), launch the chosen instantiation
 void launch_attention_d64(const AttnParams& p, hipStream_t s) {
   const int dev = attn_device();
-  const void* g_attn_zero = g_attn_zeros[dev];
-  const int g_attn_variant = sdxl::g_attn_variant.load();
-  dim3 grid((p.Nq + 127) / 128, p.B * p.H);
-  const bool aligned = ((p.ldq | p.ldk | p.vt_ld | p.ldo) & 7) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(p.Q) | reinterpret_cast<uintptr_t>(p.K) |
-                         reinterpret_cast<uintptr_t>(p.Vt) | reinterpret_cast<uintptr_t>(p.O)) & 15) == 0;
-  if (p.dt == DT_F16 && (g_attn_variant == 0 || (g_attn_variant >= 2 && g_attn_variant <= 17)) && g_attn_zero && aligned && !p.mask) {
-    // 3-slot ring = 48 KiB per block -> three blocks per CU: the 640 blocks of the 64^2 level run as ONE round (a 4-slot
-    // ring admits two per CU, a second half-empty round: 147 us vs 126 us measured); variant 3 keeps the 4-slot ring for A/B
-    const dim3 g1(grid.x * grid.y);
-    // key-split kernel (64-query blocks, waves = query sub-tile x key half): where 128-query blocks leave fewer than two
-    // waves per SIMD (self-attention at 32^2: 160 blocks per batch entry) and the keys are whole 64-key tiles.
-    // The choice must not depend on the batch size: a batch entry has to come out bit-identical whether it runs alone or
-    // next to others (tests/test_gpu_fullsize.py, split-CFG chains), so it is made on one batch entry's grid (query blocks x heads).
-    const bool ks_ok = (p.Nk % 64) == 0 && p.Nk >= 128;
-    const bool ks_pick = ks_ok && (g_attn_variant == 6 || ((g_attn_variant == 0 || g_attn_variant == 9) && (int)grid.x * p.H < 256));
-    // mixed block sizes (attn_d64_mix_kernel): the first 4/5 of the heads in 128-query blocks, the rest in 64-query key-split
-    // blocks -- two large + one small block per CU for the CFG pair at 64^2 (121 -> 107 us; alone 78 -> 64 us, two pairs 210 ->
-    // 218 us: profiles/r03_attention_block_balance.txt).  Like the pick above a function of one batch entry's shape only.
-    // Level 1 (64-query + 32-query key-quarter blocks for the 32^2 shapes) measured no gain (23.2 -> 23.3 us) and is not picked.
-    // Forced: 7 = level 0, 8 = level 1; 9 = the automatic choice without mixing (A/B).
-    int mix = -1;
-    if (ks_ok && g_attn_variant == 7) mix = 0;
-    else if (ks_ok && g_attn_variant == 8) mix = 1;
-    else if (ks_ok && g_attn_variant == 0 && !ks_pick && p.H % 5 == 0) mix = 0;
-    // level 2 where the key-split kernel would run: whole 128-key pairs of tiles, a workspace from the caller, heads divisible 4 : 1
-    else if (ks_pick && g_attn_variant == 0 && p.xws && p.xcnt && g_attn_xsplit.load() && p.H % 5 == 0 && p.H >= 5 && (p.Nk % 128) == 0 && (p.Nq % 64) == 0) mix = 2;
-    if (mix >= 0) {
-      const int big_heads = p.H >= 2 ? std::max(1, p.H * 4 / 5) : 0;
-      const int ql = mix == 0 ? 128 : 64;
-      const int nl = p.B * big_heads * ((p.Nq + ql - 1) / ql);
-      const int nsm = mix == 2 ? p.B * (p.H - big_heads) * 2 * ((p.Nq + ql - 1) / ql) : p.B * (p.H - big_heads) * ((p.Nq + ql / 2 - 1) / (ql / 2));
-      if (mix == 0) hipLaunchKernelGGL(attn_d64_mix_kernel<0>, dim3(nl + nsm), dim3(256), 3 * 2 * 64 * 128, s, p, g_attn_zero, big_heads);
-      else if (mix == 1) hipLaunchKernelGGL(attn_d64_mix_kernel<1>, dim3(nl + nsm), dim3(256), 3 * 2 * 64 * 128, s, p, g_attn_zero, big_heads);
-      else hipLaunchKernelGGL(attn_d64_mix_kernel<2>, dim3(nl + nsm), dim3(256), 3 * 2 * 64 * 128, s, p, g_attn_zero, big_heads);
+  const void* zero = g_attn_zeros[dev];
+  SelectKnobs k = select_knobs_snapshot();
+  k.zero_page = zero != nullptr;
+  const AttnChoice c = attn_select(p, k);
+  const dim3 grid(c.grid_x, c.grid_y), block(c.block);
+  switch (c.kernel) {
+    case AT_MIX:
+      if (c.mix == 0) hipLaunchKernelGGL(attn_d64_mix_kernel<0>, grid, block, c.lds, s, p, zero, c.big_heads);
+      else if (c.mix == 1) hipLaunchKernelGGL(attn_d64_mix_kernel<1>, grid, block, c.lds, s, p, zero, c.big_heads);
+      else hipLaunchKernelGGL(attn_d64_mix_kernel<2>, grid, block, c.lds, s, p, zero, c.big_heads);
       return;
-    }
-    if (ks_pick) {
-      // (round 4: a software-pipelined form of this body -- QK^T of tile t issued around the softmax of tile t - 1, K and V^T on
-      // separate rings -- measured 24.9 vs 22.6 us at the 32^2 level and was removed again: with three blocks per CU the other waves
-      // already fill the chain's gaps, and the second live score tile costs registers; profiles/r04_attention_swp_ab.txt)
-      hipLaunchKernelGGL(attn_d64_ks_kernel<2>, dim3(((p.Nq + 63) / 64) * p.B * p.H), dim3(256), 3 * 2 * 64 * 128, s, p, g_attn_zero);
-      return;
-    }
+    case AT_KS:
+      if (c.ko == 0) { hipLaunchKernelGGL(attn_d64_ks_kernel<2>, grid, block, c.lds, s, p, zero); return; }
 #ifdef SDXL_MEASURE
-    if (g_attn_variant == 4) {
-      hipLaunchKernelGGL(attn_d64_v3_kernel, g1, dim3(256), 6 * 64 * 128, s, p, g_attn_zero);
-      return;
-    }
-    if (g_attn_variant >= 11 && g_attn_variant <= 17 && ks_ok) {     // knock-out timings of the key-split body (tools/attn_knockout.py)
-      const dim3 gk(((p.Nq + 63) / 64) * p.B * p.H);
-      constexpr int lds = 3 * 2 * 64 * 128;
-      switch (g_attn_variant) {
-        case 11: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 1>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        case 12: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 2>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        case 13: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 4>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        case 14: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 8>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        case 15: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 16>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        case 16: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 1 | 4>), gk, dim3(256), lds, s, p, g_attn_zero); break;
-        default: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 2 | 8>), gk, dim3(256), lds, s, p, g_attn_zero); break;
+      switch (c.ko) {     // knock-out timings of the key-split body (tools/attn_knockout.py)
+        case 1: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 1>), grid, block, c.lds, s, p, zero); return;
+        case 2: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 2>), grid, block, c.lds, s, p, zero); return;
+        case 4: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 4>), grid, block, c.lds, s, p, zero); return;
+        case 8: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 8>), grid, block, c.lds, s, p, zero); return;
+        case 16: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 16>), grid, block, c.lds, s, p, zero); return;
+        case 1 | 4: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 1 | 4>), grid, block, c.lds, s, p, zero); return;
+        default: hipLaunchKernelGGL((attn_d64_ks_kernel<2, 2 | 8>), grid, block, c.lds, s, p, zero); return;
       }
-      return;
-    }
-    if (g_attn_variant == 3 && p.Nk > 128) {
-      constexpr int NS = 4;
-      static bool set[kMaxDev] = {};
-      if (!set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_d64_v2_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                NS * 2 * 64 * 128) != hipSuccess) throw std::runtime_error("attention: hipFuncSetAttribute failed");
-        set[dev] = true;
-      }
-      hipLaunchKernelGGL(attn_d64_v2_kernel<NS>, g1, dim3(256), NS * 2 * 64 * 128, s, p, g_attn_zero);
-      return;
-    }
 #endif
-    hipLaunchKernelGGL(attn_d64_v2_kernel<3>, g1, dim3(256), 3 * 2 * 64 * 128, s, p, g_attn_zero);
-    return;
-  }
-  if (p.dt == DT_F16 && g_attn_variant >= 0 && g_attn_zero && aligned) {
-    hipLaunchKernelGGL(attn_d64_f16_kernel, grid, dim3(256), 4 * 64 * 128, s, p, g_attn_zero);
-    return;
-  }
-  if (p.dt == DT_F16) {
-    const size_t lds = 4 * 64 * 128;
-    hipLaunchKernelGGL(attn_d64_kernel<half_t>, grid, dim3(256), lds, s, p);
-  } else {
-    const size_t lds = 4 * 64 * 256;
-    static bool set[kMaxDev] = {};
-    if (!set[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_d64_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds) != hipSuccess) throw std::runtime_error("attention: hipFuncSetAttribute failed");
-      set[dev] = true;
-    }
-    hipLaunchKernelGGL(attn_d64_kernel<float>, grid, dim3(256), lds, s, p);
+      throw std::logic_error("attention: knock-out variants exist in measure builds only");
+#ifdef SDXL_MEASURE
+    case AT_V3: hipLaunchKernelGGL(attn_d64_v3_kernel, grid, block, c.lds, s, p, zero); return;
+#endif
+    case AT_V2:
+#ifdef SDXL_MEASURE
+      if (c.ns == 4) {
+        set_max_dynamic_lds<&attn_d64_v2_kernel<4>>(c.lds, dev);
+        hipLaunchKernelGGL(attn_d64_v2_kernel<4>, grid, block, c.lds, s, p, zero);
+        return;
+      }
+#endif
+      hipLaunchKernelGGL(attn_d64_v2_kernel<3>, grid, block, c.lds, s, p, zero);
+      return;
+    case AT_F16: hipLaunchKernelGGL(attn_d64_f16_kernel, grid, block, c.lds, s, p, zero); return;
+    default:
+      if (c.elem == DT_F16) {
+        hipLaunchKernelGGL(attn_d64_kernel<half_t>, grid, block, c.lds, s, p);
+      } else {
+        set_max_dynamic_lds<&attn_d64_kernel<float>>(c.lds, dev);
+        hipLaunchKernelGGL(attn_d64_kernel<float>, grid, block, c.lds, s, p);
+      }
   }
 }
 
@@ -1749,12 +1691,7 @@ bool launch_attention_d64_hl(const AttnParams& p, hipStream_t s) {
   if ((p.ldq & 3) != 0 || (p.ldo & 3) != 0 || (p.ldk & 15) != 0 || (p.vt_ld & 63) != 0 || p.vt_ld < (int)(((p.Nk + 63) / 64) * 64)) return false;
   if (((reinterpret_cast<uintptr_t>(p.Q) | reinterpret_cast<uintptr_t>(p.K) | reinterpret_cast<uintptr_t>(p.Vt) | reinterpret_cast<uintptr_t>(p.O)) & 15) != 0) return false;
   constexpr int lds = 2 * 2 * 64 * 256;
-  static bool set[kMaxDev] = {};
-  if (!set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_d64_hl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      throw std::runtime_error("attention: hipFuncSetAttribute failed");
-    set[dev] = true;
-  }
+  set_max_dynamic_lds<&attn_d64_hl_kernel>(lds, dev);
   hipLaunchKernelGGL(attn_d64_hl_kernel, dim3(((p.Nq + 127) / 128) * p.B * p.H), dim3(256), lds, s, p, zeros);
   return true;
 }
@@ -1769,12 +1706,7 @@ bool launch_attention_hd512(const AttnParams& p, hipStream_t s) {
                          reinterpret_cast<uintptr_t>(p.Vt) | reinterpret_cast<uintptr_t>(p.O)) & 15) == 0;
   if (!aligned || p.vt_ld < ((p.Nk + 31) / 32) * 32) return false;      // V^T rows must exist (zero) up to the last 32-key tile
   constexpr int LDS = 2 * (32 * 512 * 2 + 512 * 32 * 2);
-  static bool set[kMaxDev] = {};
-  if (!set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_hd_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      throw std::runtime_error("attention: hipFuncSetAttribute failed");
-    set[dev] = true;
-  }
+  set_max_dynamic_lds<&attn_hd_kernel<512>>(LDS, dev);
   hipLaunchKernelGGL(attn_hd_kernel<512>, dim3((p.Nq + 63) / 64, p.B * p.H), dim3(256), LDS, s, p, zero);
   return true;
 }

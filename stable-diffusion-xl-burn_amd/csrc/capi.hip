@@ -2,6 +2,7 @@
 // This file: contexts, debug knobs, parameter specs, the UNet / CLIP / Diffuser / VAE handles, sampling and the weight broadcast;
 // the single-op and micro-benchmark entries are in capi_ops.hip.
 #include "capi_internal.h"
+#include "select_debug.h"
 #include <algorithm>
 #include <cstring>
 
@@ -109,23 +110,15 @@ int sdxl_ctx_create(int device_id, sdxl_ctx** out) {
 int sdxl_debug_set(const char* key, int value) {
   API_BEGIN
   SDXL_REQUIRE(key != nullptr, "null key");
-  if (std::strcmp(key, "igemm_variant") == 0) igemm_set_variant(value);
-  else if (std::strcmp(key, "attn_variant") == 0) attention_set_variant(value);
+  if (select_knob_set(key, value)) return SDXL_OK;      // the knobs of the kernel selection (SelectKnobs, select.cpp)
   else if (std::strcmp(key, "igemm_epilogue_staged") == 0) igemm_set_epilogue_staged(value);
   else if (std::strcmp(key, "hl_weights_exact") == 0) igemm_set_hl_weights_exact(value);
-  else if (std::strcmp(key, "igemm_wreg") == 0) igemm_set_wreg(value);
-  else if (std::strcmp(key, "wreg_xattn") == 0) igemm_set_wreg_xattn(value);
-  else if (std::strcmp(key, "igemm_tsw") == 0) igemm_set_tsw(value);
   else if (std::strcmp(key, "igemm_warm") == 0) igemm_set_warm(value);
-  else if (std::strcmp(key, "attn_xsplit") == 0) attention_set_xsplit(value);
   else if (std::strcmp(key, "splitk_wt") == 0) igemm_set_splitk_wt(value);
   else if (std::strcmp(key, "hl_demote") == 0) unet_set_hl_demote(value);
   else if (std::strcmp(key, "mix_classes") == 0) unet_set_mix_classes(value);
-  else if (std::strcmp(key, "hl_tile96") == 0) igemm_set_hl_tile96(value);
   else if (std::strcmp(key, "wreg_xcd2d") == 0) igemm_set_wreg_xcd2d(value);
-  else if (std::strcmp(key, "wide_db") == 0) igemm_set_wide_db(value);
 #ifdef SDXL_MEASURE
-  else if (std::strcmp(key, "igemm_unrolled") == 0) igemm_set_unrolled(value);
   else if (std::strcmp(key, "xa_vec64") == 0) igemm_set_xa_vec64(value);
   else if (std::strcmp(key, "no_cfg") == 0) g_debug_no_cfg = value != 0;
 #endif
@@ -144,6 +137,27 @@ int sdxl_debug_warm_schedule(int n, const unsigned* bytes, const unsigned char* 
   for (int i = 0; i < n; ++i)
     for (int r = 0; r < 3; ++r)
       if (ws.seq[i].warm[r]) warmed_by[(int)(reinterpret_cast<uintptr_t>(ws.seq[i].warm[r]) >> 12) - 1] = i;
+  API_END
+}
+// the kernel selection (select.cpp) on a described launch -- no device needed, the knobs come with the call
+int sdxl_debug_igemm_select(const sdxl_igemm_case* c, const sdxl_select_knobs* knobs, sdxl_igemm_choice* out) {
+  API_BEGIN
+  SDXL_REQUIRE(c && knobs && out, "null argument");
+  const IgemmParams p = select_debug_igemm(*c);
+  const SelectKnobs k = select_debug_knobs(*knobs);
+  *out = sdxl_igemm_choice{};
+  out->gn_part_ok = igemm_gn_part_ok(p, k); out->wreg_selected = igemm_wreg_selected(p, k); out->wreg_xattn_selected = igemm_wreg_xattn_selected(p, k);
+  const IgemmChoice s = igemm_select(p, c->compute_dt, k);
+  out->family = s.family; out->bm = s.bm; out->bn = s.bn; out->ns = s.ns; out->wgm = s.wgm; out->nw = s.nw; out->elem = s.elem; out->a_elem = s.a_elem;
+  out->xa = s.xa; out->xh = s.xh; out->tsw = s.tsw; out->s2 = s.s2; out->splitk = s.splitk; out->mode = s.mode; out->db = s.db; out->measure = s.measure;
+  out->grid = s.grid; out->block = s.block; out->lds = s.lds;
+  API_END
+}
+int sdxl_debug_attn_select(const sdxl_attn_case* c, const sdxl_select_knobs* knobs, sdxl_attn_choice* out) {
+  API_BEGIN
+  SDXL_REQUIRE(c && knobs && out, "null argument");
+  const AttnChoice s = attn_select(select_debug_attn(*c), select_debug_knobs(*knobs));
+  *out = sdxl_attn_choice{s.kernel, s.mix, s.big_heads, s.ns, s.elem, s.ko, s.grid_x, s.grid_y, s.block, s.lds};
   API_END
 }
 #ifdef SDXL_MEASURE

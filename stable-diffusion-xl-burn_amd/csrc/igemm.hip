@@ -307,80 +307,77 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
 }
 
 template <typename T, typename AT, int BM, int BN>
-static void launch_cfg(const IgemmParams& p, hipStream_t s) {
-  const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
-  const size_t lds = 2 * (BM + BN) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, AT, BM, BN>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((igemm_kernel<T, AT, BM, BN>), dim3(tilesM * tilesN), dim3(256), lds, s, p);
+static void launch_cfg(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+  set_max_dynamic_lds<&igemm_kernel<T, AT, BM, BN>>(c.lds, igemm_current_device());
+  hipLaunchKernelGGL((igemm_kernel<T, AT, BM, BN>), dim3(c.grid), dim3(c.block), c.lds, s, p);
 }
-
 template <typename T, typename AT>
-static void launch_tiles(const IgemmParams& p, hipStream_t s) {
-  // pick the block tile minimising (#waves of the grid over the chip) x (tile cost / relative efficiency)
-  struct Cand { int bm, bn; float eff; };
-  const Cand cands[4] = {{128, 128, 1.0f}, {128, 64, 0.85f}, {64, 128, 0.85f}, {64, 64, 0.70f}};
-  int best = 0; float best_cost = 1e30f;
-  for (int c = 0; c < 4; ++c) {
-    if (p.act == 1 && cands[c].bn < 64) continue;
-    const long tiles = (long)((p.M + cands[c].bm - 1) / cands[c].bm) * ((p.N + cands[c].bn - 1) / cands[c].bn);
-    const int slots = 256 * (cands[c].bm * cands[c].bn >= 128 * 128 ? 2 : 4);
-    const long waves = (tiles + slots - 1) / slots;
-    const float cost = (float)waves * cands[c].bm * cands[c].bn / cands[c].eff;
-    if (cost < best_cost) { best_cost = cost; best = c; }
-  }
-  switch (best) {
-    case 0: launch_cfg<T, AT, 128, 128>(p, s); break;
-    case 1: launch_cfg<T, AT, 128, 64>(p, s); break;
-    case 2: launch_cfg<T, AT, 64, 128>(p, s); break;
-    default: launch_cfg<T, AT, 64, 64>(p, s); break;
-  }
+static void launch_generic(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+  if (c.bm == 128 && c.bn == 128) launch_cfg<T, AT, 128, 128>(p, c, s);
+  else if (c.bm == 128) launch_cfg<T, AT, 128, 64>(p, c, s);
+  else if (c.bn == 128) launch_cfg<T, AT, 64, 128>(p, c, s);
+  else launch_cfg<T, AT, 64, 64>(p, c, s);
 }
 
-bool launch_igemm_glds(const IgemmParams& p, int variant, hipStream_t s);   // igemm_glds.hip
-bool launch_igemm_f32_pipe(const IgemmParams& p, hipStream_t s);             // igemm_glds.hip (strict-fp32 mode)
-bool launch_igemm_hl_pipe(const IgemmParams& p, hipStream_t s);              // igemm_glds.hip (split-operand fp32-class mode)
-static std::atomic<int> g_igemm_variant_a{0};   // test hook (sdxl_debug_set "igemm_variant"): -1 generic kernel only, 0 auto, >0 forced tile
-void igemm_set_variant(int v) { g_igemm_variant_a = v; }
+void launch_igemm_dma(const IgemmParams& p, const IgemmChoice& c, hipStream_t s);     // igemm_glds.hip
+void launch_igemm_wreg(const IgemmParams& p, const IgemmChoice& c, hipStream_t s);    // igemm_wreg.hip
+#ifdef SDXL_MEASURE
+bool launch_igemm_measure(const IgemmParams& p, int variant, hipStream_t s);          // igemm_measure.hip; false: a number it does not know / a shape it refuses
+#endif
+// knobs that are only passed on to the kernels
 static std::atomic<int> g_xa_vec64{0};
 void igemm_set_xa_vec64(int v) { g_xa_vec64 = v; }
 static std::atomic<int> g_igemm_epi_staged{0};
 void igemm_set_epilogue_staged(int v) { g_igemm_epi_staged = v; }
 static std::atomic<int> g_hl_wexact{1};
 void igemm_set_hl_weights_exact(int v) { g_hl_wexact = v; }
+static std::atomic<int> g_splitk_wt{1};   // A/B knob (sdxl_debug_set "splitk_wt"): 0 = split-K slabs by plain stores + agent-scope release (the round-2 form)
+void igemm_set_splitk_wt(int v) { g_splitk_wt = v; }
 
-void launch_igemm(const IgemmParams& pin, int compute_dt, hipStream_t s) {
+// the knobs of a launch and whether the current device has its zero page
+SelectKnobs igemm_launch_knobs() {
+  SelectKnobs k = select_knobs_snapshot();
+  k.zero_page = igemm_zero_page() != nullptr;
+  return k;
+}
+
+// select (select.cpp) on the caller's snapshot of the knobs, dispatch
+void launch_igemm(const IgemmParams& pin, int compute_dt, const SelectKnobs& knobs, hipStream_t s) {
   if (pin.M <= 0 || pin.N <= 0) return;
   IgemmParams p = pin;
   p.epi_staged = g_igemm_epi_staged.load();
   p.xa_vec64 = g_xa_vec64.load();
   p.hl_wexact_ok = g_hl_wexact.load();
-  const int g_igemm_variant = g_igemm_variant_a.load();
-  if (compute_dt == DT_F16 && g_igemm_variant >= 0 && launch_igemm_glds(p, g_igemm_variant, s)) return;
-  if (compute_dt == DT_F16 && g_igemm_variant > 0 && launch_igemm_glds(p, 0, s)) return;   // forced tile refused the shape
-  if (p.shadow && compute_dt != DT_F16) throw std::runtime_error("an f16 shadow output needs an f16 GEMM (weights-in-registers kernel)");
-  if (compute_dt == DT_F32 && g_igemm_variant >= 0 && launch_igemm_f32_pipe(p, s)) return;
-  if (compute_dt == DT_HL) {     // no generic twin: layers the HL pipeline cannot take are packed (and launched) as fp32 by the host
-    if (launch_igemm_hl_pipe(p, s)) return;
-    throw std::runtime_error("split-operand (DT_HL) GEMM: shape / alignment outside the direct-to-LDS pipeline");
+  IgemmChoice c = igemm_select(p, compute_dt, knobs);
+#ifdef SDXL_MEASURE
+  if (c.family == IG_MEASURE) {     // a number of igemm_measure.hip: it refuses what it does not know, the automatic choice then stands in once
+    SelectKnobs k = knobs;
+    IgemmParams q = p;
+    q.splitk = 1; q.splitk_wt = g_splitk_wt.load();
+    if (launch_igemm_measure(q, c.measure, s)) return;
+    if (k.igemm_variant > 0) { k.igemm_variant = 0; c = igemm_select(p, compute_dt, k); }
+    if (c.family == IG_MEASURE && launch_igemm_measure(q, c.measure, s)) return;
+    if (c.family == IG_MEASURE) throw std::runtime_error("igemm: the measure-only variant refused the shape");
   }
-  if (p.xa_k) throw std::runtime_error("fused cross-attention needs the f16 direct-to-LDS kernels");
-  if (p.shadow) throw std::runtime_error("an f16 shadow output needs the f16 weights-in-registers kernel");
-  // the generic kernels below never write the GroupNorm statistics: a caller that was promised them (run_conv tags the output
-  // Act and the consumer skips its statistics pass) must not get uninitialised memory -- forced variants, unaligned A, no zero page
-  if (p.gn_part) throw std::runtime_error("GroupNorm statistics from the epilogue (gn_part) need the f16 direct-to-LDS 256x128 kernel");
-  if (p.ln_stat || p.stat_out)
-    throw std::runtime_error("LayerNorm-folded GEMM (ln_stat / stat_out) needs the f16 direct-to-LDS kernels");
-  if (compute_dt == DT_F16) {
-    if (p.a_dt == DT_F16) launch_tiles<half_t, half_t>(p, s);
-    else launch_tiles<half_t, float>(p, s);
-  } else {
-    launch_tiles<float, float>(p, s);
+#endif
+  if (c.family != IG_GENERIC) {
+    p.splitk = c.splitk;
+    if (compute_dt == DT_F16 || c.splitk > 1) p.splitk_wt = g_splitk_wt.load();
   }
+  switch (c.family) {
+    case IG_GLDS: case IG_PIPE: case IG_WIDE: launch_igemm_dma(p, c, s); break;
+    case IG_WREG: launch_igemm_wreg(p, c, s); break;
+    case IG_GENERIC:
+      if (c.elem == DT_F16 && c.a_elem == DT_F16) launch_generic<half_t, half_t>(p, c, s);
+      else if (c.elem == DT_F16) launch_generic<half_t, float>(p, c, s);
+      else launch_generic<float, float>(p, c, s);
+      break;
+    default: throw std::logic_error("igemm: the selection returned nothing to launch");
+  }
+}
+void launch_igemm(const IgemmParams& p, int compute_dt, hipStream_t s) {
+  if (p.M <= 0 || p.N <= 0) return;
+  launch_igemm(p, compute_dt, igemm_launch_knobs(), s);
 }
 
 }  // namespace sdxl

@@ -1216,9 +1216,4 @@ __device__ __forceinline__ void xattn_inplace_hl(const IgemmParams& p, f32x16 (&
   lnA[0] = 1.f; lnC[0] = 0.f;                                         // the store adds nothing more
 }
 
-// per-device state owned by igemm_glds.hip
-const void* igemm_zero_page();          // null until igemm_glds_init() ran on the current device
-int igemm_current_device();
-constexpr int kIgemmMaxDev = 64;
-
 }  // namespace sdxl

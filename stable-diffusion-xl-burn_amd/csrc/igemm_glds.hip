@@ -1007,22 +1007,17 @@ __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, co
 #endif
 }
 
-// Per-DEVICE state: the zero page the DMA reads halo / tail rows from lives on the device that launches, and the
-// dynamic-LDS attribute (up to 147 KiB) is set once per (kernel, device).  A second sdxl_ctx on another GPU of the same
+// Per-DEVICE state: the zero page the DMA reads halo / tail rows from lives on the device that launches (the dynamic-LDS
+// attribute, up to 147 KiB, is per (kernel, device) too: set_max_dynamic_lds).  A second sdxl_ctx on another GPU of the same
 // process gets its own.
-constexpr int kMaxDev = 64;
-static const void* g_zero_pages[kMaxDev] = {};
+static const void* g_zero_pages[kMaxDevices] = {};
 static int current_device() {
   int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) throw std::runtime_error("igemm: no current HIP device");
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) throw std::runtime_error("igemm: no current HIP device");
   return d;
 }
 const void* igemm_zero_page() { return g_zero_pages[current_device()]; }
 int igemm_current_device() { return current_device(); }
-static_assert(kMaxDev == kIgemmMaxDev, "per-device tables of the two translation units must agree");
-#ifdef SDXL_MEASURE
-bool launch_igemm_measure(const IgemmParams& p, int variant, hipStream_t s);   // igemm_measure.hip
-#endif
 void igemm_glds_init() {
   const int d = current_device();
   if (g_zero_pages[d]) return;
@@ -1031,172 +1026,39 @@ void igemm_glds_init() {
     throw std::runtime_error("igemm: cannot allocate the zero page");
   g_zero_pages[d] = z;
 }
-template <typename K> static void set_lds_attr(K kernel, size_t lds, bool (&done)[kMaxDev], int dev) {
-  if (done[dev]) return;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    throw std::runtime_error("igemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-  done[dev] = true;
-}
 
+// ---- launchers: a choice of igemm_select (select.cpp) -> its template instantiation.  Nothing here looks at the shape.
 template <int BM, int BN, int NS, int MINB = 2>
-static void launch_glds(const IgemmParams& p, hipStream_t s) {
-  const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
-  const size_t lds = (size_t)NS * (BM + BN) * 128;
-  static bool attr_set[kMaxDev] = {};
+static void launch_glds(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
   const int dev = current_device();
-  set_lds_attr(&igemm_glds_kernel<BM, BN, NS, MINB>, lds, attr_set, dev);
-  hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, NS, MINB>), dim3(tilesM * tilesN), dim3(256), lds, s, p, g_zero_pages[dev]);
+  set_max_dynamic_lds<&igemm_glds_kernel<BM, BN, NS, MINB>>(c.lds, dev);
+  hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, NS, MINB>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
 }
 
 template <int BM, int BN, int NS, int WGM = 4, int NW = 8, typename T = half_t, bool XA = false, bool S2 = false, bool TSW = false, bool XH = false>
-static void launch_pipe(const IgemmParams& p, hipStream_t s) {
-  const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
-  const size_t lds = (size_t)pipe_lds_total(NS * (BM + BN) * 128, 0);   // ring + LayerNorm coefficients
-  static bool attr_set[kMaxDev] = {};
+static void launch_pipe(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+  // (the kernel carves the ring + LayerNorm coefficients out of its template arguments)
+  if (c.lds != pipe_lds_total(NS * (BM + BN) * 128, 0) || c.block != 64 * NW) throw std::logic_error("igemm: choice and kernel disagree on the LDS layout");
   const int dev = current_device();
-  set_lds_attr(&igemm_pipe_kernel<BM, BN, NS, WGM, NW, T, XA, S2, TSW, XH>, lds, attr_set, dev);
-  const int sk = (BN == 128 && p.splitk > 1) ? p.splitk : 1;
-  if (sk > 1 && (size_t)tilesM * tilesN * sk * BM * BN * 4 > p.splitk_ws_bytes) throw std::runtime_error("igemm: split-K workspace too small");
-  IgemmParams q = p;
-  q.splitk = sk;
-  hipLaunchKernelGGL((igemm_pipe_kernel<BM, BN, NS, WGM, NW, T, XA, S2, TSW, XH>), dim3(tilesM * tilesN * sk), dim3(64 * NW), lds, s, q, g_zero_pages[dev]);
+  set_max_dynamic_lds<&igemm_pipe_kernel<BM, BN, NS, WGM, NW, T, XA, S2, TSW, XH>>(c.lds, dev);
+  if (c.splitk > 1 && (size_t)c.grid * BM * BN * 4 > p.splitk_ws_bytes) throw std::runtime_error("igemm: split-K workspace too small");
+  hipLaunchKernelGGL((igemm_pipe_kernel<BM, BN, NS, WGM, NW, T, XA, S2, TSW, XH>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
 }
 
-static std::atomic<int> g_wide_db{0};     // measure builds, knob (sdxl_debug_set "wide_db"): 1 = the wide GEGLU kernel with register-double-buffered fragments
-void igemm_set_wide_db(int v) { g_wide_db = v; }
-static void launch_wide(const IgemmParams& p, hipStream_t s) {
-  // three slots (was four): the k-loop is not latency-bound and the whole ring is requested before the first MFMA -- 108 instead of
-  // 144 KiB per CU; same-box library A/B on the bench line 21.19 / 21.12 -> 21.07 / 21.09 ms per step (profiles/r04_ring_depth_lib_ab.txt)
-  constexpr int NS = 3;
-  const int tilesM = (p.M + 255) / 256, tilesN = (p.N + 319) / 320;
-  const size_t lds = (size_t)NS * (256 + 320) * 64 + 2048;   // ring + LayerNorm coefficients
-  static bool attr_set[2][kMaxDev] = {};
+static void launch_wide(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
   const int dev = current_device();
 #ifdef SDXL_MEASURE
   // register-double-buffered fragment reads (DB): measured on the bench line A/B/A/B, 21.213 / 21.179 (DB) vs 21.209 / 21.190 ms per step -- no
   // difference (profiles/r05_wide_double_buffer_ab.txt): the k-tile is LDS-bandwidth + matrix-pipe co-bound (112 KiB of fragment reads + 36 KiB of
   // DMA writes = 1156 LDS cycles against 1280 MFMA cycles), not latency-bound.  Measure builds only.
-  if (g_wide_db.load()) {
-    set_lds_attr(&igemm_wide_kernel<NS, true>, lds, attr_set[1], dev);
-    hipLaunchKernelGGL((igemm_wide_kernel<NS, true>), dim3(tilesM * tilesN), dim3(512), lds, s, p, g_zero_pages[dev]);
+  if (c.db) {
+    set_max_dynamic_lds<&igemm_wide_kernel<3, true>>(c.lds, dev);
+    hipLaunchKernelGGL((igemm_wide_kernel<3, true>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
     return;
   }
 #endif
-  set_lds_attr(&igemm_wide_kernel<NS, false>, lds, attr_set[0], dev);
-  hipLaunchKernelGGL((igemm_wide_kernel<NS, false>), dim3(tilesM * tilesN), dim3(512), lds, s, p, g_zero_pages[dev]);
-}
-
-
-// variant: 0 auto; 1 = 128x128 ring 3; 2 = 128x64 ring 4; 3 = 64x128 ring 4; 4 = 128x128 ring 2; 5 = 128x64 ring 2;
-// 6 = 64x128 ring 2; 7 = 128x128 ring 4; 8 = 64x128 ring 3.  Returns false when the shape needs the generic kernel.
-static std::atomic<int> g_splitk_wt{1};   // A/B knob (sdxl_debug_set "splitk_wt"): 0 = split-K slabs by plain stores + agent-scope release (the round-2 form)
-void igemm_set_splitk_wt(int v) { g_splitk_wt = v; }
-static std::atomic<int> g_tsw{1};      // A/B knob (sdxl_debug_set "igemm_tsw"): 0 = the V^T part of a fused QKV projection keeps the LDS-staged transposed epilogue
-void igemm_set_tsw(int v) { g_tsw = v; }
-static bool g_igemm_unrolled = true;
-void igemm_set_unrolled(int v) { g_igemm_unrolled = v != 0; }
-
-// Split-K rule.  It depends on ONE batch entry's shape (rows per entry, N, K) only -- never on the batch size -- so an entry
-// comes out bit-identical whether it runs alone or next to others (the CFG pair as one batch-2 forward, split-CFG chains).
-int igemm_splitk_slices(const IgemmParams& p) {
-  if (!p.splitk_ws || !p.splitk_cnt) return 1;
-  if (p.act != 0 || p.n_split < p.N || p.ln_stat) return 1;
-  const int nk = p.Kpad / 64;
-  // measured (profiles/r02_splitk_sweep.txt): pays from K ~ 11520 (the 32^2 convs: +4 % at K = 11520, +22 % at K = 23040); at
-  // K = 5120 (FF-out) the serial combine costs more than the 24 % fewer bytes moved buy (57 vs 44 us), so the bar is 160 k-tiles
-  // (round 6: N up to 1536 -- the refiner's 32^2 / 16^2 levels were excluded by the base model's 1280 and ran their K = 13824 ... 27648 convolutions on 12 - 48
-  //  workgroups; and EIGHT slices where an entry has one 256-row tile: the 16^2 level of the refiner / of a 512^2 base image streams 42 - 85 MB of weights through
-  //  12 x 8 workgroups instead of 12 x 3 -- profiles/r06_refiner_shape_profile.txt)
-  if (p.rpb <= 0 || p.rpb > 1024 || p.N > 1536 || nk < 160) return 1;
-  return p.rpb <= 256 ? 8 : 3;
-}
-size_t igemm_splitk_ws_bytes(int batch, int rows_per_entry, int n_max) {
-  if (n_max > 1536) n_max = 1536;          // wider outputs never split (igemm_splitk_slices)
-  const long rows3 = (long)batch * (rows_per_entry < 1024 ? rows_per_entry : 1024), rows8 = (long)batch * (rows_per_entry < 256 ? rows_per_entry : 256);
-  const size_t slabs3 = (size_t)((rows3 + 255) / 256) * 3, slabs8 = (size_t)((rows8 + 255) / 256) * 8;
-  return (slabs3 > slabs8 ? slabs3 : slabs8) * (size_t)((n_max + 127) / 128) * 256 * 128 * 4;
-}
-
-// Cost of a grid of bm x bn tiles over an M x N output with nk k-tiles (arbitrary units, ~ns).  A workgroup's k-loop time goes
-// with the bytes it stages per k-tile, (bm + bn) x 128 -- operand staging, not MFMA issue, bounds these kernels --
-// and that holds per CU: a single round costs a full tile time however few CUs it fills (128x128 over 2048 x 1280 = 160
-// workgroups takes as long per k-tile as 256 would).  Rounds after the first overlap with their predecessors' tails: a partly
-// filled last round costs its fill fraction, but never less than 2/3.  FIXED ~ 8 us of launch / prologue / epilogue per round.
-// w = 1.2 for the 8x1-wave 256x160 tile (6 fragment reads per 5 MFMAs), 1.05 for 256x320.
-static double tile_cost(int M, int N, int nk, int bm, int bn, double w) {
-  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const long full = tiles / 256, rem = tiles % 256;
-  const double frac = rem == 0 ? 0.0 : (full == 0 ? 1.0 : (rem / 256.0 > 2.0 / 3.0 ? rem / 256.0 : 2.0 / 3.0));
-  return ((double)full + frac) * (bm + bn) * nk * w + (double)(full + (rem ? 1 : 0)) * 3000.0;
-}
-
-// Tile choice by a two-term cost model fitted to the sweeps (profiles/r01_igemm_sweep.txt, r02_tile_sweep_256x160_256x320.txt,
-// r02_tile_96x128.txt) -- tile_cost() above.  What the model buys: N = 320 / 1280 convs at 128^2 / 64^2 get 256x160 tiles =
-// exactly one round (conv128 320: 95 -> 69 us, conv64 1280up: 353 -> 235 us), the GEGLU projections the one-round 256x320 tile
-// (lin64 geglu 88 -> 77 us, lin32 geglu 67 -> 63 us), and the M = 2048 x N = 1280 linears (attention out / query projections,
-// FF-out: 240 launches per step) 96x128 tiles -- 220 workgroups that each stage 12.5 % fewer bytes than the 160 of 128x128
-// (19 -> 17 us, 54 -> 47 us), and the M = 8192 x N = 640 shapes of the 64^2 level 128x160 tiles (4 waves, 32x160 wave tiles) = exactly
-// 256 workgroups where 256x128 made 160 (conv64 640 82 -> 70 us, 1920>640 243 -> 201, lin64 ff 44 -> 39; profiles/r02_tile_128x160.txt).
-// Returns the production variant id (35, 36 / 44, 45, 38, 49, 26).
-static int pick_tile(const IgemmParams& p, bool allow_128x160 = true) {
-  const int nk = p.Kpad / 64;
-  struct Cand { int v, bm, bn; double w; bool ok; };
-  const bool lin = p.ksize == 1 && p.stride == 1 && p.up == 0;
-  const Cand cands[6] = {
-      {35, 256, 128, 1.0, true},
-      {36, 128, 128, 1.0, true},
-      {45, 96, 128, 1.0, true},
-      {38, 256, 160, 1.2, p.N % 160 == 0 && !p.stat_out},
-      {49, 128, 160, 1.15, allow_128x160 && p.N % 160 == 0 && !p.stat_out && p.act == 0},
-      {26, 256, 320, 1.05, p.act == 1 && lin && p.N % 320 == 0}};
-  double best = 1e300;
-  int variant = 35;
-  for (const Cand& c : cands) {
-    if (!c.ok) continue;
-    const double cost = tile_cost(p.M, p.N, nk, c.bm, c.bn, c.w);
-    if (cost < best) { best = cost; variant = c.v; }
-  }
-  if (variant == 36 && nk >= 40) variant = 44;   // long contractions: the 5-slot ring (4 tiles in flight) is 3-6 % faster (profiles/r02_ring5_ab.txt)
-  return variant;
-}
-
-static std::atomic<int> g_hl_tile96{29};     // bit 0: 96x128 for linears, bit 1: ... for 3x3 convs too (not selected), bit 2: 4-wave 128x160 for N % 160 == 0, N % 128 != 0 layers, bit 3: ... wherever the cost model prefers it, bit 4: in-launch split-K for the K >= 10240 convolutions
-void igemm_set_hl_tile96(int v) { g_hl_tile96 = v; }
-// GroupNorm statistics from the producing GEMM's epilogue (IgemmParams::gn_part): taken by the 256x128 kernel (plain or split-K)
-// when that is the tile the selection picks anyway, whole 256-row tiles inside one batch entry, f16 operands, plain epilogue.
-bool igemm_gn_part_ok(const IgemmParams& p) {
-  if (p.a_dt == DT_HL) {
-    // split-operand convolutions (round 6): where the selection runs the 256x128 kernel anyway -- the in-launch split-K of the K >= 10240 convolutions
-    // of the 32^2 level (launch_igemm_hl_pipe; one entry's shape only) -- its staged epilogue leaves the statistics of the fp32 rows
-    if (p.c_dt != DT_F32 || (p.Cin % 32) != 0 || (p.lda % 4) != 0 || (p.Kpad % 32) != 0) return false;
-    if (p.act != 0 || p.n_split < p.N || p.stat_out || p.ln_stat || p.xa_k) return false;
-    if (p.M % 256 != 0 || p.rpb <= 0 || p.rpb % 256 != 0 || p.N % 64 != 0) return false;
-    if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-    if ((p.ldc & 3) != 0 || (reinterpret_cast<uintptr_t>(p.C) & 15) != 0) return false;
-    return (g_hl_tile96.load() & 16) && igemm_splitk_slices(p) > 1;
-  }
-  if (p.a_dt != DT_F16 || p.c_dt != DT_F16 || (p.Cin % 64) != 0 || (p.lda % 8) != 0 || (p.Kpad % 64) != 0) return false;
-  if (p.act != 0 || p.n_split < p.N || p.stat_out || p.ln_stat || p.xa_k) return false;
-  if (p.M % 256 != 0 || p.rpb <= 0 || p.rpb % 256 != 0 || p.N % 64 != 0) return false;
-  if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-  // Like the split-K rule this must depend on ONE batch entry's shape only -- the statistics path rounds differently from the
-  // statistics kernel, and an entry has to come out bit-identical alone, in the CFG pair or in a larger batch.  The tile
-  // preference is therefore evaluated for the CFG pair (2 entries), whatever the actual batch.
-  IgemmParams q = p;
-  q.M = 2 * p.rpb;
-  if (igemm_splitk_slices(p) > 1) return true;
-  if (pick_tile(q, false) != 35) return false;
-  // 128x160 tiles cannot leave the statistics (32x160 wave tiles): keep 256x128 + statistics unless the other tile saves more than
-  // the statistics launch it brings back (~13 us ~ 6000 cost units)
-  const int nk = p.Kpad / 64;
-  const bool t160 = p.N % 160 == 0;
-  return !t160 || tile_cost(q.M, q.N, nk, 256, 128, 1.0) - tile_cost(q.M, q.N, nk, 128, 160, 1.15) < 6000.0;
-}
-
-bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx) {
-  // (c_dt: f16 rows; HL16 rows for the split-precision form behind an fp32-class out-projection -- the row / staged epilogues store either)
-  return a_dt == DT_F16 && (c_dt == DT_F16 || c_dt == DT_HL) && M > 0 && N % 64 == 0 && K % 64 == 0 && rpb > 0 && rpb % 64 == 0 && M % rpb == 0 &&
-         n_ctx >= 1 && n_ctx <= 96;
+  set_max_dynamic_lds<&igemm_wide_kernel<3, false>>(c.lds, dev);
+  hipLaunchKernelGGL((igemm_wide_kernel<3, false>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
 }
 
 // Context K [B][n_ctx][C] / V^T [B][C][vt_ld] (f16) -> the operand-order image xattn_inplace reads: per (batch entry, head) 24
@@ -1232,199 +1094,36 @@ void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, i
                      reinterpret_cast<const half_t*>(Vt), reinterpret_cast<half8*>(out), B, C, nctx, vt_ld);
 }
 
-bool launch_igemm_wreg(const IgemmParams& p, int variant, hipStream_t s);   // igemm_wreg.hip
-bool launch_igemm_wreg_xattn(const IgemmParams& p, int variant, hipStream_t s);   // igemm_wreg.hip
-bool launch_igemm_glds(const IgemmParams& p, int variant, hipStream_t s) {
-  if (!g_zero_pages[current_device()]) return false;
-  if (p.act > 1) return false;   // GELU / QuickGELU epilogues (CLIP MLP, once per prompt) live in the generic kernel
-  if (p.a_dt != DT_F16 || (p.Cin % 64) != 0 || (p.lda % 8) != 0 || (p.Kpad % 64) != 0) return false;
-  if ((reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
-  if (p.n_split < p.N && (p.n_split & 3) != 0) return false;
-  if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-  if (p.stat_out && (variant == 2 || variant == 5 || variant == 19 || variant == 38)) return false;   // wave tiles narrower / other than 64 columns
-  // the DMA reads weight rows up to the tile edge: Npad is a multiple of 128 for every packed weight (pack_* kernels)
-  const bool was_auto = variant == 0;
-  IgemmParams psk = p;
-  psk.splitk = 1;
-  psk.splitk_wt = g_splitk_wt.load();
-  if (p.xa_k) {
-    // fused cross-attention: wave tiles of 64 columns only (256x128 / 128x128), chosen by the same cost model
-    if (p.act != 0 || p.n_split < p.N || p.stat_out || p.R || p.ebias ||
-        !igemm_xattn_ok(p.a_dt, p.c_dt, p.M, p.N, p.K, p.rpb, p.xa_nctx))
-      throw std::runtime_error("igemm: fused cross-attention needs a plain f16 projection (no residual / split outputs)");
-    if (!p.xa_k_lo && p.c_dt != DT_F16) throw std::runtime_error("igemm: the f16 fused cross-attention writes f16 rows");
-    const int nk = p.Kpad / 64;
-    if (p.xa_k_lo) {     // split precision: the one-MFMA-row tiles only (96x128 / 128x128), same cost model
-      const double c128 = tile_cost(p.M, p.N, nk, 128, 128, 1.0), c96 = tile_cost(p.M, p.N, nk, 96, 128, 1.0);
-      if (c96 < c128) launch_pipe<96, 128, 3, 3, 6, half_t, true, false, false, true>(psk, s);
-      else launch_pipe<128, 128, 4, 4, 8, half_t, true, false, false, true>(psk, s);
-      return true;
-    }
-    int v = variant;
-    // the f16 form of a layer whose weights also exist in fragment order: the weights-in-registers kernel with the attention behind its
-    // partial-sum exchange (igemm_wreg.hip, XA instantiation; static rule per layer, knob "wreg_xattn").  Forced pipe tiles stay forced.
-    if (v != 35 && v != 36 && v != 44 && v != 45 && launch_igemm_wreg_xattn(psk, v, s)) return true;
-    if (v != 35 && v != 36 && v != 44 && v != 45) {
-      const double c256 = tile_cost(p.M, p.N, nk, 256, 128, 1.0), c128 = tile_cost(p.M, p.N, nk, 128, 128, 1.0), c96 = tile_cost(p.M, p.N, nk, 96, 128, 1.0);
-      v = c256 <= c128 && c256 <= c96 ? 35 : (c96 < c128 ? 45 : (nk >= 40 ? 44 : 36));
-    }
-    if (v == 35) launch_pipe<256, 128, 3, 4, 8, half_t, true>(psk, s);
-    else if (v == 36) launch_pipe<128, 128, 4, 4, 8, half_t, true>(psk, s);
-    else if (v == 44) launch_pipe<128, 128, 5, 4, 8, half_t, true>(psk, s);
-    else launch_pipe<96, 128, 3, 3, 6, half_t, true>(psk, s);     // (three slots, was five: 21.47 -> 21.39 / 21.38 ms per step with three / four, profiles/r04_ring_depth_lib_ab.txt)
-    return true;
-  }
-  if (p.gn_part) {
-    if (!igemm_gn_part_ok(p)) throw std::runtime_error("igemm: GroupNorm statistics requested from a shape the 256x128 epilogue does not take");
-    variant = 0;            // (a forced test variant must not drop the statistics)
-  }
-  // plain linear layers / 1x1 convs whose weights also exist in fragment order: the weights-in-registers kernel (igemm_wreg.hip).
-  // The rule is static per layer (never the batch), so its k-summation order (even + odd k-tiles) is what such a layer always gets.
-  if (p.shadow) {      // f16 shadow of an fp32 output: written by the weights-in-registers epilogue only (run_conv asks igemm_wreg_selected before it sets the field)
-    if (!launch_igemm_wreg(psk, 0, s)) throw std::runtime_error("igemm: an f16 shadow output needs the weights-in-registers kernel");
-    return true;
-  }
-  if ((variant == 0 || (variant >= 60 && variant <= 77)) && launch_igemm_wreg(psk, variant, s)) return true;
-  if (variant >= 60 && variant <= 77) return false;
-  if (variant == 0 && igemm_splitk_slices(p) > 1) {
-    // long contractions over a small output (FF-out and the 32^2 convs of the CFG pair: M = 2048, N = 1280 is 80 tiles of
-    // 256x128 on 256 CUs): three k-slices per tile fill the chip with the tile shape that moves the fewest bytes per flop
-    psk.splitk = igemm_splitk_slices(p);
-    launch_pipe<256, 128, 3, 4, 8>(psk, s);
-    return true;
-  }
-  if (variant == 0) variant = p.gn_part ? 35 : pick_tile(p);
-#ifdef SDXL_MEASURE
-  if (was_auto && !g_igemm_unrolled) {   // A/B against the rolled loops (profiles/r01_igemm_unrolled_ab.txt)
-    if (variant == 35) variant = 11; else if (variant == 36) variant = 13; else if (variant == 38) variant = 19;
-  }
-#else
-  (void)was_auto;
-#endif
-  switch (variant) {
-    // ---- production kernels (what the auto selection launches)
-    case 4: launch_glds<128, 128, 2>(psk, s); break;                          // 4 waves, 2-3 co-resident blocks: ragged multi-round grids
-    case 6: launch_glds<64, 128, 2>(psk, s); break;
-    case 35:    // 8 waves, hand-ordered k-loop unrolled by the ring depth; outputs with a transposed part (fused QKV: V^T) take the operand-swap twin
-      if (p.n_split < p.N && g_tsw.load() && p.c_dt == DT_F16) launch_pipe<256, 128, 3, 4, 8, half_t, false, false, true>(psk, s);      // (the operand-swapped V^T epilogue writes f16 rows)
-      else launch_pipe<256, 128, 3, 4, 8>(psk, s);
-      break;
-    case 36: launch_pipe<128, 128, 4, 4, 8>(psk, s); break;
-    case 38:                                                                // 256x160 GEGLU tile (8x1 waves)
-      if (p.N % 160 != 0) return false;
-      launch_pipe<256, 160, 3, 8, 8>(psk, s); break;
-    case 44: launch_pipe<128, 128, 5, 4, 8>(psk, s); break;   // 5-slot ring = all 160 KiB of LDS: 4 tiles in flight
-    case 45: launch_pipe<96, 128, 5, 3, 6>(psk, s); break;    // 6 waves (3 x 2), 96-row tile: M = 2048 x N = 1280 -> 220 workgroups
-    case 46: launch_pipe<96, 128, 4, 3, 6>(psk, s); break;
-    // 45 with ONE rendezvous per two k-tiles (S2).  Alone, on L2-resident operands, 2 - 4 % faster on every shape of the step; inside
-    // the step, where the weights stream in cold, the tile less in flight costs more than the rendezvous saved: GEMM class 20.95 -
-    // 21.04 vs 20.76 - 20.82 ms on one box (profiles/r03_two_tiles_per_rendezvous.txt).  Kept as the A/B partner, not selected.
-    case 47: launch_pipe<96, 128, 5, 3, 6, half_t, false, true>(psk, s); break;
-    case 49:                                                                // 4 waves 4x1 (32x160 wave tiles): N = 640 at 64^2 -> exactly 256 tiles
-      if (p.N % 160 != 0 || p.stat_out) return false;
-      launch_pipe<128, 160, 3, 4, 4>(psk, s); break;
-    case 26:                                                                // 256x320, k-tile 32: linear GEGLU projections only
-      if (p.act != 1 || p.ksize != 1 || p.stride != 1 || p.up != 0 || p.N % 320 != 0 || p.Kpad % 32 != 0) return false;
-      launch_wide(psk, s); break;
-#ifdef SDXL_MEASURE
-    default: return launch_igemm_measure(psk, variant, s);   // A/B partners, measurement modes (igemm_measure.hip)
-#else
-    default: return false;
-#endif
-  }
-  return true;
-}
-
-// Strict-fp32 mode on the same direct-to-LDS pipeline (the VAE at the reference's precision, sample/main.rs:121,273, and the
-// parity configuration of the UNet): fp32 operands staged as 128-byte rows of 32 k-values, four v_mfma_f32_32x32x2_f32 per
-// fragment pair.  The f32 MFMA runs at 1/16 of the f16 rate, so these launches are matrix-pipe bound and the tile choice
-// only has to keep the rounds of 256 CUs full.  Returns false for shapes the generic kernel must take.
-bool launch_igemm_f32_pipe(const IgemmParams& p, hipStream_t s) {
-  if (!g_zero_pages[current_device()]) return false;
-  if (p.act > 1 || p.ln_stat || p.stat_out) return false;
-  if (p.a_dt != DT_F32 || (p.Cin % 32) != 0 || (p.lda % 4) != 0 || (p.Kpad % 32) != 0) return false;
-  if ((reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
-  if (p.n_split < p.N && (p.n_split & 3) != 0) return false;
-  if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-  const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-  const long t256 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-  const double eff128 = (double)t128 / (double)(((t128 + 255) / 256) * 256);
-  const double eff256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-  IgemmParams q = p;
-  q.splitk = 1;
-  if (eff256 >= eff128) launch_pipe<256, 128, 3, 4, 8, float>(q, s);
-  else launch_pipe<128, 128, 4, 4, 8, float>(q, s);
-  return true;
-}
-
-// Split-operand mode (DT_HL; igemm_common.h): HL16 operands on the same direct-to-LDS pipeline, 3 f16 MFMAs per 16-deep product.
-// Returns false for shapes the generic kernel must take (none in the VAE: its Cin % 32 != 0 layers are packed fp32).
-bool launch_igemm_hl_pipe(const IgemmParams& p, hipStream_t s) {
-  if (!g_zero_pages[current_device()]) return false;
-  if (p.act > 1 || p.ln_stat || p.stat_out || p.xa_k) return false;
-  if (p.a_dt != DT_HL || (p.Cin % 32) != 0 || (p.lda % 4) != 0 || (p.Kpad % 32) != 0) return false;
-  if (p.gn_part && !igemm_gn_part_ok(p)) throw std::runtime_error("igemm: GroupNorm statistics requested from a split-operand shape the 256x128 split-K epilogue does not take");
-  if ((reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
-  if (p.n_split < p.N && (p.n_split & 3) != 0) return false;
-  if (p.c_dt == DT_HL) {
-    // HL16 outputs are written as whole 8-column (8-key) pieces: plain outputs with aligned rows, a fully transposed one (the
-    // VAE's V^T) whose batch entries are whole pieces, or a split at a multiple of 128 columns (the UNet's q | k | V^T: a wave
-    // tile is then wholly on one side); ragged splits go out as fp32
-    if (p.n_split < p.N && p.n_split != 0 && ((p.n_split & 127) != 0 || p.act != 0)) return false;
-    const int nout = p.act == 1 ? (p.N >> 1) : p.N;
-    if (p.n_split != 0 && ((nout & 7) != 0 || (p.ldc & 15) != 0 || (reinterpret_cast<uintptr_t>(p.C) & 15) != 0)) return false;
-    if (p.n_split < p.N && ((p.ct_ld & 15) != 0 || (p.rpb & 7) != 0 || (p.M % 8) != 0 || (reinterpret_cast<uintptr_t>(p.Ct) & 15) != 0)) return false;
-  }
-  if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-  const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-  const long t256 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-  const double eff128 = (double)t128 / (double)(((t128 + 255) / 256) * 256);
-  const double eff256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-  IgemmParams q = p;
-  q.splitk = 1;
-  // round 5: the 96-row tile of the f16 engine for the shapes where it fills more of the chip's single round -- the M = 2048 x N = 1280 linears of the
-  // 32^2 level (out-projections, cross-attention query projection, FF-out: 220 workgroups instead of 160).  Same k order in every tile shape, so the
-  // choice never changes a result bit (A/B knob: sdxl_debug_set "hl_tile96").
-  const long t96 = (long)((p.M + 95) / 96) * ((p.N + 127) / 128);
-  const int t96mode = g_hl_tile96.load();      // 1: linear layers / 1x1 only (default), 2: 3x3 convolutions too (measured -0.15 % on the mixed mode's step: not selected)
-  // (never a shape the in-launch split-K below would take: split-K depends on ONE entry's shape, this tile choice on the batched M -- testing it first
-  //  would give a K >= 10240 linear layer one summation order at B <= 2 and another at B >= 3)
-  if ((t96mode & 1) && (p.ksize == 1 || (t96mode & 2)) && p.n_split >= p.N && t128 < 256 && t96 <= 256 && t96 > t128 && eff256 < (double)t96 / 256.0 &&
-      !((t96mode & 16) && igemm_splitk_slices(p) > 1)) {
-    launch_pipe<96, 128, 5, 3, 6, hl16_t>(q, s);
-    return true;
-  }
-  // (a 256x160 HL tile for the N = 320 convolutions of the 128^2 level -- no 17 % of column padding -- spills DMA pointers inside its k-loop: scratch
-  //  loads in the VM queue break the hand-counted vmcnt waits.  Not instantiated.)
-  // long contractions over a small output (the K >= 10240 convolutions of the 32^2 level: 80 tiles of 256x128): three k-slices per tile combined inside the
-  // launch, as in the f16 engine (igemm_splitk_slices: depends on one batch entry's shape only; slabs summed in slice order: bit-reproducible) -- 240
-  // workgroups instead of the 160 of 128x128 tiles.  Mixed-mode step 41.18 / 41.22 -> 40.60 / 40.56 ms, A/B/A/B; F32_SPLIT forward 2.16e-6 (was 2.12e-6),
-  // config-2 final latent 2.4e-4 (2.1e-4) from the oracle (profiles/r05_hl_tile160_ab.txt; knob hl_tile96 bit 4)
-  if ((t96mode & 16) && igemm_splitk_slices(p) > 1) {
-    q.splitk = igemm_splitk_slices(p);
-    q.splitk_wt = g_splitk_wt.load();
-    launch_pipe<256, 128, 3, 4, 8, hl16_t>(q, s);
-    return true;
-  }
-  // the 4-wave 128x160 tile (one wave per SIMD, up to 512 registers each) for layers whose width is a multiple of 160 but not of 128 -- the N = 320
-  // convolutions of the 128^2 level: two exact column tiles instead of three 128-wide ones with 17 % of padding.  Mixed-mode step 44.58 / 44.36 ->
-  // 44.11 / 44.02 ms, A/B/A/B, results bit-identical (profiles/r05_hl_tile160_ab.txt; knob hl_tile96 bit 2)
-  if ((t96mode & 4) && p.N % 160 == 0 && p.N % 128 != 0 && p.n_split >= p.N && !p.stat_out && p.act == 0) {
-    launch_pipe<128, 160, 3, 4, 4, hl16_t>(q, s);
-    return true;
-  }
-  // ... and where it fills the chip's rounds better than the 128-wide tiles (cost model of the f16 selection, tile_cost): the M = 8192 x N = 640 shapes of
-  // the 64^2 level are exactly 256 tiles of 128x160 where 256x128 makes 160 and 128x128 320.  Mixed-mode step 41.14 / 41.32 -> 40.46 / 40.49 ms, A/B/A/B, bit-identical
-  // (profiles/r05_hl_tile160_ab.txt; knob hl_tile96 bit 3)
-  if ((t96mode & 8) && p.N % 160 == 0 && p.n_split >= p.N && !p.stat_out && p.act == 0) {
-    const int nk = p.Kpad / 32;
-    const double c160 = tile_cost(p.M, p.N, nk, 128, 160, 1.15);
-    const double cbest = std::min(tile_cost(p.M, p.N, nk, 256, 128, 1.0), tile_cost(p.M, p.N, nk, 128, 128, 1.0));
-    if (c160 < cbest) { launch_pipe<128, 160, 3, 4, 4, hl16_t>(q, s); return true; }
-  }
-  if (eff256 >= eff128) launch_pipe<256, 128, 3, 4, 8, hl16_t>(q, s);
-  else launch_pipe<128, 128, 4, 4, 8, hl16_t>(q, s);
-  return true;
+void launch_igemm_dma(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+#define PIPE(BM, BN, NS, WGM, NW, T, DT, XA, S2, TSW, XH)                                                                                 \
+  if (c.family == IG_PIPE && c.bm == BM && c.bn == BN && c.ns == NS && c.wgm == WGM && c.nw == NW && c.elem == DT && c.xa == XA && c.s2 == S2 && c.tsw == TSW && c.xh == XH) \
+    return launch_pipe<BM, BN, NS, WGM, NW, T, XA, S2, TSW, XH>(p, c, s)
+  PIPE(96, 128, 3, 3, 6, half_t, DT_F16, true, false, false, true);      // fused cross-attention: split-precision form, f16 form
+  PIPE(128, 128, 4, 4, 8, half_t, DT_F16, true, false, false, true);
+  PIPE(256, 128, 3, 4, 8, half_t, DT_F16, true, false, false, false);
+  PIPE(128, 128, 4, 4, 8, half_t, DT_F16, true, false, false, false);
+  PIPE(128, 128, 5, 4, 8, half_t, DT_F16, true, false, false, false);
+  PIPE(96, 128, 3, 3, 6, half_t, DT_F16, true, false, false, false);
+  PIPE(256, 128, 3, 4, 8, half_t, DT_F16, false, false, false, false);
+  if (c.family == IG_GLDS && c.bm == 128 && c.bn == 128 && c.ns == 2) return launch_glds<128, 128, 2>(p, c, s);
+  if (c.family == IG_GLDS && c.bm == 64 && c.bn == 128 && c.ns == 2) return launch_glds<64, 128, 2>(p, c, s);
+  PIPE(256, 128, 3, 4, 8, half_t, DT_F16, false, false, true, false);
+  PIPE(128, 128, 4, 4, 8, half_t, DT_F16, false, false, false, false);
+  PIPE(256, 160, 3, 8, 8, half_t, DT_F16, false, false, false, false);
+  PIPE(128, 128, 5, 4, 8, half_t, DT_F16, false, false, false, false);
+  PIPE(96, 128, 5, 3, 6, half_t, DT_F16, false, false, false, false);
+  PIPE(96, 128, 4, 3, 6, half_t, DT_F16, false, false, false, false);
+  PIPE(96, 128, 5, 3, 6, half_t, DT_F16, false, true, false, false);
+  PIPE(128, 160, 3, 4, 4, half_t, DT_F16, false, false, false, false);
+  if (c.family == IG_WIDE && c.bm == 256 && c.bn == 320 && c.ns == 3) return launch_wide(p, c, s);
+  PIPE(256, 128, 3, 4, 8, float, DT_F32, false, false, false, false);
+  PIPE(128, 128, 4, 4, 8, float, DT_F32, false, false, false, false);
+  PIPE(96, 128, 5, 3, 6, hl16_t, DT_HL, false, false, false, false);
+  PIPE(256, 128, 3, 4, 8, hl16_t, DT_HL, false, false, false, false);
+  PIPE(128, 160, 3, 4, 4, hl16_t, DT_HL, false, false, false, false);
+  PIPE(128, 128, 4, 4, 8, hl16_t, DT_HL, false, false, false, false);
+#undef PIPE
+  throw std::logic_error("igemm: the selection chose a direct-to-LDS kernel that is not instantiated");
 }
 
 }  // namespace sdxl

@@ -928,19 +928,11 @@ __global__ __launch_bounds__(512 + 64 * NL) void igemm_ws_kernel(const IgemmPara
   igemm_epilogue_staged<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, smem + wave * (WM * WN * 4), lnA, lnC, zeros);
 }
 
-template <typename K> static void set_lds_attr_m(K kernel, size_t lds, bool (&done)[kIgemmMaxDev], int dev) {
-  if (done[dev]) return;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    throw std::runtime_error("igemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-  done[dev] = true;
-}
 template <int BM, int BN, int NS, int MINB = 2>
 static void launch_glds_m(const IgemmParams& p, hipStream_t s) {
   const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
   const size_t lds = (size_t)NS * (BM + BN) * 128;
-  static bool attr_set[kIgemmMaxDev] = {};
-  const int dev = igemm_current_device();
-  set_lds_attr_m(&igemm_glds_m_kernel<BM, BN, NS, MINB>, lds, attr_set, dev);
+  set_max_dynamic_lds<&igemm_glds_m_kernel<BM, BN, NS, MINB>>(lds, igemm_current_device());
   hipLaunchKernelGGL((igemm_glds_m_kernel<BM, BN, NS, MINB>), dim3(tilesM * tilesN), dim3(256), lds, s, p, igemm_zero_page());
 }
 template <int BM, int BN, int NS, bool PRIO, int DMODE = 0, int WGM = 4, int NW = 8, bool UNR = false, typename T = half_t, int PF = 0, bool XA = false, bool TL = false>
@@ -948,9 +940,7 @@ static void launch_pipe_m(const IgemmParams& p, hipStream_t s) {
   const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
   const size_t lds = (size_t)pipe_lds_total(NS * (BM + BN) * 128, PF > 0 ? NW * 256 : 0) + (TL ? NW * kTlWords * 4 : 0);
   static_assert(!TL || pipe_lds_total(NS * (BM + BN) * 128, PF > 0 ? NW * 256 : 0) + NW * kTlWords * 4 <= 163840, "timeline stamps do not fit behind the ring");
-  static bool attr_set[kIgemmMaxDev] = {};
-  const int dev = igemm_current_device();
-  set_lds_attr_m(&igemm_pipe_m_kernel<BM, BN, NS, PRIO, DMODE, WGM, NW, UNR, T, PF, XA, TL>, lds, attr_set, dev);
+  set_max_dynamic_lds<&igemm_pipe_m_kernel<BM, BN, NS, PRIO, DMODE, WGM, NW, UNR, T, PF, XA, TL>>(lds, igemm_current_device());
   IgemmParams q = p;
   q.splitk = 1;
   hipLaunchKernelGGL((igemm_pipe_m_kernel<BM, BN, NS, PRIO, DMODE, WGM, NW, UNR, T, PF, XA, TL>), dim3(tilesM * tilesN), dim3(64 * NW), lds, s, q, igemm_zero_page());
@@ -959,9 +949,7 @@ template <int BM, int BN, int NS, int NL>
 static void launch_ws(const IgemmParams& p, hipStream_t s) {
   const int tilesM = (p.M + BM - 1) / BM, tilesN = (p.N + BN - 1) / BN;
   const size_t lds = (size_t)NS * (BM + BN) * 128;
-  static bool attr_set[kIgemmMaxDev] = {};
-  const int dev = igemm_current_device();
-  set_lds_attr_m(&igemm_ws_kernel<BM, BN, NS, NL>, lds, attr_set, dev);
+  set_max_dynamic_lds<&igemm_ws_kernel<BM, BN, NS, NL>>(lds, igemm_current_device());
   hipLaunchKernelGGL((igemm_ws_kernel<BM, BN, NS, NL>), dim3(tilesM * tilesN), dim3(512 + 64 * NL), lds, s, p, igemm_zero_page());
 }
 

@@ -650,137 +650,37 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
 }
 
 // ---------------------------------------------------------------------------------------------------------
-static std::atomic<int> g_wreg_enable{1};
-void igemm_set_wreg(int v) { g_wreg_enable = v; }
 static std::atomic<int> g_wreg_xcd2d{0};
 void igemm_set_wreg_xcd2d(int v) { g_wreg_xcd2d = v; }
-
-// warming workgroups of a launch: the CU slots its tile grid leaves empty in its (single) round -- one workgroup per CU up to 256 tiles,
-// two up to 512 -- at most 64 (a warmer pulls ~30 GB/s out of HBM: 36 of them move 13 MB inside an out-projection's 15 us)
-static int wreg_warm_groups(const IgemmParams& p, int ntiles) {
-  if (!p.warm[0] || !p.warm_bytes[0] || ntiles > 512) return 0;
-  const int spare = (ntiles <= 256 ? 256 : 512) - ntiles;
-  return spare < 8 ? 0 : spare > 64 ? 64 : spare;
-}
-template <int BM, int L, int MODE = 0, bool XA = false>
-static void launch_wreg_t(const IgemmParams& p, hipStream_t s) {
-  constexpr size_t lds = (size_t)2 * (L + 1) * BM * 128 + (XA ? BM * 8 : 0);      // (XA: + the tile's LayerNorm coefficients)
-  static_assert(lds >= (size_t)8 * (BM / 32) * 2048 + (size_t)(2 * BM + 6 * 2 * BM) * 4, "exchange areas must fit the dead rings");
-  static bool attr_set[kIgemmMaxDev] = {};
-  const int dev = igemm_current_device();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wreg_kernel<BM, L, MODE, XA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      throw std::runtime_error("igemm_wreg: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    attr_set[dev] = true;
-  }
-  const int tilesM = (p.M + BM - 1) / BM, tilesN = p.N / 128;
-  const int ntiles = tilesM * tilesN;
-  IgemmParams q = p;
-  q.wreg_xcd2d = g_wreg_xcd2d.load();
-  hipLaunchKernelGGL((igemm_wreg_kernel<BM, L, MODE, XA>), dim3(ntiles + wreg_warm_groups(p, ntiles)), dim3(512), lds, s, q, igemm_zero_page());
-}
-
-// shapes this kernel takes: plain f16 linear layers / 1x1 convolutions whose weights were also packed in fragment order
-bool igemm_wreg_ok(const IgemmParams& p) {
-  if (!p.Wf || !igemm_zero_page()) return false;
-  if (p.a_dt != DT_F16 || (p.c_dt != DT_F16 && p.c_dt != DT_F32)) return false;
-  if (p.ksize != 1 || p.stride != 1 || p.up != 0 || p.pad != 0 || p.Hin != p.Hout || p.Win != p.Wout) return false;
-  if (p.N % 128 != 0 || p.Cin != p.K || p.K != p.Kpad || p.Kpad % 64 != 0 || p.Kpad < 128) return false;
-  if (p.act != 0 || p.n_split < p.N || p.xa_k || p.gn_part || p.ln_stat || p.acc_scale) return false;
-  if ((p.lda & 7) != 0 || (reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
-  if ((p.ldc & 7) != 0 || (reinterpret_cast<uintptr_t>(p.C) & 15) != 0) return false;
-  if (p.R && ((p.ldr & 7) != 0 || (reinterpret_cast<uintptr_t>(p.R) & 15) != 0)) return false;
-  if (p.ebias) return false;
-  // f16 shadow of an fp32 output (+ the fp32 rows' statistics): whole 16-byte pieces
-  if (p.shadow && (p.c_dt != DT_F32 || !p.shadow_gamma || (p.shadow_ld & (p.shadow_lo_scale < 0.f ? 15 : 7)) != 0 || (reinterpret_cast<uintptr_t>(p.shadow) & 15) != 0)) return false;
-  return true;
-}
-// variant 0: rows per tile from the grid it makes on 256 CUs (the k-summation order does not depend on it); 60 / 62 force 96 / 64
-// rows.  (A 128-row tile -- 64 accumulators + 4 weight stages + 2 x 4 fragments -- spilled fragment registers that were still in
-// flight and was 30 - 75 % slower than the 96-row tile on every shape of the step: removed, profiles/r04_wreg_first_ab.txt.)
 static std::atomic<int> g_warm_enable{1};
 void igemm_set_warm(int v) { g_warm_enable = v; }
 int igemm_warm_enabled() { return g_warm_enable.load(); }
-bool igemm_wreg_selected(const IgemmParams& p) {
-  if (!igemm_wreg_ok(p) || !g_wreg_enable.load()) return false;
-  const long rows = 2L * (p.rpb > 0 ? p.rpb : p.M);
-  return ((rows + 95) / 96) * (long)(p.N / 128) <= 512;
-}
-bool launch_igemm_wreg(const IgemmParams& p, int variant, hipStream_t s) {
-  if (!igemm_wreg_ok(p)) return false;
-  if (variant == 0) {
-    if (!g_wreg_enable.load()) return false;
-    // where it pays (profiles/r04_wreg_first_ab.txt, r04_wreg_ab_l2.txt): grids of at most TWO 96-row tiles per CU -- with the
-    // shallow prefetch (L = 2: 72 KiB of LDS) two workgroups share a CU, so the 64^2 level's 430 tiles are one resident round
-    // (out-projection 19.5 -> 16.9 us, FF-out 44.5 -> 41.6 us, 1920 -> 640 skip 36.1 -> 33.1 us, cold weights) like the 32^2 level's 220
-    // (18.2 -> 15.0, 47.8 -> 41.2 us).  Evaluated on the CFG PAIR's shape (2 entries of rpb rows) whatever the actual batch: the two
-    // structures sum k in different orders, and an entry must come out bit-identical alone or batched.
-    const long rows = 2L * (p.rpb > 0 ? p.rpb : p.M);
-    if (((rows + 95) / 96) * (long)(p.N / 128) > 512) return false;
-  }
-#ifdef SDXL_MEASURE
-  if (variant == 68) { launch_wreg_t<96, 3>(p, s); return true; }     // prefetch-depth A/B partners of the 96-row kernel (L = 2 in production)
-  if (variant == 69) { launch_wreg_t<96, 4>(p, s); return true; }
-  if (variant == 61) { launch_wreg_t<128, 2>(p, s); return true; }    // 128-row tile (64 accumulators) at the shallow depth
-  if (variant >= 63 && variant <= 67) {     // knock-out timing modes of the 96-row kernel (garbage results except 67)
-    if (variant == 63) launch_wreg_t<96, 2, 1>(p, s); else if (variant == 64) launch_wreg_t<96, 2, 2>(p, s);
-    else if (variant == 65) launch_wreg_t<96, 2, 3>(p, s); else if (variant == 66) launch_wreg_t<96, 2, 4>(p, s);
-    else launch_wreg_t<96, 2, 5>(p, s);
-    return true;
-  }
-  if (variant == 70) { launch_wreg_t<96, 2, 6>(p, s); return true; }     // per-stream knock-outs: weights only / activations only / contiguous activations
-  if (variant == 71) { launch_wreg_t<96, 2, 7>(p, s); return true; }
-  if (variant == 72) { launch_wreg_t<96, 2, 8>(p, s); return true; }
-  if (variant == 73) { launch_wreg_t<96, 2, 16 | 32>(p, s); return true; }                 // fetch stream + LDS reads, every byte an L2 hit
-  if (variant == 74) { launch_wreg_t<96, 2, 16 | 32 | 4096>(p, s); return true; }          // ... without the LDS reads
-  if (variant == 75) { launch_wreg_t<96, 2, 16 | 32 | 4096 | 128>(p, s); return true; }    // ... and without the rendezvous
-  if (variant == 76) { launch_wreg_t<96, 2, 16 | 4096>(p, s); return true; }               // fetch stream alone, real pointers
-  if (variant == 77) { launch_wreg_t<96, 2, 4096>(p, s); return true; }                    // MFMAs + fetch stream, no LDS reads
-#endif
-  int bm = variant == 60 ? 96 : variant == 62 ? 64 : 0;
-  if (!bm) {      // 64 rows where that is still a single round of one tile per CU (small M: 512^2 images, single entries), else 96
-    const long t64 = (long)((p.M + 63) / 64) * (p.N / 128);
-    bm = t64 <= 256 ? 64 : 96;
-  }
-  if (bm == 64) launch_wreg_t<64, 2>(p, s);
-  else launch_wreg_t<96, 2>(p, s);
-  return true;
+
+template <int BM, int L, int MODE = 0, bool XA = false>
+static void launch_wreg_t(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+  constexpr size_t lds = (size_t)2 * (L + 1) * BM * 128 + (XA ? BM * 8 : 0);      // (XA: + the tile's LayerNorm coefficients)
+  static_assert(lds >= (size_t)8 * (BM / 32) * 2048 + (size_t)(2 * BM + 6 * 2 * BM) * 4, "exchange areas must fit the dead rings");
+  if ((size_t)c.lds != lds) throw std::logic_error("igemm_wreg: choice and kernel disagree on the LDS layout");
+  set_max_dynamic_lds<&igemm_wreg_kernel<BM, L, MODE, XA>>(lds, igemm_current_device());
+  IgemmParams q = p;
+  q.wreg_xcd2d = g_wreg_xcd2d.load();
+  hipLaunchKernelGGL((igemm_wreg_kernel<BM, L, MODE, XA>), dim3(c.grid), dim3(c.block), lds, s, q, igemm_zero_page());      // (grid: tiles + warming workgroups)
 }
 
-// ---- the fused query projection + cross-attention (f16 form) on this kernel: the XA instantiation
-static std::atomic<int> g_wreg_xattn{1};
-void igemm_set_wreg_xattn(int v) { g_wreg_xattn = v; }
-// what the XA instantiation takes: a plain f16 linear layer with fragment-order weights whose epilogue is the f16 cross-attention
-// (with or without a folded LayerNorm in front) and nothing else.  The caller has checked igemm_xattn_ok (rpb % 64 == 0, <= 96 keys).
-static bool wreg_xattn_ok(const IgemmParams& p) {
-  if (!p.xa_k || p.xa_k_lo || !p.Wf || !igemm_zero_page()) return false;
-  if (p.a_dt != DT_F16 || p.c_dt != DT_F16) return false;
-  if (p.ksize != 1 || p.stride != 1 || p.up != 0 || p.pad != 0 || p.Hin != p.Hout || p.Win != p.Wout) return false;
-  if (p.N % 128 != 0 || p.Cin != p.K || p.K != p.Kpad || p.Kpad % 64 != 0 || p.Kpad < 128) return false;
-  if (p.act != 0 || p.n_split < p.N || p.gn_part || p.acc_scale || p.stat_out || p.R || p.ebias || p.shadow) return false;
-  if (p.rpb <= 0 || p.rpb % 64 != 0 || p.M % p.rpb != 0 || p.xa_nctx < 1 || p.xa_nctx > 96) return false;
-  if ((p.lda & 7) != 0 || (reinterpret_cast<uintptr_t>(p.A) & 15) != 0) return false;
-  if ((p.ldc & 7) != 0 || (reinterpret_cast<uintptr_t>(p.C) & 15) != 0) return false;
-  return true;
-}
-// the static rule of igemm_wreg_selected -- the CFG pair's grid (2 entries of rpb rows), never the actual batch: this kernel and the
-// pipe kernels sum k in different orders, and an entry must come out bit-identical alone or batched
-bool igemm_wreg_xattn_selected(const IgemmParams& p) {
-  if (!wreg_xattn_ok(p) || !g_wreg_enable.load() || !g_wreg_xattn.load()) return false;
-  const long rows = 2L * p.rpb;
-  return ((rows + 95) / 96) * (long)(p.N / 128) <= 512;
-}
-// variant 60 / 62: 96 / 64 rows per tile (the result does not depend on it); anything else: the rule of launch_igemm_wreg
-bool launch_igemm_wreg_xattn(const IgemmParams& p, int variant, hipStream_t s) {
-  if (!igemm_wreg_xattn_selected(p)) return false;
-  int bm = variant == 60 ? 96 : variant == 62 ? 64 : 0;
-  if (!bm) {
-    const long t64 = (long)((p.M + 63) / 64) * (p.N / 128);
-    bm = t64 <= 256 ? 64 : 96;
-  }
-  if (bm == 64) launch_wreg_t<64, 2, 0, true>(p, s);
-  else launch_wreg_t<96, 2, 0, true>(p, s);
-  return true;
+// a weights-in-registers choice of igemm_select (select.cpp: shapes, the CFG-pair grid rule, rows per tile, forced numbers) -> its instantiation
+void launch_igemm_wreg(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
+#define WREG(BM, L, MODE, XA) \
+  if (c.bm == BM && c.ns == L && c.mode == (MODE) && c.xa == XA) return launch_wreg_t<BM, L, (MODE), XA>(p, c, s)
+#ifdef SDXL_MEASURE
+  WREG(96, 3, 0, false); WREG(96, 4, 0, false); WREG(128, 2, 0, false);
+  WREG(96, 2, 1, false); WREG(96, 2, 2, false); WREG(96, 2, 3, false); WREG(96, 2, 4, false); WREG(96, 2, 5, false);
+  WREG(96, 2, 6, false); WREG(96, 2, 7, false); WREG(96, 2, 8, false);
+  WREG(96, 2, 16 | 32, false); WREG(96, 2, 16 | 32 | 4096, false); WREG(96, 2, 16 | 32 | 4096 | 128, false); WREG(96, 2, 16 | 4096, false); WREG(96, 2, 4096, false);
+#endif
+  WREG(64, 2, 0, false); WREG(96, 2, 0, false);
+  WREG(64, 2, 0, true); WREG(96, 2, 0, true);      // the fused query projection + cross-attention (f16 form)
+#undef WREG
+  throw std::logic_error("igemm_wreg: the selection chose a kernel that is not instantiated");
 }
 
 }  // namespace sdxl

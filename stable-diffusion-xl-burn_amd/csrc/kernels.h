@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdexcept>
 
 namespace sdxl {
 
@@ -78,7 +79,7 @@ struct IgemmParams {
   int wreg_xcd2d;   // A/B knob (sdxl_debug_set "wreg_xcd2d"): weights-in-registers kernel, XCDs own 2-D patches of tiles (half the column tiles x ~ a quarter of
                     // the row tiles each) instead of whole row-tile runs -- fewer unique operand bytes per XCD's L2; set by the launcher
   int epi_staged;   // A/B knob (sdxl_debug_set "igemm_epilogue_staged"): 1 = LDS-staged epilogue everywhere, 0 = direct row-per-lane where it applies
-  // f16 SHADOW of an fp32 residual stream (round 6; weights-in-registers kernel only, igemm_wreg_ok): next to the fp32 rows C the epilogue stores
+  // f16 SHADOW of an fp32 residual stream (round 6; weights-in-registers kernel only, igemm_wreg_selected): next to the fp32 rows C the epilogue stores
   // shadow[m][n] = f16(value * shadow_gamma[n]) -- the A operand of the GEMM behind the NEXT LayerNorm (gamma = that norm's), whose weights stay
   // un-folded: LN(x) W + b = rstd (x o gamma) W - rstd mu (gamma W) + (beta W + b).  With stat_out (the fp32 rows' statistics) the LayerNorm launch
   // between two GEMMs of a split-operand transformer block disappears.  null = off.
@@ -87,7 +88,41 @@ struct IgemmParams {
                             // < 0: the shadow is an HL16 tensor (shadow_ld in LOGICAL elements, un-scaled lo halves): read as an f16 row of 2 N columns by a GEMM whose weight is
                             // packed twice in the HL16 interleave (launch_pack_linear_hilo mode 2)
 };
-bool igemm_gn_part_ok(const IgemmParams& p);
+// ---- kernel selection (select.cpp: host-only, no HIP call).  Knobs that influence WHICH kernel runs, written by sdxl_debug_set and
+// snapshotted once per launch; zero_page is an input of the same kind, filled by the launcher (the DMA kernels' zero page exists on this device)
+struct SelectKnobs {
+  int igemm_variant = 0;    // test hook: -1 generic kernel only, 0 auto, > 0 a forced tile number -- one the shape refuses falls back to auto
+  int igemm_wreg = 1;       // 0 = the auto selection never picks the weights-in-registers kernel
+  int wreg_xattn = 1;       // 0 = the fused cross-attention stays on the pipe kernels
+  int hl_tile96 = 29;       // split-operand GEMMs.  bit 0: 96x128 for linears, bit 1: ... for 3x3 convs too (not selected), bit 2: 4-wave 128x160 for N % 160 == 0, N % 128 != 0
+                            // layers, bit 3: ... wherever the cost model prefers it, bit 4: in-launch split-K for the K >= 10240 convolutions
+  int igemm_tsw = 1;        // 0 = the V^T part of a fused QKV projection keeps the LDS-staged transposed epilogue (no operand-swapped k-loop)
+  int igemm_unrolled = 1;   // measure builds: 0 = auto selection on the rolled pipelined kernels
+  int wide_db = 0;          // measure builds: 1 = the wide GEGLU kernel with register-double-buffered fragments
+  int attn_variant = 0;     // -1: generic kernel only, 0: auto, 2: 32x32x16 deferred-max kernel, 6: key-split kernel, 7 / 8: mix level 0 / 1, 9: auto without mixing
+  int attn_xsplit = 1;      // 0 = never pick the cross-workgroup key split (mix level 2)
+  int zero_page = 0;        // not a knob: the launcher's "zero page present"
+};
+bool select_knob_set(const char* key, int value);   // false: not a selection knob
+SelectKnobs select_knobs_snapshot();                // (zero_page = 0: the launcher fills it)
+enum IgemmFamily : int { IG_NONE = 0, IG_GLDS = 1, IG_PIPE = 2, IG_WIDE = 3, IG_WREG = 4, IG_GENERIC = 5, IG_MEASURE = 6 };
+// what launch_igemm launches: the kernel family and its template arguments, the grid and the dynamic LDS bytes
+struct IgemmChoice {
+  int family;               // IgemmFamily; IG_NONE: empty output, nothing to launch; IG_MEASURE: `measure` goes to launch_igemm_measure
+  int bm, bn, ns;           // tile rows / columns, ring depth (IG_WREG: prefetch depth L)
+  int wgm, nw;              // waves along M, waves
+  int elem, a_elem;         // compute element (DT_F16 / DT_F32 / DT_HL); IG_GENERIC: element of A in memory
+  int xa, xh, tsw, s2;      // fused cross-attention, its split-precision form, operand-swapped V^T epilogue, one rendezvous per two k-tiles
+  int splitk;               // k-slices per tile (1 = off)
+  int mode, db, measure;    // measure builds: knock-out mode of the weights-in-registers kernel, double-buffered wide kernel, measure-only variant number
+  int grid, block, lds;
+};
+IgemmChoice igemm_select(const IgemmParams& p, int compute_dt, const SelectKnobs& k);
+// the same rules for run_conv, which promises its consumers a statistics buffer / a shadow and budgets weight warming BEFORE the launch
+// (on the snapshot it then launches with: igemm_launch_knobs)
+bool igemm_gn_part_ok(const IgemmParams& p, const SelectKnobs& k);
+bool igemm_wreg_selected(const IgemmParams& p, const SelectKnobs& k);         // the auto selection would run this launch on the weights-in-registers kernel
+bool igemm_wreg_xattn_selected(const IgemmParams& p, const SelectKnobs& k);   // ... a fused query projection + cross-attention (xa_k, f16 form)
 // shapes the fused cross-attention epilogue takes (f16 operands, head dim 64, <= 96 context tokens); otherwise run the
 // projection and the attention kernel separately
 bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx);
@@ -97,33 +132,37 @@ void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, i
 int igemm_splitk_slices(const IgemmParams& p);                       // 1 or 3: depends on one batch entry's shape only
 size_t igemm_splitk_ws_bytes(int batch, int rows_per_entry, int n_max);   // slab bytes a plan must provide
 constexpr int kSplitkCounters = 4096;                                // arrival counters a plan must provide (zeroed once)
-void launch_igemm(const IgemmParams& p, int compute_dt, hipStream_t s);
+SelectKnobs igemm_launch_knobs();      // the process's knobs + the current device's zero page (igemm.hip)
+void launch_igemm(const IgemmParams& p, int compute_dt, const SelectKnobs& knobs, hipStream_t s);
+void launch_igemm(const IgemmParams& p, int compute_dt, hipStream_t s);      // ... on a snapshot of its own
 // [Npad][Kpad] f16 row-major packed weights -> fragment order (same bytes): per 32-row block and 64-deep k-tile four 1-KiB MFMA
 // A-operand fragments, contiguous over k -- what igemm_wreg_kernel streams straight into registers.  Npad % 32 == 0, Kpad % 64 == 0.
 void launch_repack_wfrag(const void* w, void* wf, int Npad, int Kpad, hipStream_t s);
-bool igemm_wreg_ok(const IgemmParams& p);   // shapes the weights-in-registers kernel takes (plain f16 linear / 1x1, N % 128 == 0, Wf set)
-void igemm_set_tsw(int v);       // A/B knob (sdxl_debug_set "igemm_tsw"): 0 = no operand-swapped k-loop for the transposed part of a fused QKV projection
-bool igemm_wreg_selected(const IgemmParams& p);   // the auto selection (variant 0) would run this launch on the weights-in-registers kernel
-bool igemm_wreg_xattn_selected(const IgemmParams& p);   // a fused query projection + cross-attention (xa_k, f16 form) would run on the weights-in-registers kernel
-void igemm_set_wreg_xattn(int v);   // A/B knob (sdxl_debug_set "wreg_xattn"): 0 = the fused cross-attention stays on the pipe kernels
 void igemm_set_warm(int v);      // A/B knob (sdxl_debug_set "igemm_warm"): 0 = no weight warming workgroups; read when a UNet plan records its GEMM sequence
 int igemm_warm_enabled();
 void igemm_set_splitk_wt(int v);
-void igemm_set_hl_tile96(int v); // A/B knob (sdxl_debug_set "hl_tile96"): 0 = the split-operand GEMMs never take the 96-row tile
 void igemm_set_wreg_xcd2d(int v);
-void igemm_set_wide_db(int v);   // A/B knob (sdxl_debug_set "wide_db"): 0 = wide GEGLU kernel with the rolled fragment reads
-void igemm_set_wreg(int v);      // A/B knob (sdxl_debug_set "igemm_wreg"): 0 = the auto selection never picks the weights-in-registers kernel
-void igemm_set_variant(int v);   // debug / benchmarking knob: -1 generic kernel only, 0 auto, 1..3 forced fast-path tile
 void igemm_set_hl_weights_exact(int v); // A/B: 0 keeps all three MFMAs per product even where the packed weights are exact f16 values
 void igemm_set_xa_vec64(int v);          // measure builds: see IgemmParams::xa_vec64
 void igemm_set_epilogue_staged(int v);   // A/B: 1 forces the LDS-staged epilogue (default 0: direct row-per-lane epilogue on whole wave tiles)
-void igemm_set_unrolled(int v);   // auto selection: pipelined kernels with the k-loop unrolled by the ring depth (default on)
 #ifdef SDXL_MEASURE
 void igemm_set_timeline(void* device_buf);
 void igemm_set_wreg_timeline(void* device_buf);   // igemm_wreg.hip: [workgroups][8 waves][16] coarse stamps
 void igemm_set_wide_timeline(void* device_buf);   // igemm_glds.hip: [workgroups][8 waves][8] coarse stamps of the wide (GEGLU) kernel   // igemm_measure.hip: stamp buffer of the timeline kernel variants
 int igemm_timeline_words();
 #endif
+// the dynamic-LDS limit of a kernel (up to 160 KiB), raised once per (kernel, device); dev = the current device, < kMaxDevices
+constexpr int kMaxDevices = 64;
+template <auto Kernel> inline void set_max_dynamic_lds(size_t lds, int dev) {
+  static bool done[kMaxDevices] = {};
+  if (done[dev]) return;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  done[dev] = true;
+}
+// per-device state owned by igemm_glds.hip
+const void* igemm_zero_page();          // null until igemm_glds_init() ran on the current device
+int igemm_current_device();
 void igemm_glds_init();          // allocates the zero page the DMA fast path reads halo pixels from (call once per process)
 
 // per-entry scale workspace of launch_f32_to_hl_scaled (declared further down)
@@ -192,7 +231,15 @@ struct AttnParams {
 };
 size_t attention_xsplit_ws_bytes(int B, int H, int Nq);
 size_t attention_xsplit_counters(int B, int H, int Nq);
-void attention_set_xsplit(int v);      // A/B knob (sdxl_debug_set "attn_xsplit"): 0 = never pick the cross-workgroup key split
+enum AttnKernel : int { AT_GENERIC = 0, AT_F16 = 1, AT_V2 = 2, AT_KS = 3, AT_MIX = 4, AT_V3 = 5 };
+// what launch_attention_d64 launches
+struct AttnChoice {
+  int kernel;               // AttnKernel: generic (elem DT_F16 / DT_F32), DMA-staged 16x16x32, 32x32x16 deferred-max (ns ring slots), key-split, mixed block sizes
+  int mix, big_heads;       // AT_MIX: level 0 / 1 / 2 (-1 otherwise) and the heads that run in the large blocks
+  int ns, elem, ko;         // (ko: measure builds, knock-out bits of the key-split body)
+  int grid_x, grid_y, block, lds;
+};
+AttnChoice attn_select(const AttnParams& p, const SelectKnobs& k);
 void launch_attention_d64(const AttnParams& p, hipStream_t s);
 // split-operand (fp32-class) head-dim-64 attention: Q / O fp32 (ldq / ldo in floats), K [B][Nk] rows and Vt [B][H*64][vt_ld] rows in
 // HL16 (ldk / vt_ld in LOGICAL elements: a row is 2 * ld halfs), no mask; vt_ld a multiple of 64 keys, zero beyond Nk.  Returns false
@@ -206,7 +253,6 @@ void attention_init();                 // zero page for the DMA-staged f16 kerne
 #ifdef SDXL_MEASURE
 void attention_set_timeline(void* device_buf);   // [workgroups][4 waves][8] coarse stamps of the key-split attention body
 #endif
-void attention_set_variant(int v);     // -1: generic kernel only, 0: auto, 1: DMA-staged 16x16x32 kernel, 2: 32x32x16 deferred-max kernel, 6: key-split kernel
 
 // row softmax for the unfused attention path (VAE mid block, d=512, 1 head): P[r][:] = softmax(S[r][:]*scale + mask)
 // S fp32 [rows][lds] (scores from igemm), P in dtype p_dt [rows][ldp]; columns n..npad-1 of P are zero filled.

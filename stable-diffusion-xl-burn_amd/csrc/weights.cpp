@@ -444,11 +444,12 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
   p.acc_scale = w.acc_scale;
   p.a_scale = (w.dt >= 0 ? w.dt : ex.cdt) == DT_HL ? a.a_scale : nullptr;
   p.a_scale_rpb = (p.a_scale && a.a_scale_n > 1) ? p.M / a.a_scale_n : 0;      // (M = entries x output rows per entry)
+  const SelectKnobs knobs = igemm_launch_knobs();      // one snapshot for the predicates below and the launch
   // GroupNorm statistics of the output from this GEMM's epilogue -- only when the kernel the selection picks anyway can do it
   p.gn_part = nullptr;
   {
     const int wdt_ = w.dt >= 0 ? w.dt : ex.cdt;      // (f16 engines; round 6: the split-operand convolutions that run the 256x128 split-K kernel)
-    if (e.gn_part && (wdt_ == DT_F16 || wdt_ == DT_HL) && wdt_ == ex.cdt) { p.gn_part = e.gn_part; if (!igemm_gn_part_ok(p)) p.gn_part = nullptr; }
+    if (e.gn_part && (wdt_ == DT_F16 || wdt_ == DT_HL) && wdt_ == ex.cdt) { p.gn_part = e.gn_part; if (!igemm_gn_part_ok(p, knobs)) p.gn_part = nullptr; }
   }
   // f16 shadow of an fp32 output (+ its row statistics) for the GEMM behind the next LayerNorm: only where the selection picks the
   // weights-in-registers kernel anyway; otherwise neither is written and the caller runs the LayerNorm launch.  (Decided on the filled
@@ -456,7 +457,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
   if (e.shadow_done) *e.shadow_done = false;
   if (e.shadow) {
     p.shadow = e.shadow; p.shadow_ld = e.shadow_ld; p.shadow_gamma = e.shadow_gamma; p.shadow_lo_scale = e.shadow_lo_scale;
-    const bool ok = (w.dt >= 0 ? w.dt : ex.cdt) == DT_F16 && igemm_wreg_selected(p);
+    const bool ok = (w.dt >= 0 ? w.dt : ex.cdt) == DT_F16 && igemm_wreg_selected(p, knobs);
     if (!ok) { p.shadow = nullptr; p.shadow_gamma = nullptr; p.stat_out = nullptr; p.shadow_lo_scale = 0.f; }
     if (e.shadow_done) *e.shadow_done = ok;
   }
@@ -473,7 +474,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     WarmSeq& ws = *ex.warm;
     // the region the launch reads cold: its weights and the per-column vectors next to them in the arena (allocation order: packed
     // weights, bias, [column sums, eps of a folded LayerNorm], [fragment-order image])
-    const bool host = igemm_wreg_selected(p) || igemm_wreg_xattn_selected(p);
+    const bool host = igemm_wreg_selected(p, knobs) || igemm_wreg_xattn_selected(p, knobs);
     const size_t wbytes = (size_t)w.Npad * w.Kpad * 2;
     const char* lo; const char* hi;
     if (host) {
@@ -499,7 +500,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
       }
     }
   }
-  launch_igemm(p, w.dt >= 0 ? w.dt : ex.cdt, ex.s);
+  launch_igemm(p, w.dt >= 0 ? w.dt : ex.cdt, knobs, ex.s);
   {   // a refused launch (bad grid / LDS attribute) must not pass silently
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess)
