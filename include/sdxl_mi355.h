@@ -165,6 +165,37 @@ int sdxl_unet_set_gn_from_producer(sdxl_unet* u, int enabled);
  * create time) falls back to SDXL_DTYPE_F32_SPLIT_MIX's classes (1 | 2 | 1024 = the GEGLU weights as (hi, lo) f16 pairs along K): this is how a caller sees it. */
 int sdxl_unet_mix_classes(sdxl_unet* u, int* classes_out);
 
+/* ---- create-time adapters (LoRA): the model is built from base weights + sum of scale * left @ right, merged on the device while the
+ * weights are packed.  The result is a static merged model: nothing on the per-step path changes and nothing is paid per step.
+ * An entry adds scale * left[rows, rank] @ right[rank, cols] to the MATRIX VIEW of parameter `param_index` (sdxl_unet_param_spec order):
+ * rows = shape[0], cols = the product of the remaining dimensions.  In terms of the usual PyTorch adapter tensors
+ * (down.weight [r, in...], up.weight [out, r]):
+ *   SDXL_PARAM_LINEAR_W [d_in, d_out]:       left = down.weight^T [d_in, r],  right = up.weight^T [r, d_out]
+ *   SDXL_PARAM_CONV_W   [Cout, Cin, kh, kw]: left = up.weight [Cout, r],      right = down.weight flattened to [r, Cin * kh * kw]
+ * left / right: contiguous fp32, host or device (the rule of weights_flat); they are read during the create call only.  Entries on the same
+ * parameter are applied in the order given.  The fused QKV / KV packing, GEGLU interleave and every other packed form are the engine's business:
+ * an entry always addresses one canonical parameter.
+ * Arithmetic (fixed, so a merged model is reproducible): per element acc = 0; acc = fma(left[r][j], right[j][c], acc) for j = 0 .. rank-1;
+ * w = fma(scale, acc, w), all fp32.  scale == 0 leaves the tensor untouched.
+ * SDXL_LORA_ROUND_F16: every ADAPTED tensor is rounded to IEEE f16 and widened again after its last entry -- what a half-precision record saved
+ * after merging would hold.  Merged tensors are in general not f16 values, so without the flag SDXL_DTYPE_F32_SPLIT_MIX_F16W, _GEGLU2 and
+ * SDXL_DTYPE_F32_SPLIT_F16W fall back exactly as for any checkpoint that is not f16-valued (sdxl_unet_mix_classes tells); with it they keep their classes
+ * (given an f16-valued base). */
+typedef struct { int32_t param_index, rank; const float* left; const float* right; float scale; } sdxl_lora_entry;
+enum { SDXL_LORA_ROUND_F16 = 1 };
+/* host logic only, no device: every entry names a LINEAR_W / CONV_W parameter of cfg, rank >= 1, non-NULL arrays, finite scale.
+ * SDXL_ERR_INVALID with the first complaint in sdxl_last_error() otherwise.  n_entries == 0 is valid. */
+int sdxl_lora_check(const sdxl_unet_config* cfg, const sdxl_lora_entry* entries, int n_entries);
+/* the single op the models run (parity tests): w_dev [rows, cols] fp32 on the device, in place; left [rows, rank], right [rank, cols] host or device;
+ * flags: SDXL_LORA_ROUND_F16 rounds w_dev afterwards */
+int sdxl_lora_merge(sdxl_ctx* ctx, void* stream, float* w_dev, int rows, int cols, const float* left, const float* right,
+                    int rank, float scale, int flags);
+/* sdxl_unet_create / _create_f16 / _create_synthetic with adapters.  Exactly one base: weights_flat, weights_flat_f16, or (both NULL) the synthetic
+ * seed.  Both bases non-NULL, an entry sdxl_lora_check refuses or unknown flag bits: SDXL_ERR_INVALID, nothing is created, *out is untouched.
+ * n_entries == 0 gives the same bits as the plain create call. */
+int sdxl_unet_create_lora(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, const float* weights_flat, const uint16_t* weights_flat_f16,
+                          uint64_t synthetic_seed, const sdxl_lora_entry* entries, int n_entries, int flags, sdxl_unet** out);
+
 /* ---- Backend::qkv_attention (src/backend.rs:4-19; generic body :88-128, LibTorch override :32-79)
  * q [B,Nq,n_head*d], k,v [B,Nk,n_head*d], mask additive [Nq,Nk] or NULL, out [B,Nq,n_head*d]; fp32 device tensors.
  * dtype SDXL_DTYPE_F32_SPLIT: d = 64 and mask == NULL only (the UNet's attention), anything else is refused with an error. */
@@ -180,6 +211,10 @@ int sdxl_diffuser_create_f16(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dty
                              const float* alphas_cumprod_host, int n_train_steps, sdxl_diffuser** out);
 int sdxl_diffuser_create_synthetic(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, uint64_t seed,
                                    const float* alphas_cumprod_host, int n_train_steps, sdxl_diffuser** out);
+/* the Diffuser with create-time adapters on its UNet: arguments and errors as sdxl_unet_create_lora */
+int sdxl_diffuser_create_lora(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, const float* weights_flat, const uint16_t* weights_flat_f16,
+                              uint64_t synthetic_seed, const sdxl_lora_entry* entries, int n_entries, int flags,
+                              const float* alphas_cumprod_host, int n_train_steps, sdxl_diffuser** out);
 void sdxl_diffuser_destroy(sdxl_diffuser* d);
 sdxl_unet* sdxl_diffuser_unet(sdxl_diffuser* d);   /* Diffuser.diffusion (:312), borrowed */
 /* Diffuser::sample_latent(conditioning, cfg, n_steps) (:317-332).  noise0 [n,4,h/8,w/8] plays gen_noise() (:378-388). */

@@ -3,4 +3,9 @@
 _Static_assert(SDXL_OK == 0, "status code");
 _Static_assert(SDXL_DTYPE_F32 == 0 && SDXL_DTYPE_F16 == 1 && SDXL_DTYPE_F16_F32RES == 2 && SDXL_DTYPE_F32_SPLIT == 3 && SDXL_DTYPE_F32_SPLIT_MIX == 4 && SDXL_DTYPE_F32_SPLIT_MIX_F16W == 5 && SDXL_DTYPE_F32_SPLIT_MIX_F16W_GEGLU2 == 6 && SDXL_DTYPE_F32_SPLIT_F16W == 7, "dtype codes");
 _Static_assert(sizeof(sdxl_conditioning) == 8 * sizeof(void*) + 4 * sizeof(int32_t), "sdxl_conditioning layout");
+#include <stddef.h>
+_Static_assert(SDXL_LORA_ROUND_F16 == 1, "lora flags");
+_Static_assert(offsetof(sdxl_lora_entry, param_index) == 0 && offsetof(sdxl_lora_entry, rank) == 4 && offsetof(sdxl_lora_entry, left) == 8 &&
+               offsetof(sdxl_lora_entry, right) == 8 + sizeof(void*) && offsetof(sdxl_lora_entry, scale) == 8 + 2 * sizeof(void*) &&
+               sizeof(sdxl_lora_entry) == 16 + 2 * sizeof(void*), "sdxl_lora_entry layout (LP64)");
 int sdxl_mi355_abi_check(void) { return SDXL_OK; }

@@ -282,6 +282,65 @@ impl DiffuserConfig {
         });
         Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, seed: std::cell::Cell::new(None), _b: std::marker::PhantomData }
     }
+    /// `init_with_weights` with create-time adapters merged into the UNet while it is built (`sdxl_diffuser_create_lora`): a static merged
+    /// model, nothing changes per step.  `round_f16`: `SDXL_LORA_ROUND_F16`, adapted tensors rounded to f16 values (keeps the `*F16W` modes' classes)
+    pub fn init_with_weights_lora<B: BurnBackend>(&self, ctx: &Mi355Context, precision: Precision, weights_flat: &[f32], adapters: &[LoraAdapter],
+                                                  round_f16: bool, alphas_cumprod: &[f32]) -> Result<Diffuser<B>, Box<dyn std::error::Error>> {
+        let cfg = self.to_c();
+        let need = param_numel(&cfg);
+        if weights_flat.len() != need {
+            return Err(format!("expected {need} weight values, got {}", weights_flat.len()).into());
+        }
+        let entries = lora_entries(&cfg, adapters)?;
+        let mut raw = ptr::null_mut();
+        try_check(unsafe {
+            ffi::sdxl_diffuser_create_lora(ctx.raw, &cfg, precision as c_int, weights_flat.as_ptr(), ptr::null(), 0, entries.as_ptr(),
+                                           entries.len() as c_int, if round_f16 { ffi::SDXL_LORA_ROUND_F16 as c_int } else { 0 },
+                                           alphas_cumprod.as_ptr(), alphas_cumprod.len() as c_int, &mut raw)
+        })?;
+        Ok(Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, seed: std::cell::Cell::new(None), _b: std::marker::PhantomData })
+    }
+    /// `init_synthetic` with create-time adapters
+    pub fn init_synthetic_lora<B: BurnBackend>(&self, ctx: &Mi355Context, precision: Precision, seed: u64, adapters: &[LoraAdapter], round_f16: bool,
+                                               alphas_cumprod: &[f32]) -> Result<Diffuser<B>, Box<dyn std::error::Error>> {
+        let cfg = self.to_c();
+        let entries = lora_entries(&cfg, adapters)?;
+        let mut raw = ptr::null_mut();
+        try_check(unsafe {
+            ffi::sdxl_diffuser_create_lora(ctx.raw, &cfg, precision as c_int, ptr::null(), ptr::null(), seed, entries.as_ptr(),
+                                           entries.len() as c_int, if round_f16 { ffi::SDXL_LORA_ROUND_F16 as c_int } else { 0 },
+                                           alphas_cumprod.as_ptr(), alphas_cumprod.len() as c_int, &mut raw)
+        })?;
+        Ok(Diffuser { raw, n_steps: alphas_cumprod.len(), is_refiner: self.is_refiner, seed: std::cell::Cell::new(None), _b: std::marker::PhantomData })
+    }
+}
+/// One adapter on one parameter, already in the engine's layout (`sdxl_lora_entry`): `W += scale * left @ right` on the matrix view of parameter
+/// `param_index` (`param_names` order), rows = shape[0], cols = the product of the other dimensions, `left` [rows, rank], `right` [rank, cols], row-major.
+/// From the usual adapter tensors (`down.weight` [r, in...], `up.weight` [out, r]): a Linear parameter [d_in, d_out] takes `left = down^T`,
+/// `right = up^T`; a Conv2d parameter [out, in, kh, kw] takes `left = up`, `right = down` flattened to [r, in * kh * kw].  `scale = strength * alpha / rank`.
+#[derive(Clone, Debug)]
+pub struct LoraAdapter {
+    pub param_index: usize,
+    pub rank: usize,
+    pub left: Vec<f32>,
+    pub right: Vec<f32>,
+    pub scale: f32,
+}
+/// the C entries over host arrays the adapters own; extents are checked here (the C ABI cannot see them), the rest by `sdxl_lora_check`
+fn lora_entries(cfg: &ffi::sdxl_unet_config, adapters: &[LoraAdapter]) -> Result<Vec<ffi::sdxl_lora_entry>, Box<dyn std::error::Error>> {
+    let mut entries = Vec::with_capacity(adapters.len());
+    for (i, a) in adapters.iter().enumerate() {
+        let (mut name, mut ndim, mut shape, mut kind, mut sc, mut mean) = (ptr::null(), 0, [0i64; 4], 0, 0f32, 0f32);
+        try_check(unsafe { ffi::sdxl_unet_param_spec(cfg, a.param_index as c_int, &mut name, &mut ndim, shape.as_mut_ptr(), &mut kind, &mut sc, &mut mean) })?;
+        let rows = shape[0] as usize;
+        let cols = shape[1..ndim as usize].iter().product::<i64>() as usize;
+        if a.left.len() != rows * a.rank || a.right.len() != a.rank * cols {
+            return Err(format!("lora adapter {i}: expected left {rows} x {} and right {} x {cols}", a.rank, a.rank).into());
+        }
+        entries.push(ffi::sdxl_lora_entry { param_index: a.param_index as i32, rank: a.rank as i32, left: a.left.as_ptr(), right: a.right.as_ptr(), scale: a.scale });
+    }
+    try_check(unsafe { ffi::sdxl_lora_check(cfg, entries.as_ptr(), entries.len() as c_int) })?;
+    Ok(entries)
 }
 fn param_numel(cfg: &ffi::sdxl_unet_config) -> usize {
     let n = unsafe { ffi::sdxl_unet_param_count(cfg) };

@@ -69,6 +69,15 @@ class _ConditioningC(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class LoraEntry(ctypes.Structure):
+    """sdxl_lora_entry: W += scale * left[rows, rank] @ right[rank, cols] on the matrix view of parameter `param_index` (lora_entry builds one
+    from PyTorch-style adapter tensors and keeps the arrays alive)"""
+    _fields_ = [("param_index", ctypes.c_int32), ("rank", ctypes.c_int32), ("left", _f_p), ("right", _f_p), ("scale", ctypes.c_float)]
+
+
+LORA_ROUND_F16 = 1   # SDXL_LORA_ROUND_F16: adapted tensors rounded to f16 values after merging (what a half-precision record saved after merging holds)
+
+
 # every symbol include/sdxl_mi355.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "sdxl_last_error", "sdxl_build_info", "sdxl_ctx_create", "sdxl_ctx_destroy", "sdxl_ctx_synchronize",
@@ -87,6 +96,7 @@ ABI_SYMBOLS = [
     "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
     "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
+    "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
     "sdxl_clip_config_clip_l", "sdxl_clip_config_open_clip_bigg", "sdxl_clip_param_count", "sdxl_clip_param_spec",
     "sdxl_clip_create", "sdxl_clip_create_synthetic", "sdxl_clip_destroy", "sdxl_clip_forward_hidden",
     "sdxl_clip_forward_hidden_pooled", "sdxl_conditioning_embedding", "sdxl_clip_weight_arena",
@@ -323,11 +333,118 @@ class Conditioning:
         return c, keep
 
 
+class InvalidArgument(EngineError):
+    """SDXL_ERR_INVALID: arguments outside what the entry supports"""
+
+
+def _check_invalid(rc: int):
+    if rc == 1:
+        raise InvalidArgument(lib().sdxl_last_error().decode())
+    _check(rc)
+
+
+# ---------------------------------------------------------------------------------------------------------------- adapters
+
+def param_index(specs: Sequence[ParamSpec], name: str) -> int:
+    """index of parameter `name` in a spec list (unet_param_specs): the param_index of a LoraEntry"""
+    for i, p in enumerate(specs):
+        if p.name == name:
+            return i
+    raise EngineError(f"unknown parameter {name!r}")
+
+
+def _f32_matrix(a, transpose: bool):
+    """(contiguous fp32 2-d array kept alive, pointer): numpy arrays stay on the host, torch tensors stay where they are (host or device)"""
+    if hasattr(a, "data_ptr"):      # torch tensor
+        torch = _torch()
+        t = a.detach().to(torch.float32).reshape(a.shape[0], -1)
+        t = (t.t() if transpose else t).contiguous()
+        return t, ctypes.c_void_p(t.data_ptr())
+    n = np.asarray(a, dtype=np.float32)
+    n = n.reshape(n.shape[0], -1)
+    n = np.ascontiguousarray(n.T if transpose else n)
+    return n, n.ctypes.data_as(ctypes.c_void_p)
+
+
+def lora_entry(spec_index: int, down_weight, up_weight, alpha: Optional[float] = None, strength: float = 1.0) -> LoraEntry:
+    """A LoraEntry from the usual PyTorch adapter pair, numpy arrays or torch tensors (host or device):
+      Linear (down_weight [r, d_in], up_weight [d_out, r]) on a [d_in, d_out] parameter: left = down^T, right = up^T;
+      Conv2d (down_weight [r, Cin, kh, kw] -- four dimensions --, up_weight [Cout, r] or [Cout, r, 1, 1]) on a [Cout, Cin, kh, kw] parameter:
+      left = up, right = down flattened to [r, Cin * kh * kw].
+    scale = strength * alpha / r (alpha defaults to r).  The C ABI cannot see the arrays' extents; UNet / Diffuser compare the shapes recorded here
+    with the parameter's matrix view before they hand the entries over."""
+    conv = len(down_weight.shape) == 4
+    rank = int(down_weight.shape[0])
+    if int(up_weight.shape[1]) != rank:
+        raise EngineError(f"lora_entry: down_weight has rank {rank}, up_weight {tuple(up_weight.shape)}")
+    if conv:
+        left, pl = _f32_matrix(up_weight, False)
+        right, pr = _f32_matrix(down_weight, False)
+    else:
+        left, pl = _f32_matrix(down_weight, True)
+        right, pr = _f32_matrix(up_weight, True)
+    e = LoraEntry(int(spec_index), rank, pl, pr, float(strength) * float(rank if alpha is None else alpha) / rank)
+    e.keep = (left, right)      # the arrays the pointers name
+    e.left_shape, e.right_shape = tuple(left.shape), tuple(right.shape)
+    return e
+
+
+def _lora_array(entries: Sequence[LoraEntry], cfg: Optional[UNetConfig] = None):
+    """(sdxl_lora_entry array, count); with cfg: the shapes lora_entry recorded must fit the parameter (a wrong extent would read past the arrays)"""
+    n = len(entries)
+    if cfg is not None and n:
+        specs = unet_param_specs(cfg)
+        for i, e in enumerate(entries):
+            if 0 <= e.param_index < len(specs) and hasattr(e, "left_shape"):
+                shape = specs[e.param_index].shape
+                rows, cols = int(shape[0]), int(np.prod(shape[1:], dtype=np.int64))
+                if e.left_shape != (rows, e.rank) or e.right_shape != (e.rank, cols):
+                    raise EngineError(f"lora entry {i}: {specs[e.param_index].name} {tuple(shape)} takes left {(rows, e.rank)} and right {(e.rank, cols)}, "
+                                      f"got {e.left_shape} and {e.right_shape}")
+    return ((LoraEntry * n)(*entries) if n else None), n
+
+
+def _lora_base(weights):
+    """(weights_flat, weights_flat_f16, array kept alive) of the *_create_lora calls: at most one base, none = the synthetic seed"""
+    if weights is None:
+        return None, None, None
+    if np.asarray(weights).dtype == np.float16:
+        w = np.ascontiguousarray(weights)
+        return None, w.ctypes.data_as(ctypes.c_void_p), w
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    return w.ctypes.data_as(ctypes.c_void_p), None, w
+
+
+def lora_check(cfg: UNetConfig, entries: Sequence[LoraEntry]):
+    """sdxl_lora_check (host logic, no GPU needed): raises InvalidArgument with the first complaint"""
+    c = cfg.to_c()
+    arr, n = _lora_array(entries)
+    _check_invalid(lib().sdxl_lora_check(ctypes.byref(c), arr, n))
+
+
+def lora_merge(ctx: Context, w, left, right, scale: float, flags: int = 0):
+    """sdxl_lora_merge, the op the models run at create time: returns w + scale * left @ right on the matrix view of w (rows = w.shape[0]) as a new
+    CUDA tensor of w's shape (w itself is not written); left [rows, rank], right [rank, cols]: numpy arrays or torch tensors, host or device."""
+    w, _ = _dev(w)
+    out = w.clone()
+    left, pl = _f32_matrix(left, False)
+    right, pr = _f32_matrix(right, False)
+    rows = int(out.shape[0])
+    cols = int(out.numel() // rows) if rows else 0
+    if tuple(left.shape) != (rows, int(right.shape[0])) or int(right.shape[1]) != cols:
+        raise EngineError(f"lora_merge: w {tuple(out.shape)}, left {tuple(left.shape)}, right {tuple(right.shape)}")
+    _check_invalid(lib().sdxl_lora_merge(ctx.h, _stream(), ctypes.c_void_p(out.data_ptr()), rows, cols, pl, pr, int(right.shape[0]),
+                                         ctypes.c_float(scale), int(flags)))
+    _torch().cuda.synchronize()
+    return out
+
+
 class UNet:
     """reference UNet<B> (src/model/unet/mod.rs:432-493)"""
 
     def __init__(self, ctx: Context, cfg: UNetConfig, dtype: int = DTYPE_F16, weights: Optional[np.ndarray] = None,
-                 seed: int = 0, _borrowed=None):
+                 seed: int = 0, _borrowed=None, lora: Optional[Sequence[LoraEntry]] = None, lora_flags: int = 0):
+        """lora: LoraEntry list (lora_entry) merged into the weights while the model is built, in the order given; lora_flags: LORA_ROUND_F16"""
         self.ctx, self.cfg, self.dtype = ctx, cfg, dtype
         self._owned = _borrowed is None
         if _borrowed is not None:
@@ -335,7 +452,12 @@ class UNet:
             return
         self.h = ctypes.c_void_p()
         c = cfg.to_c()
-        if weights is None:
+        if lora is not None:
+            wf, wf16, keep = _lora_base(weights)
+            arr, n = _lora_array(lora, cfg)
+            _check_invalid(lib().sdxl_unet_create_lora(ctx.h, ctypes.byref(c), dtype, wf, wf16, ctypes.c_uint64(seed), arr, n, int(lora_flags),
+                                                       ctypes.byref(self.h)))
+        elif weights is None:
             _check(lib().sdxl_unet_create_synthetic(ctx.h, ctypes.byref(c), dtype, ctypes.c_uint64(seed), ctypes.byref(self.h)))
         elif np.asarray(weights).dtype == np.float16:     # flat f16 (burn HalfPrecisionSettings records): no fp32 expansion
             w = np.ascontiguousarray(weights)
@@ -658,7 +780,9 @@ class Diffuser:
     """reference Diffuser<B> (src/model/stablediffusion/mod.rs:308-542)"""
 
     def __init__(self, ctx: Context, cfg: UNetConfig, dtype: int = DTYPE_F16, weights: Optional[np.ndarray] = None,
-                 seed: int = 0, alphas_cumprod: Optional[np.ndarray] = None, empty: bool = False):
+                 seed: int = 0, alphas_cumprod: Optional[np.ndarray] = None, empty: bool = False,
+                 lora: Optional[Sequence[LoraEntry]] = None, lora_flags: int = 0):
+        """lora / lora_flags: as UNet"""
         self.ctx, self.cfg, self.dtype = ctx, cfg, dtype
         a = np.ascontiguousarray(default_alphas_cumprod() if alphas_cumprod is None else alphas_cumprod, dtype=np.float32)
         self.n_train = int(a.shape[0])
@@ -666,7 +790,14 @@ class Diffuser:
         c = cfg.to_c()
         ap = a.ctypes.data_as(ctypes.c_void_p)
         if empty:   # replica rank: arena laid out, contents arrive by broadcast
+            if lora is not None:
+                raise EngineError("an empty replica receives rank 0's merged arena: it takes no adapters")
             _check(lib().sdxl_diffuser_create_empty(ctx.h, ctypes.byref(c), dtype, ap, self.n_train, ctypes.byref(self.h)))
+        elif lora is not None:
+            wf, wf16, keep = _lora_base(weights)
+            arr, n = _lora_array(lora, cfg)
+            _check_invalid(lib().sdxl_diffuser_create_lora(ctx.h, ctypes.byref(c), dtype, wf, wf16, ctypes.c_uint64(seed), arr, n, int(lora_flags),
+                                                           ap, self.n_train, ctypes.byref(self.h)))
         elif weights is None:
             _check(lib().sdxl_diffuser_create_synthetic(ctx.h, ctypes.byref(c), dtype, ctypes.c_uint64(seed), ap,
                                                        self.n_train, ctypes.byref(self.h)))
@@ -1025,10 +1156,6 @@ def conv2d_group_norm(ctx: Context, x, weight, bias, gamma, beta, eps: float = 1
 
 FORM_NATIVE, FORM_F16, FORM_F16_WHILO, FORM_F16_AHILO, FORM_X2 = 0, 1, 2, 3, 4   # include/sdxl_mi355.h SDXL_FORM_*
 PROJ_QKV, PROJ_QUERY, PROJ_GEGLU = 0, 1, 2                                      # include/sdxl_mi355.h SDXL_PROJ_*
-
-
-class InvalidArgument(EngineError):
-    """SDXL_ERR_INVALID: arguments outside what the entry supports"""
 
 
 def transformer_projection(ctx: Context, r, gamma, beta, weight, bias, proj: int, form: int, eps: float = 1e-5, shadow: bool = False,

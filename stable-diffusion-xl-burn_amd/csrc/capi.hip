@@ -78,6 +78,33 @@ int spec_out(const std::vector<ParamSpec>& specs, int index, const char** name, 
   if (mean) *mean = p.mean;
   return SDXL_OK;
 }
+// the *_create_lora entries: argument errors are SDXL_ERR_INVALID before anything is built; then `make` gets the adapter source over the one base given
+std::vector<LoraEntry> to_lora(const sdxl_lora_entry* e, int n) {
+  std::vector<LoraEntry> v;
+  for (int i = 0; i < n; ++i) { LoraEntry l; l.param_index = e[i].param_index; l.rank = e[i].rank; l.left = e[i].left; l.right = e[i].right; l.scale = e[i].scale; v.push_back(l); }
+  return v;
+}
+template <class F>
+int create_with_lora(sdxl_ctx* ctx, const sdxl_unet_config* cfg, const float* weights_flat, const uint16_t* weights_flat_f16, uint64_t seed,
+                     const sdxl_lora_entry* entries, int n_entries, int flags, F make) {
+  if (!ctx || !cfg) return fail(SDXL_ERR_INVALID, "null argument");
+  if (weights_flat && weights_flat_f16) return fail(SDXL_ERR_INVALID, "lora: exactly one base -- weights_flat, weights_flat_f16, or both NULL for the synthetic seed");
+  if (flags & ~SDXL_LORA_ROUND_F16) return fail(SDXL_ERR_INVALID, "lora: unknown flag bits (SDXL_LORA_ROUND_F16)");
+  if (n_entries < 0 || (n_entries > 0 && !entries)) return fail(SDXL_ERR_INVALID, n_entries < 0 ? "lora: n_entries is negative" : "lora: entries is NULL");
+  API_BEGIN
+  const std::vector<ParamSpec> specs = unet_param_specs(to_cfg(cfg));
+  const std::vector<LoraEntry> le = to_lora(entries, n_entries);
+  const std::string bad = lora_check(specs, le.data(), n_entries);
+  if (!bad.empty()) return fail(SDXL_ERR_INVALID, bad);
+  use(ctx);
+  std::unique_ptr<WeightSource> base;
+  if (weights_flat) base.reset(new FlatSource(weights_flat, specs));
+  else if (weights_flat_f16) base.reset(new FlatSourceF16(weights_flat_f16, specs));
+  else base.reset(new SyntheticSource(seed));
+  LoraSource src(*base, specs, le.data(), n_entries, flags);
+  return make(src);
+  API_END
+}
 }  // namespace
 
 extern "C" {
@@ -274,6 +301,20 @@ int sdxl_unet_create_synthetic(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int d
   return unet_create_impl(ctx, cfg, dtype, src, out);
   API_END
 }
+int sdxl_lora_check(const sdxl_unet_config* cfg, const sdxl_lora_entry* entries, int n_entries) {
+  if (!cfg) return fail(SDXL_ERR_INVALID, "null config");
+  if (n_entries < 0 || (n_entries > 0 && !entries)) return fail(SDXL_ERR_INVALID, n_entries < 0 ? "lora: n_entries is negative" : "lora: entries is NULL");
+  API_BEGIN
+  const std::vector<LoraEntry> le = to_lora(entries, n_entries);
+  const std::string bad = lora_check(unet_param_specs(to_cfg(cfg)), le.data(), n_entries);
+  if (!bad.empty()) return fail(SDXL_ERR_INVALID, bad);
+  API_END
+}
+int sdxl_unet_create_lora(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, const float* weights_flat, const uint16_t* weights_flat_f16,
+                          uint64_t synthetic_seed, const sdxl_lora_entry* entries, int n_entries, int flags, sdxl_unet** out) {
+  return create_with_lora(ctx, cfg, weights_flat, weights_flat_f16, synthetic_seed, entries, n_entries, flags,
+                          [&](WeightSource& src) { return unet_create_impl(ctx, cfg, dtype, src, out); });
+}
 void sdxl_unet_destroy(sdxl_unet* u) {
   if (!u) return;
   if (u->owned) delete u->u;
@@ -440,6 +481,12 @@ int sdxl_diffuser_create_synthetic(sdxl_ctx* ctx, const sdxl_unet_config* cfg, i
   SyntheticSource src(seed);
   return diffuser_create_impl(ctx, cfg, dtype, src, alphas, n_train, out);
   API_END
+}
+int sdxl_diffuser_create_lora(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, const float* weights_flat, const uint16_t* weights_flat_f16,
+                              uint64_t synthetic_seed, const sdxl_lora_entry* entries, int n_entries, int flags, const float* alphas, int n_train,
+                              sdxl_diffuser** out) {
+  return create_with_lora(ctx, cfg, weights_flat, weights_flat_f16, synthetic_seed, entries, n_entries, flags,
+                          [&](WeightSource& src) { return diffuser_create_impl(ctx, cfg, dtype, src, alphas, n_train, out); });
 }
 int sdxl_diffuser_create_empty(sdxl_ctx* ctx, const sdxl_unet_config* cfg, int dtype, const float* alphas, int n_train,
                                sdxl_diffuser** out) {

@@ -637,4 +637,24 @@ int sdxl_conv2d_group_norm(sdxl_ctx* ctx, void* stream, const float* x, const fl
   API_END
 }
 
+// the create-time adapter merge on one resident tensor, through the source the models are built through (LoraSource: staging of host / device
+// arrays, the merge kernel, the optional f16 rounding)
+int sdxl_lora_merge(sdxl_ctx* ctx, void* stream, float* w_dev, int rows, int cols, const float* left, const float* right, int rank, float scale,
+                    int flags) {
+  if (!ctx || !w_dev) return fail(SDXL_ERR_INVALID, "null argument");
+  if (rows < 1 || cols < 1) return fail(SDXL_ERR_INVALID, "lora_merge: rows, cols must be >= 1");
+  if (flags & ~SDXL_LORA_ROUND_F16) return fail(SDXL_ERR_INVALID, "lora: unknown flag bits (SDXL_LORA_ROUND_F16)");
+  const std::vector<ParamSpec> specs{ParamSpec{"w", {rows, cols}, PK_LINEAR_W, 0.f, 0.f}};
+  LoraEntry e; e.param_index = 0; e.rank = rank; e.left = left; e.right = right; e.scale = scale;
+  const std::string bad = lora_check(specs, &e, 1);
+  if (!bad.empty()) return fail(SDXL_ERR_INVALID, bad);
+  API_BEGIN
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  struct Resident : WeightSource { void fetch(const ParamSpec&, size_t, float*, hipStream_t) override {} } resident;      // the tensor is where fetch() would put it
+  LoraSource src(resident, specs, &e, 1, flags);
+  src.fetch(specs[0], 0, w_dev, s);
+  API_END
+}
+
 }  // extern "C"

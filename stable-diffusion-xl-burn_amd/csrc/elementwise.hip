@@ -453,6 +453,50 @@ __global__ void round_f16_kernel(float* p, size_t n) {
 void launch_round_f16(float* p, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(round_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, n);
 }
+// Create-time adapter merge (LoraSource, sdxl_lora_merge): W[rows][cols] += scale * left[rows][rank] @ right[rank][cols], fp32 in place.
+// The arithmetic is fixed -- per element acc = 0; acc = fmaf(left[r][j], right[j][c], acc) for j ascending; w = fmaf(scale, acc, w) -- so two
+// runs give the same bits whatever the grid, and a host bound follows.  A block owns a 16-row x 64-column tile: the lanes of a wave run along the
+// columns (coalesced loads / stores of W and of the right panel, LDS reads of consecutive words), each thread carries 4 rows; the left row panel is
+// read as a broadcast.  Both panels go through LDS in chunks of 32 ranks; the accumulators stay in registers across the chunks.
+constexpr int kLoraRows = 16, kLoraCols = 64, kLoraRank = 32;
+__global__ __launch_bounds__(256) void lora_merge_kernel(float* w, size_t rows, size_t cols, const float* left, const float* right, int rank, float scale,
+                                                         unsigned col_tiles) {
+  __shared__ float sl[kLoraRows][kLoraRank];
+  __shared__ float sr[kLoraRank][kLoraCols];
+  const size_t r0 = (size_t)(blockIdx.x / col_tiles) * kLoraRows, c0 = (size_t)(blockIdx.x % col_tiles) * kLoraCols;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < rank; k0 += kLoraRank) {
+    const int jn = rank - k0 < kLoraRank ? rank - k0 : kLoraRank;      // (the last chunk may be partial: the loop below never reads past it)
+    for (int e = threadIdx.x; e < kLoraRows * kLoraRank; e += 256) {
+      const int r = e / kLoraRank, j = e % kLoraRank;
+      sl[r][j] = (r0 + r < rows && j < jn) ? left[(r0 + r) * (size_t)rank + k0 + j] : 0.f;
+    }
+    for (int e = threadIdx.x; e < kLoraRank * kLoraCols; e += 256) {
+      const int j = e / kLoraCols, c = e % kLoraCols;
+      sr[j][c] = (j < jn && c0 + c < cols) ? right[(size_t)(k0 + j) * cols + c0 + c] : 0.f;
+    }
+    __syncthreads();
+    for (int j = 0; j < jn; ++j) {
+      const float b = sr[j][tx];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[i] = fmaf(sl[ty * 4 + i][j], b, acc[i]);
+    }
+    __syncthreads();
+  }
+  if (c0 + tx >= cols) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const size_t r = r0 + ty * 4 + i;
+    if (r < rows) { float* p = w + r * cols + c0 + tx; *p = fmaf(scale, acc[i], *p); }
+  }
+}
+void launch_lora_merge(float* w, size_t rows, size_t cols, const float* left, const float* right, int rank, float scale, hipStream_t s) {
+  if (!rows || !cols || rank < 1 || scale == 0.f) return;      // (scale 0 is the identity on every bit pattern of W, -0 and non-finite products included)
+  const size_t col_tiles = (cols + kLoraCols - 1) / kLoraCols, tiles = col_tiles * ((rows + kLoraRows - 1) / kLoraRows);
+  if (tiles > 0x7fffffffull) throw std::runtime_error("lora_merge: tensor too large for one launch");
+  hipLaunchKernelGGL(lora_merge_kernel, dim3((unsigned)tiles), dim3(256), 0, s, w, rows, cols, left, right, rank, scale, (unsigned)col_tiles);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // CLIP text-encoder glue (clip/mod.rs:99-105 embedding sum, :139-147 eot pooling, backend.rs attn_decoder_mask)

@@ -111,6 +111,32 @@ struct FlatSourceF16 : WeightSource {   // flat IEEE-f16 buffer (host or device)
   void fetch(const ParamSpec& s, size_t index, float* dst_dev, hipStream_t st) override;
 };
 
+// Create-time adapters (C ABI: sdxl_lora_entry): W += scale * left @ right on the matrix view of a PK_LINEAR_W / PK_CONV_W parameter,
+// rows = shape[0], cols = product of the other dimensions; left [rows, rank], right [rank, cols], fp32, host or device.  In terms of the usual
+// PyTorch adapter tensors (down.weight [r, in...], up.weight [out, r]):
+//   PK_LINEAR_W [d_in, d_out]:      left = down.weight^T,  right = up.weight^T
+//   PK_CONV_W   [Cout, Cin, kh, kw]: left = up.weight,      right = down.weight flattened to [r, Cin * kh * kw]
+struct LoraEntry { int param_index = 0, rank = 0; const float* left = nullptr; const float* right = nullptr; float scale = 0.f; };
+constexpr int kLoraRoundF16 = 1;      // C ABI: SDXL_LORA_ROUND_F16
+// empty string: every entry names a PK_LINEAR_W / PK_CONV_W parameter of specs, rank >= 1, non-null arrays, finite scale; else the first complaint (host logic only)
+std::string lora_check(const std::vector<ParamSpec>& specs, const LoraEntry* entries, int n_entries);
+// A source that wraps another one: fetch() asks the inner source, then merges every entry of that parameter into dst_dev in the order the entries were
+// given (launch_lora_merge: several adapters on one tensor stack), last -- kLoraRoundF16 -- rounds the adapted tensor to f16 values (what a half-precision
+// record saved after merging holds).  It sits in front of WeightBuilder, so every packing form, every dtype and the f16-exactness guard
+// (WeightBuilder::all_f16_exact) see the merged tensor; nothing downstream knows adapters exist.  The entries' arrays are staged per fetch into a
+// device buffer this source owns; they must stay alive while the model is built.
+struct LoraSource : WeightSource {
+  WeightSource& inner;
+  std::vector<LoraEntry> entries;
+  std::vector<std::vector<int>> by_param;      // entry indices per parameter, in the order given
+  int flags;
+  float* stage = nullptr; size_t stage_numel = 0;
+  LoraSource(WeightSource& in, const std::vector<ParamSpec>& specs, const LoraEntry* e, int n_entries, int flags);
+  ~LoraSource() override;
+  void fetch(const ParamSpec& s, size_t index, float* dst_dev, hipStream_t st) override;
+  bool empty() const override { return inner.empty(); }
+};
+
 struct Lin {        // packed dense weight: [Npad][Kpad] compute dtype + fp32 bias [Npad]
   const void* w = nullptr; const float* b = nullptr;
   const void* wf = nullptr;        // f16 linear layers / 1x1 convs with N % 128 == 0: the same weights in MFMA fragment order (igemm_wreg.hip)

@@ -303,6 +303,9 @@ void launch_f16_to_hl(const void* src, int lds, void* dst, int ldd, size_t rows,
 void launch_f32_to_f16_pair(const float* src, int lds, void* hi, void* lo, int ld16, size_t rows, int C, hipStream_t s);
 void launch_hl_zero_lo(void* dst, int ldd, size_t rows, int C, hipStream_t s);   // HL16 rows: lo halves := 0 (precision-frontier instrument, UNet hl_demote)
 void launch_round_f16(float* p, size_t n, hipStream_t s);   // p[i] = float(half(p[i])): parameters as a HalfPrecisionSettings record holds them
+// create-time adapter merge: w[rows][cols] += scale * left[rows][rank] @ right[rank][cols], fp32 device tensors, in place.  Fixed arithmetic: per element
+// acc = 0; acc = fmaf(left[r][j], right[j][c], acc) for j = 0 .. rank-1; w = fmaf(scale, acc, w).  scale == 0 launches nothing.
+void launch_lora_merge(float* w, size_t rows, size_t cols, const float* left, const float* right, int rank, float scale, hipStream_t s);
 void launch_i32_to_f32(const int* src, float* dst, int n, hipStream_t s);
 // CLIP text encoder (clip/mod.rs:99-105,139-147): x[b][t][:] = tok[ids[b][t]][:] + pos[t][:] (tables in dtype w_dt);
 // eot[b] = first index of max(ids[b][:]); sel[b][:] = x[b][eot[b]][:] as fp32; additive causal mask [n][n] (0 / -inf)

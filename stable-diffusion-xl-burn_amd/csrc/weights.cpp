@@ -107,6 +107,50 @@ void FlatSourceF16::fetch(const ParamSpec& s, size_t index, float* dst, hipStrea
   launch_copy_rows(stage, DT_F16, 1, dst, DT_F32, 1, (int)s.numel(), 1, st);   // exact widening: every f16 is an fp32
 }
 
+// ------------------------------------------------------------------------------------------ adapters
+std::string lora_check(const std::vector<ParamSpec>& specs, const LoraEntry* entries, int n_entries) {
+  if (n_entries < 0) return "lora: n_entries is negative";
+  if (n_entries > 0 && !entries) return "lora: entries is NULL";
+  for (int i = 0; i < n_entries; ++i) {
+    const LoraEntry& e = entries[i];
+    const std::string at = "lora entry " + std::to_string(i) + ": ";
+    if (e.param_index < 0 || e.param_index >= (int)specs.size())
+      return at + "param_index " + std::to_string(e.param_index) + " out of range (0.." + std::to_string((int)specs.size() - 1) + ")";
+    const ParamSpec& p = specs[e.param_index];
+    if (p.kind != PK_LINEAR_W && p.kind != PK_CONV_W) return at + "'" + p.name + "' is not a LINEAR_W / CONV_W parameter (biases, norm gamma / beta / eps take no adapter)";
+    if (e.rank < 1) return at + "rank must be >= 1";
+    if (!e.left || !e.right) return at + "left / right array is NULL";
+    if (!std::isfinite(e.scale)) return at + "scale is not finite";
+  }
+  return std::string();
+}
+LoraSource::LoraSource(WeightSource& in, const std::vector<ParamSpec>& specs, const LoraEntry* e, int n_entries, int f)
+    : inner(in), entries(e, e + (n_entries > 0 ? n_entries : 0)), by_param(specs.size()), flags(f) {
+  const std::string bad = lora_check(specs, entries.data(), (int)entries.size());
+  if (!bad.empty()) throw Error(bad);
+  for (size_t i = 0; i < entries.size(); ++i) by_param[entries[i].param_index].push_back((int)i);
+}
+LoraSource::~LoraSource() { if (stage) (void)hipFree(stage); }
+void LoraSource::fetch(const ParamSpec& s, size_t index, float* dst, hipStream_t st) {
+  inner.fetch(s, index, dst, st);
+  if (index >= by_param.size() || by_param[index].empty()) return;
+  const size_t rows = (size_t)s.shape[0], cols = s.numel() / rows;
+  for (int i : by_param[index]) {
+    const LoraEntry& e = entries[i];
+    const size_t nl = rows * (size_t)e.rank, nr = (size_t)e.rank * cols;
+    if (nl + nr > stage_numel) {     // (stream order: the kernels that read the old buffer are done before hipFree returns)
+      if (stage) { SDXL_HIP(hipStreamSynchronize(st)); SDXL_HIP(hipFree(stage)); stage = nullptr; stage_numel = 0; }
+      SDXL_HIP(hipMalloc((void**)&stage, (nl + nr) * sizeof(float)));
+      stage_numel = nl + nr;
+    }
+    SDXL_HIP(hipMemcpyAsync(stage, e.left, nl * sizeof(float), hipMemcpyDefault, st));
+    SDXL_HIP(hipMemcpyAsync(stage + nl, e.right, nr * sizeof(float), hipMemcpyDefault, st));
+    launch_lora_merge(dst, rows, cols, stage, stage + nl, e.rank, e.scale, st);
+  }
+  if (flags & kLoraRoundF16) launch_round_f16(dst, s.numel(), st);
+  SDXL_HIP(hipStreamSynchronize(st));   // pageable host arrays, and the next fetch may restage
+}
+
 // ------------------------------------------------------------------------------------------ builder
 WeightBuilder::WeightBuilder(const std::vector<ParamSpec>& sp, WeightSource& s, DeviceArena& a, int dtype, hipStream_t stream)
     : specs(sp), src(s), arena(a), dt(dtype), st(stream) {
