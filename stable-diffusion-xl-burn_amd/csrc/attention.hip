@@ -44,6 +44,64 @@ template <> struct AMma<float> {
   }
 };
 
+// ---- the two pieces attn_d64_kernel<T> and attn_d64_f16_kernel share (their softmax steps differ: scale on the scores / on Q, exp2f / v_exp_f32)
+// O^T[d][query] += V^T P^T in f16, k-step u (32 keys) of a tile: the probabilities a lane holds become the B fragments; tile rows of 128 bytes, chunks
+// swizzled by row & 7.  (The loop over u stays with the caller: inside the helper the generic kernel took two more VGPRs, 170 -- one wave per SIMD less.)
+__device__ __forceinline__ void attn16_pv_f16(int u, const char* vb, const f32x4 (&st)[4][2], f32x4 (&ot)[4][2], int g, int fr) {
+  constexpr int MQ = 2;
+  {
+    i32x4 pf[MQ];
+#pragma unroll
+    for (int mq = 0; mq < MQ; ++mq) {
+      half8 hh;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { hh[r] = (half_t)st[2 * u][mq][r]; hh[4 + r] = (half_t)st[2 * u + 1][mq][r]; }
+      pf[mq] = __builtin_bit_cast(i32x4, hh);
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int row = dt * 16 + fr;
+      // keys u*32 + g*4 .. +3 (bytes 64u+8g) and u*32+16+g*4 .. +3 (bytes 64u+32+8g)
+      const int c1 = 4 * u + (g >> 1), c2 = c1 + 2, sub = (g & 1) * 8;
+      const i32x2 v1 = *reinterpret_cast<const i32x2*>(vb + row * 128 + ((c1 ^ (row & 7)) << 4) + sub);
+      const i32x2 v2 = *reinterpret_cast<const i32x2*>(vb + row * 128 + ((c2 ^ (row & 7)) << 4) + sub);
+      const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
+#pragma unroll
+      for (int mq = 0; mq < MQ; ++mq) ot[dt][mq] = AMma<half_t>::run(vf, pf[mq], ot[dt][mq]);
+    }
+  }
+}
+// normalise and store: lane holds O[query = lane&15][d = dt*16 + g*4 + r] of the 32 queries from q0 on
+template <typename T>
+__device__ __forceinline__ void attn16_store(const AttnParams& p, const f32x4 (&ot)[4][2], const float (&lrun)[2], int b, int h, int q0, int g, int fr) {
+  T* Og = reinterpret_cast<T*>(p.O) + (size_t)b * p.Nq * p.ldo + h * 64;
+#pragma unroll
+  for (int mq = 0; mq < 2; ++mq) {
+    float l = lrun[mq];
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    const float inv = 1.0f / l;
+    const int q = q0 + mq * 16 + fr;
+    if (q < p.Nq) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        T* dst = Og + (size_t)q * p.ldo + dt * 16 + g * 4;
+        if constexpr (sizeof(T) == 2) {
+          half4 o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[r] = (half_t)(ot[dt][mq][r] * inv);
+          *reinterpret_cast<half4*>(dst) = o;
+        } else {
+          f32x4 o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[r] = ot[dt][mq][r] * inv;
+          *reinterpret_cast<f32x4*>(dst) = o;
+        }
+      }
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_d64_kernel(const AttnParams p) {
   constexpr int D = 64, KV = 64, MQ = 2;
@@ -178,27 +236,7 @@ __global__ __launch_bounds__(256, 2) void attn_d64_kernel(const AttnParams p) {
     // ---- O^T[d][query] += V^T P^T
     if constexpr (sizeof(T) == 2) {
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        i32x4 pf[MQ];
-#pragma unroll
-        for (int mq = 0; mq < MQ; ++mq) {
-          half8 hh;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { hh[r] = (half_t)st[2 * u][mq][r]; hh[4 + r] = (half_t)st[2 * u + 1][mq][r]; }
-          pf[mq] = __builtin_bit_cast(i32x4, hh);
-        }
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int row = dt * 16 + fr;
-          // keys u*32 + g*4 .. +3 (bytes 64u+8g) and u*32+16+g*4 .. +3 (bytes 64u+32+8g)
-          const int c1 = 4 * u + (g >> 1), c2 = c1 + 2, sub = (g & 1) * 8;
-          const i32x2 v1 = *reinterpret_cast<const i32x2*>(vb + row * RB + ((c1 ^ (row & 7)) << 4) + sub);
-          const i32x2 v2 = *reinterpret_cast<const i32x2*>(vb + row * RB + ((c2 ^ (row & 7)) << 4) + sub);
-          const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
-#pragma unroll
-          for (int mq = 0; mq < MQ; ++mq) ot[dt][mq] = AMma<T>::run(vf, pf[mq], ot[dt][mq]);
-        }
-      }
+      for (int u = 0; u < 2; ++u) attn16_pv_f16(u, vb, st, ot, g, fr);
     } else {
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
@@ -217,33 +255,7 @@ __global__ __launch_bounds__(256, 2) void attn_d64_kernel(const AttnParams p) {
     __syncthreads();
   }
 
-  // ---- normalise and store: lane holds O[query = lane&15][d = dt*16 + g*4 + r]
-  T* Og = reinterpret_cast<T*>(p.O) + (size_t)b * p.Nq * p.ldo + h * D;
-#pragma unroll
-  for (int mq = 0; mq < MQ; ++mq) {
-    float l = lrun[mq];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
-    const int q = q0 + mq * 16 + fr;
-    if (q < p.Nq) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        T* dst = Og + (size_t)q * p.ldo + dt * 16 + g * 4;
-        if constexpr (sizeof(T) == 2) {
-          half4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (half_t)(ot[dt][mq][r] * inv);
-          *reinterpret_cast<half4*>(dst) = o;
-        } else {
-          f32x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = ot[dt][mq][r] * inv;
-          *reinterpret_cast<f32x4*>(dst) = o;
-        }
-      }
-    }
-  }
+  attn16_store<T>(p, ot, lrun, b, h, q0, g, fr);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -380,57 +392,46 @@ __global__ __launch_bounds__(256, 2) void attn_d64_f16_kernel(const AttnParams p
         for (int r = 0; r < 4; ++r) ot[dt][mq][r] *= alpha;
     }
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      i32x4 pf[MQ];
-#pragma unroll
-      for (int mq = 0; mq < MQ; ++mq) {
-        half8 hh;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { hh[r] = (half_t)st[2 * u][mq][r]; hh[4 + r] = (half_t)st[2 * u + 1][mq][r]; }
-        pf[mq] = __builtin_bit_cast(i32x4, hh);
-      }
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int row = dt * 16 + fr;
-        const int c1 = 4 * u + (g >> 1), c2 = c1 + 2, sub = (g & 1) * 8;
-        const i32x2 v1 = *reinterpret_cast<const i32x2*>(vb + row * 128 + ((c1 ^ (row & 7)) << 4) + sub);
-        const i32x2 v2 = *reinterpret_cast<const i32x2*>(vb + row * 128 + ((c2 ^ (row & 7)) << 4) + sub);
-        const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
-#pragma unroll
-        for (int mq = 0; mq < MQ; ++mq) ot[dt][mq] = AMma<half_t>::run(vf, pf[mq], ot[dt][mq]);
-      }
-    }
+    for (int u = 0; u < 2; ++u) attn16_pv_f16(u, vb, st, ot, g, fr);
   }
-  half_t* Og = reinterpret_cast<half_t*>(p.O) + (size_t)b * p.Nq * p.ldo + h * D;
-#pragma unroll
-  for (int mq = 0; mq < MQ; ++mq) {
-    float l = lrun[mq];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
-    const int q = q0 + mq * 16 + fr;
-    if (q < p.Nq) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        half4 o;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (half_t)(ot[dt][mq][r] * inv);
-        *reinterpret_cast<half4*>(Og + (size_t)q * p.ldo + dt * 16 + g * 4) = o;
-      }
-    }
-  }
+  attn16_store<half_t>(p, ot, lrun, b, h, q0, g, fr);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// f16 production variant 2 (no additive mask): 32x32x16 MFMA, deferred running max, 3-slot DMA ring, coalesced output.
-//   * S^T = K Q^T with v_mfma_f32_32x32x16_f16: a lane owns ONE query (lane&31) and 32 of the tile's 64 keys, its partner
-//     lane^32 the other 32 -> the row max is 16 v_max3 in-lane; the cross-lane exchange and the O / l rescale only run when
+// The 32x32-MFMA f16 family (no additive mask): 32x32x16 MFMA, deferred running max, 3-slot DMA ring, coalesced output.
+//   * S^T = K Q^T with v_mfma_f32_32x32x16_f16: a lane owns ONE query (lane&31) and 16 keys of every 32-key sub-tile, its partner
+//     lane^32 the other 16 -> the row max is v_max3 in-lane; the cross-lane exchange and the O / l rescale only run when
 //     some query's tile max exceeds the running reference by more than 2^THR (wave-uniform vote).  Between such events the
 //     reference m is folded into the accumulator init (acc = -m), so the MFMA output is already s - m and the per-score
 //     work is one v_exp_f32, one add and half a cvt_pk.  P <= 2^THR fits fp16 with full relative precision; l and O are fp32.
 //   * P stays in registers as the B operand of O^T = V^T P^T (key order of a k-step = the two 4-key runs a lane holds).
 //   * K / V^T tiles: global_load_lds into a 3-slot ring, counted vmcnt (two tiles in flight), one raw barrier per tile.
 //   * O is normalised, parked in LDS per wave and written as whole 128-byte rows.
+// One tile-loop body, attn_d64_body<KP, ...>, serves all of it; KP = key parts per 32-query sub-tile says how a block's four waves divide the work:
+//   KP = 1 (variant 2): a block is 128 queries, a wave takes 32 of them and BOTH 32-key halves of every 64-key tile (two score sub-tiles, NU = 2).
+//     Any Nk: rows past Nk are staged from the zero page and their scores set to -inf on the last tile.  No merge; a wave parks its output rows at
+//     smem + wave * 4096.
+//   KP = 2 (key split, variant 6): variant 2 for grids that leave most SIMDs with ONE wave.  Self-attention at 32^2 (Nq = Nk = 1024, 40
+//     batch-heads) is 320 blocks of 128 queries = 1280 waves on 1024 SIMDs: a wave alone on its SIMD runs QK^T (MFMA), softmax (VALU, the longer
+//     part) and PV (MFMA) strictly in turn, and the SIMDs that carry two waves set the kernel time while the others idle half of it.  Here a block is
+//     64 queries and its four waves are {query sub-tile} x {key half}: every wave takes 32 queries and the 32 keys of its parity out of each 64-key
+//     tile (NU = 1), with its own (m, l, O) -- half the work per wave, twice the waves (2.5 per SIMD: softmax of one under the MFMAs of another, worst
+//     SIMD 3 half-units instead of 2 whole ones).  At the end the odd-half waves park (m, l, O) in the dead ring and the even-half waves merge:
+//     O = O0 2^(m0-m) + O1 2^(m1-m).  Needs Nk % 64 == 0 (no key tail inside a half) -- attn_select sends everything else to KP = 1.
+//   KP = 4 (key quarters, the small blocks of attn_d64_mix_kernel<1>): one step finer: a block is ONE 32-query sub-tile and its four waves are
+//     {tile parity} x {key half}: a wave computes on every other 64-key tile only (it still stages its DMA pieces and takes the barrier of every
+//     tile), and wave 0 merges three partners.  Nk % 64 == 0 as well.
+// Further parameters:
+//   NS: ring slots (3; 4 is an A/B partner of KP = 1 in measure builds).
+//   PRIO = 2: the softmax / PV phase of a wave runs at raised issue priority (s_setprio), the score MFMAs at base priority -- with three
+//     waves per SIMD in different phases the exp-heavy phase is the one that must not wait (measured, profiles/r03_attention_block_balance.txt:
+//     113.4 -> 111.1 us at 64^2, key split 22.0 -> 21.6 us at 32^2, mixed blocks 101.2 -> 99.8 us; raising the MFMA phase instead: no change)
+//   KO (measure builds, attn_variant 11 ..; KP = 2): knock-outs that time one resource of the k-loop alone (results are garbage): bit 0 no DMA
+//     inside the loop, 1 no softmax arithmetic (scores converted as they are), 2 no per-tile barrier, 3 no MFMAs, 4 no LDS fragment reads
+//   XH (KP = 2, level 2 of attn_d64_mix_kernel): the block takes key HALF kx of its 64 queries -- tiles [kx nt / 2, (kx + 1) nt / 2) -- and its partner
+//     block the other half.  Each merging wave parks its (m, l, O) image in the workspace slot of (pair, half, query sub-tile) and draws a ticket; the
+//     wave that draws the second one merges   O = O_0 2^(m_0 - m) + O_1 2^(m_1 - m)   in the fixed order half 0, half 1 -- so the result does not
+//     depend on which block arrived last -- and stores the output rows.  Nobody waits for anybody: no co-residency is assumed.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // 1-D grid, XCD-aware: hardware block b runs on XCD b % 8; remap so that every XCD owns a CONTIGUOUS range of logical ids =
@@ -441,12 +442,59 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-// body of variant 2: the block's four waves take the 128 queries [128 qb, 128 qb + 128) of batch entry b, head hd
-// PRIO = 2: the softmax / PV phase of a wave runs at raised issue priority (s_setprio), the score MFMAs at base priority -- with three
-// waves per SIMD in different phases the exp-heavy phase is the one that must not wait (measured, profiles/r03_attention_block_balance.txt:
-// 113.4 -> 111.1 us at 64^2, key split 22.0 -> 21.6 us at 32^2, mixed blocks 101.2 -> 99.8 us; raising the MFMA phase instead: no change)
-// wave-level hand-over of an un-normalised (m, l, O) image between the two key halves of a query block that live on DIFFERENT workgroups (XH bodies
-// below): nine write-through 16-byte pieces per lane, a ticket per slot; returns false in the wave that arrived first (its partner finishes the
+// ---- softmax steps of a 64-key tile that the body and the split-operand kernel (attn_d64_hl_kernel) share.  sv[u][r] = score (minus the reference m)
+// of query lane & 31 against key 32 u + 8 (r >> 2) + 4 h + (r & 3) of the tile, h = lane >> 5; NU = score sub-tiles the wave holds
+// key tail: on the last tile the scores of keys past Nk become -inf (wave-uniform branch)
+__device__ __forceinline__ void attn_key_tail(f32x16 (&sv)[2], int t, int nt, int h, int Nk) {
+  if (t == nt - 1 && (Nk & 63) != 0) {
+    asm volatile("" ::: "memory");                            // a real branch: as selects this was 32 v_cndmask in EVERY tile
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (t * 64 + u * 32 + 8 * (r >> 2) + 4 * h + (r & 3) >= Nk) sv[u][r] = -INFINITY;
+  }
+}
+// the lane's maximum over its keys of the tile
+// (2 NU independent chains: as one chain the v_max3 are each other's operands and the wave issues nothing else meanwhile)
+template <int NU>
+__device__ __forceinline__ float attn_row_max(const f32x16 (&sv)[NU]) {
+  float lm[2 * NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) { lm[2 * u] = sv[u][0]; lm[2 * u + 1] = sv[u][8]; }
+#pragma unroll
+  for (int r = 1; r < 8; ++r)
+#pragma unroll
+    for (int u = 0; u < NU; ++u) { lm[2 * u] = fmaxf(lm[2 * u], sv[u][r]); lm[2 * u + 1] = fmaxf(lm[2 * u + 1], sv[u][8 + r]); }
+  if constexpr (NU == 2) return fmaxf(fmaxf(lm[0], lm[1]), fmaxf(lm[2], lm[3]));
+  else return fmaxf(lm[0], lm[1]);
+}
+// deferred max: the wave's first tile sets the reference m; later it moves (by whole delta, never down) only when some query's tile maximum exceeds
+// it by more than thr -- rare after the first tiles, wave-uniform.  minit = -m is a live 16-register accumulator image: the first MFMA of every score
+// tile takes it as its C operand directly (rebuilding it cost 16 v_mov per tile)
+template <int NU>
+__device__ __forceinline__ void attn_rescale(bool first, float lmax, float thr, float& m, float& l, f32x16& minit, f32x16 (&o)[2], f32x16 (&sv)[NU]) {
+  if (first || __any(lmax > thr)) {
+    const float pm = fmaxf(lmax, __shfl_xor(lmax, 32));
+    const float delta = first ? pm : fmaxf(pm, 0.f);          // never lower the reference
+    const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
+    m = first ? delta : m + delta;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) minit[r] = -m;
+    l *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sv[u][r] -= delta;
+  }
+}
+
+// wave-level hand-over of an un-normalised (m, l, O) image between the two key halves of a query block that live on DIFFERENT workgroups (XH):
+// nine write-through 16-byte pieces per lane, a ticket per slot; returns false in the wave that arrived first (its partner finishes the
 // rows), true -- with (m, l, O) merged in the fixed order half 0, half 1 -- in the wave that arrived second.  No fence on either side: the image
 // lines were never in the reader's L2 (a launch starts with the caches acquired, an image is read once), and nobody waits for anybody.
 // (First form: plain stores + agent-scope release = an L2 write-back per wave: 33.6 against 21.2 us per launch of the 32^2 self-attention.)
@@ -492,14 +540,41 @@ __device__ __forceinline__ bool attn_xhalf_merge(const AttnParams& p, int slot, 
   return true;
 }
 
-template <int NS, int PRIO = 2>
-__device__ __forceinline__ void attn_d64_v2_body(const AttnParams& p, const void* zeros, char* smem, int b, int hd, int qb) {
+#ifdef SDXL_MEASURE
+// coarse s_memtime stamps of the key-part bodies, KP = 2 / 4 (tools/attn_timeline.py): [workgroup][wave][8] = entry, Q loaded + first tiles issued,
+// k-loop done, merge done (key part 0 only), output stores issued; words 6 / 7 = s_memrealtime (100 MHz) at entry / exit
+__device__ unsigned* g_attn_tl = nullptr;
+void attention_set_timeline(void* buf) {
+  unsigned* b = reinterpret_cast<unsigned*>(buf);
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_tl), &b, sizeof(b)) != hipSuccess) throw std::runtime_error("attention: cannot set the timeline buffer");
+}
+#define ATTN_STAMP(i) do { if constexpr (KP != 1) atl[i] = (unsigned)__builtin_amdgcn_s_memtime(); } while (0)
+#define ATTN_DUMP() do { if constexpr (KP != 1) { atl[7] = (unsigned)__builtin_amdgcn_s_memrealtime(); if (g_attn_tl && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 8; ++i_) g_attn_tl[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + i_] = atl[i_]; } } } while (0)
+#else
+#define ATTN_STAMP(i) do { } while (0)
+#define ATTN_DUMP() do { } while (0)
+#endif
+// the block's four waves take query block qb (128 / 64 / 32 queries for KP = 1 / 2 / 4) of batch entry b, head hd; XH: key half kx of workspace slot pair
+template <int KP, int NS = 3, int PRIO = 2, int KO = 0, bool XH = false>
+__device__ __forceinline__ void attn_d64_body(const AttnParams& p, const void* zeros, char* smem, int b, int hd, int qb, int kx = 0, int pair = 0) {
+  static_assert(KP == 1 || KP == 2 || KP == 4, "key parts per query sub-tile");
+  static_assert(!XH || KP == 2, "cross-workgroup key halves: 64-query blocks");
+  static_assert(KP == 1 || NS == 3, "the merge images and the output rows of the key parts are laid out in a 3-slot ring");
+#ifdef SDXL_MEASURE
+  unsigned atl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (KP != 1) atl[6] = (unsigned)__builtin_amdgcn_s_memrealtime();
+#endif
+  ATTN_STAMP(0);
   constexpr int KV = 64, TILE = 64 * 128;
+  constexpr int NU = KP == 1 ? 2 : 1;           // 32-key score sub-tiles per wave and tile
   constexpr float THR = 8.0f;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qs = KP == 1 ? wave : KP == 2 ? (wave & 1) : 0, kp = KP == 1 ? 0 : KP == 2 ? (wave >> 1) : wave;      // query sub-tile, key part
+  const int kh = KP == 2 ? kp : (kp & 1), tp = kp >> 1;                             // (KP > 1) key half inside a tile; (KP = 4) tile parity
   const int fr = lane & 31, h = lane >> 5;
-  const int q0 = qb * 128 + wave * 32;
+  const int q0 = qb * (128 / KP) + qs * 32;
+  (void)zeros;
   const half_t* Qg = reinterpret_cast<const half_t*>(p.Q) + (size_t)b * p.Nq * p.ldq + hd * 64;
   const half_t* Kg = reinterpret_cast<const half_t*>(p.K) + (size_t)b * p.Nk * p.ldk + hd * 64;
   const half_t* Vg = reinterpret_cast<const half_t*>(p.Vt) + ((size_t)b * p.H + hd) * 64 * p.vt_ld;
@@ -537,11 +612,13 @@ __device__ __forceinline__ void attn_d64_v2_body(const AttnParams& p, const void
     const char* kt = reinterpret_cast<const char*>(Kg + (size_t)k0 * p.ldk);
     const char* vt = reinterpret_cast<const char*>(Vg + k0);
     const char* ks[2] = {kt + kofs[0], kt + kofs[1]};
-    if (k0 + KV > p.Nk) {                                        // key tail (wave-uniform, last tile only): rows past Nk read zeros
-      asm volatile("" ::: "memory");                             // (keeps the selects out of the full tiles' path)
+    if constexpr (KP == 1) {
+      if (k0 + KV > p.Nk) {                                        // key tail (wave-uniform, last tile only): rows past Nk read zeros
+        asm volatile("" ::: "memory");                             // (keeps the selects out of the full tiles' path)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        if (k0 + wave * 16 + j * 8 + lrow >= p.Nk) ks[j] = reinterpret_cast<const char*>(zeros);
+        for (int j = 0; j < 2; ++j)
+          if (k0 + wave * 16 + j * 8 + lrow >= p.Nk) ks[j] = reinterpret_cast<const char*>(zeros);
+      }
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -549,14 +626,14 @@ __device__ __forceinline__ void attn_d64_v2_body(const AttnParams& p, const void
       __builtin_amdgcn_global_load_lds((agptr_t)(vt + vofs[j]), (alptr_t)(lv + j * 1024), 16, 0, 0);
     }
   };
-  // fragment byte offsets inside a tile
-  int koff[2], voff[2];
+  // fragment byte offsets inside a tile: K rows 32 u + fr of the wave's sub-tiles (KP = 1: both; else the one of key half kh); V^T rows dt*32 + fr
+  int koff[NU];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int row = u * 32 + fr;
+  for (int u = 0; u < NU; ++u) {
+    const int row = (KP == 1 ? u : kh) * 32 + fr;
     koff[u] = row * 128 + ((h ^ ((row >> 1) & 7)) << 4);          // K chunk of k-step ks: ^ (ks << 5)
-    voff[u] = row * 128;                                           // V^T row dt*32 + fr; chunk swizzle below
   }
+  const int voff[2] = {fr * 128, (32 + fr) * 128};                 // chunk swizzle below
   const int vsw[2] = {(fr ^ (fr >> 3)) & 7, ((32 + fr) ^ ((32 + fr) >> 3)) & 7};
 
   f32x16 o[2];
@@ -565,106 +642,135 @@ __device__ __forceinline__ void attn_d64_v2_body(const AttnParams& p, const void
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
   float m = 0.f, l = 0.f;
-  // -m as a live 16-register accumulator image: the first MFMA of every score tile takes it as its C operand directly
-  // (rebuilding it cost 16 v_mov per tile); it changes only in the rare rescale branch
-  f32x16 minit;
+  f32x16 minit;                                 // -m, the C operand of every score tile's first MFMA (attn_rescale)
 #pragma unroll
   for (int r = 0; r < 16; ++r) minit[r] = 0.f;
-  const int nt = (p.Nk + KV - 1) / KV;
+  const int nt = KP == 1 ? (p.Nk + KV - 1) / KV : XH ? (p.Nk / KV) >> 1 : p.Nk / KV;      // tiles of this block
+  const int tb = XH ? kx * nt : 0;                                                        // its first tile
 #pragma unroll
   for (int s0 = 0; s0 < NS - 1; ++s0)
-    if (s0 < nt) stage(s0, s0);
+    if (s0 < nt) stage(tb + s0, s0);
+  ATTN_STAMP(1);
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
     // own pieces of tile t landed; tiles t+1 .. t+NS-2 (4 pieces each) may stay in flight
     if (t + NS - 2 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NS - 2)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    if constexpr (!(KO & 4)) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (t + NS - 1 < nt) stage(t + NS - 1, cur == 0 ? NS - 1 : cur - 1);       // slot of tile t-1
+    if (t == 0) ATTN_STAMP(2);
+    if constexpr (!(KO & 1)) { if (t + NS - 1 < nt) stage(tb + t + NS - 1, cur == 0 ? NS - 1 : cur - 1); }       // slot of tile t-1
     const char* kb = smem + cur * 2 * TILE;
     const char* vb = kb + TILE;
-    // ---- S^T - m
+    cur = cur == NS - 1 ? 0 : cur + 1;
+    if (KP == 4 && (t & 1) != tp) continue;                    // the other parity's tile (wave-uniform)
+    const bool first = KP == 4 ? t == tp : t == 0;             // this wave's first tile sets the reference
+    // ---- S^T - m for this wave's 32 NU keys
     if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    f32x16 sv[2];
+    f32x16 sv[NU];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const half8 kf = *reinterpret_cast<const half8*>(kb + (koff[u] ^ (ks << 5)));
-        sv[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? minit : sv[u], 0, 0, 0);
+      for (int u = 0; u < NU; ++u) {
+        half8 kf;
+        if constexpr (KO & 16) kf = qf[ks]; else kf = *reinterpret_cast<const half8*>(kb + (koff[u] ^ (ks << 5)));
+        if constexpr (KO & 8) { if (ks == 0) sv[u] = minit; asm volatile("" ::"v"(kf), "v"(qf[ks])); }
+        else sv[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? minit : sv[u], 0, 0, 0);
       }
     if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(2);
-    if (t == nt - 1 && (p.Nk & 63) != 0) {                      // key tail (wave-uniform branch)
-      asm volatile("" ::: "memory");                            // a real branch: as selects this was 32 v_cndmask in EVERY tile
+    if constexpr (KP == 1) attn_key_tail(sv, t, nt, h, p.Nk);
+    const float lmax = (KO & 2) ? 0.f : attn_row_max<NU>(sv);
+    if constexpr (!(KO & 2)) attn_rescale<NU>(first, lmax, THR, m, l, minit, o, sv);
+    // ---- P = exp2(S - m), row sums, fp16 B fragments: k-step s4 = u*2 + hf holds registers 8*hf .. 8*hf+7 of sub-tile u
+    half8 pf[2 * NU];
 #pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (t * KV + u * 32 + 8 * (r >> 2) + 4 * h + (r & 3) >= p.Nk) sv[u][r] = -INFINITY;
-    }
-    // (four independent chains: as one chain the 16 v_max3 are each other's operands and the wave issues nothing else meanwhile)
-    float lm[4] = {sv[0][0], sv[0][8], sv[1][0], sv[1][8]};
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-      lm[0] = fmaxf(lm[0], sv[0][r]); lm[1] = fmaxf(lm[1], sv[0][8 + r]);
-      lm[2] = fmaxf(lm[2], sv[1][r]); lm[3] = fmaxf(lm[3], sv[1][8 + r]);
-    }
-    const float lmax = fmaxf(fmaxf(lm[0], lm[1]), fmaxf(lm[2], lm[3]));
-    if (t == 0 || __any(lmax > THR)) {                          // rare after the first tiles; wave-uniform
-      const float pm = fmaxf(lmax, __shfl_xor(lmax, 32));
-      const float delta = t == 0 ? pm : fmaxf(pm, 0.f);         // never lower the reference
-      const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
-      m = t == 0 ? delta : m + delta;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) minit[r] = -m;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sv[u][r] -= delta;
-    }
-    // ---- P = exp2(S - m), row sums, fp16 B fragments: k-step s4 = u*2 + hf holds registers 8*hf .. 8*hf+7 of key tile u
-    half8 pf[4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
+    for (int u = 0; u < NU; ++u)
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         half8 hh;
-        float ls = 0.f;                       // per-fragment partial sum: four short add chains instead of one of 32
+        float ls = 0.f;                       // per-fragment partial sum: short add chains instead of one of 16 NU
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(sv[u][8 * hf + e]);
-          ls += pe;
+          const float pe = (KO & 2) ? sv[u][8 * hf + e] : __builtin_amdgcn_exp2f(sv[u][8 * hf + e]);
+          if constexpr (!(KO & 2)) ls += pe;
           hh[e] = (half_t)pe;
         }
         l += ls;
         pf[u * 2 + hf] = hh;
       }
-    // ---- O^T += V^T P^T: k-step s4 covers keys base + {4h..4h+3, 8+4h..8+4h+3}, base = u*32 + 16*hf
+    // ---- O^T += V^T P^T: k-step s4 covers keys base + {4h..4h+3, 8+4h..8+4h+3}, base = 32 (sub-tile u, or key half kh) + 16 hf
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int base = (s4 >> 1) * 32 + (s4 & 1) * 16;
+    for (int s4 = 0; s4 < 2 * NU; ++s4) {
+      const int base = (KP == 1 ? (s4 >> 1) : kh) * 32 + (s4 & 1) * 16;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const int b1 = (base + 4 * h) * 2, b2 = b1 + 16;           // byte offsets of the two 4-key runs in the row
-        const i32x2 v1 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b1 >> 4)) ^ vsw[dt]) << 4) + (b1 & 15));
-        const i32x2 v2 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b2 >> 4)) ^ vsw[dt]) << 4) + (b2 & 15));
+        i32x2 v1, v2;
+        if constexpr (KO & 16) { v1 = i32x2{b1, b2}; v2 = i32x2{b2, b1}; }
+        else {
+          v1 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b1 >> 4)) ^ vsw[dt]) << 4) + (b1 & 15));
+          v2 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b2 >> 4)) ^ vsw[dt]) << 4) + (b2 & 15));
+        }
         const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, vf), pf[s4], o[dt], 0, 0, 0);
+        if constexpr (KO & 8) asm volatile("" ::"v"(vf), "v"(pf[s4]));
+        else o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, vf), pf[s4], o[dt], 0, 0, 0);
       }
     }
-    cur = cur == NS - 1 ? 0 : cur + 1;
+  }
+  ATTN_STAMP(3);
+  l += __shfl_xor(l, 32);
+  char* ob;                                     // where this wave parks its 32 output rows
+  if constexpr (KP == 1) {
+    __syncthreads();
+    ob = smem + wave * 4096;
+  } else {
+    if (KP == 4 && tp >= nt) m = -INFINITY;       // (a wave that saw no tile of its parity: weight 0 in the merge; the launcher asks Nk >= 128)
+    // ---- merge the key parts of each query sub-tile through the dead ring: parked images of [34][64 lanes] floats at smem + 0
+    //      (KP = 2: one per query sub-tile; KP = 4: the three partners of wave 0)
+    constexpr int NPARK = KP == 2 ? 2 : 3, NMERGE = KP == 2 ? 1 : 3;
+    __syncthreads();
+    float* mbase = reinterpret_cast<float*>(smem) + lane;
+    if (kp != 0) {
+      float* mb = mbase + (KP == 2 ? qs : kp - 1) * (34 * 64);
+      mb[0] = m; mb[64] = l;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mb[(2 + dt * 16 + r) * 64] = o[dt][r];
+    }
+    __syncthreads();
+    if (kp != 0) { ATTN_DUMP(); return; }
+    {
+      const float* mb = mbase + (KP == 2 ? qs : 0) * (34 * 64);
+      float mm = m;
+#pragma unroll
+      for (int j = 0; j < NMERGE; ++j) mm = fmaxf(mm, mb[j * (34 * 64)]);
+      const float a0 = __builtin_amdgcn_exp2f(m - mm);
+      m = mm;
+      l *= a0;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] *= a0;
+#pragma unroll
+      for (int j = 0; j < NMERGE; ++j) {
+        const float* mj = mb + j * (34 * 64);
+        const float aj = __builtin_amdgcn_exp2f(mj[0] - mm);
+        l += mj[64] * aj;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[dt][r] += mj[(2 + dt * 16 + r) * 64] * aj;
+      }
+    }
+    ATTN_STAMP(4);
+    if constexpr (XH) {
+      if (!attn_xhalf_merge(p, pair * 2 + qs, kx, lane, m, l, o)) { ATTN_DUMP(); return; }
+    }
+    ob = smem + ((NPARK * 8704 + 4095) & ~4095) + qs * 4096;          // behind the parked images (8704 B each)
   }
   // ---- normalise, park per wave in LDS ([query][d] fp16, 16-byte chunks swizzled by query&7), store whole rows
-  l += __shfl_xor(l, 32);
   const float inv = 1.0f / l;
-  __syncthreads();
-  char* ob = smem + wave * 4096;
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -682,19 +788,33 @@ __device__ __forceinline__ void attn_d64_v2_body(const AttnParams& p, const void
     const int q = q0 + row;
     if (q < p.Nq) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(Og + (size_t)q * p.ldo + piece * 8), "v"(v) : "memory");
   }
+  ATTN_STAMP(5);
+  ATTN_DUMP();
 }
 
-template <int NS>
+// variant 2: 128-query blocks, KP = 1
 // launch bound 2 waves/SIMD: with a 256-register budget hipcc keeps the MFMA accumulators in VGPRs; at the default
 // bound it parks S and O in AGPRs and pays ~240 v_accvgpr_read/write per 64-key tile around the softmax (measured: VALU
 // active 1370 cycles per wave-tile, 2.7x the MFMA time)
+template <int NS>
 __global__ __launch_bounds__(256, 2) void attn_d64_v2_kernel(const AttnParams p, const void* zeros) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [NS][K tile | V^T tile]
   const int nqb = (p.Nq + 127) / 128;
   const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   const int bh = bid / nqb, qb = bid - bh * nqb;
   const int b = bh / p.H;
-  attn_d64_v2_body<NS>(p, zeros, smem, b, bh - b * p.H, qb);
+  attn_d64_body<1, NS>(p, zeros, smem, b, bh - b * p.H, qb);
+}
+
+// variant 6 (key split): 64-query blocks, KP = 2
+template <int PRIO = 2, int KO = 0>
+__global__ __launch_bounds__(256, 2) void attn_d64_ks_kernel(const AttnParams p, const void* zeros) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // [3][K tile | V^T tile]
+  const int nqb = (p.Nq + 63) / 64;
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
+  const int bh = bid / nqb, qb = bid - bh * nqb;
+  const int b = bh / p.H;
+  attn_d64_body<2, 3, PRIO, KO>(p, zeros, smem, b, bh - b * p.H, qb);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -716,11 +836,7 @@ __global__ __launch_bounds__(256, 2) void attn_d64_hl_kernel(const AttnParams p,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 31, h = lane >> 5;
   const int nqb = (p.Nq + 127) / 128;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   const int bh = bid / nqb, qb = bid - bh * nqb;
   const int b = bh / p.H, hd = bh - b * p.H;
   const int q0 = qb * 128 + wave * 32;
@@ -817,39 +933,8 @@ __global__ __launch_bounds__(256, 2) void attn_d64_hl_kernel(const AttnParams p,
         sv[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(khi, ql[ks], sv[u], 0, 0, 0);
         sv[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(klo, qh[ks], sv[u], 0, 0, 0);
       }
-    if (t == nt - 1 && (p.Nk & 63) != 0) {                      // key tail (wave-uniform branch)
-      asm volatile("" ::: "memory");                            // a real branch: as selects this was 32 v_cndmask in EVERY tile
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (t * KV + u * 32 + 8 * (r >> 2) + 4 * h + (r & 3) >= p.Nk) sv[u][r] = -INFINITY;
-    }
-    // (four independent chains: as one chain the 16 v_max3 are each other's operands and the wave issues nothing else meanwhile)
-    float lm[4] = {sv[0][0], sv[0][8], sv[1][0], sv[1][8]};
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-      lm[0] = fmaxf(lm[0], sv[0][r]); lm[1] = fmaxf(lm[1], sv[0][8 + r]);
-      lm[2] = fmaxf(lm[2], sv[1][r]); lm[3] = fmaxf(lm[3], sv[1][8 + r]);
-    }
-    const float lmax = fmaxf(fmaxf(lm[0], lm[1]), fmaxf(lm[2], lm[3]));
-    if (t == 0 || __any(lmax > THR)) {                          // rare after the first tiles; wave-uniform
-      const float pm = fmaxf(lmax, __shfl_xor(lmax, 32));
-      const float delta = t == 0 ? pm : fmaxf(pm, 0.f);
-      const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
-      m = t == 0 ? delta : m + delta;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) minit[r] = -m;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sv[u][r] -= delta;
-    }
+    attn_key_tail(sv, t, nt, h, p.Nk);
+    attn_rescale<2>(t == 0, attn_row_max<2>(sv), THR, m, l, minit, o, sv);
     // ---- P = exp2(S - m) as (hi, lo) B fragments: k-step s4 = u*2 + hf holds registers 8*hf .. 8*hf+7 of key tile u
     half8 ph[4], pl[4];
 #pragma unroll
@@ -944,271 +1029,6 @@ __global__ __launch_bounds__(256, 2) void attn_d64_hl_kernel(const AttnParams p,
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// f16 variant "key split" (variant 6): variant 2 for grids that leave most SIMDs with ONE wave.
-//   Self-attention at 32^2 (Nq = Nk = 1024, 40 batch-heads) is 320 blocks of 128 queries = 1280 waves on 1024 SIMDs: a wave
-//   alone on its SIMD runs QK^T (MFMA), softmax (VALU, the longer part) and PV (MFMA) strictly in turn, and the SIMDs that
-//   carry two waves set the kernel time while the others idle half of it.  Here a block is 64 queries and its four waves are
-//   {query sub-tile} x {key half}: every wave takes 32 queries and the 32 keys of its parity out of each 64-key tile, with
-//   its own (m, l, O) -- half the work per wave, twice the waves (2.5 per SIMD: softmax of one under the MFMAs of another,
-//   worst SIMD 3 half-units instead of 2 whole ones).  The ring, the DMA pieces and the barriers are variant 2's.  At the end
-//   the odd-half waves park (m, l, O) in the dead ring and the even-half waves merge:  O = O0 2^(m0-m) + O1 2^(m1-m).
-//   Needs Nk % 64 == 0 (no key tail inside a half) -- the launcher sends everything else to variant 2.
-//   KP = 4 is the same body one step finer (the small blocks of attn_d64_mix_kernel): a block is ONE 32-query sub-tile and its
-//   four waves are key QUARTERS = {tile parity} x {key half}: a wave computes on every other 64-key tile only (it still stages
-//   its DMA pieces and takes the barrier of every tile), and wave 0 merges three partners.
-#ifdef SDXL_MEASURE
-// coarse s_memtime stamps of the key-split body (tools/attn_timeline.py): [workgroup][wave][8] = entry, Q loaded + first tiles issued,
-// k-loop done, merge done (key part 0 only), output stores issued; words 6 / 7 = s_memrealtime (100 MHz) at entry / exit
-__device__ unsigned* g_attn_tl = nullptr;
-void attention_set_timeline(void* buf) {
-  unsigned* b = reinterpret_cast<unsigned*>(buf);
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_tl), &b, sizeof(b)) != hipSuccess) throw std::runtime_error("attention: cannot set the timeline buffer");
-}
-#define ATTN_STAMP(i) do { atl[i] = (unsigned)__builtin_amdgcn_s_memtime(); } while (0)
-#define ATTN_DUMP() do { atl[7] = (unsigned)__builtin_amdgcn_s_memrealtime(); if (g_attn_tl && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 8; ++i_) g_attn_tl[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + i_] = atl[i_]; } } while (0)
-#else
-#define ATTN_STAMP(i) do { } while (0)
-#define ATTN_DUMP() do { } while (0)
-#endif
-// KO (measure builds, attn_variant 11 ..): knock-outs that time one resource of the k-loop alone (results are garbage): bit 0 no DMA inside the
-// loop, 1 no softmax arithmetic (scores converted as they are), 2 no per-tile barrier, 3 no MFMAs, 4 no LDS fragment reads
-// XH (level 2 of attn_d64_mix_kernel): the block takes key HALF kx of its 64 queries -- tiles [kx nt / 2, (kx + 1) nt / 2) -- and its partner block
-// the other half.  Each merging wave parks its (m, l, O) image in the workspace slot of (pair, half, query sub-tile), releases at agent scope and draws a
-// ticket; the wave that draws the second one acquires, merges   O = O_0 2^(m_0 - m) + O_1 2^(m_1 - m)   in the fixed order half 0, half 1 -- so the
-// result does not depend on which block arrived last -- and stores the output rows.  Nobody waits for anybody: no co-residency is assumed.
-template <int KP, int PRIO = 2, int KO = 0, bool XH = false>
-__device__ __forceinline__ void attn_d64_ks_body(const AttnParams& p, const void* zeros, char* smem, int b, int hd, int qb, int kx = 0, int pair = 0) {
-  static_assert(KP == 2 || KP == 4, "key parts per query sub-tile");
-  static_assert(!XH || KP == 2, "cross-workgroup key halves: 64-query blocks");
-#ifdef SDXL_MEASURE
-  unsigned atl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  atl[6] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
-  ATTN_STAMP(0);
-  constexpr int KV = 64, TILE = 64 * 128, NS = 3;
-  constexpr float THR = 8.0f;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int qs = KP == 2 ? (wave & 1) : 0, kp = KP == 2 ? (wave >> 1) : wave;      // query sub-tile, key part
-  const int kh = KP == 2 ? kp : (kp & 1), tp = kp >> 1;                             // key half inside a tile; (KP = 4) tile parity
-  const int fr = lane & 31, h = lane >> 5;
-  const int q0 = qb * (KP == 2 ? 64 : 32) + qs * 32;
-  (void)zeros;
-  const half_t* Qg = reinterpret_cast<const half_t*>(p.Q) + (size_t)b * p.Nq * p.ldq + hd * 64;
-  const half_t* Kg = reinterpret_cast<const half_t*>(p.K) + (size_t)b * p.Nk * p.ldk + hd * 64;
-  const half_t* Vg = reinterpret_cast<const half_t*>(p.Vt) + ((size_t)b * p.H + hd) * 64 * p.vt_ld;
-  const float sc = p.scale * 1.44269504088896340736f;
-
-  half8 qf[4];
-  {
-    const int q = q0 + fr;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      half8 v = half8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (q < p.Nq) v = *reinterpret_cast<const half8*>(Qg + (size_t)q * p.ldq + ks * 16 + h * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * sc);
-      qf[ks] = v;
-    }
-  }
-  // DMA geometry (as variant 2): wave w stages tile rows [16w, 16w+16) of K and of V^T, two 1-KiB pieces each
-  const int lrow = lane >> 3, slot = lane & 7;
-  unsigned kofs[2], vofs[2];                   // loop-invariant byte offsets of this lane's source chunks from the tile bases
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = wave * 16 + j * 8 + lrow;
-    kofs[j] = (unsigned)(row * p.ldk + (slot ^ ((row >> 1) & 7)) * 8) * 2u;
-    vofs[j] = (unsigned)(row * p.vt_ld + (slot ^ ((row ^ (row >> 3)) & 7)) * 8) * 2u;
-  }
-  auto stage = [&](int t, int buf) {
-    const int k0 = t * KV;
-    char* lk = smem + buf * 2 * TILE + wave * 2048;
-    char* lv = lk + TILE;
-    const char* kt = reinterpret_cast<const char*>(Kg + (size_t)k0 * p.ldk);
-    const char* vt = reinterpret_cast<const char*>(Vg + k0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      __builtin_amdgcn_global_load_lds((agptr_t)(kt + kofs[j]), (alptr_t)(lk + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((agptr_t)(vt + vofs[j]), (alptr_t)(lv + j * 1024), 16, 0, 0);
-    }
-  };
-  // fragment byte offsets inside a tile: K rows kh*32 + fr; V^T rows dt*32 + fr, keys of this wave's half
-  const int krow = kh * 32 + fr;
-  const int koff = krow * 128 + ((h ^ ((krow >> 1) & 7)) << 4);   // chunk of k-step ks: ^ (ks << 5)
-  const int voff[2] = {fr * 128, (32 + fr) * 128};
-  const int vsw[2] = {(fr ^ (fr >> 3)) & 7, ((32 + fr) ^ ((32 + fr) >> 3)) & 7};
-
-  f32x16 o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-  float m = 0.f, l = 0.f;
-  f32x16 minit;                                 // -m, the C operand of every score tile's first MFMA (see variant 2)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) minit[r] = 0.f;
-  const int nt = XH ? (p.Nk / KV) >> 1 : p.Nk / KV;      // tiles of this block
-  const int tb = XH ? kx * nt : 0;                       // its first tile
-#pragma unroll
-  for (int s0 = 0; s0 < NS - 1; ++s0)
-    if (s0 < nt) stage(tb + s0, s0);
-  ATTN_STAMP(1);
-  int cur = 0;
-  for (int t = 0; t < nt; ++t) {
-    if (t + NS - 2 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NS - 2)) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (!(KO & 4)) __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (t == 0) ATTN_STAMP(2);
-    if constexpr (!(KO & 1)) { if (t + NS - 1 < nt) stage(tb + t + NS - 1, cur == 0 ? NS - 1 : cur - 1); }
-    const char* kb = smem + cur * 2 * TILE;
-    const char* vb = kb + TILE;
-    cur = cur == NS - 1 ? 0 : cur + 1;
-    if (KP == 4 && (t & 1) != tp) continue;                    // the other parity's tile (wave-uniform)
-    const bool first = KP == 2 ? t == 0 : t == tp;             // this wave's first tile sets the reference
-    // ---- S^T - m for this wave's 32 keys
-    if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    f32x16 sv;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      half8 kf;
-      if constexpr (KO & 16) kf = qf[ks]; else kf = *reinterpret_cast<const half8*>(kb + (koff ^ (ks << 5)));
-      if constexpr (KO & 8) { if (ks == 0) sv = minit; asm volatile("" ::"v"(kf), "v"(qf[ks])); }
-      else sv = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? minit : sv, 0, 0, 0);
-    }
-    if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(2);
-    float lm[2] = {sv[0], sv[8]};                 // (two independent chains, see variant 2)
-#pragma unroll
-    for (int r = 1; r < 8; ++r) { lm[0] = fmaxf(lm[0], sv[r]); lm[1] = fmaxf(lm[1], sv[8 + r]); }
-    const float lmax = (KO & 2) ? 0.f : fmaxf(lm[0], lm[1]);
-    if (!(KO & 2) && (first || __any(lmax > THR))) {
-      const float pm = fmaxf(lmax, __shfl_xor(lmax, 32));
-      const float delta = first ? pm : fmaxf(pm, 0.f);
-      const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
-      m = first ? delta : m + delta;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) minit[r] = -m;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sv[r] -= delta;
-    }
-    // ---- P = exp2(S - m): k-step hf holds registers 8*hf .. 8*hf+7
-    half8 pf[2];
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      half8 hh;
-      float ls = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float pe = (KO & 2) ? sv[8 * hf + e] : __builtin_amdgcn_exp2f(sv[8 * hf + e]);
-        if constexpr (!(KO & 2)) ls += pe;
-        hh[e] = (half_t)pe;
-      }
-      l += ls;
-      pf[hf] = hh;
-    }
-    // ---- O^T += V^T P^T: k-step hf covers keys kh*32 + 16*hf + {4h..4h+3, 8+4h..8+4h+3}
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int base = kh * 32 + hf * 16;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int b1 = (base + 4 * h) * 2, b2 = b1 + 16;
-        i32x2 v1, v2;
-        if constexpr (KO & 16) { v1 = i32x2{b1, b2}; v2 = i32x2{b2, b1}; }
-        else {
-          v1 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b1 >> 4)) ^ vsw[dt]) << 4) + (b1 & 15));
-          v2 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b2 >> 4)) ^ vsw[dt]) << 4) + (b2 & 15));
-        }
-        const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
-        if constexpr (KO & 8) asm volatile("" ::"v"(vf), "v"(pf[hf]));
-        else o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, vf), pf[hf], o[dt], 0, 0, 0);
-      }
-    }
-  }
-  ATTN_STAMP(3);
-  l += __shfl_xor(l, 32);
-  if (KP == 4 && tp >= nt) m = -INFINITY;       // (a wave that saw no tile of its parity: weight 0 in the merge; the launcher asks Nk >= 128)
-  // ---- merge the key parts of each query sub-tile through the dead ring: parked images of [34][64 lanes] floats at smem + 0
-  //      (KP = 2: one per query sub-tile; KP = 4: the three partners of wave 0)
-  constexpr int NPARK = KP == 2 ? 2 : 3, NMERGE = KP == 2 ? 1 : 3;
-  __syncthreads();
-  float* mbase = reinterpret_cast<float*>(smem) + lane;
-  if (kp != 0) {
-    float* mb = mbase + (KP == 2 ? qs : kp - 1) * (34 * 64);
-    mb[0] = m; mb[64] = l;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mb[(2 + dt * 16 + r) * 64] = o[dt][r];
-  }
-  __syncthreads();
-  if (kp != 0) { ATTN_DUMP(); return; }
-  {
-    const float* mb = mbase + (KP == 2 ? qs : 0) * (34 * 64);
-    float mm = m;
-#pragma unroll
-    for (int j = 0; j < NMERGE; ++j) mm = fmaxf(mm, mb[j * (34 * 64)]);
-    const float a0 = __builtin_amdgcn_exp2f(m - mm);
-    m = mm;
-    l *= a0;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] *= a0;
-#pragma unroll
-    for (int j = 0; j < NMERGE; ++j) {
-      const float* mj = mb + j * (34 * 64);
-      const float aj = __builtin_amdgcn_exp2f(mj[0] - mm);
-      l += mj[64] * aj;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] += mj[(2 + dt * 16 + r) * 64] * aj;
-    }
-  }
-  ATTN_STAMP(4);
-  if constexpr (XH) {
-    if (!attn_xhalf_merge(p, pair * 2 + qs, kx, lane, m, l, o)) { ATTN_DUMP(); return; }
-  }
-  const float inv = 1.0f / l;
-  char* ob = smem + ((NPARK * 8704 + 4095) & ~4095) + qs * 4096;          // behind the parked images (8704 B each)
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      half4 hv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hv[r] = (half_t)(o[dt][g * 4 + r] * inv);
-      *reinterpret_cast<half4*>(ob + fr * 128 + (((dt * 4 + g) ^ (fr & 7)) << 4) + 8 * h) = hv;
-    }
-  half_t* Og = reinterpret_cast<half_t*>(p.O) + (size_t)b * p.Nq * p.ldo + hd * 64;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + (lane >> 3), piece = lane & 7;
-    const i32x4 v = *reinterpret_cast<const i32x4*>(ob + row * 128 + ((piece ^ (row & 7)) << 4));
-    const int q = q0 + row;
-    if (q < p.Nq) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(Og + (size_t)q * p.ldo + piece * 8), "v"(v) : "memory");
-  }
-  ATTN_STAMP(5);
-  ATTN_DUMP();
-}
-
-template <int PRIO = 2, int KO = 0>
-__global__ __launch_bounds__(256, 2) void attn_d64_ks_kernel(const AttnParams p, const void* zeros) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [3][K tile | V^T tile]
-  const int nqb = (p.Nq + 63) / 64;
-  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb, qb = bid - bh * nqb;
-  const int b = bh / p.H;
-  attn_d64_ks_body<2, PRIO, KO>(p, zeros, smem, b, bh - b * p.H, qb);
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // f16 "mixed block sizes" (variants 7 / 8): one launch of LARGE blocks followed by SMALL blocks of half their queries.
 //   Self-attention of the CFG pair is 640 equal blocks at both levels (64^2: 128-query blocks of variant 2; 32^2: 64-query
 //   blocks of the key-split variant) on 256 CUs with room for three blocks each: half the CUs carry three blocks, the other half
@@ -1242,217 +1062,16 @@ __global__ __launch_bounds__(256, 2) void attn_d64_mix_kernel(const AttnParams p
   if (large) {
     const int per = big_heads * nql;
     const int b = bid / per, r = bid - b * per, hd = r / nql, qb = r - hd * nql;
-    if constexpr (LEVEL == 0) attn_d64_v2_body<3, PRIO>(p, zeros, smem, b, hd, qb);
-    else attn_d64_ks_body<2, PRIO>(p, zeros, smem, b, hd, qb);
+    if constexpr (LEVEL == 0) attn_d64_body<1, 3, PRIO>(p, zeros, smem, b, hd, qb);
+    else attn_d64_body<2, 3, PRIO>(p, zeros, smem, b, hd, qb);
   } else {
     const int per = (p.H - big_heads) * nqs;
     const int b = bid / per, r = bid - b * per, hs = r / nqs, qb = r - hs * nqs;
-    if constexpr (LEVEL == 0) attn_d64_ks_body<2, PRIO>(p, zeros, smem, b, big_heads + hs, qb);
-    else if constexpr (LEVEL == 1) attn_d64_ks_body<4, PRIO>(p, zeros, smem, b, big_heads + hs, qb);
-    else attn_d64_ks_body<2, PRIO, 0, true>(p, zeros, smem, b, big_heads + hs, qb >> 1, qb & 1, (b * (p.H - big_heads) + hs) * (nqs >> 1) + (qb >> 1));
+    if constexpr (LEVEL == 0) attn_d64_body<2, 3, PRIO>(p, zeros, smem, b, big_heads + hs, qb);
+    else if constexpr (LEVEL == 1) attn_d64_body<4, 3, PRIO>(p, zeros, smem, b, big_heads + hs, qb);
+    else attn_d64_body<2, 3, PRIO, 0, true>(p, zeros, smem, b, big_heads + hs, qb >> 1, qb & 1, (b * (p.H - big_heads) + hs) * (nqs >> 1) + (qb >> 1));
   }
 }
-
-#ifdef SDXL_MEASURE   // lost its A/B (see the MEASURED note below): built only by `build.py --measure`
-// ---------------------------------------------------------------------------------------------------------
-// f16 variant 3: variant 2 with the two GEMMs of consecutive tiles software-pipelined inside each wave.
-//   iteration t:  [row max of S(t), rare rescale]  ->  { S(t+1) = K(t+1) Q^T  (8 MFMA)  ||  P = exp2(S(t)), row sums, fp16
-//   fragments (VALU) }  ->  O^T += V^T(t) P^T (8 MFMA).  The matrix pipe and the VALU are separate: in variant 2 a wave ran
-//   QK^T, softmax and PV strictly one after the other.  K runs one tile ahead of V, so K and V^T have separate 3-slot rings
-//   (48 KiB together, three blocks per CU): after the barrier of iteration t the wave stages {K(t+3), V(t+2)} -- both slots
-//   were last read in iteration t-1 -- and waits with vmcnt(4) for {K(t+1), V(t)} only (two iterations of prefetch).
-//   Tile indices past the end are clamped (a few redundant DMA pieces keep the counts uniform).
-//   MEASURED (profiles/r01_attention_bench.txt): slower than variant 2 -- the second score tile costs 49 VGPRs (189 vs 140),
-//   i.e. two blocks per CU instead of three (155 vs 136 us at 64^2); bounded to 168 VGPRs it spills inside the loop (181 us).
-//   Kept as forced variant 4 for the record; variant 2 is what runs.
-__global__ __launch_bounds__(256, 2) void attn_d64_v3_kernel(const AttnParams p, const void* zeros) {
-  constexpr int KV = 64, TILE = 64 * 128;
-  constexpr float THR = 8.0f;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [3] K tiles | [3] V^T tiles
-  char* sK = smem;
-  char* sV = smem + 3 * TILE;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 31, h = lane >> 5;
-  const int nqb = (p.Nq + 127) / 128;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int bh = bid / nqb, qb = bid - bh * nqb;
-  const int b = bh / p.H, hd = bh - b * p.H;
-  const int q0 = qb * 128 + wave * 32;
-  const half_t* Qg = reinterpret_cast<const half_t*>(p.Q) + (size_t)b * p.Nq * p.ldq + hd * 64;
-  const half_t* Kg = reinterpret_cast<const half_t*>(p.K) + (size_t)b * p.Nk * p.ldk + hd * 64;
-  const half_t* Vg = reinterpret_cast<const half_t*>(p.Vt) + ((size_t)b * p.H + hd) * 64 * p.vt_ld;
-  const float sc = p.scale * 1.44269504088896340736f;
-  const int nt = (p.Nk + KV - 1) / KV;
-
-  half8 qf[4];
-  {
-    const int q = q0 + fr;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      half8 v = half8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (q < p.Nq) v = *reinterpret_cast<const half8*>(Qg + (size_t)q * p.ldq + ks * 16 + h * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * sc);
-      qf[ks] = v;
-    }
-  }
-  const int lrow = lane >> 3, slot = lane & 7;
-  auto stage_k = [&](int t) {           // K tile t (clamped) -> K slot t % 3: rows [16w, 16w+16) of this wave, two pieces
-    const int tc = t < nt ? t : nt - 1;
-    char* lk = sK + (t % 3) * TILE + wave * 2048;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = wave * 16 + j * 8 + lrow;
-      const int key = tc * KV + row;
-      const half_t* ks = key < p.Nk ? Kg + (size_t)key * p.ldk + (slot ^ ((row >> 1) & 7)) * 8 : reinterpret_cast<const half_t*>(zeros);
-      __builtin_amdgcn_global_load_lds((agptr_t)ks, (alptr_t)(lk + j * 1024), 16, 0, 0);
-    }
-  };
-  auto stage_v = [&](int t) {
-    const int tc = t < nt ? t : nt - 1;
-    char* lv = sV + (t % 3) * TILE + wave * 2048;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = wave * 16 + j * 8 + lrow;
-      const half_t* vs = Vg + (size_t)row * p.vt_ld + tc * KV + (slot ^ ((row ^ (row >> 3)) & 7)) * 8;
-      __builtin_amdgcn_global_load_lds((agptr_t)vs, (alptr_t)(lv + j * 1024), 16, 0, 0);
-    }
-  };
-  int koff[2], voff[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int row = u * 32 + fr;
-    koff[u] = row * 128 + ((h ^ ((row >> 1) & 7)) << 4);
-    voff[u] = row * 128;
-  }
-  const int vsw[2] = {(fr ^ (fr >> 3)) & 7, ((32 + fr) ^ ((32 + fr) >> 3)) & 7};
-  auto qk = [&](const char* kb, float init, f32x16 (&sv)[2]) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sv[u][r] = init;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const half8 kf = *reinterpret_cast<const half8*>(kb + (koff[u] ^ (ks << 5)));
-        sv[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], sv[u], 0, 0, 0);
-      }
-  };
-
-  f32x16 o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-  float m = 0.f, l = 0.f;
-  // prologue: K(0) | {K(1), V(0)} | {K(2), V(1)}; wait for K(0) only
-  stage_k(0);
-  stage_k(1); stage_v(0);
-  stage_k(2); stage_v(1);
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  f32x16 sc_[2];                       // S(t) - m
-  qk(sK, 0.f, sc_);
-  for (int t = 0; t < nt; ++t) {
-    // group t = {K(t+1), V(t)} landed (group t+1 may stay in flight); everyone is done with K(t) and V(t-1)
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    stage_k(t + 3); stage_v(t + 2);
-    if (t == nt - 1 && (p.Nk & 63) != 0) {                      // key tail (wave-uniform)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (t * KV + u * 32 + 8 * (r >> 2) + 4 * h + (r & 3) >= p.Nk) sc_[u][r] = -INFINITY;
-    }
-    float lmax = sc_[0][0];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) lmax = fmaxf(lmax, sc_[0][r]);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) lmax = fmaxf(lmax, sc_[1][r]);
-    if (t == 0 || __any(lmax > THR)) {
-      const float pm = fmaxf(lmax, __shfl_xor(lmax, 32));
-      const float delta = t == 0 ? pm : fmaxf(pm, 0.f);
-      const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
-      m = t == 0 ? delta : m + delta;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc_[u][r] -= delta;
-    }
-    // ---- S(t+1) - m on the matrix pipe while the VALU turns S(t) into P
-    f32x16 sn[2];
-    qk(sK + ((t + 1) % 3) * TILE, -m, sn);                     // past the last tile: a clamped copy, never used
-    half8 pf[4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        half8 hh;
-        float ls = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(sc_[u][8 * hf + e]);
-          ls += pe;
-          hh[e] = (half_t)pe;
-        }
-        l += ls;
-        pf[u * 2 + hf] = hh;
-      }
-    // ---- O^T += V^T(t) P^T
-    const char* vb = sV + (t % 3) * TILE;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int base = (s4 >> 1) * 32 + (s4 & 1) * 16;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int b1 = (base + 4 * h) * 2, b2 = b1 + 16;
-        const i32x2 v1 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b1 >> 4)) ^ vsw[dt]) << 4) + (b1 & 15));
-        const i32x2 v2 = *reinterpret_cast<const i32x2*>(vb + voff[dt] + ((((b2 >> 4)) ^ vsw[dt]) << 4) + (b2 & 15));
-        const i32x4 vf = i32x4{v1[0], v1[1], v2[0], v2[1]};
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, vf), pf[s4], o[dt], 0, 0, 0);
-      }
-    }
-    sc_[0] = sn[0]; sc_[1] = sn[1];
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // clamped look-ahead pieces still in flight
-  l += __shfl_xor(l, 32);
-  const float inv = 1.0f / l;
-  __syncthreads();
-  char* ob = smem + wave * 4096;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      half4 hv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hv[r] = (half_t)(o[dt][g * 4 + r] * inv);
-      *reinterpret_cast<half4*>(ob + fr * 128 + (((dt * 4 + g) ^ (fr & 7)) << 4) + 8 * h) = hv;
-    }
-  half_t* Og = reinterpret_cast<half_t*>(p.O) + (size_t)b * p.Nq * p.ldo + hd * 64;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + (lane >> 3), piece = lane & 7;
-    const i32x4 v = *reinterpret_cast<const i32x4*>(ob + row * 128 + ((piece ^ (row & 7)) << 4));
-    const int q = q0 + row;
-    if (q < p.Nq) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(Og + (size_t)q * p.ldo + piece * 8), "v"(v) : "memory");
-  }
-}
-
-#endif  // SDXL_MEASURE
 
 // ---------------------------------------------------------------------------------------------------------
 // Flash attention for ONE wide head: head dim 512 (the VAE mid block, ConvSelfAttentionBlock::forward, reference
@@ -1611,27 +1230,11 @@ __global__ __launch_bounds__(256, 1) void attn_hd_kernel(const AttnParams p, con
   }
 }
 
-// per-DEVICE zero page (key-tail / padded rows of the DMA-staged kernels)
-constexpr int kMaxDev = kMaxDevices;
-static const void* g_attn_zeros[kMaxDev] = {};
-static int attn_device() {
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) throw std::runtime_error("attention: no current HIP device");
-  return d;
-}
-void attention_init() {
-  const int d = attn_device();
-  if (g_attn_zeros[d]) return;
-  void* z = nullptr;
-  if (hipMalloc(&z, 4096) != hipSuccess || hipMemset(z, 0, 4096) != hipSuccess)
-    throw std::runtime_error("attention: cannot allocate the zero page");
-  g_attn_zeros[d] = z;
-}
-
+// Key-tail / padded rows of the DMA-staged kernels read the per-device zero page of the GEMMs (igemm_zero_page, igemm_glds.hip).
 // snapshot the knobs, select (attn_select, select.cpp), launch the chosen instantiation
 void launch_attention_d64(const AttnParams& p, hipStream_t s) {
-  const int dev = attn_device();
-  const void* zero = g_attn_zeros[dev];
+  const int dev = igemm_current_device();
+  const void* zero = igemm_zero_page();
   SelectKnobs k = select_knobs_snapshot();
   k.zero_page = zero != nullptr;
   const AttnChoice c = attn_select(p, k);
@@ -1656,9 +1259,6 @@ void launch_attention_d64(const AttnParams& p, hipStream_t s) {
       }
 #endif
       throw std::logic_error("attention: knock-out variants exist in measure builds only");
-#ifdef SDXL_MEASURE
-    case AT_V3: hipLaunchKernelGGL(attn_d64_v3_kernel, grid, block, c.lds, s, p, zero); return;
-#endif
     case AT_V2:
 #ifdef SDXL_MEASURE
       if (c.ns == 4) {
@@ -1683,8 +1283,8 @@ void launch_attention_d64(const AttnParams& p, hipStream_t s) {
 // split-operand attention (attn_d64_hl_kernel): Q / O fp32, K / V^T in HL16.  Returns false when the shape / alignment needs the
 // fp32 kernel (masked attention, unaligned rows).
 bool launch_attention_d64_hl(const AttnParams& p, hipStream_t s) {
-  const int dev = attn_device();
-  const void* zeros = g_attn_zeros[dev];
+  const int dev = igemm_current_device();
+  const void* zeros = igemm_zero_page();
   if (!zeros || p.mask) return false;
   if (p.o_dt != DT_F32 && (p.o_dt != DT_HL || (p.ldo & 15) != 0) && (p.o_dt != DT_F16 || (p.ldo & 7) != 0)) return false;
   if (p.q_dt != DT_F32 && (p.q_dt != DT_HL || (p.ldq & 15) != 0)) return false;
@@ -1698,8 +1298,8 @@ bool launch_attention_d64_hl(const AttnParams& p, hipStream_t s) {
 
 // one wide head (d = 512, f16, no mask): see attn_hd_kernel.  Returns false when the shape / alignment needs the unfused path.
 bool launch_attention_hd512(const AttnParams& p, hipStream_t s) {
-  const int dev = attn_device();
-  const void* zero = g_attn_zeros[dev];
+  const int dev = igemm_current_device();
+  const void* zero = igemm_zero_page();
   if (!zero || p.dt != DT_F16 || p.mask) return false;
   const bool aligned = ((p.ldq | p.ldk | p.vt_ld | p.ldo) & 7) == 0 &&
                        ((reinterpret_cast<uintptr_t>(p.Q) | reinterpret_cast<uintptr_t>(p.K) |

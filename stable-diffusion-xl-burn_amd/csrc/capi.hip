@@ -130,7 +130,6 @@ int sdxl_ctx_create(int device_id, sdxl_ctx** out) {
   c->device = device_id;
   SDXL_HIP(hipStreamCreate(&c->stream));
   igemm_glds_init();
-  attention_init();
   *out = c;
   API_END
 }

@@ -1007,7 +1007,7 @@ __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, co
 #endif
 }
 
-// Per-DEVICE state: the zero page the DMA reads halo / tail rows from lives on the device that launches (the dynamic-LDS
+// Per-DEVICE state: the zero page the DMA reads halo / tail rows from (GEMM and attention kernels alike) lives on the device that launches (the dynamic-LDS
 // attribute, up to 147 KiB, is per (kernel, device) too: set_max_dynamic_lds).  A second sdxl_ctx on another GPU of the same
 // process gets its own.
 static const void* g_zero_pages[kMaxDevices] = {};

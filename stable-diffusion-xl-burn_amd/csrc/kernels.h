@@ -163,7 +163,7 @@ template <auto Kernel> inline void set_max_dynamic_lds(size_t lds, int dev) {
 // per-device state owned by igemm_glds.hip
 const void* igemm_zero_page();          // null until igemm_glds_init() ran on the current device
 int igemm_current_device();
-void igemm_glds_init();          // allocates the zero page the DMA fast path reads halo pixels from (call once per process)
+void igemm_glds_init();          // allocates the zero page the DMA fast paths read from: halo pixels of the convolutions, key-tail rows of the attention kernels (call once per process)
 
 // per-entry scale workspace of launch_f32_to_hl_scaled (declared further down)
 constexpr int kHlAbsBlocks = 128;
@@ -231,7 +231,7 @@ struct AttnParams {
 };
 size_t attention_xsplit_ws_bytes(int B, int H, int Nq);
 size_t attention_xsplit_counters(int B, int H, int Nq);
-enum AttnKernel : int { AT_GENERIC = 0, AT_F16 = 1, AT_V2 = 2, AT_KS = 3, AT_MIX = 4, AT_V3 = 5 };
+enum AttnKernel : int { AT_GENERIC = 0, AT_F16 = 1, AT_V2 = 2, AT_KS = 3, AT_MIX = 4 };   // (5 stays unused: it named the software-pipelined kernel in recorded choices)
 // what launch_attention_d64 launches
 struct AttnChoice {
   int kernel;               // AttnKernel: generic (elem DT_F16 / DT_F32), DMA-staged 16x16x32, 32x32x16 deferred-max (ns ring slots), key-split, mixed block sizes
@@ -249,7 +249,6 @@ bool launch_attention_d64_hl(const AttnParams& p, hipStream_t s);
 // hold the heads at columns h*512, Vt is [B][H*512][vt_ld] with zero columns up to a multiple of 32 keys.  f16, no mask;
 // returns false when the shape / alignment needs the unfused path.  p.scale = d^-1/2.
 bool launch_attention_hd512(const AttnParams& p, hipStream_t s);
-void attention_init();                 // zero page for the DMA-staged f16 kernel (once per process)
 #ifdef SDXL_MEASURE
 void attention_set_timeline(void* device_buf);   // [workgroups][4 waves][8] coarse stamps of the key-split attention body
 #endif

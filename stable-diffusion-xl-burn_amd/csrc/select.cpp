@@ -539,7 +539,6 @@ AttnChoice attn_select(const AttnParams& p, const SelectKnobs& k) {
     }
     c.grid_x = qb128 * p.B * p.H;
 #ifdef SDXL_MEASURE
-    if (v == 4) { c.kernel = AT_V3; c.lds = 6 * 64 * 128; return c; }
     if (ks_ok) for (const AttnKnockout& o : kAttnKnockouts) if (o.number == v) { c.kernel = AT_KS; c.ko = o.ko; c.grid_x = qb64 * p.B * p.H; return c; }
     if (v == 3 && p.Nk > 128) { c.kernel = AT_V2; c.ns = 4; c.lds = 4 * 2 * 64 * 128; return c; }
 #endif

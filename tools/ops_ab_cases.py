@@ -1,4 +1,4 @@
-"""Record-only cases for tools/ops_ab_record.py that the op tests do not call on every path: null bias in f16 and F32_SPLIT, GEGLU in both, the four fused values"""
+"""Record-only cases for tools/ops_ab_record.py that the op tests do not call on every path: null bias in f16 and F32_SPLIT, GEGLU in both, the four fused values, the generic f16 attention kernel"""
 import os
 import sys
 
@@ -61,6 +61,18 @@ def test_ln_query_fused_values(pkg, ctx, fused, B, Nq, Nk, C):
         pkg.ln_query_cross_attention(ctx, x.cuda(), g.cuda(), bt.cuda(), wq.cuda(), k.cuda(), v.cuda(), 1e-5, fused)
     except Exception:      # recorded by the plugin: both libraries must refuse alike
         pass
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,Nq,Nk,heads", [(2, 300, 77, 10), (1, 320, 320, 1)])
+def test_attention_generic_f16(pkg, ctx, B, Nq, Nk, heads):
+    # attn_variant -1 in f16: attn_d64_kernel<_Float16>, which no op test forces
+    q, k, v = arb(19, B, Nq, 64 * heads), arb(20, B, Nk, 64 * heads), arb(21, B, Nk, 64 * heads)
+    pkg.debug_set("attn_variant", -1)
+    try:
+        pkg.qkv_attention(ctx, q.cuda(), k.cuda(), v.cuda(), None, heads, 1)
+    finally:
+        pkg.debug_set("attn_variant", 0)
 
 
 @pytest.mark.gpu

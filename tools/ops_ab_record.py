@@ -14,6 +14,8 @@ import numpy as np
 
 OPS = ["qkv_attention", "attn_decoder_mask", "group_norm", "layer_norm", "conv2d", "linear", "layer_norm_linear",
        "ln_query_cross_attention", "transformer_projection", "conv2d_group_norm"]
+if os.environ.get("RECORD_OPS"):      # a comma-separated subset, e.g. the attention entries only
+    OPS = [n for n in OPS if n in os.environ["RECORD_OPS"].split(",")]
 OUT = os.environ["RECORD_OPS_DIR"]
 _calls = []
 _n = [0]
