@@ -392,6 +392,9 @@ int sdxl_bench_attention(sdxl_ctx* ctx, void* stream, int B, int H, int Nq, int 
  * "hl_demote": bit set of GEMM classes (csrc/engine.h DemoteClass) that a SDXL_DTYPE_F32_SPLIT UNet runs on operands with zero lo halves --
  *   the f16 engine's operand rounding class by class on the split engine's kernels: the precision-frontier instrument
  *   (tools/precision_frontier.py, profiles/r05_precision_frontier.json); takes effect at the next set_context / trajectory; default 0;
+ * "upsample_fold": 0 = the nearest-2x upsample convolutions (f16 UNet, split-operand VAE decoder, sdxl_conv2d_upsample_folded) keep the 3x3 weights and the
+ *   index >> 1 gather instead of the four-phase launch on folded weights (A/B and tests; results differ by the fold's weight rounding; read per launch, a
+ *   captured UNet plan keeps what it recorded; default 1);
  * "igemm_unrolled": 0 = auto selection launches the rolled k-loop kernels (A/B; default 1);
  * "split_cfg": 1 = a batch-2 UNet::forward runs its two entries as two concurrent batch-1 chains (bit-identical results);
  * "split_offset": GEMM launches of the first chain before the second is released; "no_cfg": base model without the
@@ -400,6 +403,10 @@ int sdxl_debug_set(const char* key, int value);
 /* host logic of the weight-warming schedule on a synthetic launch sequence (no device needed; tests): bytes[j] / host[j] = what entry j reads and
  * whether its kernel can carry warming workgroups; warmed_by[j] receives the index of the entry that warms j, -1 if nobody does */
 int sdxl_debug_warm_schedule(int n, const unsigned* bytes, const unsigned char* host, int* warmed_by);
+/* the weight fold of the upsample convolutions on HOST arrays (no device needed; tests): weight [cout][cin][3][3] -> out [4][cout][cin][2][2], phase
+ * 2a + b of output pixel (2i + a, 2j + b), W_ab[dy][dx] = the taps of row set R_a(dy) x column set R_b(dx) summed in fp32, ky major, kx minor
+ * (R_0(0) = {0}, R_0(1) = {1, 2}, R_1(0) = {0, 1}, R_1(1) = {2}) */
+int sdxl_debug_upsample_fold(const float* weight, int cout, int cin, float* out);
 /* the kernel selection on a described launch (no device needed, no process-wide state read or written; tests): which kernel instantiation, grid and LDS
  * bytes a GEMM / a head-dim-64 attention call with these integer fields, optional operands and knob values would launch.  Optional operands are named by
  * the SDXL_SEL_* bits of `present`; `misaligned` != 0 puts every operand 8 bytes off a 16-byte boundary.  A status != 0 (text in sdxl_last_error())
@@ -439,6 +446,13 @@ int sdxl_layer_norm(sdxl_ctx* ctx, void* stream, const float* x, const float* ga
 /* burn Conv2d on NCHW fp32: weight [Cout,Cin,k,k], bias [Cout]; upsample!=0 applies nearest-2x first (unet/mod.rs:744-750) */
 int sdxl_conv2d(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int B, int Cin,
                 int H, int W, int Cout, int ksize, int stride, int pad, int upsample, int dtype, float* out);
+/* nearest-2x upsample + Conv2d 3x3 pad 1 (Upsample::forward, unet/mod.rs:742-752; the decoder's upsampler) as the f16 UNet and the split-operand VAE
+ * decoder run it: the upsample folded into the weights -- four 2x2-tap phase matrices, summed in fp32 and then packed (one more weight rounding in the
+ * f16 engine than sdxl_conv2d(..., upsample = 1), which keeps the 3x3 weights) -- and one phase-ordered launch.  dtype: SDXL_DTYPE_F16 (Cin % 64 == 0) or
+ * SDXL_DTYPE_F32_SPLIT (Cin % 32 == 0).  Shapes without such a launch (H * W % 128 != 0) and sdxl_debug_set("upsample_fold", 0) take the gather form on
+ * the 3x3 weights; *folded (may be NULL) reports which ran.  x [B,Cin,H,W], weight [Cout,Cin,3,3], out [B,Cout,2H,2W], fp32 device tensors. */
+int sdxl_conv2d_upsample_folded(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int B, int Cin, int H, int W,
+                                int Cout, int dtype, int* folded, float* out);
 /* burn nn::Linear: y = x[M,K] @ W[K,N] + b; geglu!=0 returns x_half * gelu_erf(gate_half) (unet/mod.rs:942-956) */
 int sdxl_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int M, int K, int N,
                 int geglu, int dtype, float* out);

@@ -93,7 +93,7 @@ ABI_SYMBOLS = [
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
-    "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
+    "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
     "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
@@ -1072,6 +1072,24 @@ def conv2d(ctx: Context, x, weight, bias, stride: int = 1, padding: int = 0, ups
     _check(lib().sdxl_conv2d(ctx.h, _stream(), px, pw, pb, B, Cin, H, W, Cout, k, stride, padding, int(upsample), dtype,
                             ctypes.c_void_p(out.data_ptr())))
     return out
+
+
+def conv2d_upsample_folded(ctx: Context, x, weight, bias, dtype: int = DTYPE_F16):
+    """nearest-2x upsample + Conv2d 3x3 pad 1 on the folded phase weights, as the f16 UNet / the split-operand VAE decoder run it; returns
+    (out [B,Cout,2H,2W], folded): folded = False where the shape (or debug_set("upsample_fold", 0)) keeps the gather form"""
+    torch = _torch()
+    x, px = _dev(x)
+    weight, pw = _dev(weight)
+    pb = None
+    if bias is not None:
+        bias, pb = _dev(bias)
+    B, Cin, H, W = x.shape
+    Cout = int(weight.shape[0])
+    out = torch.empty((B, Cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
+    took = ctypes.c_int(0)
+    _check(lib().sdxl_conv2d_upsample_folded(ctx.h, _stream(), px, pw, pb, int(B), int(Cin), int(H), int(W), Cout, dtype, ctypes.byref(took),
+                                            ctypes.c_void_p(out.data_ptr())))
+    return out, bool(took.value)
 
 
 def linear(ctx: Context, x, weight, bias, geglu: bool = False, dtype: int = DTYPE_F16):

@@ -50,7 +50,7 @@ def _flags() -> list:
 
 def _deps_hash(src: str) -> str:
     h = hashlib.sha256()
-    for f in [src] + [os.path.join(CSRC, x) for x in ("kernels.h", "engine.h", "igemm_common.h", "capi_internal.h", "select_debug.h")] + \
+    for f in [src] + [os.path.join(CSRC, x) for x in ("kernels.h", "engine.h", "igemm_common.h", "capi_internal.h", "select_debug.h", "upsample_fold.h")] + \
             [os.path.join(HERE, "..", "include", "sdxl_mi355.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())

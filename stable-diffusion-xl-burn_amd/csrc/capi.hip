@@ -3,6 +3,7 @@
 // the single-op and micro-benchmark entries are in capi_ops.hip.
 #include "capi_internal.h"
 #include "select_debug.h"
+#include "upsample_fold.h"
 #include <algorithm>
 #include <cstring>
 
@@ -144,6 +145,7 @@ int sdxl_debug_set(const char* key, int value) {
   else if (std::strcmp(key, "hl_demote") == 0) unet_set_hl_demote(value);
   else if (std::strcmp(key, "mix_classes") == 0) unet_set_mix_classes(value);
   else if (std::strcmp(key, "wreg_xcd2d") == 0) igemm_set_wreg_xcd2d(value);
+  else if (std::strcmp(key, "upsample_fold") == 0) set_upsample_fold(value);
 #ifdef SDXL_MEASURE
   else if (std::strcmp(key, "xa_vec64") == 0) igemm_set_xa_vec64(value);
   else if (std::strcmp(key, "no_cfg") == 0) g_debug_no_cfg = value != 0;
@@ -163,6 +165,13 @@ int sdxl_debug_warm_schedule(int n, const unsigned* bytes, const unsigned char* 
   for (int i = 0; i < n; ++i)
     for (int r = 0; r < 3; ++r)
       if (ws.seq[i].warm[r]) warmed_by[(int)(reinterpret_cast<uintptr_t>(ws.seq[i].warm[r]) >> 12) - 1] = i;
+  API_END
+}
+// the weight fold of the upsample convolutions (upsample_fold.h) on host arrays -- no device needed: the arithmetic the model builders run per element
+int sdxl_debug_upsample_fold(const float* weight, int cout, int cin, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(weight && out && cout > 0 && cin > 0, "bad argument");
+  fold_upsample_weights(weight, out, (size_t)cout, (size_t)cin);
   API_END
 }
 // the kernel selection (select.cpp) on a described launch -- no device needed, the knobs come with the call

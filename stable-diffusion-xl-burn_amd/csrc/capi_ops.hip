@@ -364,6 +364,43 @@ int sdxl_conv2d(sdxl_ctx* ctx, void* stream, const float* x, const float* weight
   SDXL_HIP(hipStreamSynchronize(s));
   API_END
 }
+// nearest-2x upsample + 3x3 convolution (pad 1) the way the f16 UNet and the split-operand VAE decoder run it: the weights folded into four 2x2-tap
+// phase matrices at pack time (WeightBuilder::conv fold_up), one phase-ordered launch where the shape has one (*folded reports it), else the gather form
+int sdxl_conv2d_upsample_folded(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int B, int Cin, int H, int W,
+                                int Cout, int dtype, int* folded, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(ctx && x && weight && out, "null argument");
+  SDXL_REQUIRE(dtype == SDXL_DTYPE_F16 || dtype == SDXL_DTYPE_F32_SPLIT, "the folded upsample convolution exists in the f16 and the split-operand engines");
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  const int cdt = dtype == SDXL_DTYPE_F16 ? DT_F16 : DT_HL, sdt = cdt;
+  SDXL_REQUIRE(Cin % (cdt == DT_HL ? 32 : 64) == 0, "the folded upsample convolution needs whole k-tiles per tap (Cin % 64, split-operand: Cin % 32)");
+  Operands ops;
+  add_conv(ops, "conv", Cout, Cin, 3, weight, bias);
+  Packed pk(ops, cdt, s);
+  const Lin l = pk.wb.conv("conv", true);
+  Tmp tmp;
+  const size_t rows = (size_t)B * H * W;
+  void* xi = tmp.get(rows * Cin * dt_size(sdt));
+  float* yo = (float*)tmp.get(4 * rows * Cout * sizeof(float));
+  Act xa(xi, Cin, sdt);
+  if (cdt == DT_HL) {      // (as sdxl_conv2d: one range factor per batch entry)
+    float* x32 = (float*)tmp.get(rows * Cin * sizeof(float));
+    float* sc = (float*)tmp.get(hl_scale_floats(B) * sizeof(float));
+    launch_nchw_to_nhwc(x, Cin * H * W, x32, DT_F32, B, Cin, H * W, Cin, 1.0f, s);
+    launch_f32_to_hl_scaled(x32, Cin, xi, Cin, rows, Cin, sc, s, B);
+    xa.a_scale = hl_scale_inv(sc, B); xa.a_scale_n = B;
+  } else launch_nchw_to_nhwc(x, Cin * H * W, xi, sdt, B, Cin, H * W, Cin, 1.0f, s);
+  Exec ex; ex.s = s; ex.cdt = cdt; ex.sdt = sdt;
+  give_splitk_ws(ex, tmp, B, 4 * H * W, Cout, s);
+  Epi e; e.fold = true;
+  bool took = false; e.fold_done = &took;
+  run_conv(ex, l, xa, Cin, ConvGeom{B, H, W, 2 * H, 2 * W, 3, 1, 1, 1}, Act(yo, Cout, DT_F32), e);
+  if (folded) *folded = took ? 1 : 0;
+  launch_nhwc_to_nchw(yo, DT_F32, Cout, out, B, Cout, 4 * H * W, 1.0f, s);
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
 int sdxl_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int M, int K, int N,
                 int geglu, int dtype, float* out) {
   API_BEGIN

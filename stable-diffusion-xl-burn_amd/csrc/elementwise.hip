@@ -2,6 +2,7 @@
 // attention path), sinusoidal timestep embedding, layout conversion at the NCHW API boundary, the fused
 // CFG-combine + DDIM update, image <-> activation conversion, synthetic weight fill and weight packing.
 #include "kernels.h"
+#include "upsample_fold.h"
 #include <algorithm>
 #include <stdexcept>
 
@@ -917,6 +918,15 @@ __global__ void pack_conv_kernel(const float* src, void* dst, int dt, int Cout, 
 void launch_pack_conv(const float* src, void* dst, int dt, int Cout, int Cin, int ks, int Kpad, int Npad, hipStream_t s, float wscale) {
   const size_t total = (size_t)Npad * Kpad;
   hipLaunchKernelGGL(pack_conv_kernel, dim3((total + 255) / 256), dim3(256), 0, s, src, dst, dt, Cout, Cin, ks, Kpad, Npad, wscale);
+}
+// canonical 3x3 conv [Cout][Cin][3][3] -> the four 2x2 phase convolutions of "nearest-2x upsample, then that conv" [4][Cout][Cin][2][2] (upsample_fold.h)
+__global__ void fold_upsample_kernel(const float* src, float* dst, size_t pairs) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < 16 * pairs) dst[e] = fold_element(src, pairs, e);
+}
+void launch_fold_upsample(const float* src, float* dst, int Cout, int Cin, hipStream_t s) {
+  const size_t pairs = (size_t)Cout * Cin;
+  hipLaunchKernelGGL(fold_upsample_kernel, dim3((unsigned)((16 * pairs + 255) / 256)), dim3(256), 0, s, src, dst, pairs);
 }
 __global__ void pack_bias_kernel(const float* src, float* dst, int N, int Npad, int geglu, int n_offset) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

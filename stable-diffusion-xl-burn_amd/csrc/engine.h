@@ -151,6 +151,10 @@ struct Lin {        // packed dense weight: [Npad][Kpad] compute dtype + fp32 bi
   int dt = -1;                     // dtype the weight was packed in when it differs from the model's compute dtype (-1: the model's):
                                    // a DT_HL model packs the layers its pipeline cannot take (Cin % 32 != 0) as fp32
   const float* acc_scale = nullptr;   // DT_HL packing: device scalar (weight arena) 1 / (power-of-two factor the packed weights carry)
+  // 3x3 convolutions behind a nearest-2x upsample (WeightBuilder::conv fold_up): the four 2x2-tap phase matrices of upsample + conv (upsample_fold.h),
+  // [4][Npad][4 cin] packed like w, with their own accumulator scale (the sums of up to four taps have their own range).  run_conv takes them where the
+  // caller allows it (Epi::fold) and the launch fits the phase form (IgemmParams::ph_rows); null: the layer has the gather form only
+  const void* w_fold = nullptr; const float* fold_acc_scale = nullptr;
 };
 // eps lives in the weight arena (device scalar, read by the kernels): replicas that receive the arena by broadcast need no
 // host-side copy, and a checkpoint's per-norm eps (groupnorm/load.rs:19, layernorm/load.rs:17) travels with the weights
@@ -170,7 +174,7 @@ struct WeightBuilder {
   // wfrag: the model keeps fragment-order images of its plain f16 linear / 1x1 weights (attach_wfrag) -- only the UNet's layers can be
   // routed to the weights-in-registers kernel, so the CLIP towers and the VAE leave it off (half the arena / broadcast bytes for those layers)
   bool wfrag = true;
-  static size_t arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag = true);
+  static size_t arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag = true, bool fold_up = false);   // fold_up: the model builds its upsample convolutions with conv(name, true)
   const ParamSpec& spec(const std::string& name, size_t* idx = nullptr) const;
   bool has(const std::string& name) const { return index.count(name) != 0; }
   const float* fetch(const std::string& name);            // canonical fp32 tensor in tmp
@@ -181,6 +185,7 @@ struct WeightBuilder {
   //     // dup: (w | w / kHiLoScale) for an A operand of (hi | lo * kHiLoScale) ACTIVATION halves
       // f16 GEMM on (hi | lo * kHiLoScale) weight halves along a doubled K: un-rounded weights (MIX_GEGLU_HILO)
   float hl_scale(Lin& l, const std::vector<std::string>& weight_names);     // DT_HL packing: power-of-two factor, inverse into the arena
+  float hl_scale_of(const float* dev, size_t n, const float*& acc_scale);   // the same for one device tensor that is not a parameter (folded weights)
   // the same with the preceding LayerNorm(gamma, beta) folded into weight / bias / column sums
   // xattn_query: the attn2 query projection -- also packed in fragment order, for the weights-in-registers form of the fused cross-attention
   Lin linear_ln(const std::string& name, bool geglu, const std::string& norm, bool xattn_query = false);
@@ -193,7 +198,10 @@ struct WeightBuilder {
   // AND of "every value of these tensors is exactly one f16" (device flag read back): what SDXL_DTYPE_F32_SPLIT_MIX_F16W asks of the classes it moves to f16
   bool all_f16_exact(const std::vector<std::string>& names);
   float* tmp2 = nullptr; size_t tmp2_numel = 0;   // scratch for folded biases (device)
-  Lin conv(const std::string& name);                                        // name.weight [Cout,Cin,k,k] + bias
+  // fold_up: a 3x3 conv that runs behind a nearest-2x upsample also gets its folded phase matrices (Lin::w_fold) -- f16 and split-operand packings
+  // with whole k-tiles per tap; folded from the fetched tensor, i.e. after any adapter merge; allocated on empty replicas too (identical arena layout)
+  Lin conv(const std::string& name, bool fold_up = false);                  // name.weight [Cout,Cin,k,k] + bias
+  static bool folds_upsample(const ParamSpec& p, int dt);                   // the rule of fold_up for an upsample.conv / upsampler parameter (arena_bound)
   void attach_wfrag(Lin& l, bool fill, bool folded = false);    // second image of a plain f16 linear / 1x1 weight in fragment order (arena; no-op for other layers)
   NormW norm(const std::string& name);
 };
@@ -306,12 +314,15 @@ struct Epi {
   // room for the GroupNorm statistics of the output ([M/256][N] float pairs); run_conv reports whether the kernel it picked
   // filled it (igemm_gn_part_ok), the caller then tags the output Act
   float* gn_part = nullptr;
+  bool* fold_done = nullptr;   // (optional) run_conv reports whether the launch took the folded form
+  bool fold = false; // an upsample convolution (ConvGeom::up) may run as the four folded phase convolutions (Lin::w_fold) where the launch fits
   int cls = 0;       // DemoteClass bit of this GEMM (UNet call sites): label of the launch in the per-launch profile dump, nothing else
   // f16 shadow of an fp32 output for the GEMM behind the next LayerNorm (IgemmParams::shadow): asked for by the caller, written only when the kernel the
   // selection picks can (weights-in-registers kernel) -- *shadow_done tells; stat_out then holds the fp32 rows' statistics
   void* shadow = nullptr; int shadow_ld = 0; const float* shadow_gamma = nullptr; bool* shadow_done = nullptr; float shadow_lo_scale = 0.f;
 };
 bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, const Act& out, const Epi& e = Epi());   // true: e.gn_part was filled
+void set_upsample_fold(int v);     // A/B knob (sdxl_debug_set "upsample_fold", default 1): 0 = every upsample convolution keeps the gather form (read per launch; a captured plan keeps what it recorded)
 bool run_linear(Exec& ex, const Lin& w, const Act& a, int M, const Act& out, const Epi& e = Epi());
 // have_max: a hl_scale_floats(nb) buffer whose max|x| partials a GroupNorm statistics pass over x already wrote (run_groupnorm absmax_out): no absmax pass
 Act hl_operand(Exec& ex, const Lin& w, const Act& x, size_t rows, int C, int nb = 1, float* have_max = nullptr);    // HL16 copy of an fp32 stream tensor (nb batch entries of rows / nb rows, one power-of-two scale each) for a split-operand GEMM (else x)
@@ -500,7 +511,9 @@ class Vae {
   bool has_dec_ = false, has_enc_ = false;
   // decoder
   Lin post_quant_, d_conv_in_, d_conv_out_; NormW d_norm_out_; VaeMidW d_mid_;
-  struct DecBlk { VaeResW r[3]; Lin up; bool has_up = false; };
+  // up_fold: the upsampler runs on its folded phase matrices (Lin::w_fold) -- the general three-MFMA form only: a layer whose parameters are all single f16
+  // values keeps the 3x3 weights and their two-MFMA form.  -1 = not read yet (the flag lives in the arena: replicas know it after the broadcast)
+  struct DecBlk { VaeResW r[3]; Lin up; bool has_up = false; int up_fold = -1; };
   std::vector<DecBlk> d_blocks_;
   // encoder
   Lin quant_, e_conv_in_, e_conv_out_; NormW e_norm_out_; VaeMidW e_mid_;

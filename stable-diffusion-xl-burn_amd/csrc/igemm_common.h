@@ -185,6 +185,15 @@ struct LnCoop {
   }
 };
 
+// Row of C that GEMM row m is stored to.  Phase form of an upsample convolution (IgemmParams::ph_rows): row (phase 2a + b, entry, i, j) of the
+// phase-ordered GEMM is pixel (2i + a, 2j + b) of the entry's 2 Hin x 2 Win output; every other launch stores row m.  m < M.
+__device__ __forceinline__ size_t igemm_out_row(const IgemmParams& p, int m) {
+  if (p.ph_rows == 0) return (size_t)m;
+  const int ph = m / p.ph_rows, r = m - ph * p.ph_rows;
+  const int hw = p.Hin * p.Win, e = r / hw, q = r - e * hw, i = q / p.Win, j = q - i * p.Win;
+  return ((size_t)e * (2 * p.Hin) + (2 * i + (ph >> 1))) * (size_t)(2 * p.Win) + (size_t)(2 * j + (ph & 1));
+}
+
 template <int TM, int TN>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, const f32x16 (&acc)[TM][TN], int mw, int nw, int fr, int fh,
                                                const float (&lnA)[TM], const float (&lnC)[TM]) {
@@ -195,6 +204,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, const f32x1
     const int m = mw + i * 32 + fr;
     if (m >= p.M) continue;
     const int bidx = m / p.rpb;
+    const size_t mo = igemm_out_row(p, m);
     const int key = m - bidx * p.rpb;
     const float lna = lnA[i], lnc = lnC[i];
 #pragma unroll
@@ -254,16 +264,16 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, const f32x1
           }
           if (vec && p.c_dt == DT_F16 && (p.ldc & 3) == 0) {
             half4 h; h[0] = (half_t)v[0]; h[1] = (half_t)v[1]; h[2] = (half_t)v[2]; h[3] = (half_t)v[3];
-            *reinterpret_cast<half4*>(reinterpret_cast<half_t*>(p.C) + (size_t)m * p.ldc + nout) = h;
+            *reinterpret_cast<half4*>(reinterpret_cast<half_t*>(p.C) + mo * p.ldc + nout) = h;
           } else if (vec && p.c_dt == DT_F32 && (p.ldc & 3) == 0) {
             f32x4 o = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + nout) = o;
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + mo * p.ldc + nout) = o;
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
               if (nout + r < nlim) {
-                if (p.c_dt == DT_F16) reinterpret_cast<half_t*>(p.C)[(size_t)m * p.ldc + nout + r] = (half_t)v[r];
-                else reinterpret_cast<float*>(p.C)[(size_t)m * p.ldc + nout + r] = v[r];
+                if (p.c_dt == DT_F16) reinterpret_cast<half_t*>(p.C)[mo * p.ldc + nout + r] = (half_t)v[r];
+                else reinterpret_cast<float*>(p.C)[mo * p.ldc + nout + r] = v[r];
               }
           }
         } else {
@@ -475,6 +485,7 @@ __device__ __forceinline__ void igemm_epilogue_staged_impl(const IgemmParams& p,
       const bool valid = m < p.M && n0 < nlim;
       float rr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the stored (rounded) values: what the consumer will read
       if (valid) {
+      const size_t mo = igemm_out_row(p, m);
       float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
       const bool full = n0 + 8 <= nlim;
       if (rfast[it]) {
@@ -508,7 +519,7 @@ __device__ __forceinline__ void igemm_epilogue_staged_impl(const IgemmParams& p,
         for (int e = 0; e < 8; ++e) rr[e] = p.c_dt == DT_F16 ? (float)(half_t)v[e] : v[e];
       }
       if (p.c_dt == DT_F16) {
-        half_t* cp = reinterpret_cast<half_t*>(p.C) + (size_t)m * p.ldc + n0;
+        half_t* cp = reinterpret_cast<half_t*>(p.C) + mo * p.ldc + n0;
         if (full && (reinterpret_cast<uintptr_t>(cp) & 15) == 0) {
           half8 h;
 #pragma unroll
@@ -519,9 +530,9 @@ __device__ __forceinline__ void igemm_epilogue_staged_impl(const IgemmParams& p,
           for (int e = 0; e < 8; ++e) if (n0 + e < nlim) cp[e] = (half_t)v[e];
         }
       } else if (p.c_dt == DT_HL) {       // (whole 8-column pieces only: the launcher admits N % 8 == 0, ldc % 16 == 0 outputs)
-        if (full) store_hl8(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc, n0, v);
+        if (full) store_hl8(reinterpret_cast<float*>(p.C) + mo * p.ldc, n0, v);
       } else {
-        float* cp = reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n0;
+        float* cp = reinterpret_cast<float*>(p.C) + mo * p.ldc + n0;
         if (full && (reinterpret_cast<uintptr_t>(cp) & 15) == 0) {
           *reinterpret_cast<f32x4*>(cp) = f32x4{v[0], v[1], v[2], v[3]};
           *reinterpret_cast<f32x4*>(cp + 4) = f32x4{v[4], v[5], v[6], v[7]};
@@ -699,12 +710,14 @@ __device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, const 
   constexpr int NP = NQ / 2;                   // 8-column pieces per tile and lane after the half swap
   const int nwo = GEGLU ? (nw >> 1) : nw;
   int m[TM], bidx[TM];
+  size_t mo[TM];      // row of C (igemm_out_row)
   bool mok[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     m[i] = mw + i * 32 + fr;
     mok[i] = m[i] < p.M;
     bidx[i] = (p.ebias && mok[i]) ? m[i] / p.rpb : 0;
+    mo[i] = mok[i] ? igemm_out_row(p, m[i]) : 0;
   }
   // residual pieces: requested first (oldest entries of the vmcnt queue), consumed last
   const bool r16 = p.R && p.r_dt == DT_F16, r32 = p.R && p.r_dt == DT_F32;
@@ -788,7 +801,7 @@ __device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, const 
           half8 h;
 #pragma unroll
           for (int e = 0; e < 8; ++e) h[e] = (half_t)w[e];
-          if (mok[i]) *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(p.C) + (size_t)m[i] * p.ldc + n0) = h;
+          if (mok[i]) *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(p.C) + mo[i] * p.ldc + n0) = h;
           if constexpr (TN == 2 && !GEGLU) {
             if (p.stat_out) {
 #pragma unroll
@@ -796,9 +809,9 @@ __device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, const 
             }
           }
         } else if (p.c_dt == DT_HL) {
-          if (mok[i]) store_hl8(reinterpret_cast<float*>(p.C) + (size_t)m[i] * p.ldc, n0, w);
+          if (mok[i]) store_hl8(reinterpret_cast<float*>(p.C) + mo[i] * p.ldc, n0, w);
         } else if (mok[i]) {
-          float* cp = reinterpret_cast<float*>(p.C) + (size_t)m[i] * p.ldc + n0;
+          float* cp = reinterpret_cast<float*>(p.C) + mo[i] * p.ldc + n0;
           *reinterpret_cast<f32x4*>(cp) = f32x4{w[0], w[1], w[2], w[3]};
           *reinterpret_cast<f32x4*>(cp + 4) = f32x4{w[4], w[5], w[6], w[7]};
         }

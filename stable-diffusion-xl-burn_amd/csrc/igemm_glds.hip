@@ -245,6 +245,10 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
   if ((size_t)p.N * p.K > (size_t)p.M * p.Cin) { tn = bid / tilesM; tm = bid - tn * tilesM; }
   else { tm = bid / tilesN; tn = bid - tm * tilesN; }
   const int m0 = tm * BM, n0 = tn * BN;
+  // phase form of an upsample convolution (IgemmParams::ph_rows; a row tile lies in one phase): this tile's phase 2a + b selects its weights and
+  // the pad of each axis (tap (dy, dx) of row (i, j) reads source pixel (i + dy - pad + a, j + dx - pad + b)); mph = the phase's first row
+  const int ph = p.ph_rows ? m0 / p.ph_rows : 0;
+  const int mph = ph * p.ph_rows, pady = p.pad - (ph >> 1), padx = p.pad - (ph & 1);
   // TSW: the whole tile in the transposed part, whole 8-key pieces inside one batch entry, f16 out -> operand-swapped k-loop + direct transposed store
   bool tsw_swapped = false;
   if constexpr (TSW) {
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
 #pragma unroll
   for (int j = 0; j < BJ; ++j) {
     const int row = (j * NW + wave) * 8 + lrow;
-    wptr[j] = reinterpret_cast<const T*>(p.W) + (size_t)(n0 + row) * p.Kpad + (slot ^ ((row >> 1) & 7)) * CE;
+    wptr[j] = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.W) + (size_t)ph * p.ph_wbytes) + (size_t)(n0 + row) * p.Kpad + (slot ^ ((row >> 1) & 7)) * CE;
   }
   // this workgroup's k-tiles [kbeg, kbeg + nk) of the Kpad / KT of the contraction (split-K: slice `slice` of SK)
   const int nk_all = p.Kpad / KT;
@@ -311,9 +315,10 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
     if (!lin_rows) {
       if (m < p.M) {
         int b, rem, oy;
-        if (pow2) { b = m >> sh_hw; rem = m & (HWo - 1); oy = rem >> sh_w; }
-        else { b = m / HWo; rem = m - b * HWo; oy = rem / p.Wout; }
-        rb[j] = b; ry[j] = oy * p.stride - p.pad; rx[j] = (rem - oy * p.Wout) * p.stride - p.pad;
+        const int ml = m - mph;      // (phase form: row inside the phase, entries of Hout x Wout = Hin x Win rows)
+        if (pow2) { b = ml >> sh_hw; rem = ml & (HWo - 1); oy = rem >> sh_w; }
+        else { b = ml / HWo; rem = ml - b * HWo; oy = rem / p.Wout; }
+        rb[j] = b; ry[j] = oy * p.stride - pady; rx[j] = (rem - oy * p.Wout) * p.stride - padx;
       } else { rb[j] = -1; ry[j] = -(1 << 28); rx[j] = 0; }
     }
   }
@@ -540,7 +545,7 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int m = m0 + wm * WM + i * 32 + fr;
-      const int be = p.a_scale_rpb > 0 ? (m < p.M ? m : p.M - 1) / p.a_scale_rpb : 0;
+      const int be = p.a_scale_rpb > 0 ? ((m < p.M ? m : p.M - 1) - mph) / p.a_scale_rpb : 0;      // (phase form: a_scale_rpb = source rows per entry)
       lnA[i] = wsc * (p.a_scale ? p.a_scale[be] : 1.f); lnC[i] = 0.f;
     }
     // (readfirstlane: the compiler must SEE that the choice is wave-uniform -- as a vector condition it runs both k-loops one after

@@ -87,6 +87,14 @@ struct IgemmParams {
   float shadow_lo_scale;    // > 0: the shadow row is [hi (N columns) | lo (N columns)], lo = f16((value * gamma - hi) * shadow_lo_scale): the (hi, lo) A operand of a GEMM packed (w | w / scale).
                             // < 0: the shadow is an HL16 tensor (shadow_ld in LOGICAL elements, un-scaled lo halves): read as an f16 row of 2 N columns by a GEMM whose weight is
                             // packed twice in the HL16 interleave (launch_pack_linear_hilo mode 2)
+  // Nearest-2x upsample + 3x3 convolution as FOUR 2x2-tap convolutions on the source (upsample_fold.h), one launch: the rows are ordered
+  // [phase = 2a + b][entry][i][j] (M = 4 ph_rows), ph_rows = B * Hin * Win rows per phase, a multiple of the tile's rows so that a row tile lies in one
+  // phase.  Geometry of ONE phase: ksize = 2, stride = 1, up = 0, Hout = Hin, Wout = Win; tap (dy, dx) of row (i, j) reads source pixel
+  // (i + dy - pad + a, j + dx - pad + b) with pad = 1 -- a pad that differs per phase and axis; pixels outside the source come from the zero page.
+  // Phase ph multiplies the weights at W + ph * ph_wbytes ([Npad][Kpad] each, K = 4 Cin) and its row (entry, i, j) is stored to output row
+  // (entry * 2 Hin + 2 i + a) * 2 Win + 2 j + b.  Plain epilogue only (bias, accumulator scales; no residual / statistics / split output).
+  // Pipe kernels on f16 and split-operand elements (igemm_glds.hip); 0 = off: every other kernel ignores the fields, the selection refuses them.
+  int ph_rows; unsigned ph_wbytes;
 };
 // ---- kernel selection (select.cpp: host-only, no HIP call).  Knobs that influence WHICH kernel runs, written by sdxl_debug_set and
 // snapshotted once per launch; zero_page is an input of the same kind, filled by the launcher (the DMA kernels' zero page exists on this device)
@@ -126,6 +134,9 @@ bool igemm_wreg_xattn_selected(const IgemmParams& p, const SelectKnobs& k);   //
 // shapes the fused cross-attention epilogue takes (f16 operands, head dim 64, <= 96 context tokens); otherwise run the
 // projection and the attention kernel separately
 bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx);
+// the phase form of an upsample convolution (IgemmParams::ph_rows, filled): the selection has a pipe tile for it.  Asked by run_conv before it
+// hands the launch the folded weights; false: the layer keeps the gather form.  A function of one entry's shape (rows per phase and entry, N, K).
+bool igemm_phase_ok(const IgemmParams& p, int compute_dt, const SelectKnobs& k);
 // K [B][n_ctx][C], V^T [B][C][vt_ld] (f16) -> operand-order image of xattn_pack_bytes(B, C) bytes (once per prompt)
 size_t xattn_pack_bytes(int B, int C);
 void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, int n_ctx, int vt_ld, hipStream_t s);
@@ -389,6 +400,9 @@ void launch_beta_dot(const float* w, const float* beta, const float* bias, float
 // canonical conv [Cout][Cin][kh][kw] fp32 -> packed [Npad][Kpad], k = (kh*kw_idx)*Cin + c
 void launch_pack_conv(const float* src, void* dst, int dt, int Cout, int Cin, int ks, int Kpad, int Npad,
                       hipStream_t s, float wscale = 1.0f);   // wscale: power-of-two factor of the DT_HL packing (undone by IgemmParams::acc_scale)
+// canonical 3x3 conv [Cout][Cin][3][3] fp32 -> [4][Cout][Cin][2][2]: the four 2x2-tap phase convolutions of a nearest-2x upsample in front of it
+// (upsample_fold.h; fp32 sums in one fixed order); each phase then packs like any convolution (launch_pack_conv, ks = 2)
+void launch_fold_upsample(const float* src, float* dst, int Cout, int Cin, hipStream_t s);
 void launch_absmax(const float* src, size_t n, float* out_dev, hipStream_t s, bool accumulate = false);   // *out_dev = max(|src[i]|[, *out_dev])
 // bias vector permuted the same way as GEGLU-packed columns (fp32 -> fp32)
 void launch_pack_bias(const float* src, float* dst, int N, int Npad, int geglu, int n_offset, hipStream_t s);

@@ -123,6 +123,29 @@ int pick_tile(const IgemmParams& p, std::initializer_list<int> among) {
   return number;
 }
 
+// Phase form of an upsample convolution (IgemmParams::ph_rows): four 2x2-tap convolutions in one launch, a row tile inside one phase.
+// The folded weights are rounded once more than the 3x3 ones, so WHETHER a layer runs folded changes bits: the rule looks at one entry
+// (rows per entry and phase a multiple of 128: the 128-row tiles then fit any batch) and at nothing the batch changes.  Which of the fitting
+// tiles runs changes no bit (same k order in all of them): tile_cost on the folded shape among the tiles whose rows divide a phase.
+bool phase_shape_ok(const IgemmParams& p, int kt) {
+  if (p.ph_rows <= 0 || p.ph_wbytes == 0 || p.B <= 0 || p.ph_rows != p.B * p.Hin * p.Win || p.M != 4 * p.ph_rows) return false;
+  if (p.ksize != 2 || p.stride != 1 || p.up != 0 || p.pad != 1 || p.Hout != p.Hin || p.Wout != p.Win) return false;
+  if ((p.Hin * p.Win) % 128 != 0 || p.Cin % kt != 0 || p.K != 4 * p.Cin || p.Kpad != p.K) return false;
+  return p.act == 0 && p.n_split >= p.N && !p.R && !p.ebias && !p.stat_out && !p.gn_part && !p.ln_stat && !p.xa_k && !p.shadow;
+}
+int pick_phase_tile(const IgemmParams& p, int nk, bool hl) {
+  double best = 1e300;
+  int number = 36;
+  for (int n : {35, 36, 38, 49}) {
+    const Tile& t = tile(n);
+    if (p.ph_rows % t.bm != 0 || !tile_takes(t, p) || (hl && n == 38)) continue;      // (no split-operand 256x160 instantiation)
+    const double cost = tile_cost(p.M, p.N, nk, t.bm, t.bn, t.w);
+    if (cost < best) { best = cost; number = n; }
+  }
+  if (!hl && number == 36 && nk >= 40) number = 44;      // as pick_tile
+  return number;
+}
+
 // chip fill of the single-precision-class engines' 128-wide tiles: the f32 MFMA runs at 1/16 of the f16 rate and the split-operand
 // product takes three, so those launches are matrix-pipe bound and the tile choice only has to keep the rounds of 256 CUs full
 struct Fill { long t96, t128, t256; double eff128, eff256; };
@@ -237,6 +260,11 @@ bool select_f16(const IgemmParams& p, int v, const SelectKnobs& k, IgemmChoice& 
   // (the DMA reads weight rows up to the tile edge: Npad is a multiple of 128 for every packed weight, pack_* kernels)
   const bool was_auto = v == 0;
   const int nk = p.Kpad / 64;
+  if (p.ph_rows) {      // phase form of an upsample convolution: pipe tiles only, forced numbers do not apply
+    if (!phase_shape_ok(p, 64)) throw std::runtime_error("igemm: the phase form of an upsample convolution was given a launch it does not take");
+    c = from_tile(pick_phase_tile(p, nk, false), DT_F16, p);
+    return true;
+  }
   if (p.xa_k) {
     // fused cross-attention: wave tiles of 64 columns only, chosen by the same cost model
     if (p.act != 0 || p.n_split < p.N || p.stat_out || p.R || p.ebias ||
@@ -342,7 +370,12 @@ bool select_hl(const IgemmParams& p, const SelectKnobs& k, IgemmChoice& c) {
     if (p.n_split < p.N && ((p.ct_ld & 15) != 0 || (p.rpb & 7) != 0 || (p.M % 8) != 0 || misaligned16(p.Ct))) return false;
   }
   if (p.ebias && (p.ebias_ld & 3) != 0) return false;
-  const int t96mode = k.hl_tile96;      // bit 0: linear layers / 1x1 only (default), bit 1: 3x3 convolutions too (measured -0.15 % on the mixed mode's step: not selected)
+  if (p.ph_rows) {      // phase form of an upsample convolution (fp32 or HL16 rows out)
+    if (!phase_shape_ok(p, 32)) throw std::runtime_error("igemm: the phase form of an upsample convolution was given a launch it does not take");
+    c = from_tile(pick_phase_tile(p, p.Kpad / 32, true), DT_HL, p);
+    return true;
+  }
+  const int t96mode = k.hl_tile96;     // bit 0: linear layers / 1x1 only (default), bit 1: 3x3 convolutions too (measured -0.15 % on the mixed mode's step: not selected)
   const bool splitk = (t96mode & 16) && igemm_splitk_slices(p) > 1;
   const bool plain160 = p.N % 160 == 0 && p.n_split >= p.N && !p.stat_out && p.act == 0;
   // round 5: the 96-row tile of the f16 engine for the shapes where it fills more of the chip's single round -- the M = 2048 x N = 1280 linears of the
@@ -452,6 +485,11 @@ bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx)
   return a_dt == DT_F16 && (c_dt == DT_F16 || c_dt == DT_HL) && M > 0 && N % 64 == 0 && K % 64 == 0 && rpb > 0 && rpb % 64 == 0 && M % rpb == 0 &&
          n_ctx >= 1 && n_ctx <= 96;
 }
+bool igemm_phase_ok(const IgemmParams& p, int compute_dt, const SelectKnobs& k) {
+  if (k.igemm_variant < 0 || !phase_shape_ok(p, compute_dt == DT_HL ? 32 : 64)) return false;
+  IgemmChoice c{};
+  return compute_dt == DT_F16 ? select_f16(p, 0, k, c) : (compute_dt == DT_HL && select_hl(p, k, c));
+}
 bool igemm_wreg_selected(const IgemmParams& p, const SelectKnobs& k) { return wreg_takes(p, k, false) && k.igemm_wreg && wreg_pair_grid_fits(p); }
 bool igemm_wreg_xattn_selected(const IgemmParams& p, const SelectKnobs& k) {
   return wreg_takes(p, k, true) && k.igemm_wreg && k.wreg_xattn && wreg_pair_grid_fits(p);
@@ -463,6 +501,7 @@ IgemmChoice igemm_select(const IgemmParams& p, int compute_dt, const SelectKnobs
   const int v = k.igemm_variant;          // -1 generic kernel only, 0 auto, > 0 a forced number
   if (compute_dt == DT_F16 && v >= 0 && select_f16(p, v, k, c)) return c;
   if (compute_dt == DT_F16 && v > 0 && select_f16(p, 0, k, c)) return c;   // forced tile refused the shape
+  if (p.ph_rows && compute_dt != DT_HL) throw std::runtime_error("the phase form of an upsample convolution needs the f16 / split-operand direct-to-LDS kernels (igemm_phase_ok)");
   if (p.shadow && compute_dt != DT_F16) throw std::runtime_error("an f16 shadow output needs an f16 GEMM (weights-in-registers kernel)");
   if (compute_dt == DT_F32 && v >= 0 && select_f32(p, k, c)) return c;
   if (compute_dt == DT_HL) {     // no generic twin: layers the HL pipeline cannot take are packed (and launched) as fp32 by the host

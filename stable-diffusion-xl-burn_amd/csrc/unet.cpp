@@ -312,7 +312,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
     x2 = x2 || pl.qkv == LF_X2 || pl.out1 == LF_X2 || pl.q2 == LF_X2 || pl.out2 == LF_X2 || pl.geglu == LF_X2 || pl.ff == LF_X2;
     attn16_ = attn16_ || pl.attn_f16;
   }
-  size_t bound = WeightBuilder::arena_bound(specs, cdt_);
+  size_t bound = WeightBuilder::arena_bound(specs, cdt_, true, fuse_ln_);
   if (x2)      // f16 x 2 K images carry a fragment-order twin the split-operand bound does not count
     for (const ParamSpec& ps : specs) if (ps.kind == PK_LINEAR_W) bound += round_up(ps.shape[1], 128) * round_up((size_t)ps.shape[0], 64) * 4 + 256;
   warena_.reserve(bound);
@@ -332,7 +332,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
       default:
         b.res = load_res(wb, p + ".res", d.c_in, d.c_out, emb_names, emb_off);
         if (d.kind == BK_REST || d.kind == BK_RESTU) b.st = load_st(wb, p + ".transformer", d.c_out, d.n_head, d.depth, fuse_ln_, plans[sti++]);
-        if (d.kind == BK_RESTU || d.kind == BK_RESU) b.conv = wb.conv(p + ".upsample.conv");
+        if (d.kind == BK_RESTU || d.kind == BK_RESU) b.conv = wb.conv(p + ".upsample.conv", fuse_ln_);      // f16 engine: + the folded phase matrices (Lin::w_fold)
     }
     return b;
   };
@@ -756,8 +756,10 @@ void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
     } else {
       res_block(ex, b.res, cat[j], B, h, w, dest);
     }
-    if (up) {   // Upsample::forward :742-752 -- nearest 2x fused into the conv gather
-      run_conv(ex, b.conv, hl_op(ex, b.conv, dest, (size_t)B * h * w, b.d.c_out, DM_CONV_UPDOWN, B), b.d.c_out, ConvGeom{B, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, next, tag_epi(DM_CONV_UPDOWN));
+    if (up) {   // Upsample::forward :742-752 -- nearest 2x folded into the conv weights (four 2x2-tap phase convolutions) or, where the shape has no such launch, fused into the conv gather
+      Epi up_epi = tag_epi(DM_CONV_UPDOWN);
+      up_epi.fold = true;      // (run_conv: only layers that carry folded weights -- the f16 engine's)
+      run_conv(ex, b.conv, hl_op(ex, b.conv, dest, (size_t)B * h * w, b.d.c_out, DM_CONV_UPDOWN, B), b.d.c_out, ConvGeom{B, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, next, up_epi);
       h *= 2; w *= 2;
     }
     ex.act->reset(mk);

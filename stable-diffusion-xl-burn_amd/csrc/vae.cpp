@@ -32,7 +32,7 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
   const std::vector<ParamSpec> dspecs = vae_decoder_param_specs(cfg_), especs = vae_encoder_param_specs(cfg_);
   size_t bound = 0;
   // (no fragment-order weight images: the VAE's 1x1 convs run on >= 4096 rows per entry, never on the weights-in-registers kernel)
-  if (dec_src) bound += WeightBuilder::arena_bound(dspecs, cdt_, false);
+  if (dec_src) bound += WeightBuilder::arena_bound(dspecs, cdt_, false, cdt_ == DT_HL);
   if (enc_src) bound += WeightBuilder::arena_bound(especs, cdt_, false);
   warena_.reserve(bound + 4096);
   if (dec_src) {
@@ -48,7 +48,7 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
       b.r[1] = load_res(wb, p + ".res2", cfg_.dec[i].second, cfg_.dec[i].second);
       b.r[2] = load_res(wb, p + ".res3", cfg_.dec[i].second, cfg_.dec[i].second);
       b.has_up = i + 1 != cfg_.dec.size();
-      if (b.has_up) b.up = wb.conv(p + ".upsampler");
+      if (b.has_up) b.up = wb.conv(p + ".upsampler", cdt_ == DT_HL);      // split-operand decoder: + the folded phase matrices (Lin::w_fold)
       d_blocks_.push_back(b);
     }
     d_norm_out_ = wb.norm("decoder.norm_out");
@@ -212,7 +212,7 @@ void Vae::run_decode(Exec& ex, const Act& in, int n, int h, int w, const Act& ou
   run_conv(ex, d_conv_in_, z, 4, ConvGeom{n, h, w, h, w, 3, 1, 1, 0}, cur);
   mid(ex, d_mid_, cur, n, h, w);
   for (size_t i = 0; i < d_blocks_.size(); ++i) {
-    const DecBlk& b = d_blocks_[i];
+    DecBlk& b = d_blocks_[i];
     const int co = cfg_.dec[i].second;
     const size_t M = (size_t)n * h * w;
     Act next = b.has_up ? ex.alloc(4 * M, co, ex.sdt) : ex.alloc(M, co, ex.sdt);
@@ -223,7 +223,17 @@ void Vae::run_decode(Exec& ex, const Act& in, int n, int h, int w, const Act& ou
     res_block(ex, b.r[1], a, n, h, w, bb);
     if (b.has_up) {
       res_block(ex, b.r[2], bb, n, h, w, a);
-      run_conv(ex, b.up, hl_operand(ex, b.up, a, M, co, n), co, ConvGeom{n, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, next);
+      Epi eu;
+      if (!ex.dry && b.up.w_fold) {
+        if (b.up_fold < 0) {      // acc_scale[1] != 0: every 3x3 weight of the layer is one f16 value
+          float sc[2] = {0.f, 0.f};
+          SDXL_HIP(hipMemcpyAsync(sc, b.up.acc_scale, sizeof(sc), hipMemcpyDeviceToHost, ex.s));
+          SDXL_HIP(hipStreamSynchronize(ex.s));
+          b.up_fold = sc[1] == 0.f ? 1 : 0;
+        }
+        eu.fold = b.up_fold == 1;
+      }
+      run_conv(ex, b.up, hl_operand(ex, b.up, a, M, co, n), co, ConvGeom{n, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, next, eu);
       h *= 2; w *= 2;
     } else {
       res_block(ex, b.r[2], bb, n, h, w, next);

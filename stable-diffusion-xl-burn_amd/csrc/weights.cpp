@@ -5,6 +5,7 @@
 // shared by the UNet and VAE drivers.
 #include "engine.h"
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -162,7 +163,7 @@ WeightBuilder::WeightBuilder(const std::vector<ParamSpec>& sp, WeightSource& s, 
 }
 WeightBuilder::~WeightBuilder() { if (tmp) (void)hipFree(tmp); if (tmp2) (void)hipFree(tmp2); }
 
-size_t WeightBuilder::arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag) {
+size_t WeightBuilder::arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag, bool fold_up) {
   size_t total = 1 << 20;
   for (const ParamSpec& p : specs) {
     if (p.kind == PK_LINEAR_W) total += round_up(p.shape[1], 128) * round_up(p.shape[0], 64) * dt_size(dt) + 768;   // (+ the DT_HL scale scalar)
@@ -174,6 +175,10 @@ size_t WeightBuilder::arena_bound(const std::vector<ParamSpec>& specs, int dt, b
     // fragment-order image of the f16 linear / 1x1 weights (attach_wfrag)
     if (wfrag && dt == DT_F16 && p.kind == PK_LINEAR_W) total += round_up(p.shape[1], 128) * round_up(p.shape[0], 64) * 2 + 256;
     if (wfrag && dt == DT_F16 && p.kind == PK_CONV_W && p.shape[2] == 1) total += round_up(p.shape[0], 128) * round_up((size_t)p.shape[1], 64) * 2 + 256;
+    // folded phase matrices of the upsample convolutions (conv fold_up): 4 x [Npad][4 cin] (+ their DT_HL scale scalar)
+    auto ends_with = [&](const char* t) { const size_t n = std::strlen(t); return p.name.size() >= n && p.name.compare(p.name.size() - n, n, t) == 0; };
+    if (fold_up && (ends_with(".upsample.conv.weight") || ends_with(".upsampler.weight")) && folds_upsample(p, dt))
+      total += 4 * round_up(p.shape[0], 128) * 4 * (size_t)p.shape[1] * dt_size(dt) + 768;
   }
   return total;
 }
@@ -196,12 +201,15 @@ const float* WeightBuilder::fetch(const std::string& name) {
 // weight down to 2^-11 of the largest stay f16-normal (22 significand bits); unscaled, |w| ~ 0.02 would push every lo into the
 // subnormals (~20 bits).  The factor is exact, a function of the tensor(s) only, and the GEMM epilogue undoes it with the device
 // scalar this returns through l.acc_scale (it lives in the arena, so replicas receive it with the weights).
-float WeightBuilder::hl_scale(Lin& l, const std::vector<std::string>& weight_names) {
-  float* sc = (float*)arena.alloc(2 * sizeof(float));     // [0] 1 / factor, [1] "every weight is one f16" (allocated on empty replicas too: identical arena layout)
-  l.acc_scale = sc;
-  if (src.empty()) return 1.f;
+// (each(f): calls f(device tensor, numel) for every tensor of the matrix; called twice -- range, then exactness at the chosen factor)
+template <typename Each>
+static float hl_scale_over(WeightBuilder& wb, const float*& acc_scale, Each each) {
+  float* sc = (float*)wb.arena.alloc(2 * sizeof(float));     // [0] 1 / factor, [1] "every weight is one f16" (allocated on empty replicas too: identical arena layout)
+  acc_scale = sc;
+  if (wb.src.empty()) return 1.f;
+  hipStream_t st = wb.st;
   SDXL_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(float), st));
-  for (const std::string& n : weight_names) launch_absmax(fetch(n), spec(n).numel(), sc, st, true);
+  each([&](const float* t, size_t n) { launch_absmax(t, n, sc, st, true); });
   float h = 0.f;
   SDXL_HIP(hipMemcpyAsync(&h, sc, sizeof(float), hipMemcpyDeviceToHost, st));
   SDXL_HIP(hipStreamSynchronize(st));
@@ -214,8 +222,14 @@ float WeightBuilder::hl_scale(Lin& l, const std::vector<std::string>& weight_nam
   // real SDXL records hold f16 parameters: where every scaled weight of the matrix is exactly one f16 the lo halves are zero and the
   // kernel leaves out a third of its MFMAs (igemm_glds.hip, WX).  (gamma-folded weights never qualify: the split mode does not fold.)
   bool first = true;
-  for (const std::string& n : weight_names) { launch_f16_exact(fetch(n), spec(n).numel(), wscale, sc + 1, st, !first); first = false; }
+  each([&](const float* t, size_t n) { launch_f16_exact(t, n, wscale, sc + 1, st, !first); first = false; });
   return wscale;
+}
+float WeightBuilder::hl_scale(Lin& l, const std::vector<std::string>& weight_names) {
+  return hl_scale_over(*this, l.acc_scale, [&](auto f) { for (const std::string& n : weight_names) f(fetch(n), spec(n).numel()); });
+}
+float WeightBuilder::hl_scale_of(const float* dev, size_t n, const float*& acc_scale) {
+  return hl_scale_over(*this, acc_scale, [&](auto f) { f(dev, n); });
 }
 
 // Plain f16 linear layers / 1x1 convolutions whose width is a multiple of 128 keep a second image of the packed weights in MFMA
@@ -397,7 +411,10 @@ Lin WeightBuilder::fold_ln(const std::vector<std::string>& names, const std::str
   else launch_colsum_packed(w, dt, l.Kpad, l.Npad, cs, st);
   return l;
 }
-Lin WeightBuilder::conv(const std::string& name) {
+bool WeightBuilder::folds_upsample(const ParamSpec& p, int dt) {
+  return p.kind == PK_CONV_W && p.shape[2] == 3 && p.shape[3] == 3 && ((dt == DT_F16 && p.shape[1] % 64 == 0) || (dt == DT_HL && p.shape[1] % 32 == 0));
+}
+Lin WeightBuilder::conv(const std::string& name, bool fold_up) {
   const ParamSpec& s = spec(name + ".weight");
   Lin l; l.N = s.shape[0]; l.cin = s.shape[1]; l.ksize = s.shape[2];
   l.K = l.cin * l.ksize * l.ksize;
@@ -411,8 +428,23 @@ Lin WeightBuilder::conv(const std::string& name) {
   float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
   l.w = w; l.b = b;
   const float wscale = wdt == DT_HL ? hl_scale(l, {name + ".weight"}) : 1.f;
+  // nearest-2x upsample + this conv as four 2x2-tap phase convolutions (upsample_fold.h): fp32 sums of the fetched taps first, then the packing of
+  // w -- one f16 rounding, or the (hi, lo) split at a factor of the SUMS' own range
+  const bool fold = fold_up && folds_upsample(s, wdt);
+  const size_t fold_numel = 16 * (size_t)l.N * l.cin, fold_kpad = 4 * (size_t)l.cin;      // (cin is a multiple of the k-tile: no padding along K)
+  char* wfold = fold ? (char*)arena.alloc(4 * l.Npad * fold_kpad * dt_size(wdt)) : nullptr;
+  l.w_fold = wfold;
+  if (fold && !src.empty() && fold_numel > tmp2_numel) {
+    if (tmp2) SDXL_HIP(hipFree(tmp2));
+    SDXL_HIP(hipMalloc((void**)&tmp2, fold_numel * sizeof(float)));
+    tmp2_numel = fold_numel;
+  }
+  if (fold && !src.empty()) launch_fold_upsample(fetch(name + ".weight"), tmp2, l.N, l.cin, st);
+  const float fscale = fold && wdt == DT_HL ? hl_scale_of(tmp2, fold_numel, l.fold_acc_scale) : 1.f;
   if (src.empty()) { attach_wfrag(l, false); return l; }
   launch_pack_conv(fetch(name + ".weight"), w, wdt, l.N, l.cin, l.ksize, l.Kpad, l.Npad, st, wscale);
+  for (int ph = 0; fold && ph < 4; ++ph)
+    launch_pack_conv(tmp2 + (size_t)ph * 4 * l.N * l.cin, wfold + (size_t)ph * l.Npad * fold_kpad * dt_size(wdt), wdt, l.N, l.cin, 2, (int)fold_kpad, l.Npad, st, fscale);
   launch_pack_bias(fetch(name + ".bias"), b, l.N, l.Npad, 0, 0, st);
   attach_wfrag(l, true);
   return l;
@@ -465,6 +497,8 @@ void WarmSeq::finish() {
     std::fprintf(stderr, "[warm] %zu entries, %.1f MB read per forward, %.1f MB of it warmed\n", n, tb / 1048576.0, cb / 1048576.0);
   }
 }
+static std::atomic<int> g_upsample_fold{1};
+void set_upsample_fold(int v) { g_upsample_fold = v; }
 bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, const Act& out, const Epi& e) {
   if (ex.dry) return false;
   SDXL_REQUIRE(cin == w.cin, "run_conv: channel mismatch");
@@ -505,6 +539,19 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     if (!ok) { p.shadow = nullptr; p.shadow_gamma = nullptr; p.stat_out = nullptr; p.shadow_lo_scale = 0.f; }
     if (e.shadow_done) *e.shadow_done = ok;
   }
+  // nearest-2x upsample + 3x3 conv as the four 2x2-tap phase convolutions of the folded weights (IgemmParams::ph_rows), 4/9 of the products: where the
+  // layer has them, the caller allows it, the knob is on and the selection has a tile for the shape -- else the gather form on the 3x3 weights
+  size_t wbytes_f16 = (size_t)w.Npad * w.Kpad * 2;      // (f16 weights this launch reads: weight warming)
+  if (g.up == 1 && e.fold && w.w_fold && g_upsample_fold.load() && g.ksize == 3 && g.stride == 1 && g.pad == 1 && g.Hout == 2 * g.Hin && g.Wout == 2 * g.Win) {
+    const int wdt_ = w.dt >= 0 ? w.dt : ex.cdt;
+    IgemmParams q = p;
+    q.W = w.w_fold; q.Wf = nullptr; q.acc_scale = w.fold_acc_scale;
+    q.ksize = 2; q.up = 0; q.Hout = g.Hin; q.Wout = g.Win; q.K = q.Kpad = 4 * cin;
+    q.ph_rows = g.B * g.Hin * g.Win; q.ph_wbytes = (unsigned)((size_t)w.Npad * q.Kpad * dt_size(wdt_));
+    q.a_scale_rpb = p.a_scale_rpb / 4;      // (rows per scale entry inside ONE phase)
+    if (igemm_phase_ok(q, wdt_, knobs)) { p = q; wbytes_f16 = 4 * (size_t)w.Npad * q.Kpad * 2; }
+  }
+  if (e.fold_done) *e.fold_done = p.ph_rows != 0;
   SDXL_REQUIRE(!e.xa_k || igemm_xattn_ok(a.dt, out.dt, p.M, p.N, p.K, p.rpb, e.xa_nctx), "fused cross-attention: unsupported shape");
   SDXL_REQUIRE(!e.ln_stat || (w.ln_k ? w.ln_k : w.K) % 64 == 0, "LayerNorm-folded GEMM needs K % 64 == 0");
   SDXL_REQUIRE(!e.stat_out || (w.N % 64 == 0 && (e.n_split < 0 || e.n_split >= w.N) && e.act == 0), "row statistics need a plain N % 64 == 0 output");
@@ -519,7 +566,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     // the region the launch reads cold: its weights and the per-column vectors next to them in the arena (allocation order: packed
     // weights, bias, [column sums, eps of a folded LayerNorm], [fragment-order image])
     const bool host = igemm_wreg_selected(p, knobs) || igemm_wreg_xattn_selected(p, knobs);
-    const size_t wbytes = (size_t)w.Npad * w.Kpad * 2;
+    const size_t wbytes = wbytes_f16;
     const char* lo; const char* hi;
     if (host) {
       const char* f = reinterpret_cast<const char*>(p.Wf), *b = reinterpret_cast<const char*>(w.b);
