@@ -456,6 +456,16 @@ int sdxl_conv2d_upsample_folded(sdxl_ctx* ctx, void* stream, const float* x, con
 /* burn nn::Linear: y = x[M,K] @ W[K,N] + b; geglu!=0 returns x_half * gelu_erf(gate_half) (unet/mod.rs:942-956) */
 int sdxl_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, int M, int K, int N,
                 int geglu, int dtype, float* out);
+/* The small-M linear of the UNet's conditioning path (time / label embedding MLPs, unet/mod.rs:458-468, and the ResBlocks' lin_embed(silu(emb)),
+ * :1088-1089), on the GEMV kernel and launcher UNet::forward runs:  out[b] = silu_out?(silu_in?(x[b]) @ W[K,N] + bias) + yadd[b].
+ * x [Bm,K], weight [K,N] (in,out), bias [N] or NULL, yadd [Bm,N] or NULL, out [Bm,N]; dense fp32 device tensors, any Bm >= 1 (the launcher splits the
+ * rows over launches of at most 8 rows and 64 KiB of staged inputs; K beyond one row of that is an error).  dtype: SDXL_DTYPE_F32 (fp32 weights),
+ * SDXL_DTYPE_F16 (f16 weights), SDXL_DTYPE_F32_SPLIT (fp32 weights: what a split-operand UNet packs for this kernel); accumulation is fp32 in all. */
+int sdxl_gemv(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, const float* yadd, int Bm, int K, int N,
+              int silu_in, int silu_out, int dtype, float* out);
+/* timestep_embedding (unet/mod.rs:21-39) of n fp32 device timesteps: out [n,dim] = [cos(t f) | sin(t f)], f_j = exp(j * -ln(10000) / (dim / 2));
+ * dim even */
+int sdxl_timestep_embedding(sdxl_ctx* ctx, void* stream, const float* t, int n, int dim, float* out);
 /* LayerNorm::forward (layernorm/mod.rs:34-49) followed by nn::Linear, as TransformerBlock::forward pairs them
  * (unet/mod.rs:885-891): y = LN(x[M,K]; gamma, beta, eps) @ W[K,N] + b (bias may be NULL), optional GEGLU.  Runs the path
  * the UNet runs in that dtype: SDXL_DTYPE_F16 = LayerNorm folded into the GEMM (row statistics from the producer's

@@ -94,7 +94,7 @@ ABI_SYMBOLS = [
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
     "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
-    "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
+    "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_gemv", "sdxl_timestep_embedding", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
     "sdxl_clip_config_clip_l", "sdxl_clip_config_open_clip_bigg", "sdxl_clip_param_count", "sdxl_clip_param_spec",
@@ -1104,6 +1104,38 @@ def linear(ctx: Context, x, weight, bias, geglu: bool = False, dtype: int = DTYP
     M = int(x.numel() // K)
     out = torch.empty(tuple(x.shape[:-1]) + ((N // 2) if geglu else N,), device=x.device, dtype=torch.float32)
     _check(lib().sdxl_linear(ctx.h, _stream(), px, pw, pb, M, K, N, int(geglu), dtype, ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
+def gemv(ctx: Context, x, weight, bias=None, yadd=None, silu_in: bool = False, silu_out: bool = False, dtype: int = DTYPE_F16, out=None):
+    """the conditioning path's small-M linear on the UNet's GEMV kernel (time / label MLPs unet/mod.rs:458-468, lin_embed(silu(emb)) :1088-1089):
+    silu_out?(silu_in?(x[Bm,K]) @ weight[K,N] + bias) + yadd[Bm,N].  dtype: DTYPE_F32 / DTYPE_F32_SPLIT (fp32 weights) or DTYPE_F16 (f16 weights).
+    out: a contiguous fp32 CUDA tensor of at least Bm rows of N to write into (rows past Bm are left alone); returns its first Bm rows."""
+    torch = _torch()
+    x, px = _dev(x)
+    weight, pw = _dev(weight)
+    pb = py = None
+    if bias is not None:
+        bias, pb = _dev(bias)
+    if yadd is not None:
+        yadd, py = _dev(yadd)
+    K, N = weight.shape
+    Bm = int(x.numel() // K)
+    if out is None:
+        out = torch.empty((Bm, N), device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == N and out.shape[0] >= Bm):
+        raise EngineError("gemv: out must be a contiguous fp32 CUDA tensor [>= Bm, N]")
+    _check(lib().sdxl_gemv(ctx.h, _stream(), px, pw, pb, py, Bm, int(K), int(N), int(silu_in), int(silu_out), dtype, ctypes.c_void_p(out.data_ptr())))
+    return out[:Bm]
+
+
+def timestep_embedding(ctx: Context, t, dim: int):
+    """timestep_embedding (unet/mod.rs:21-39) of the fp32 timesteps t [n] -> [n, dim] = [cos(t f) | sin(t f)]"""
+    torch = _torch()
+    t, pt = _dev(t)
+    n = int(t.numel())
+    out = torch.empty((n, dim), device=t.device, dtype=torch.float32)
+    _check(lib().sdxl_timestep_embedding(ctx.h, _stream(), pt, n, int(dim), ctypes.c_void_p(out.data_ptr())))
     return out
 
 

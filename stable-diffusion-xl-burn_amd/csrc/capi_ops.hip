@@ -431,6 +431,45 @@ int sdxl_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* weight
   SDXL_HIP(hipStreamSynchronize(s));
   API_END
 }
+// the conditioning path's small-M linear (UNet::run / UNet::set_context: time and label MLPs, the hoisted lin_embed(silu(emb))): the weight packed as
+// the UNet of that dtype packs its GEMV weights (gemv_weight_dt), the launcher's row chunking included; x / yadd / out are used in place (dense rows)
+int sdxl_gemv(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, const float* bias, const float* yadd, int Bm, int K, int N,
+              int silu_in, int silu_out, int dtype, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(ctx && x && weight && out, "null argument");
+  SDXL_REQUIRE(Bm >= 1 && K >= 1 && N >= 1, "gemv: Bm, K, N must be >= 1");
+  SDXL_REQUIRE(dtype == SDXL_DTYPE_F32 || dtype == SDXL_DTYPE_F16 || dtype == SDXL_DTYPE_F32_SPLIT,
+               "sdxl_gemv takes SDXL_DTYPE_F32, SDXL_DTYPE_F16 or SDXL_DTYPE_F32_SPLIT");
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  const int cdt = dtype == SDXL_DTYPE_F16 ? DT_F16 : dtype == SDXL_DTYPE_F32_SPLIT ? DT_HL : DT_F32;
+  Operands ops;
+  add_linear(ops, "lin", K, N, weight, bias);
+  Packed pk(ops, cdt, s);
+  const Lin l = pk.wb.linear("lin", false, gemv_weight_dt(cdt));
+  GemvParams p{};
+  p.X = x; p.ldx = K; p.W = l.w; p.w_dt = l.dt >= 0 ? l.dt : cdt; p.Kpad = l.Kpad; p.bias = bias ? l.b : nullptr;
+  p.Y = out; p.ldy = N; p.Yadd = yadd; p.Bm = Bm; p.N = l.N; p.K = l.K;
+  p.silu_in = silu_in != 0; p.silu_out = silu_out != 0;
+  (void)hipGetLastError();      // (every call before this one was checked: what is read below belongs to the GEMV launches)
+  launch_gemv(p, s);
+  SDXL_HIP(hipGetLastError());
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
+// timestep_embedding (unet/mod.rs:21-39) of n fp32 timesteps: out[i] = [cos(t[i] f) | sin(t[i] f)], f_j = exp(-ln(10000) j / (dim / 2))
+int sdxl_timestep_embedding(sdxl_ctx* ctx, void* stream, const float* t, int n, int dim, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(ctx && t && out, "null argument");
+  SDXL_REQUIRE(n >= 1 && dim >= 2 && dim % 2 == 0, "timestep_embedding: n >= 1 and an even dim >= 2");
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  (void)hipGetLastError();
+  launch_timestep_embedding(t, 1, out, n, dim, s);
+  SDXL_HIP(hipGetLastError());
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
 int sdxl_layer_norm_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps,
                            const float* weight, const float* bias, int M, int K, int N, int geglu, int dtype, float* out) {
   API_BEGIN

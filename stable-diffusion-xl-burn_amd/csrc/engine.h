@@ -160,6 +160,10 @@ struct Lin {        // packed dense weight: [Npad][Kpad] compute dtype + fp32 bi
 // host-side copy, and a checkpoint's per-norm eps (groupnorm/load.rs:19, layernorm/load.rs:17) travels with the weights
 struct NormW { const float* gamma = nullptr; const float* beta = nullptr; const float* eps = nullptr; int C = 0; };
 
+// dt_override of the M <= 8 GEMV weights (time / label MLPs, the hoisted lin_embed) for a model of compute dtype cdt: a split-operand model packs them
+// fp32 (gemv_kernel reads f16 or fp32 rows, not HL16), every other model in its own dtype (-1).  One rule for UNet's constructor and sdxl_gemv.
+inline int gemv_weight_dt(int cdt) { return cdt == DT_HL ? DT_F32 : -1; }
+
 struct WeightBuilder {
   const std::vector<ParamSpec>& specs;
   std::map<std::string, size_t> index;

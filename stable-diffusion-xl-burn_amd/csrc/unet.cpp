@@ -316,7 +316,7 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
   if (x2)      // f16 x 2 K images carry a fragment-order twin the split-operand bound does not count
     for (const ParamSpec& ps : specs) if (ps.kind == PK_LINEAR_W) bound += round_up(ps.shape[1], 128) * round_up((size_t)ps.shape[0], 64) * 4 + 256;
   warena_.reserve(bound);
-  const int gv = cdt_ == DT_HL ? DT_F32 : -1;     // the M <= 8 GEMV weights of a split-operand model are packed fp32
+  const int gv = gemv_weight_dt(cdt_);     // the M <= 8 GEMV weights of a split-operand model are packed fp32
   lin1_t_ = wb.linear("lin1_time_embed", false, gv);
   lin2_t_ = wb.linear("lin2_time_embed", false, gv);
   lin1_l_ = wb.linear("lin1_label_embed", false, gv);
