@@ -279,6 +279,44 @@ int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out);
  * 0..n_train_steps-1, capacity_steps too small, an unknown solver, alphas outside (0, 1): SDXL_ERR_INVALID, out untouched. */
 int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver,
                              double eta, double* out, int capacity_steps);
+/* ---- guidance: how the two UNet branches of an iteration become the noise prediction e, a per-handle option all six trajectory
+ * calls above honour, with both solvers, explicit and seeded noise, and inpainting.  The default is the reference's line (:539-540),
+ * e = eu + (ec - eu) s with the call's scalar s on every iteration, and a handle with default options runs exactly what it ran before
+ * these options existed.  Per batch entry b and iteration i at timestep t_i:
+ *   SDXL_GUIDANCE_OFF   the conditional branch alone, e = ec, as a batch-n forward (distilled checkpoints: Turbo, Lightning, LCM).
+ *                       The unconditional tensors of sdxl_conditioning may be NULL, the scale argument is ignored, n may reach 8.
+ *   inactive iteration  (t_i outside [t_lo, t_hi]; guidance interval, Kynkaanniemi et al. 2024): e = ec exactly.  Both branches
+ *                       still run: the batch-2n forward is one captured graph per handle.
+ *   active iteration    ecfg = fma(ec - eu, s_b, eu), s_b = scales[b] where n_scales > 0, else the call's scalar;
+ *                       rescale = 0: e = ecfg.   rescale = phi > 0 (CFG rescale, Lin et al. 2023, section 3.4):
+ *                           e = ecfg f_b,   f_b = fma(phi, r_b, 1 - phi),   r_b = sqrt(M2(ec) / M2(ecfg))
+ *                       M2 the centred sum of squares over the 4 HW values of entry b (the ratio of standard deviations, whichever
+ *                       of N, N-1 divides them); M2(ecfg) == 0 gives f_b = 1.  f_b has the same bits for an entry alone and batched.
+ * Everything behind e -- x0, the DDIM / 2M update, the sigma noise, the inpainting blend -- is unchanged.  Not offered: per-entry
+ * negative prompts (the sdxl_conditioning layout holds one unconditional tensor). */
+enum { SDXL_GUIDANCE_CFG = 0, SDXL_GUIDANCE_OFF = 1 };
+typedef struct {
+  int32_t mode;        /* SDXL_GUIDANCE_CFG (default) or SDXL_GUIDANCE_OFF */
+  float   rescale;     /* phi in [0, 1]; 0 = off (default) */
+  int32_t n_scales;    /* 0 (default: the call's scalar) or the trajectory's cond.n */
+  float   scales[8];   /* per-entry guidance scales, replace the call's scalar */
+  int32_t t_lo, t_hi;  /* guidance is active on iterations whose timestep t has t_lo <= t <= t_hi; default 0 .. INT32_MAX */
+} sdxl_guidance;
+void sdxl_guidance_default(sdxl_guidance* g);
+/* host logic only, no device.  SDXL_ERR_INVALID with the first complaint in sdxl_last_error() for: an unknown mode; rescale outside
+ * [0, 1] (NaN included); n_scales outside 0..8; a non-finite scale; t_lo < 0 or t_lo > t_hi; SDXL_GUIDANCE_OFF together with any
+ * other non-default field; is_refiner != 0 with anything but the default or SDXL_GUIDANCE_OFF (the refiner has no unconditional branch). */
+int sdxl_guidance_check(const sdxl_guidance* g, int is_refiner);
+/* g == NULL: the default.  Options sdxl_guidance_check refuses for this handle: SDXL_ERR_INVALID, the handle keeps its options.
+ * A trajectory call with n_scales != 0 && n_scales != cond.n returns SDXL_ERR_INVALID before anything is launched. */
+int sdxl_diffuser_set_guidance(sdxl_diffuser* d, const sdxl_guidance* g);
+int sdxl_diffuser_get_guidance(sdxl_diffuser* d, sdxl_guidance* out);
+/* the single op behind rescale, the two kernels the sampler runs: eps = UNet output rows [2n, HW, 4] fp32 (device; cond entries
+ * first), scales: host array [n], 1 <= n <= 8, factors_out: device array [n] that receives f_b.  1 <= HW <= 2^22 (the latent of a
+ * 16384 x 16384 image): one wavefront per entry merges the ceil(HW / 256) block partials one after the other, which is what keeps
+ * the result reproducible -- 64 merges at 1024 x 1024, and a cost that grows with HW */
+int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int n, int HW, const float* scales, float rescale,
+                             float* factors_out);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

@@ -8,4 +8,8 @@ _Static_assert(SDXL_LORA_ROUND_F16 == 1, "lora flags");
 _Static_assert(offsetof(sdxl_lora_entry, param_index) == 0 && offsetof(sdxl_lora_entry, rank) == 4 && offsetof(sdxl_lora_entry, left) == 8 &&
                offsetof(sdxl_lora_entry, right) == 8 + sizeof(void*) && offsetof(sdxl_lora_entry, scale) == 8 + 2 * sizeof(void*) &&
                sizeof(sdxl_lora_entry) == 16 + 2 * sizeof(void*), "sdxl_lora_entry layout (LP64)");
+_Static_assert(SDXL_GUIDANCE_CFG == 0 && SDXL_GUIDANCE_OFF == 1, "guidance modes");
+_Static_assert(offsetof(sdxl_guidance, mode) == 0 && offsetof(sdxl_guidance, rescale) == 4 && offsetof(sdxl_guidance, n_scales) == 8 &&
+               offsetof(sdxl_guidance, scales) == 12 && offsetof(sdxl_guidance, t_lo) == 44 && offsetof(sdxl_guidance, t_hi) == 48 &&
+               sizeof(sdxl_guidance) == 52, "sdxl_guidance layout");
 int sdxl_mi355_abi_check(void) { return SDXL_OK; }

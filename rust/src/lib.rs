@@ -392,6 +392,41 @@ pub enum Solver {
     /// DPM-Solver++(2M) on the same schedule, with `eta > 0` its SDE form: second order at one UNet evaluation per iteration
     Dpmpp2M = ffi::SDXL_SOLVER_DPMPP_2M as isize,
 }
+/// how the two UNet branches of an iteration become the noise prediction (`sdxl_guidance`): a per-handle option all trajectory methods
+/// honour.  `Guidance::default()` is the reference's line, one scalar scale on every iteration.
+#[derive(Clone, Debug, PartialEq)]
+pub struct Guidance {
+    /// `SDXL_GUIDANCE_OFF`: the conditional branch alone as a batch-n forward (distilled checkpoints); takes no other option
+    pub off: bool,
+    /// phi of CFG rescale (Lin et al. 2023, section 3.4) in [0, 1]; 0.0 = off
+    pub rescale: f32,
+    /// one guidance scale per batch entry (at most 8), replacing the call's scalar; empty = the call's scalar
+    pub scales: Vec<f32>,
+    /// guidance only on iterations whose timestep `t` has `t_lo <= t <= t_hi`; `None` = every iteration
+    pub t_range: Option<(i32, i32)>,
+}
+impl Default for Guidance {
+    fn default() -> Self {
+        Guidance { off: false, rescale: 0.0, scales: Vec::new(), t_range: None }
+    }
+}
+impl Guidance {
+    fn to_c(&self) -> ffi::sdxl_guidance {
+        let mut g: ffi::sdxl_guidance = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sdxl_guidance_default(&mut g) };
+        g.mode = if self.off { ffi::SDXL_GUIDANCE_OFF as i32 } else { ffi::SDXL_GUIDANCE_CFG as i32 };
+        g.rescale = self.rescale;
+        g.n_scales = self.scales.len() as i32;      // more than 8: the engine reports it
+        for (dst, src) in g.scales.iter_mut().zip(self.scales.iter()) {
+            *dst = *src;
+        }
+        if let Some((lo, hi)) = self.t_range {
+            g.t_lo = lo;
+            g.t_hi = hi;
+        }
+        g
+    }
+}
 impl<B: BurnBackend> Drop for Diffuser<B> {
     fn drop(&mut self) {
         unsafe { ffi::sdxl_diffuser_destroy(self.raw) };
@@ -486,6 +521,13 @@ impl<B: BurnBackend> Diffuser<B> {
         let mut v: c_int = 0;
         check(unsafe { ffi::sdxl_diffuser_get_solver(self.raw, &mut v) });
         if v == Solver::Dpmpp2M as c_int { Solver::Dpmpp2M } else { Solver::Ddim }
+    }
+    /// every following trajectory of this handle runs `guidance` (`sdxl_diffuser_set_guidance`); options the engine refuses
+    /// (`sdxl_guidance_check`: values out of range, anything but the default or `off` on a refiner) are an `Err` with its message and
+    /// leave the handle as it was
+    pub fn set_guidance(&self, guidance: &Guidance) -> Result<(), Box<dyn std::error::Error>> {
+        let g = guidance.to_c();
+        try_check(unsafe { ffi::sdxl_diffuser_set_guidance(self.raw, &g) })
     }
     fn entry_seeds(seed: u64, conditioning: &Conditioning<B>) -> Vec<u64> {
         let [n, _, _] = conditioning.context_full.dims();

@@ -75,6 +75,23 @@ class LoraEntry(ctypes.Structure):
     _fields_ = [("param_index", ctypes.c_int32), ("rank", ctypes.c_int32), ("left", _f_p), ("right", _f_p), ("scale", ctypes.c_float)]
 
 
+class Guidance(ctypes.Structure):
+    """sdxl_guidance: a Diffuser handle's guidance options (Diffuser.set_guidance builds one from keywords; guidance_default() is the default)"""
+    _fields_ = [("mode", ctypes.c_int32), ("rescale", ctypes.c_float), ("n_scales", ctypes.c_int32), ("scales", ctypes.c_float * 8),
+                ("t_lo", ctypes.c_int32), ("t_hi", ctypes.c_int32)]
+
+    def __eq__(self, other):
+        return isinstance(other, Guidance) and bytes(self) == bytes(other)
+
+    def __repr__(self):
+        return (f"Guidance(mode={self.mode}, rescale={self.rescale}, scales={list(self.scales)[:self.n_scales]}, "
+                f"t_range=({self.t_lo}, {self.t_hi}))")
+
+
+GUIDANCE_CFG = 0     # SDXL_GUIDANCE_CFG: classifier-free guidance (default)
+GUIDANCE_OFF = 1     # SDXL_GUIDANCE_OFF: the conditional branch alone (distilled checkpoints); unconditional tensors may be None
+_GUIDANCE_MODES = {"cfg": GUIDANCE_CFG, "off": GUIDANCE_OFF}
+
 LORA_ROUND_F16 = 1   # SDXL_LORA_ROUND_F16: adapted tensors rounded to f16 values after merging (what a half-precision record saved after merging holds)
 
 
@@ -90,6 +107,7 @@ ABI_SYMBOLS = [
     "sdxl_diffuser_enable_step_timing", "sdxl_diffuser_step_times", "sdxl_diffuser_set_trace",
     "sdxl_gen_noise", "sdxl_sample_latent_seeded", "sdxl_sample_latent_with_inpainting_seeded", "sdxl_refine_latent_seeded",
     "sdxl_diffuser_set_solver", "sdxl_diffuser_get_solver", "sdxl_solver_coefficients",
+    "sdxl_guidance_default", "sdxl_guidance_check", "sdxl_diffuser_set_guidance", "sdxl_diffuser_get_guidance", "sdxl_cfg_rescale_factors",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -136,6 +154,14 @@ def lib() -> ctypes.CDLL:
             l.sdxl_diffuser_get_solver.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
             l.sdxl_solver_coefficients.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                    ctypes.c_void_p, ctypes.c_int]
+        if hasattr(l, "sdxl_cfg_rescale_factors"):
+            l.sdxl_guidance_default.restype = None
+            l.sdxl_guidance_default.argtypes = [ctypes.POINTER(Guidance)]
+            l.sdxl_guidance_check.argtypes = [ctypes.POINTER(Guidance), ctypes.c_int]
+            l.sdxl_diffuser_set_guidance.argtypes = [ctypes.c_void_p, ctypes.POINTER(Guidance)]
+            l.sdxl_diffuser_get_guidance.argtypes = [ctypes.c_void_p, ctypes.POINTER(Guidance)]
+            l.sdxl_cfg_rescale_factors.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_float, ctypes.c_void_p]
         _lib = l
     return _lib
 
@@ -751,6 +777,55 @@ def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp
     return out
 
 
+def guidance_default() -> Guidance:
+    """sdxl_guidance_default (host logic: no GPU needed)"""
+    g = Guidance()
+    lib().sdxl_guidance_default(ctypes.byref(g))
+    return g
+
+
+def make_guidance(mode="cfg", rescale: float = 0.0, scales=None, t_range=None) -> Guidance:
+    """a Guidance from keywords: mode "cfg" / "off" (or the GUIDANCE_* value), rescale = phi of CFG rescale, scales = one guidance scale per
+    batch entry (replaces the call's scalar), t_range = (t_lo, t_hi): guidance only on iterations with t_lo <= t <= t_hi.  Nothing is
+    checked here: guidance_check / Diffuser.set_guidance report what the engine refuses."""
+    g = guidance_default()
+    if isinstance(mode, str):
+        if mode not in _GUIDANCE_MODES:
+            raise InvalidArgument(f"unknown guidance mode {mode!r}: one of {sorted(_GUIDANCE_MODES)}")
+        mode = _GUIDANCE_MODES[mode]
+    g.mode, g.rescale = int(mode), float(rescale)
+    if scales is not None:
+        v = [float(x) for x in scales]
+        g.n_scales = len(v)       # more than 8 travels on as a count: the engine reports it
+        for b, x in enumerate(v[:8]):
+            g.scales[b] = x
+    if t_range is not None:
+        g.t_lo, g.t_hi = int(t_range[0]), int(t_range[1])
+    return g
+
+
+def guidance_check(g: Guidance, is_refiner: bool = False):
+    """sdxl_guidance_check (host logic, no GPU needed): raises InvalidArgument with the first complaint"""
+    _check_invalid(lib().sdxl_guidance_check(ctypes.byref(g), int(is_refiner)))
+
+
+def cfg_rescale_factors(ctx: Context, eps, scales, rescale: float):
+    """sdxl_cfg_rescale_factors, the op the sampler runs under CFG rescale: eps [2n, HW, 4] float32 CUDA tensor (UNet output rows, cond entries
+    first), scales: n guidance scales -> float32 CUDA tensor [n] of f_b = fma(rescale, sqrt(M2(ec_b) / M2(ecfg_b)), 1 - rescale)"""
+    torch = _torch()
+    eps, pe = _dev(eps)
+    if eps.dim() != 3 or eps.shape[0] % 2 or eps.shape[2] != 4:
+        raise InvalidArgument("eps must be [2n, HW, 4]")
+    n, HW = int(eps.shape[0]) // 2, int(eps.shape[1])
+    v = [float(x) for x in scales]
+    if len(v) != n:
+        raise InvalidArgument(f"expected {n} scales (one per batch entry), got {len(v)}")
+    out = torch.empty((n,), dtype=torch.float32, device="cuda")
+    _check_invalid(lib().sdxl_cfg_rescale_factors(ctx.h, _stream(), pe, n, HW, (ctypes.c_float * max(n, 1))(*v), ctypes.c_float(rescale),
+                                                  ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 def _seeds(seeds, n: int):
     """host uint64 array [n] (None stays NULL: the engine reports it)"""
     if seeds is None:
@@ -823,7 +898,7 @@ class Diffuser:
         c, keep = conditioning.to_c()
         if seeds is not None or noise0 is None:
             out = torch.empty(self._latent_shape(conditioning), dtype=torch.float32, device="cuda")
-            _check(lib().sdxl_sample_latent_seeded(self.h, _stream(), ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+            _check_invalid(lib().sdxl_sample_latent_seeded(self.h, _stream(), ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
                                                   n_steps, _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
                                                   ctypes.c_void_p(out.data_ptr())))
             return out
@@ -831,7 +906,7 @@ class Diffuser:
         noise0, pn = _dev(noise0)
         assert tuple(noise0.shape) == self._latent_shape(conditioning)
         out = torch.empty_like(noise0)
-        _check(lib().sdxl_sample_latent(self.h, _stream(), ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+        _check_invalid(lib().sdxl_sample_latent(self.h, _stream(), ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
                                        n_steps, pn, ctypes.c_void_p(out.data_ptr())))
         return out
 
@@ -845,7 +920,7 @@ class Diffuser:
             reference, pr = _dev(reference)
             mask, pm = _dev(mask, torch.uint8)
             out = torch.empty_like(reference)
-            _check(lib().sdxl_sample_latent_with_inpainting_seeded(self.h, _stream(), ctypes.byref(c),
+            _check_invalid(lib().sdxl_sample_latent_with_inpainting_seeded(self.h, _stream(), ctypes.byref(c),
                                                                   ctypes.c_double(unconditional_guidance_scale), n_steps, pr, pm,
                                                                   _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
                                                                   ctypes.c_void_p(out.data_ptr())))
@@ -856,7 +931,7 @@ class Diffuser:
         mask, pm = _dev(mask, torch.uint8)
         step_noise, ps = _dev(step_noise)
         out = torch.empty_like(noise0)
-        _check(lib().sdxl_sample_latent_with_inpainting(self.h, _stream(), ctypes.byref(c),
+        _check_invalid(lib().sdxl_sample_latent_with_inpainting(self.h, _stream(), ctypes.byref(c),
                                                        ctypes.c_double(unconditional_guidance_scale), n_steps, pr, pm, pn,
                                                        ps, ctypes.c_void_p(out.data_ptr())))
         return out
@@ -869,14 +944,14 @@ class Diffuser:
         latent, pl = _dev(latent)
         if seeds is not None or noise is None:
             out = torch.empty_like(latent)
-            _check(lib().sdxl_refine_latent_seeded(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+            _check_invalid(lib().sdxl_refine_latent_seeded(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
                                                   step_start, n_steps, _seeds(seeds, out.shape[0]), ctypes.c_double(eta),
                                                   ctypes.c_void_p(out.data_ptr())))
             return out
         _explicit_eta(eta)
         noise, pn = _dev(noise)
         out = torch.empty_like(latent)
-        _check(lib().sdxl_refine_latent(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
+        _check_invalid(lib().sdxl_refine_latent(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale),
                                        step_start, n_steps, pn, ctypes.c_void_p(out.data_ptr())))
         return out
 
@@ -889,6 +964,22 @@ class Diffuser:
         v = ctypes.c_int(-1)
         _check(lib().sdxl_diffuser_get_solver(self.h, ctypes.byref(v)))
         return {v: k for k, v in _SOLVER_NAMES.items()}[v.value]
+
+    def set_guidance(self, guidance: Optional[Guidance] = None, **options):
+        """sdxl_diffuser_set_guidance: the guidance options every following trajectory of this handle runs -- a Guidance, or the keywords of
+        make_guidance (mode=, rescale=, scales=, t_range=); no argument restores the default.  Options the engine refuses raise
+        InvalidArgument and the handle keeps what it had."""
+        if guidance is not None and options:
+            raise InvalidArgument("give a Guidance or keywords, not both")
+        if options:
+            guidance = make_guidance(**options)
+        _check_invalid(lib().sdxl_diffuser_set_guidance(self.h, None if guidance is None else ctypes.byref(guidance)))
+
+    @property
+    def guidance(self) -> Guidance:
+        g = Guidance()
+        _check(lib().sdxl_diffuser_get_guidance(self.h, ctypes.byref(g)))
+        return g
 
     def enable_step_timing(self, enabled: bool = True):
         _check(lib().sdxl_diffuser_enable_step_timing(self.h, int(enabled)))

@@ -534,6 +534,13 @@ void sdxl_diffuser_destroy(sdxl_diffuser* d) {
 }
 sdxl_unet* sdxl_diffuser_unet(sdxl_diffuser* d) { return d ? &d->view : nullptr; }
 
+// per-entry guidance scales are one per batch entry of the call: refused before anything is launched
+static const char* guidance_call_error(const sdxl_diffuser* d, const sdxl_conditioning* c) {
+  if (!d || !c) return nullptr;     // reported by the call itself
+  const Guidance& g = d->d->guidance();
+  if (g.n_scales != 0 && g.n_scales != c->n) return "guidance: n_scales differs from the batch (cond.n)";
+  return nullptr;
+}
 static Conditioning to_cond(const sdxl_conditioning* c) {
   SDXL_REQUIRE(c != nullptr, "null conditioning");
   Conditioning o;
@@ -550,6 +557,7 @@ static Conditioning to_cond(const sdxl_conditioning* c) {
 }
 int sdxl_sample_latent(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double cfg, int n_steps,
                        const float* noise0, float* out) {
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && noise0 && out, "null argument");
   use(d->ctx);
@@ -559,6 +567,7 @@ int sdxl_sample_latent(sdxl_diffuser* d, void* stream, const sdxl_conditioning* 
 int sdxl_sample_latent_with_inpainting(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double cfg, int n_steps,
                                        const float* reference, const uint8_t* mask, const float* noise0,
                                        const float* step_noise, float* out) {
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && noise0 && out, "null argument");
   use(d->ctx);
@@ -567,6 +576,7 @@ int sdxl_sample_latent_with_inpainting(sdxl_diffuser* d, void* stream, const sdx
 }
 int sdxl_refine_latent(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond, double cfg,
                        int step_start, int n_steps, const float* noise, float* out) {
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && latent && noise && out, "null argument");
   use(d->ctx);
@@ -591,6 +601,7 @@ int sdxl_gen_noise(sdxl_ctx* ctx, void* stream, const uint64_t* seeds, uint32_t 
 int sdxl_sample_latent_seeded(sdxl_diffuser* d, void* stream, const sdxl_conditioning* cond, double cfg, int n_steps,
                               const uint64_t* seeds, double eta, float* out) {
   if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && out, "null argument");
   use(d->ctx);
@@ -601,6 +612,7 @@ int sdxl_sample_latent_with_inpainting_seeded(sdxl_diffuser* d, void* stream, co
                                               const float* reference, const uint8_t* mask, const uint64_t* seeds, double eta,
                                               float* out) {
   if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && out, "null argument");
   use(d->ctx);
@@ -610,6 +622,7 @@ int sdxl_sample_latent_with_inpainting_seeded(sdxl_diffuser* d, void* stream, co
 int sdxl_refine_latent_seeded(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond, double cfg,
                               int step_start, int n_steps, const uint64_t* seeds, double eta, float* out) {
   if (const char* m = seeded_args_error(seeds, eta)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   SDXL_REQUIRE(d && latent && out, "null argument");
   use(d->ctx);
@@ -650,6 +663,56 @@ int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps
   std::vector<double> rows((size_t)4 * iters);
   Diffuser::solver_coefficients(alphas.data(), n_train_steps, n_steps, step_start, solver, eta, rows.data());
   std::copy(rows.begin(), rows.end(), out);
+  API_END
+}
+// guidance: a per-handle option; options the check refuses are an argument error and leave the handle as it was
+static Guidance to_guidance(const sdxl_guidance* g) {
+  Guidance o;
+  if (!g) return o;
+  o.mode = g->mode; o.rescale = g->rescale; o.n_scales = g->n_scales; o.t_lo = g->t_lo; o.t_hi = g->t_hi;
+  for (int b = 0; b < kMaxSeeds; ++b) o.scales[b] = g->scales[b];
+  return o;
+}
+void sdxl_guidance_default(sdxl_guidance* g) {
+  if (!g) return;
+  const Guidance o;
+  g->mode = o.mode; g->rescale = o.rescale; g->n_scales = o.n_scales; g->t_lo = o.t_lo; g->t_hi = o.t_hi;
+  for (int b = 0; b < kMaxSeeds; ++b) g->scales[b] = o.scales[b];
+}
+int sdxl_guidance_check(const sdxl_guidance* g, int is_refiner) {
+  if (!g) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = Diffuser::guidance_error(to_guidance(g), is_refiner != 0)) return fail(SDXL_ERR_INVALID, m);
+  return SDXL_OK;
+}
+int sdxl_diffuser_set_guidance(sdxl_diffuser* d, const sdxl_guidance* g) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  const Guidance o = to_guidance(g);
+  if (const char* m = Diffuser::guidance_error(o, d->d->is_refiner())) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  d->d->set_guidance(o);
+  API_END
+}
+int sdxl_diffuser_get_guidance(sdxl_diffuser* d, sdxl_guidance* out) {
+  if (!d || !out) return fail(SDXL_ERR_INVALID, "null argument");
+  const Guidance& o = d->d->guidance();
+  out->mode = o.mode; out->rescale = o.rescale; out->n_scales = o.n_scales; out->t_lo = o.t_lo; out->t_hi = o.t_hi;
+  for (int b = 0; b < kMaxSeeds; ++b) out->scales[b] = o.scales[b];
+  return SDXL_OK;
+}
+int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int n, int HW, const float* scales, float rescale,
+                             float* factors_out) {
+  if (!ctx || !eps || !scales || !factors_out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (n < 1 || n > kMaxSeeds || HW < 1 || HW > 1 << 22) return fail(SDXL_ERR_INVALID, "cfg_rescale_factors: n (1..8) or HW (1..2^22) out of range");
+  if (!(rescale >= 0.f && rescale <= 1.f)) return fail(SDXL_ERR_INVALID, "guidance: rescale must be a finite value in [0, 1]");
+  API_BEGIN
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  CfgScales k{};
+  for (int b = 0; b < n; ++b) k.v[b] = scales[b];
+  Tmp tmp;
+  float* partials = (float*)tmp.get(cfg_moments_floats(n, HW) * sizeof(float));
+  launch_cfg_rescale_factors(eps, DT_F32, 4, n, HW, k, rescale, partials, factors_out, s);
+  SDXL_HIP(hipStreamSynchronize(s));     // the scratch goes away with this call
   API_END
 }
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled) {

@@ -759,6 +759,192 @@ void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s) {
   }
   hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, do_update);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Guidance options (kernels.h GuidedParams): CFG rescale factors, then the per-step kernel with the guidance lines.
+// Chan merge of (nb, mb, M2b) into (na, ma, M2a), as in norm.hip
+__device__ __forceinline__ void moments_merge(float& na, float& ma, float& m2a, float nb, float mb, float m2b) {
+  if (nb == 0.f) return;
+  const float n = na + nb;
+  const float d = mb - ma;
+  const float f = nb / n;
+  ma = ma + d * f;
+  m2a = m2a + m2b + d * d * na * f;
+  na = n;
+}
+// One thread per latent pixel, grid (ceil(HW / 256), n): blockIdx.y is the entry, so the partition of an entry's pixels depends on HW alone.
+// Each thread turns its four channel values of ec and of ecfg = fma(ec - eu, s_b, eu) into (4, mean, M2); lanes merge downwards
+// (lane l takes lane l + o, o = 32 .. 1), wave 0..3 in order through LDS, and thread 0 leaves the block's two triples at
+// partials[(b * blocks + block) * 6 ..].  Values are taken relative to the entry's pixel 0, channel 0 (M2 does not move under a shift, and
+// every difference is then of the size of the spread, not of the mean): the means of the triples are relative to that pivot.
+__global__ __launch_bounds__(kCfgMomentsBlock) void cfg_moments_kernel(const void* eps, int eps_dt, int eps_ld, int n, int HW,
+                                                                       CfgScales scales, float* partials) {
+#pragma clang fp contract(off)
+  __shared__ float wave_part[kCfgMomentsBlock / 64][6];
+  const int b = blockIdx.y;
+  const int hw = blockIdx.x * kCfgMomentsBlock + threadIdx.x;
+  const float sb = scales.v[b];
+  const float pivot_c = ld_f(eps, (size_t)b * HW * eps_ld, eps_dt);
+  const float pivot_u = ld_f(eps, (size_t)(n + b) * HW * eps_ld, eps_dt);
+  const float pivot_g = __builtin_fmaf(pivot_c - pivot_u, sb, pivot_u);
+  float cnt = 0.f, mc = 0.f, qc = 0.f, mg = 0.f, qg = 0.f;
+  if (hw < HW) {
+    float dc[4], dg[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float ec = ld_f(eps, ((size_t)b * HW + hw) * eps_ld + c, eps_dt);
+      const float eu = ld_f(eps, ((size_t)(n + b) * HW + hw) * eps_ld + c, eps_dt);
+      dc[c] = ec - pivot_c;
+      dg[c] = __builtin_fmaf(ec - eu, sb, eu) - pivot_g;
+    }
+    cnt = 4.f;
+    mc = ((dc[0] + dc[1]) + (dc[2] + dc[3])) * 0.25f;
+    mg = ((dg[0] + dg[1]) + (dg[2] + dg[3])) * 0.25f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      qc = __builtin_fmaf(dc[c] - mc, dc[c] - mc, qc);
+      qg = __builtin_fmaf(dg[c] - mg, dg[c] - mg, qg);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float nb = __shfl_down(cnt, o), mcb = __shfl_down(mc, o), qcb = __shfl_down(qc, o), mgb = __shfl_down(mg, o), qgb = __shfl_down(qg, o);
+    float ng = cnt;
+    moments_merge(cnt, mc, qc, nb, mcb, qcb);
+    moments_merge(ng, mg, qg, nb, mgb, qgb);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    wave_part[wave][0] = cnt; wave_part[wave][1] = mc; wave_part[wave][2] = qc;
+    wave_part[wave][3] = cnt; wave_part[wave][4] = mg; wave_part[wave][5] = qg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ng = cnt;
+    for (int w = 1; w < kCfgMomentsBlock / 64; ++w) {
+      moments_merge(cnt, mc, qc, wave_part[w][0], wave_part[w][1], wave_part[w][2]);
+      moments_merge(ng, mg, qg, wave_part[w][3], wave_part[w][4], wave_part[w][5]);
+    }
+    float* out = partials + ((size_t)b * gridDim.x + blockIdx.x) * 6;
+    out[0] = cnt; out[1] = mc; out[2] = qc; out[3] = ng; out[4] = mg; out[5] = qg;
+  }
+}
+// One wavefront per entry: 64 partials at a time are loaded one per lane, then merged in block-index order (every lane runs the same merge on
+// the broadcast values, so the chain is arithmetic, not loads).  f_b = fma(phi, sqrt(M2c / M2g), 1 - phi); M2g == 0 gives 1.
+__global__ __launch_bounds__(64) void cfg_factor_kernel(const float* partials, int blocks, float phi, float* factors) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* part = partials + (size_t)b * blocks * 6;
+  float nc = 0.f, mc = 0.f, qc = 0.f, ng = 0.f, mg = 0.f, qg = 0.f;
+  for (int base = 0; base < blocks; base += 64) {
+    float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (base + lane < blocks) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) v[j] = part[(size_t)(base + lane) * 6 + j];
+    }
+    const int m = min(64, blocks - base);
+    for (int j = 0; j < m; ++j) {
+      moments_merge(nc, mc, qc, __shfl(v[0], j), __shfl(v[1], j), __shfl(v[2], j));
+      moments_merge(ng, mg, qg, __shfl(v[3], j), __shfl(v[4], j), __shfl(v[5], j));
+    }
+  }
+  if (lane == 0) factors[b] = qg == 0.f ? 1.f : __builtin_fmaf(phi, sqrtf(qc / qg), 1.f - phi);
+}
+void launch_cfg_rescale_factors(const void* eps, int eps_dt, int eps_ld, int n, int HW, const CfgScales& scales, float phi, float* partials,
+                                float* factors, hipStream_t s) {
+  const int blocks = cfg_moments_blocks(HW);
+  hipLaunchKernelGGL(cfg_moments_kernel, dim3(blocks, n), dim3(kCfgMomentsBlock), 0, s, eps, eps_dt, eps_ld, n, HW, scales, partials);
+  hipLaunchKernelGGL(cfg_factor_kernel, dim3(n), dim3(64), 0, s, (const float*)partials, blocks, phi, factors);
+}
+// The update launch of a handle with guidance options: ddim_kernel (SOLVER = kSolverDdim) or dpmpp2m_kernel (kSolverDpmpp2M) at do_update = 1
+// and use_cfg = 1, line for line -- the channel-0/1 rounding of the DDIM update included -- except the one CFG line, which becomes
+//     active iteration (g.active[idx]):  e = fma(ec - eu, g.scales.v[b], eu);  e = e * g.factors[b] where g.factors != nullptr
+//     inactive iteration:                e = ec   (eu is not read)
+// With scales all equal to the call's scalar, no factors and every iteration active this is the default kernel's arithmetic bit for bit.
+template <int SOLVER, bool SEEDED>
+__global__ void guided_step_kernel(const DdimParams p, const GuidedParams g) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)p.n * p.HW) return;
+  const int b = i / p.HW;
+  const int hw = i - (size_t)b * p.HW;
+  const int idx = *p.step_idx;
+  const int next = idx + 1;
+  const bool active = g.active[idx] != 0;
+  const float sb = g.scales.v[b];
+  const float fb = active && g.factors ? g.factors[b] : 1.f;
+  float x[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = p.latent[((size_t)b * 4 + c) * p.HW + hw];
+  const StepCoef k = p.table[idx];
+  float x0p[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (SOLVER == kSolverDpmpp2M) {
+    if (k.c_1 != 0.f) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
+    float e = ec;
+    if (active) {
+      const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
+      e = __builtin_fmaf(ec - eu, sb, eu);
+      if (g.factors) e = e * fb;
+    }
+    const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
+    if constexpr (SOLVER == kSolverDpmpp2M) {
+      p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
+      float acc = k.c_1 * x0p[c];
+      acc = __builtin_fmaf(x0, k.c_0, acc);
+      x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+    } else {
+      const float en = e * k.sqrt_1map;
+      x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
+    }
+  }
+  if constexpr (SEEDED) {
+    const float cz = SOLVER == kSolverDpmpp2M ? k.c_z : k.sigma;
+    if (cz != 0.f) {
+      float z[4];
+      seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], cz, x[c]);
+    }
+  }
+  if (p.mask && next < p.n_steps_total) {
+    const StepCoef kn = p.table[next];
+    float z[4];
+    if constexpr (SEEDED) seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_blend((uint32_t)next), z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const size_t e = ((size_t)b * 4 + c) * p.HW + hw;
+      if (!p.mask[e]) {
+        float zn;
+        if constexpr (SEEDED) zn = z[c]; else zn = p.step_noise[(size_t)next * p.n * 4 * p.HW + e];
+        x[c] = p.ref[e] * kn.sqrt_a + zn * kn.sqrt_1ma;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) p.latent[((size_t)b * 4 + c) * p.HW + hw] = x[c];
+  for (int r = 0; r < p.in_rep; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) st_f(p.unet_in, ((size_t)(r * p.n + b) * p.HW + hw) * p.in_ld + c, p.in_dt, x[c]);
+}
+void launch_guided_step(const DdimParams& p, const GuidedParams& g, hipStream_t s) {
+  const size_t total = (size_t)p.n * p.HW;
+  const dim3 grid((total + 255) / 256), block(256);
+  if (p.solver == kSolverDpmpp2M) {
+    if (p.seeded) hipLaunchKernelGGL((guided_step_kernel<kSolverDpmpp2M, true>), grid, block, 0, s, p, g);
+    else hipLaunchKernelGGL((guided_step_kernel<kSolverDpmpp2M, false>), grid, block, 0, s, p, g);
+  } else {
+    if (p.seeded) hipLaunchKernelGGL((guided_step_kernel<kSolverDdim, true>), grid, block, 0, s, p, g);
+    else hipLaunchKernelGGL((guided_step_kernel<kSolverDdim, false>), grid, block, 0, s, p, g);
+  }
+  hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, 1);
+}
 __global__ void axpby_kernel(float* dst, const float* a, float sa, const float* b, float sb, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = a[i] * sa + b[i] * sb;

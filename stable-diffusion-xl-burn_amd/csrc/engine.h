@@ -585,6 +585,17 @@ extern bool g_debug_no_cfg;   // sdxl_debug_set("no_cfg"): base model without th
                               // measurement builds only)
 #endif
 
+// sdxl_guidance of the public header: how the two branches of an iteration become e (formulas there)
+constexpr int kGuidanceCfg = 0, kGuidanceOff = 1;
+struct Guidance {
+  int mode = kGuidanceCfg;
+  float rescale = 0.f;
+  int n_scales = 0;
+  float scales[kMaxSeeds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int t_lo = 0, t_hi = 0x7fffffff;
+  bool plain() const { return mode == kGuidanceCfg && rescale == 0.f && n_scales == 0 && t_lo == 0 && t_hi == 0x7fffffff; }
+};
+
 class Diffuser {
  public:
   Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, const float* alphas_host, int n_train,
@@ -616,6 +627,13 @@ class Diffuser {
   // kSolverDdim (default) or kSolverDpmpp2M: the update every following trajectory of this handle runs
   void set_solver(int solver);
   int solver() const { return solver_; }
+  // guidance options, a per-handle choice like the solver.  guidance_error: host logic only -- the first complaint about `g` (for a refiner
+  // handle: anything but the default or kGuidanceOff), nullptr where it is valid.  set_guidance requires a valid `g`.  A handle with
+  // Guidance{} launches exactly what it launched before the options existed; kGuidanceOff runs the conditional branch alone (batch n).
+  static const char* guidance_error(const Guidance& g, bool is_refiner);
+  void set_guidance(const Guidance& g);
+  const Guidance& guidance() const { return guidance_; }
+  bool is_refiner() const { return is_refiner_; }
   std::vector<float> step_ms;   // per-iteration GPU time of the last trajectory (hipEvent), for "UNet step ms p50"
   bool time_steps = false;
   // parity instrumentation: after DDIM iteration i the latent [n,4,h,w] is copied to trace + i * numel (device, caller-owned)
@@ -635,6 +653,11 @@ class Diffuser {
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
   float* hist_ = nullptr; size_t hist_cap_ = 0;       // kSolverDpmpp2M: x0 of the previous iteration [n,4,h,w], allocated with the latent
   int solver_ = kSolverDdim;
+  Guidance guidance_;
+  // non-default guidance only: the per-iteration active flags next to the table, the CFG rescale partials and the n factors
+  int* active_ = nullptr; int active_cap_ = 0;
+  float* moments_ = nullptr; size_t moments_cap_ = 0;
+  float* factors_ = nullptr;
   StepCoef* table_ = nullptr; int table_cap_ = 0;
   int* step_idx_ = nullptr; float* t_dev_ = nullptr;
   float* ctx_buf_ = nullptr; size_t ctx_cap_ = 0;     // [2n][77][ctx] cond then uncond

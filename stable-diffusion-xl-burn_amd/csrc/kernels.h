@@ -370,6 +370,26 @@ struct DdimParams {
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
 // input and timestep.  do_update=1: DDIM (or, p.solver, DPM-Solver++(2M)) update with table[*step_idx], blend for the next step, then advances.
 void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s);
+// Guidance options (include/sdxl_mi355.h, sdxl_guidance): what a handle with non-default options runs in place of the update launch of
+// launch_ddim_step.  On an active iteration e = fma(ec - eu, scales[b], eu), times factors[b] where factors != nullptr (CFG rescale);
+// on an inactive one e = ec.  Everything behind e is the text of ddim_kernel / dpmpp2m_kernel.
+struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, passed by value in the kernel arguments like the seeds
+struct GuidedParams {
+  CfgScales scales;
+  const int* active;         // device [iterations]: 1 where guidance is on at that iteration's timestep (read at *step_idx)
+  const float* factors;      // device [n]: f_b of this iteration, left by launch_cfg_rescale_factors on the same stream; nullptr = no rescale
+};
+// the do_update = 1 launch pair of launch_ddim_step (update kernel + advance) with the guidance lines; p.use_cfg must be 1
+void launch_guided_step(const DdimParams& p, const GuidedParams& g, hipStream_t s);
+// CFG rescale (Lin et al. 2023, section 3.4): factors[b] = fma(phi, sqrt(M2(ec_b) / M2(ecfg_b)), 1 - phi), M2 the centred sum of squares over the
+// 4 * HW values of entry b, ecfg = fma(ec - eu, scales[b], eu); M2(ecfg_b) == 0 gives 1.  eps: rows [2n][HW][eps_ld] of eps_dt, cond entries
+// first.  Two launches: per-block (count, mean, M2) partials, grid (cfg_moments_blocks(HW), n), then one block per entry that merges them in
+// block-index order.  partials: device scratch of cfg_moments_floats(n, HW) floats.  No atomics: an entry's factor has the same bits alone and batched.
+constexpr int kCfgMomentsBlock = 256;
+inline int cfg_moments_blocks(int HW) { return (HW + kCfgMomentsBlock - 1) / kCfgMomentsBlock; }
+inline size_t cfg_moments_floats(int n, int HW) { return (size_t)n * cfg_moments_blocks(HW) * 6; }
+void launch_cfg_rescale_factors(const void* eps, int eps_dt, int eps_ld, int n, int HW, const CfgScales& scales, float phi, float* partials,
+                                float* factors, hipStream_t s);
 // gen_noise (:378-388) with a seed: out [n][4][HW] fp32, entry b from seeds[b] (host array, n <= kMaxSeeds per launch), the
 // same values the seeded ddim kernel draws in registers for (seed, hw, draw)
 void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n, int HW, hipStream_t s);

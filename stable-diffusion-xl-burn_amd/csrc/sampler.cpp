@@ -12,6 +12,9 @@
 //     blend (:463) and the gen_noise()*sigma term (:427, sigma from eta) in the registers of the per-step kernel.
 //   * the update itself is a per-handle choice (set_solver): the reference's DDIM, or DPM-Solver++(2M) on the same schedule, same table
 //     mechanism and same fused kernel position, with one more latent-sized buffer for the previous data prediction.
+//   * how the pair becomes e is a per-handle choice too (set_guidance): the reference's one line by default; the conditional branch alone as a
+//     batch-n forward; or per-entry scales, a timestep interval and CFG rescale, run by launch_guided_step in the per-step kernel's place with
+//     two small launches in front of it where rescale is on.  A handle with default options launches what it always launched.
 #include "engine.h"
 
 #include <algorithm>
@@ -38,7 +41,8 @@ Diffuser::Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSour
   SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
 }
 Diffuser::~Diffuser() {
-  for (void* p : {(void*)latent_, (void*)noise_, (void*)hist_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_})
+  for (void* p : {(void*)latent_, (void*)noise_, (void*)hist_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_,
+                  (void*)active_, (void*)moments_, (void*)factors_})
     if (p) (void)hipFree(p);
 }
 
@@ -52,6 +56,25 @@ static void ddim_terms(double a, double ap, double eta, double& sqrt_ap, double&
 void Diffuser::set_solver(int solver) {
   SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
   solver_ = solver;
+}
+
+const char* Diffuser::guidance_error(const Guidance& g, bool is_refiner) {
+  if (g.mode != kGuidanceCfg && g.mode != kGuidanceOff) return "guidance: unknown mode (SDXL_GUIDANCE_CFG, SDXL_GUIDANCE_OFF)";
+  if (!(g.rescale >= 0.f && g.rescale <= 1.f)) return "guidance: rescale must be a finite value in [0, 1]";
+  if (g.n_scales < 0 || g.n_scales > kMaxSeeds) return "guidance: n_scales out of range (0..8)";
+  for (int b = 0; b < g.n_scales; ++b)
+    if (!std::isfinite(g.scales[b])) return "guidance: scales must be finite";
+  if (g.t_lo < 0 || g.t_lo > g.t_hi) return "guidance: interval needs 0 <= t_lo <= t_hi";
+  if (g.mode == kGuidanceOff && (g.rescale != 0.f || g.n_scales != 0 || g.t_lo != 0 || g.t_hi != 0x7fffffff))
+    return "guidance: SDXL_GUIDANCE_OFF takes no rescale, scales or interval";
+  if (is_refiner && !(g.plain() || g.mode == kGuidanceOff))
+    return "guidance: a refiner handle has no unconditional branch (default options or SDXL_GUIDANCE_OFF only)";
+  return nullptr;
+}
+void Diffuser::set_guidance(const Guidance& g) {
+  const char* m = guidance_error(g, is_refiner_);
+  SDXL_REQUIRE(m == nullptr, m ? m : "");
+  guidance_ = g;
 }
 
 void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out) {
@@ -102,14 +125,26 @@ bool g_debug_no_cfg = false;
 static constexpr bool g_debug_no_cfg = false;
 #endif
 
+static void ensure_latent(float*& buf, size_t& cap, size_t elems) {
+  if (elems > cap) {
+    if (buf) SDXL_HIP(hipFree(buf));
+    SDXL_HIP(hipMalloc((void**)&buf, elems * sizeof(float)));
+    cap = elems;
+  }
+}
+
 void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale,
                        const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s,
                        const uint64_t* seeds, double eta) {
   // diffuse_latent :390-432 / diffuse_latent_with_inpainting :434-483
   UNet& u = *unet_;
   const UNetCfg& uc = u.cfg();
-  const bool single = is_refiner_ || g_debug_no_cfg;   // debug knob: conditional branch only (concurrency experiments)
+  const Guidance& go = guidance_;
+  // kGuidanceOff: conditional branch only, as for a refiner (debug knob: the same for concurrency experiments)
+  const bool single = is_refiner_ || go.mode == kGuidanceOff || g_debug_no_cfg;
+  const bool guided = !single && !go.plain();          // non-default options: the update launch is launch_guided_step
   const int n = c.n, B = single ? n : 2 * n;
+  SDXL_REQUIRE(!guided || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
   SDXL_REQUIRE(n >= 1 && B <= 8, "batch out of range");
   static_assert(kMaxSeeds >= 8, "one seed per batch entry");
   const int h = c.height / 8, w = c.width / 8, HW = h * w;
@@ -147,6 +182,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   const int iters = (int)ts.size();
   const int step_size = n_train_ / n_steps;
   std::vector<StepCoef> tab(iters + 1);
+  std::vector<int> act(guided ? iters : 0);            // guidance interval: iteration i is active where t_lo <= t_i <= t_hi
   std::vector<double> c2m;
   if (solver_ == kSolverDpmpp2M) {
     c2m.resize((size_t)4 * iters);
@@ -171,6 +207,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
       k.sigma = (float)sigma;
     }
     tab[i] = k;
+    if (guided) act[i] = t >= go.t_lo && t <= go.t_hi;
   }
   tab[iters] = StepCoef{};
   if (iters + 1 > table_cap_) {
@@ -179,6 +216,23 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
     table_cap_ = iters + 1;
   }
   SDXL_HIP(hipMemcpyAsync(table_, tab.data(), (size_t)(iters + 1) * sizeof(StepCoef), hipMemcpyHostToDevice, s));
+  GuidedParams gp{};
+  if (guided) {
+    if (iters > active_cap_) {
+      if (active_) SDXL_HIP(hipFree(active_));
+      active_ = nullptr;
+      SDXL_HIP(hipMalloc((void**)&active_, (size_t)iters * sizeof(int)));
+      active_cap_ = iters;
+    }
+    SDXL_HIP(hipMemcpyAsync(active_, act.data(), (size_t)iters * sizeof(int), hipMemcpyHostToDevice, s));
+    for (int b = 0; b < n; ++b) gp.scales.v[b] = go.n_scales ? go.scales[b] : (float)cfg_scale;
+    gp.active = active_;
+    if (go.rescale > 0.f) {
+      ensure_latent(moments_, moments_cap_, cfg_moments_floats(n, HW));
+      if (!factors_) SDXL_HIP(hipMalloc((void**)&factors_, kMaxSeeds * sizeof(float)));
+      gp.factors = factors_;
+    }
+  }
   SDXL_HIP(hipStreamSynchronize(s));   // tab is a stack-owned host buffer
 
   DdimParams p{};
@@ -204,7 +258,12 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   }
   for (int i = 0; i < iters; ++i) {
     u.forward(B, h, w, t_dev_, 0, s);     // one timestep shared by every batch entry (:416)
-    launch_ddim_step(p, 1, s);
+    if (guided) {     // moments, factor, step on an active iteration with rescale; the step kernel alone otherwise
+      if (gp.factors && act[i]) launch_cfg_rescale_factors(p.eps, p.eps_dt, p.eps_ld, n, HW, gp.scales, go.rescale, moments_, factors_, s);
+      launch_guided_step(p, gp, s);
+    } else {
+      launch_ddim_step(p, 1, s);
+    }
     if (trace && i < trace_cap)
       SDXL_HIP(hipMemcpyAsync(trace + (size_t)i * n * 4 * HW, latent, (size_t)n * 4 * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (time_steps) SDXL_HIP(hipEventRecord(ev[i + 1], s));
@@ -217,13 +276,6 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   }
 }
 
-static void ensure_latent(float*& buf, size_t& cap, size_t elems) {
-  if (elems > cap) {
-    if (buf) SDXL_HIP(hipFree(buf));
-    SDXL_HIP(hipMalloc((void**)&buf, elems * sizeof(float)));
-    cap = elems;
-  }
-}
 void Diffuser::ensure_state(size_t elems) {
   ensure_latent(latent_, latent_cap_, elems);
   if (solver_ == kSolverDpmpp2M) ensure_latent(hist_, hist_cap_, elems);
