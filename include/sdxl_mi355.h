@@ -101,7 +101,7 @@ typedef struct {
   const float* channel_context;                       /* [n, adm]              */
   const float* channel_context_refiner;               /* [n, adm_refiner]      */
   int32_t n;                                          /* batch of prompts      */
-  int32_t n_ctx;                                      /* tokens (77)           */
+  int32_t n_ctx;                                      /* tokens: 77 per chunk  */
   int32_t height, width;                              /* resolution: [usize;2] */
 } sdxl_conditioning;
 
@@ -152,8 +152,12 @@ int sdxl_unet_set_graph(sdxl_unet* u, int enabled);   /* hipGraph replay of the 
  * runs as two concurrent batch-1 chains on two streams inside the captured graph, the second released after
  * `release_offset` GEMM launches of the first.  Bit-identical results; measured -2.6 % step time. */
 int sdxl_unet_set_split_cfg(sdxl_unet* u, int enabled, int release_offset);
-/* per-handle option (default on, f16 engines): the transformer blocks' cross-attention (77 context keys; unet/mod.rs:731-795)
- * runs inside the epilogue of the query projection instead of as its own kernel.  Off = projection + attention kernel. */
+/* per-handle option (default on, f16 engines): the transformer blocks' cross-attention (unet/mod.rs:731-795) runs inside the
+ * epilogue of the query projection instead of as its own kernel.  Off = projection + attention kernel.  Up to 96 context keys
+ * (one 77-token prompt chunk) every epilogue form takes it; 97 .. 384 keys (two to four chunks) the f16 engine's weights-in-registers
+ * form walks the context in 96-key blocks with an online softmax (widths that are multiples of 128, whole 64-row blocks per entry;
+ * knob "xattn_long"); the split-precision form and every other shape run projection + attention kernel above 96 keys, as do all
+ * contexts above 384. */
 int sdxl_unet_set_fused_cross_attention(sdxl_unet* u, int enabled);
 /* per-handle option (default on, f16 engines): GroupNorm statistics come out of the producing convolution's epilogue where
  * its kernel can leave them (256-row tiles: the 64^2 / 32^2 levels at 1024^2) -- groupnorm/mod.rs:52-82 without the statistics pass.
@@ -416,6 +420,9 @@ int sdxl_bench_attention(sdxl_ctx* ctx, void* stream, int B, int H, int Nq, int 
  * "wreg_xattn": 0 = the fused query projection + cross-attention of the f16 engine stays on the pipe kernels instead of the weights-in-registers
  *   GEMM with the attention behind its partial-sum exchange (csrc/igemm_wreg.hip, XA instantiation; A/B, default 1; the two sum k in different
  *   orders, so the results differ at rounding level; a UNet picks it up on its next forward, its weight-warming schedule when it is next recorded);
+ * "xattn_long": 0 = contexts of more than 96 keys (prompts of two to four 77-token chunks) keep projection + attention kernel instead of the long form of
+ *   the fused launch (csrc/igemm_common.h xattn_unit_long: 96-key blocks, online softmax; A/B, default 1; results differ at rounding level); read when a
+ *   context is set (sdxl_unet_forward, the trajectory calls), so a UNet picks it up with its next context and re-captures its graph;
  * "igemm_warm": 0 = no weight-warming workgroups (spare workgroups of a weights-in-registers launch read a later GEMM's weights into the
  * Infinity Cache; results unchanged; A/B, default 1; a UNet picks it up on its next forward);
  * "attn_xsplit": 0 = the self-attention of the 32^2 level never runs 1/5 of its heads as two half-key blocks per 64 queries merged across
@@ -514,7 +521,10 @@ int sdxl_layer_norm_linear(sdxl_ctx* ctx, void* stream, const float* x, const fl
 /* LayerNorm -> attn2 query projection (no bias) -> qkv_attention over the already projected context, 64 channels per head:
  * SpatialTransformer block attn2 up to its output projection (src/model/unet/mod.rs:731-795, attention via backend.rs:88-128).
  * x [B,Nq,C], wq [C,C] (in,out), k,v [B,Nk,C], out [B,Nq,C]; fp32 device tensors, f16 engine arithmetic.
- * fused != 0: ONE launch, the attention runs in the projection's epilogue (needs Nq % 64 == 0, Nk <= 96);
+ * fused != 0: ONE launch, the attention runs in the projection's epilogue (needs Nq % 64 == 0).  fused == 1: Nk <= 96 at any C, and
+ *   97 <= Nk <= 384 where C % 128 == 0 (the weights-in-registers form walks the context in 96-key blocks); other widths above 96 keys
+ *   and Nk > 384 return "fused cross-attention: unsupported shape" and launch nothing -- they are never run un-fused silently.
+ *   fused == 2 (split precision): Nk <= 96;
  * fused == 0: projection + attention kernel. */
 int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps,
                                   const float* wq, const float* k, const float* v, int B, int Nq, int Nk, int C, int fused,

@@ -760,41 +760,89 @@ impl<B: BurnBackend, T1: Tokenizer, T2: Tokenizer> Embedder<B, T1, T2> {
         ids.resize(n_ctx, tok.padding_token() as i32);
         ids
     }
-    /// one prompt through one tower: (penultimate hidden state [77, n_state], pooled projection [embed_dim] when asked for)
-    fn run_tower(&self, tower: *mut ffi::sdxl_clip, ids: &[i32], n_state: usize, embed_dim: usize, hidden_idx: i32, pooled: bool) -> (Vec<f32>, Vec<f32>) {
+    /// `tokenize_text_chunks` of the Python package: a prompt beyond the 77-token window as up to `max_chunks` (<= 4) windows.  The text is
+    /// encoded without sot / eot and cut into pieces of `n_ctx - 2` ids; every piece becomes sot + piece + eot, padded with the tokenizer's pad
+    /// id; at least one chunk; text beyond `max_chunks` chunks is dropped.  `max_chunks == 1` is `tokens` itself, truncation included.  The
+    /// chunks are encoded as batch rows (`sdxl_clip_forward_hidden(tower, ids, c, 77, ..)`), concatenated along the token axis (`[c, 77, n]` is
+    /// `[77 c, n]` in memory), the pooled embedding is chunk 0's, and the UNet is given `n_ctx = 77 c` for both contexts.
+    pub fn tokens_chunked(tok: &dyn Tokenizer, text: &str, n_ctx: usize, max_chunks: usize) -> Vec<Vec<i32>> {
+        assert!((1..=4).contains(&max_chunks), "max_chunks must be 1 .. 4");
+        if max_chunks == 1 {
+            return vec![Self::tokens(tok, text, n_ctx)];
+        }
+        let ids: Vec<i32> = tok.encode(text, false, false).into_iter().map(|t| t as i32).collect();
+        let n = n_ctx - 2;
+        let mut pieces: Vec<&[i32]> = ids.chunks(n).take(max_chunks).collect();
+        if pieces.is_empty() {
+            pieces.push(&[]);
+        }
+        let (sot, eot) = (tok.encode("", true, false)[0] as i32, tok.encode("", false, true)[0] as i32);
+        pieces.iter().map(|p| {
+            let mut c = Vec::with_capacity(n_ctx);
+            c.push(sot);
+            c.extend_from_slice(p);
+            c.push(eot);
+            c.resize(n_ctx, tok.padding_token() as i32);
+            c
+        }).collect()
+    }
+    /// one prompt -- its `rows` chunks of 77 ids as batch rows -- through one tower: (penultimate hidden state [rows * 77, n_state]: the chunks side by
+    /// side along the token axis; pooled projection [embed_dim] of chunk 0 when asked for)
+    fn run_tower(&self, tower: *mut ffi::sdxl_clip, ids: &[i32], rows: usize, n_state: usize, embed_dim: usize, hidden_idx: i32, pooled: bool) -> (Vec<f32>, Vec<f32>) {
+        let seq = ids.len() / rows;
         let d_ids = DeviceBuf::new(ids.len() * 4);
         assert_eq!(unsafe { hipMemcpy(d_ids.ptr, ids.as_ptr() as *const c_void, ids.len() * 4, HIP_MEMCPY_HOST_TO_DEVICE) }, 0);
         let hidden = DeviceBuf::new(ids.len() * n_state * 4);
-        let pool = DeviceBuf::new(embed_dim * 4);
+        let pool = DeviceBuf::new(rows * embed_dim * 4);
         if pooled {
             check(unsafe {
-                ffi::sdxl_clip_forward_hidden_pooled(tower, ptr::null_mut(), d_ids.ptr as *const i32, 1, ids.len() as c_int, hidden_idx,
+                ffi::sdxl_clip_forward_hidden_pooled(tower, ptr::null_mut(), d_ids.ptr as *const i32, rows as c_int, seq as c_int, hidden_idx,
                                                      hidden.f32_mut(), pool.f32_mut())
             });
         } else {
-            check(unsafe { ffi::sdxl_clip_forward_hidden(tower, ptr::null_mut(), d_ids.ptr as *const i32, 1, ids.len() as c_int, hidden_idx, hidden.f32_mut()) });
+            check(unsafe { ffi::sdxl_clip_forward_hidden(tower, ptr::null_mut(), d_ids.ptr as *const i32, rows as c_int, seq as c_int, hidden_idx, hidden.f32_mut()) });
         }
-        (hidden.to_f32(), pool.to_f32())
+        let mut p = pool.to_f32();
+        p.truncate(embed_dim);
+        (hidden.to_f32(), p)
     }
     /// reference signature (`:661-667`)
     pub fn text_to_conditioning(&self, text: &str, size: Tensor<B, 2, Int>, crop: Tensor<B, 2, Int>, ar: Tensor<B, 1, Int>) -> Conditioning<B> {
+        self.text_to_conditioning_chunked(text, "", 1, size, crop, ar)
+    }
+    /// `Embedder.text_to_conditioning(text, size, crop, ar, negative=, max_chunks=)` of the Python package: a negative prompt, and prompts beyond
+    /// the 77-token window as up to `max_chunks` (<= 4) chunks.  `c` = the largest chunk count among the four tokenisations; shorter ones are filled
+    /// with chunks of the empty prompt, so that both contexts have 77 c tokens.  `("", 1)` is the reference's call.
+    pub fn text_to_conditioning_chunked(&self, text: &str, negative: &str, max_chunks: usize, size: Tensor<B, 2, Int>, crop: Tensor<B, 2, Int>,
+                                        ar: Tensor<B, 1, Int>) -> Conditioning<B> {
         let device = size.device();
         let ar_v: Vec<i64> = ar.clone().into_data().value.iter().map(|x| x.elem::<i64>()).collect();
         let resolution = [ar_v[0] as usize, ar_v[1] as usize];
-        const N_CTX: usize = 77;
+        const CHUNK: usize = 77;
+        let chunks = |tok: &dyn Tokenizer, t: &str| Self::tokens_chunked(tok, t, CHUNK, max_chunks);
+        let mut ids = [chunks(&self.clip_tokenizer, text), chunks(&self.open_clip_tokenizer, text),
+                       chunks(&self.clip_tokenizer, negative), chunks(&self.open_clip_tokenizer, negative)];
+        let c = ids.iter().map(|v| v.len()).max().unwrap();
+        for (i, v) in ids.iter_mut().enumerate() {
+            let tok: &dyn Tokenizer = if i % 2 == 0 { &self.clip_tokenizer as &dyn Tokenizer } else { &self.open_clip_tokenizer as &dyn Tokenizer };
+            while v.len() < c {
+                v.push(Self::tokens(tok, "", CHUNK));
+            }
+        }
+        let n_ctx = CHUNK * c;
         // CLIP-L: hidden state after 11 of 12 blocks; OpenCLIP bigG: after 31 of 32 + pooled text embedding (`:676-688`)
-        let embed = |text: &str| {
-            let (h1, _) = self.run_tower(self.clip, &Self::tokens(&self.clip_tokenizer, text, N_CTX), 768, 768, 11, false);
-            let (h2, pooled) = self.run_tower(self.open_clip, &Self::tokens(&self.open_clip_tokenizer, text, N_CTX), 1280, 1280, 31, true);
-            let mut full = Vec::with_capacity(N_CTX * 2048);
-            for t in 0..N_CTX {
+        let embed = |clip_ids: &Vec<Vec<i32>>, open_ids: &Vec<Vec<i32>>| {
+            let (h1, _) = self.run_tower(self.clip, &clip_ids.concat(), c, 768, 768, 11, false);
+            let (h2, pooled) = self.run_tower(self.open_clip, &open_ids.concat(), c, 1280, 1280, 31, true);
+            let mut full = Vec::with_capacity(n_ctx * 2048);
+            for t in 0..n_ctx {
                 full.extend_from_slice(&h1[t * 768..(t + 1) * 768]);
                 full.extend_from_slice(&h2[t * 1280..(t + 1) * 1280]);
             }
             (full, h2, pooled)
         };
-        let (full, open, pooled) = embed(text);
-        let (ufull, uopen, upooled) = embed("");
+        let (full, open, pooled) = embed(&ids[0], &ids[1]);
+        let (ufull, uopen, upooled) = embed(&ids[2], &ids[3]);
         // conditioning_embedding (`unet/mod.rs:41-57`): pooled | sinusoid(size, crop, ar); the refiner variant swaps ar for
         // the aesthetic score 6 (`stablediffusion/mod.rs:709,740`)
         let ints = |t: Tensor<B, 2, Int>| -> Vec<i32> { t.into_data().value.iter().map(|x| x.elem::<i32>()).collect() };
@@ -811,7 +859,7 @@ impl<B: BurnBackend, T1: Tokenizer, T2: Tokenizer> Embedder<B, T1, T2> {
         };
         let base_vals: Vec<i32> = [&size_v[..2], &crop_v[..2], &[ar_v[0] as i32, ar_v[1] as i32][..]].concat();
         let refiner_vals: Vec<i32> = [&size_v[..2], &crop_v[..2], &[6][..]].concat();
-        let t2 = |v: Vec<f32>, c: usize| Tensor::<B, 2>::from_data(Data::new(v, Shape::new([N_CTX, c])).convert(), &device);
+        let t2 = |v: Vec<f32>, c: usize| Tensor::<B, 2>::from_data(Data::new(v, Shape::new([n_ctx, c])).convert(), &device);
         let t1 = |v: Vec<f32>| { let n = v.len(); Tensor::<B, 1>::from_data(Data::new(v, Shape::new([n])).convert(), &device) };
         Conditioning {
             unconditional_context_full: t2(ufull, 2048),

@@ -674,17 +674,30 @@ class Embedder:
                 conditioning_embedding(self.ctx, pooled, 256, size, crop, aesthetic))
 
     def tokens_to_conditioning(self, clip_ids, open_ids, uncond_clip_ids, uncond_open_ids, size, crop, ar) -> Conditioning:
-        """text_to_conditioning (:661-696) after tokenize_text: ids [1, n_ctx]; size / crop [n, 2] ints, ar [2] ints"""
+        """text_to_conditioning (:661-696) after tokenize_text: ids [1, n_ctx] -- or [c, n_ctx], the c <= 4 chunks of a long prompt
+        (tokenizer.tokenize_text_chunks; the same c for all four); size / crop [n, 2] ints, ar [2] ints.  Every chunk is encoded as a
+        batch row of its own (the position table stays n_ctx long), the hidden states are concatenated along the token axis to
+        [1, c n_ctx, .] and the pooled embedding is chunk 0's."""
         torch = _torch()
         size, crop, ar = torch.as_tensor(size), torch.as_tensor(crop), torch.as_tensor(ar)
         n = int(size.shape[0])
         bar = ar.reshape(1, -1).repeat(n, 1)
-        # the reference encodes "" and the prompt in two passes (:680-683); here they ride one batch-2 pass per encoder (the
+        rows = lambda a: torch.as_tensor(a).reshape(-1, torch.as_tensor(a).shape[-1])   # noqa: E731
+        ids = [rows(a) for a in (uncond_clip_ids, clip_ids, uncond_open_ids, open_ids)]
+        c = int(ids[0].shape[0])
+        if any(int(a.shape[0]) != c for a in ids):
+            raise ValueError("the four token id tensors must hold the same number of chunks")
+        if not 1 <= c <= 4:
+            raise ValueError("a prompt is 1 .. 4 chunks of token ids")
+        # the reference encodes "" and the prompt in two passes (:680-683); here they ride one batch-2c pass per encoder (the
         # rows of a batch are independent -- bit-identical to separate passes, tests/test_gpu_clip.py) and are split after
-        cat = lambda a, b: torch.cat([torch.as_tensor(a).reshape(1, -1), torch.as_tensor(b).reshape(1, -1)], dim=0)   # noqa: E731
-        clip_ctx = self.clip.forward_hidden(cat(uncond_clip_ids, clip_ids), self.clip.num_layers() - 1)      # :759-770
-        open_ctx, pooled = self.open_clip.forward_hidden_pooled(cat(uncond_open_ids, open_ids), self.open_clip.num_layers() - 1)
+        cat = lambda a, b: torch.cat([a, b], dim=0)   # noqa: E731
+        clip_ctx = self.clip.forward_hidden(cat(ids[0], ids[1]), self.clip.num_layers() - 1)      # :759-770
+        open_ctx, pooled = self.open_clip.forward_hidden_pooled(cat(ids[2], ids[3]), self.open_clip.num_layers() - 1)
         full = torch.cat([clip_ctx, open_ctx], dim=2)
+        if c > 1:      # [2c, n_ctx, .] -> [2, c n_ctx, .]: the chunks of a prompt side by side along the token axis; pooled: chunk 0
+            full, open_ctx = (t.reshape(2, c * t.shape[1], t.shape[2]) for t in (full, open_ctx))
+            pooled = pooled[0::c].contiguous()
         ucf, uco, ucc, uccr = self._finish(full[0:1], open_ctx[0:1], pooled[0:1], size, crop, bar)
         cf, co, cc, ccr = self._finish(full[1:2], open_ctx[1:2], pooled[1:2], size, crop, bar)
         return Conditioning(context_full=cf, channel_context=cc, unconditional_context_full=ucf.squeeze(0),
@@ -692,16 +705,25 @@ class Embedder:
                             unconditional_context_open_clip=uco.squeeze(0), unconditional_channel_context_refiner=uccr.squeeze(0),
                             resolution=(int(ar[0]), int(ar[1])))
 
-    def text_to_conditioning(self, text: str, size, crop, ar) -> Conditioning:
-        """Embedder::text_to_conditioning (:661-696); the unconditional prompt is "" (:703-705)"""
+    def text_to_conditioning(self, text: str, size, crop, ar, *, negative: str = "", max_chunks: int = 1) -> Conditioning:
+        """Embedder::text_to_conditioning (:661-696); the unconditional prompt is "" (:703-705) unless `negative` names one.
+        max_chunks > 1 (up to 4): a prompt longer than the 77-token window is encoded in chunks of 77 (tokenize_text_chunks) and the
+        UNet sees n_ctx = 77 c tokens, c the largest chunk count among the prompt and the negative prompt on both tokenizers; the
+        shorter ones are filled with chunks of the empty prompt, so both contexts share n_ctx.  The defaults are the reference's call."""
         if self.clip_tokenizer is None or self.open_clip_tokenizer is None:
             raise EngineError("Embedder was built without tokenizers (asset files not available): use tokens_to_conditioning")
-        from .tokenizer import tokenize_text
+        from .tokenizer import MAX_PROMPT_CHUNKS, tokenize_text_chunks
+        if not 1 <= int(max_chunks) <= MAX_PROMPT_CHUNKS:
+            raise ValueError(f"max_chunks must be 1 .. {MAX_PROMPT_CHUNKS}")
         torch = _torch()
-        ids = lambda t, tok, m: torch.tensor([tokenize_text(t, tok, m.max_sequence_length())], dtype=torch.int32)   # noqa: E731
-        return self.tokens_to_conditioning(ids(text, self.clip_tokenizer, self.clip), ids(text, self.open_clip_tokenizer, self.open_clip),
-                                           ids("", self.clip_tokenizer, self.clip), ids("", self.open_clip_tokenizer, self.open_clip),
-                                           size, crop, ar)
+        pairs = [(t, tok, m.max_sequence_length()) for t in (text, negative)
+                 for tok, m in ((self.clip_tokenizer, self.clip), (self.open_clip_tokenizer, self.open_clip))]
+        chunks = [tokenize_text_chunks(t, tok, n, int(max_chunks)) for t, tok, n in pairs]
+        c = max(len(ch) for ch in chunks)
+        for ch, (_, tok, n) in zip(chunks, pairs):
+            ch.extend(tokenize_text_chunks("", tok, n, 1) * (c - len(ch)))
+        ids = [torch.tensor(ch, dtype=torch.int32) for ch in chunks]      # prompt: clip, open_clip; negative: clip, open_clip
+        return self.tokens_to_conditioning(ids[0], ids[1], ids[2], ids[3], size, crop, ar)
 
 
 class _ArenaView:
@@ -1254,7 +1276,8 @@ def layer_norm_linear(ctx: Context, x, gamma, beta, weight, bias, eps: float = 1
 def ln_query_cross_attention(ctx: Context, x, gamma, beta, wq, k, v, eps: float = 1e-5, fused: bool = True):
     """attn2 of a transformer block up to its output projection (unet/mod.rs:731-795): LayerNorm -> query projection (no
     bias) -> qkv_attention over the projected context k, v [B,Nk,C] with 64 channels per head.  f16 engine arithmetic.
-    fused=True runs the attention inside the projection's epilogue (one launch), False as projection + attention kernel; fused=2: that epilogue at
+    fused=True runs the attention inside the projection's epilogue (one launch: Nk <= 96, or Nk <= 384 where C % 128 == 0 -- the long form walks the
+    context in 96-key blocks; anything else is refused), False as projection + attention kernel; fused=2 (Nk <= 96): that epilogue at
     split precision (context, q and P as (hi, lo) f16 pairs, three MFMAs per product: what SDXL_DTYPE_F32_SPLIT_MIX_F16W runs)."""
     torch = _torch()
     x, px = _dev(x)

@@ -144,6 +144,7 @@ int sdxl_debug_set(const char* key, int value) {
   else if (std::strcmp(key, "splitk_wt") == 0) igemm_set_splitk_wt(value);
   else if (std::strcmp(key, "hl_demote") == 0) unet_set_hl_demote(value);
   else if (std::strcmp(key, "mix_classes") == 0) unet_set_mix_classes(value);
+  else if (std::strcmp(key, "xattn_long") == 0) unet_set_xattn_long(value);
   else if (std::strcmp(key, "wreg_xcd2d") == 0) igemm_set_wreg_xcd2d(value);
   else if (std::strcmp(key, "upsample_fold") == 0) set_upsample_fold(value);
 #ifdef SDXL_MEASURE

@@ -509,7 +509,8 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
                                   float* out) {
   // attn2 of a transformer block up to (not including) the output projection: LayerNorm -> query projection (no bias) ->
   // qkv_attention over the projected context, 64 channels per head.  f16 engine only (the UNet's production mode); fused != 0
-  // runs the attention inside the projection's epilogue, fused == 0 as projection + attention kernel; fused == 2: the epilogue at split precision
+  // runs the attention inside the projection's epilogue (Nk <= 96; fused == 1 also 97 .. 384 keys where C % 128 == 0: the long form of the
+  // weights-in-registers launch), fused == 0 as projection + attention kernel; fused == 2: the epilogue at split precision
   // (context, q and P as (hi, lo) f16 pairs: the SDXL_DTYPE_F32_SPLIT_MIX_F16W form).
   API_BEGIN
   SDXL_REQUIRE(ctx && x && gamma && beta && wq && k && v && out, "null argument");
@@ -517,7 +518,8 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
   use(ctx);
   hipStream_t s = pick(ctx, stream);
   const int M = B * Nq, vt_ld = (int)round_up(Nk, 64), H = C / 64;
-  SDXL_REQUIRE(!fused || igemm_xattn_ok(DT_F16, DT_F16, M, C, C, Nq, Nk), "fused cross-attention: unsupported shape");
+  // (fused == 1 runs on fragment-order weights: up to 384 keys where the weights-in-registers form takes the width; the other forms up to 96)
+  SDXL_REQUIRE(!fused || igemm_xattn_ok(DT_F16, DT_F16, M, C, C, Nq, Nk, igemm_launch_knobs(), fused != 2 && fused != 3), "fused cross-attention: unsupported shape");
   Operands ops;
   add_linear(ops, "lin", C, C, wq, nullptr);
   add_norm(ops, "norm", C, gamma, beta, eps);
@@ -547,7 +549,7 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
     void* vh = tmp.get((size_t)B * C * vt_ld * 2); void* vl = tmp.get((size_t)B * C * vt_ld * 2);
     launch_f32_to_f16_pair(k, C, kh, kl, C, (size_t)B * Nk, C, s);
     launch_f32_to_f16_pair((const float*)stage_vt(tmp, v, B, Nk, C, DT_F32, vt_ld, s), vt_ld, vh, vl, vt_ld, (size_t)B * C, vt_ld, s);
-    void* xa = tmp.get(xattn_pack_bytes(B, C)); void* xal = tmp.get(xattn_pack_bytes(B, C));
+    void* xa = tmp.get(xattn_pack_bytes(B, C, Nk)); void* xal = tmp.get(xattn_pack_bytes(B, C, Nk));
     launch_xattn_pack(kh, vh, xa, B, C, Nk, vt_ld, s);
     launch_xattn_pack(kl, vl, xal, B, C, Nk, vt_ld, s);
     e.xa_k = xa; e.xa_k_lo = xal; e.xa_nctx = Nk; e.xa_scale = 0.125f;
@@ -558,7 +560,7 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
     launch_copy_rows(k, DT_F32, C, kd, DT_F16, C, B * Nk, C, s);
     void* vt = stage_vt(tmp, v, B, Nk, C, DT_F16, vt_ld, s);
     if (fused) {
-      void* xa = tmp.get(xattn_pack_bytes(B, C));
+      void* xa = tmp.get(xattn_pack_bytes(B, C, Nk));
       launch_xattn_pack(kd, vt, xa, B, C, Nk, vt_ld, s);
       e.xa_k = xa; e.xa_nctx = Nk; e.xa_scale = 0.125f;
       run_linear(ex, l, xi, M, Act(od, C, DT_F16), e);

@@ -299,6 +299,7 @@ enum DemoteClass { DM_QKV = 1, DM_ATTN = 2, DM_OUT = 4, DM_XATTN = 8, DM_GEGLU =
                    DM_CONV_IO = 256, DM_CONV_UPDOWN = 512, DM_CONV_PROJ = 1024 };
 void unet_set_mix_classes(int v);
 void unet_set_hl_demote(int mask);
+void unet_set_xattn_long(int v);     // A/B knob (sdxl_debug_set "xattn_long", default 1): 0 = contexts above 96 keys keep the un-fused cross-attention; read by UNet::set_context
 int unet_hl_demote();
 
 // thin launch helpers shared by unet.cpp / vae.cpp (skip the launch on dry runs)
@@ -451,6 +452,7 @@ class UNet {
   std::vector<const STW*> st_list_;
   DeviceArena ctx_arena_;
   int ctx_B_ = 0, n_ctx_ = 0, vt_ld_ctx_ = 0;
+  bool ctx_xa_ = false;      // set_context packed the operand-order context image (kv_[..].xa) for this n_ctx_
   float* label_emb_ = nullptr;           // [B][4mc]
   // plan
   int pB_ = 0, pH_ = 0, pW_ = 0;

@@ -1120,6 +1120,92 @@ __device__ __forceinline__ void xattn_unit(const half8 (&qf)[4], const half8 (&k
   }
 }
 
+// The same unit over a LONG context (96 < nctx <= 384 keys: two to four 77-token chunks of a prompt): the image holds NB = ceil(nctx / 96)
+// blocks of the 24 fragments per (entry, head) (launch_xattn_pack) and the unit walks them with an online softmax.  Per block: the S MFMAs in
+// k-step order, keys >= nctx masked by the block's key offset, the block maximum; m' = max(m, m_blk), and the running row sum l and both output
+// accumulators are rescaled by exp2(m - m') in fp32; P = exp2(s - m') is rounded to f16 as in xattn_unit and the O MFMAs accumulate into the
+// running output; one multiply by 1 / l at the end.  Block 0 is peeled: it seeds m and l, so no (-inf) - (-inf) is ever formed, and every later
+// block holds at least one live key (NB is the ceiling), so its maximum is finite.  l is kept as the lane's partial sum -- both lanes of a
+// query share m after the xor-32 exchange, so they rescale alike -- and crosses the lane halves once, at the end.
+// kf / vf hold block 0 on entry (requested early, where the short form requests its only block); block b + 1's K fragments are requested
+// behind block b's S MFMAs and its V^T fragments behind block b's O MFMAs, into the same registers: compiler-counted VMEM.  fx = block 0 of
+// this (entry, head) in the image, the lane's 16 bytes.  The pipe kernels' epilogue forms (xattn_inplace, xattn_inplace_hl) have no such
+// sibling: above 96 keys they keep the un-fused projection + attention kernel (select.cpp igemm_xattn_ok).
+__device__ __forceinline__ void xattn_unit_long(const half8 (&qf)[4], half8 (&kf)[3][4], half8 (&vf)[2][6], const half8* fx, int nctx, int fh, f32x16 (&o)[2]) {
+  const int nb = (nctx + 95) / 96;
+  float m = 0.f, l = 0.f;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+  for (int b = 0; b < nb; ++b) {
+    f32x16 sv[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sv[t][r] = 0.f;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) sv[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[t][s4], qf[s4], sv[t], 0, 0, 0);
+    }
+    const half8* fn = fx + (size_t)(b + 1) * (24 * 64);
+    if (b + 1 < nb) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) kf[t][s4] = fn[(t * 4 + s4) * 64];
+    }
+    const int k0 = 96 * b + 4 * fh;
+    float mb = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (k0 + 32 * t + 8 * (r >> 2) + (r & 3) >= nctx) sv[t][r] = -INFINITY;
+        mb = fmaxf(mb, sv[t][r]);
+      }
+    mb = fmaxf(mb, __shfl_xor(mb, 32));
+    if (b == 0) m = mb;                                              // (block 0: all 96 keys live, nothing to rescale)
+    else {
+      const float mn = fmaxf(m, mb);
+      const float alpha = __builtin_amdgcn_exp2f(m - mn);            // both finite
+      l *= alpha;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+      m = mn;
+    }
+    half8 pf[6];
+#pragma unroll
+    for (int s6 = 0; s6 < 6; ++s6) {
+      float ls = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float pe = __builtin_amdgcn_exp2f(sv[s6 >> 1][8 * (s6 & 1) + e] - m);
+        ls += pe;
+        pf[s6][e] = (half_t)pe;
+      }
+      l += ls;
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int s6 = 0; s6 < 6; ++s6) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[dt][s6], pf[s6], o[dt], 0, 0, 0);
+    if (b + 1 < nb) {
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int s6 = 0; s6 < 6; ++s6) vf[dt][s6] = fn[(12 + dt * 6 + s6) * 64];
+    }
+  }
+  l += __shfl_xor(l, 32);
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] *= inv;
+}
+
 // ---- the same fusion at split precision (IgemmParams::xa_k_lo; round 6): q stays what the projection's fp32 accumulators hold -- it is split into
 // (hi, lo) f16 pairs here, like the probabilities (times 2^11, so that the lo halves of small probabilities stay out of the f16 subnormals), and meets
 // context keys / values that were split once per prompt: three MFMAs per product, fp32 accumulation, fp32 softmax -- the arithmetic of the stand-alone

@@ -1066,15 +1066,17 @@ static void launch_wide(const IgemmParams& p, const IgemmChoice& c, hipStream_t 
   hipLaunchKernelGGL((igemm_wide_kernel<3, false>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
 }
 
-// Context K [B][n_ctx][C] / V^T [B][C][vt_ld] (f16) -> the operand-order image xattn_inplace reads: per (batch entry, head) 24
-// fragments of 64 lanes x 8 halfs -- 12 of K (key tile t, k-step s4: key = 32t + lane&31, d = 16 s4 + 8(e>>2) + 4(lane>>5) + (e&3))
-// then 12 of V^T (d tile dt, k-step s6: d = 32dt + lane&31, key = 16 s6 + 8(e>>2) + 4(lane>>5) + (e&3)); keys >= n_ctx are zero.
+// Context K [B][n_ctx][C] / V^T [B][C][vt_ld] (f16) -> the operand-order image the fused cross-attention reads: per (batch entry, head)
+// NB = ceil(n_ctx / 96) blocks of 24 fragments of 64 lanes x 8 halfs; block blk holds keys 96 blk .. + 95 -- 12 fragments of K (key tile t,
+// k-step s4: key = 96 blk + 32t + lane&31, d = 16 s4 + 8(e>>2) + 4(lane>>5) + (e&3)) then 12 of V^T (d tile dt, k-step s6: d = 32dt + lane&31,
+// key = 96 blk + 16 s6 + 8(e>>2) + 4(lane>>5) + (e&3)); keys >= n_ctx are zero.  n_ctx <= 96: one block, the image xattn_inplace and xattn_unit
+// read; more blocks are read by xattn_unit_long (igemm_wreg.hip) alone.
 __global__ void xattn_pack_kernel(const half_t* K, const half_t* Vt, half8* out, int B, int C, int nctx, int vt_ld) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int H = C >> 6;
-  if (i >= (size_t)B * H * 24 * 64) return;
+  const int H = C >> 6, NB = (nctx + 95) / 96;
+  if (i >= (size_t)B * H * NB * 24 * 64) return;
   const int lane = (int)(i & 63), f = (int)((i >> 6) % 24);
-  const int bh = (int)(i / (24 * 64)), b = bh / H, h = bh - b * H;
+  const int bhb = (int)(i / (24 * 64)), bh = bhb / NB, k0 = 96 * (bhb - bh * NB), b = bh / H, h = bh - b * H;
   const int fr = lane & 31, fh = lane >> 5;
   half8 v;
 #pragma unroll
@@ -1082,19 +1084,20 @@ __global__ void xattn_pack_kernel(const half_t* K, const half_t* Vt, half8* out,
     const int sub = 8 * (e >> 2) + 4 * fh + (e & 3);
     half_t x = (half_t)0.f;
     if (f < 12) {
-      const int key = 32 * (f >> 2) + fr, d = 16 * (f & 3) + sub;
+      const int key = k0 + 32 * (f >> 2) + fr, d = 16 * (f & 3) + sub;
       if (key < nctx) x = K[((size_t)b * nctx + key) * C + h * 64 + d];
     } else {
-      const int g = f - 12, d = 32 * (g / 6) + fr, key = 16 * (g % 6) + sub;
+      const int g = f - 12, d = 32 * (g / 6) + fr, key = k0 + 16 * (g % 6) + sub;
       if (key < nctx) x = Vt[((size_t)b * C + h * 64 + d) * vt_ld + key];
     }
     v[e] = x;
   }
   out[i] = v;
 }
-size_t xattn_pack_bytes(int B, int C) { return (size_t)B * (C / 64) * 24 * 64 * 16; }
+size_t xattn_pack_bytes(int B, int C, int n_ctx) { return (size_t)B * (C / 64) * ((n_ctx + 95) / 96) * 24 * 64 * 16; }
 void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, int nctx, int vt_ld, hipStream_t s) {
-  const size_t n = (size_t)B * (C / 64) * 24 * 64;
+  const size_t n = xattn_pack_bytes(B, C, nctx) / 16;
+  if (n == 0) return;
   hipLaunchKernelGGL(xattn_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const half_t*>(K),
                      reinterpret_cast<const half_t*>(Vt), reinterpret_cast<half8*>(out), B, C, nctx, vt_ld);
 }

@@ -240,13 +240,16 @@ __device__ __forceinline__ void wreg_epilogue(const IgemmParams& p, const f32x16
 // the rings) and the wave's column vectors are requested BEFORE the exchange, like the plain epilogue's residual rows; all of it is
 // compiler-counted VMEM / SMEM behind the k-loop's last counted wait, so the hand-kept VMEM queue above is unchanged.
 // A 32-row block lies in one batch entry (rpb % 64 == 0); a 96-row tile may straddle two, so the entry is looked up per unit.
+// LONG (XA = 2, 97 .. 384 context keys): the image holds ceil(n_ctx / 96) blocks of the 24 fragments per (entry, head); block 0 is requested
+// here like the short form's only block, the tail hands kf / vf to xattn_unit_long (igemm_common.h), which walks the blocks with an online
+// softmax and loads blocks 1 .. into the same registers on the way -- still compiler-counted VMEM behind the k-loop.
 template <int BM> struct WregXaOperands {
   LnCoop<BM, 4 * BM> ln;
   half8 kf[3][4], vf[2][6];
   f32x4 cz[2], bz[2];
   bool unit;
 };
-template <int BM>
+template <int BM, bool LONG>
 __device__ __forceinline__ void wreg_xattn_request(const IgemmParams& p, int m0, int n0, int lane, int wave, const void* zeros, WregXaOperands<BM>& op) {
   constexpr int TM = BM / 32;
   static_assert((4 * BM) % 64 == 0 && 4 * BM <= 512 && LnCoop<BM, 4 * BM>::OK, "four statistics threads per tile row, whole waves");
@@ -256,7 +259,8 @@ __device__ __forceinline__ void wreg_xattn_request(const IgemmParams& p, int m0,
   op.unit = wave < 2 * TM && mu < p.M;
   if (op.unit) {
     const int b = __builtin_amdgcn_readfirstlane(mu / p.rpb);
-    const half8* fx = reinterpret_cast<const half8*>(p.xa_k) + ((size_t)b * (p.N >> 6) + ((n0 >> 6) + (wave & 1))) * (24 * 64) + lane;
+    const int nblk = LONG ? (p.xa_nctx + 95) / 96 : 1;      // (long form: block 0 of the unit's NB blocks; the tail loads the others)
+    const half8* fx = reinterpret_cast<const half8*>(p.xa_k) + ((size_t)b * (p.N >> 6) + ((n0 >> 6) + (wave & 1))) * nblk * (24 * 64) + lane;
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -286,9 +290,9 @@ __device__ __forceinline__ void wreg_xattn_coef(const IgemmParams& p, int m0, in
     coef[tid * 2] = a; coef[tid * 2 + 1] = c;
   }
 }
-template <int BM, int L>
+template <int BM, int L, bool LONG>
 __device__ __forceinline__ void wreg_xattn_tail(const IgemmParams& p, const f32x16 (&acc)[BM / 32], int m0, int n0, int lane, int wave, char* smem,
-                                                const float* coef, const WregXaOperands<BM>& op) {
+                                                const float* coef, WregXaOperands<BM>& op) {
   constexpr int TM = BM / 32, SLOT = BM * 128, RING = (L + 1) * SLOT;
   static_assert(TM * 4 * 1024 == SLOT, "a head's q fragments fill one ring slot");
   const int fr = lane & 31, fh = lane >> 5, g = wave >> 2, w = wave & 3;
@@ -315,6 +319,12 @@ __device__ __forceinline__ void wreg_xattn_tail(const IgemmParams& p, const f32x
 #pragma unroll
   for (int s4 = 0; s4 < 4; ++s4) qf[s4] = qr[s4 * 64];
   f32x16 o[2];
+  if constexpr (LONG) {      // 96 < n_ctx <= 384: blocks of 96 keys, online softmax; blocks 1 .. are loaded into kf / vf on the way
+    const int b = __builtin_amdgcn_readfirstlane((m0 + 32 * ui) / p.rpb);
+    const int nblk = (p.xa_nctx + 95) / 96;
+    const half8* fx = reinterpret_cast<const half8*>(p.xa_k) + ((size_t)b * (p.N >> 6) + ((n0 >> 6) + uh)) * nblk * (24 * 64) + lane;
+    xattn_unit_long(qf, op.kf, op.vf, fx, p.xa_nctx, fh, o);
+  } else
   xattn_unit(qf, op.kf, op.vf, p.xa_nctx, fh, o);
   const int m = m0 + 32 * ui + fr;
   half_t* crow = reinterpret_cast<half_t*>(p.C) + (size_t)(m < p.M ? m : 0) * p.ldc + n0 + 64 * uh + 8 * fh;
@@ -356,8 +366,9 @@ void igemm_set_wreg_timeline(void* buf) {
 constexpr int wreg_mode_flags(int m) {
   return m >= 16 ? m : m == 1 ? 16 : m == 2 ? 32 : m == 3 ? 64 : m == 4 ? 128 : m == 5 ? 256 : m == 6 ? 512 : m == 7 ? 1024 : m == 8 ? 2048 : 0;
 }
-// XA: the query projection of a cross-attention with the attention behind it (IgemmParams::xa_k, f16 form; block comment above)
-template <int BM, int L, int MODE = 0, bool XA = false>
+// XA: the query projection of a cross-attention with the attention behind it (IgemmParams::xa_k, f16 form; block comment above): 1 = up to 96
+// context keys, one block held in registers (xattn_unit); 2 = the long form, 97 .. 384 keys in blocks of 96 (xattn_unit_long)
+template <int BM, int L, int MODE = 0, int XA = 0>
 __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, const void* zeros) {
 #ifdef SDXL_MEASURE
   unsigned wtl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -606,7 +617,7 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
   WregEpiOperands<TM> eop;
   WregXaOperands<XA ? BM : 64> xop;
   float* const xa_coef = reinterpret_cast<float*>(smem + NG * RING);      // XA: the tile's LayerNorm (a, c) pairs, behind the rings
-  if constexpr (XA) { static_assert(MODE == 0, "production arithmetic only"); wreg_xattn_request<BM>(p, m0, n0, lane, wave, zeros, xop); }
+  if constexpr (XA) { static_assert(MODE == 0, "production arithmetic only"); wreg_xattn_request<BM, XA == 2>(p, m0, n0, lane, wave, zeros, xop); }
   else wreg_epilogue_request<TM>(p, m0, n0 + w * 32, lane, g, zeros, eop);
   static_assert(4 * TM * 2 * 64 * 16 <= L * SLOT, "a group's four exchange pieces must fit its dead slots 0 .. L - 1");
   f32x4* xw = reinterpret_cast<f32x4*>(smem + g * RING) + (size_t)w * (TM * 2 * 64) + lane;                    // written by (g, w): own group's slots 0 ..
@@ -638,7 +649,7 @@ __global__ __launch_bounds__(512) void igemm_wreg_kernel(const IgemmParams p, co
   WREG_STAMP(4);
   static_assert((2 * BM + 6 * 2 * BM) * 4 <= SLOT, "statistics exchange must fit one slot");
   float* xch = reinterpret_cast<float*>(smem + L * SLOT);           // statistics exchange: slot L of ring 0 (dead behind the exchange rendezvous)
-  if constexpr (XA) wreg_xattn_tail<BM, L>(p, acc, m0, n0, lane, wave, smem, xa_coef, xop);
+  if constexpr (XA) wreg_xattn_tail<BM, L, XA == 2>(p, acc, m0, n0, lane, wave, smem, xa_coef, xop);
   else wreg_epilogue<TM>(p, acc, m0, n0 + w * 32, lane, w, g, xch, eop);
 #ifdef SDXL_MEASURE
   WREG_STAMP(5);
@@ -656,7 +667,7 @@ static std::atomic<int> g_warm_enable{1};
 void igemm_set_warm(int v) { g_warm_enable = v; }
 int igemm_warm_enabled() { return g_warm_enable.load(); }
 
-template <int BM, int L, int MODE = 0, bool XA = false>
+template <int BM, int L, int MODE = 0, int XA = 0>
 static void launch_wreg_t(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
   constexpr size_t lds = (size_t)2 * (L + 1) * BM * 128 + (XA ? BM * 8 : 0);      // (XA: + the tile's LayerNorm coefficients)
   static_assert(lds >= (size_t)8 * (BM / 32) * 2048 + (size_t)(2 * BM + 6 * 2 * BM) * 4, "exchange areas must fit the dead rings");
@@ -670,15 +681,16 @@ static void launch_wreg_t(const IgemmParams& p, const IgemmChoice& c, hipStream_
 // a weights-in-registers choice of igemm_select (select.cpp: shapes, the CFG-pair grid rule, rows per tile, forced numbers) -> its instantiation
 void launch_igemm_wreg(const IgemmParams& p, const IgemmChoice& c, hipStream_t s) {
 #define WREG(BM, L, MODE, XA) \
-  if (c.bm == BM && c.ns == L && c.mode == (MODE) && c.xa == XA) return launch_wreg_t<BM, L, (MODE), XA>(p, c, s)
+  if (c.bm == BM && c.ns == L && c.mode == (MODE) && (c.xa > 1 ? 2 : c.xa) == XA) return launch_wreg_t<BM, L, (MODE), XA>(p, c, s)
 #ifdef SDXL_MEASURE
-  WREG(96, 3, 0, false); WREG(96, 4, 0, false); WREG(128, 2, 0, false);
-  WREG(96, 2, 1, false); WREG(96, 2, 2, false); WREG(96, 2, 3, false); WREG(96, 2, 4, false); WREG(96, 2, 5, false);
-  WREG(96, 2, 6, false); WREG(96, 2, 7, false); WREG(96, 2, 8, false);
-  WREG(96, 2, 16 | 32, false); WREG(96, 2, 16 | 32 | 4096, false); WREG(96, 2, 16 | 32 | 4096 | 128, false); WREG(96, 2, 16 | 4096, false); WREG(96, 2, 4096, false);
+  WREG(96, 3, 0, 0); WREG(96, 4, 0, 0); WREG(128, 2, 0, 0);
+  WREG(96, 2, 1, 0); WREG(96, 2, 2, 0); WREG(96, 2, 3, 0); WREG(96, 2, 4, 0); WREG(96, 2, 5, 0);
+  WREG(96, 2, 6, 0); WREG(96, 2, 7, 0); WREG(96, 2, 8, 0);
+  WREG(96, 2, 16 | 32, 0); WREG(96, 2, 16 | 32 | 4096, 0); WREG(96, 2, 16 | 32 | 4096 | 128, 0); WREG(96, 2, 16 | 4096, 0); WREG(96, 2, 4096, 0);
 #endif
-  WREG(64, 2, 0, false); WREG(96, 2, 0, false);
-  WREG(64, 2, 0, true); WREG(96, 2, 0, true);      // the fused query projection + cross-attention (f16 form)
+  WREG(64, 2, 0, 0); WREG(96, 2, 0, 0);
+  WREG(64, 2, 0, 1); WREG(96, 2, 0, 1);      // the fused query projection + cross-attention (f16 form)
+  WREG(64, 2, 0, 2); WREG(96, 2, 0, 2);      // ... over a long context: IgemmChoice::xa = its 2 .. 4 blocks of 96 keys
 #undef WREG
   throw std::logic_error("igemm_wreg: the selection chose a kernel that is not instantiated");
 }

@@ -120,7 +120,7 @@ struct IgemmChoice {
   int bm, bn, ns;           // tile rows / columns, ring depth (IG_WREG: prefetch depth L)
   int wgm, nw;              // waves along M, waves
   int elem, a_elem;         // compute element (DT_F16 / DT_F32 / DT_HL); IG_GENERIC: element of A in memory
-  int xa, xh, tsw, s2;      // fused cross-attention, its split-precision form, operand-swapped V^T epilogue, one rendezvous per two k-tiles
+  int xa, xh, tsw, s2;      // fused cross-attention (IG_WREG: the context's 96-key blocks, 1 .. 4; else 0 / 1), its split-precision form, operand-swapped V^T epilogue, one rendezvous per two k-tiles
   int splitk;               // k-slices per tile (1 = off)
   int mode, db, measure;    // measure builds: knock-out mode of the weights-in-registers kernel, double-buffered wide kernel, measure-only variant number
   int grid, block, lds;
@@ -131,14 +131,21 @@ IgemmChoice igemm_select(const IgemmParams& p, int compute_dt, const SelectKnobs
 bool igemm_gn_part_ok(const IgemmParams& p, const SelectKnobs& k);
 bool igemm_wreg_selected(const IgemmParams& p, const SelectKnobs& k);         // the auto selection would run this launch on the weights-in-registers kernel
 bool igemm_wreg_xattn_selected(const IgemmParams& p, const SelectKnobs& k);   // ... a fused query projection + cross-attention (xa_k, f16 form)
-// shapes the fused cross-attention epilogue takes (f16 operands, head dim 64, <= 96 context tokens); otherwise run the
-// projection and the attention kernel separately
-bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx);
+// launches the fused cross-attention epilogue takes (f16 operands, head dim 64); otherwise run the projection and the attention kernel separately.
+// n_ctx <= 96: every form -- the pipe kernels' epilogue (xattn_inplace), its split-precision twin (xattn_inplace_hl) and the weights-in-registers XA
+// instantiation; a function of the shape alone.  96 < n_ctx <= 384 (two to four 77-token chunks): the weights-in-registers XA instantiation alone, which
+// walks the context in 96-key blocks (xattn_unit_long); true only where the selection will run that form -- `wreg_form`: the launch carries fragment-order
+// weights and the plain f16 context image (no xa_k_lo); `k`: the knobs it will be launched with.  The pipe and split-precision forms keep their 96-key
+// limit and the un-fused fallback above it.  The ONE predicate of the plan (UNet::set_context, spatial_transformer), run_conv, the single-op entry and
+// the selection (wreg_takes).
+constexpr int xattn_long_max_blocks = 4;      // 96-key blocks the long form is selected for (the kernel has no limit of its own)
+bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx, const SelectKnobs& k, bool wreg_form);
 // the phase form of an upsample convolution (IgemmParams::ph_rows, filled): the selection has a pipe tile for it.  Asked by run_conv before it
 // hands the launch the folded weights; false: the layer keeps the gather form.  A function of one entry's shape (rows per phase and entry, N, K).
 bool igemm_phase_ok(const IgemmParams& p, int compute_dt, const SelectKnobs& k);
-// K [B][n_ctx][C], V^T [B][C][vt_ld] (f16) -> operand-order image of xattn_pack_bytes(B, C) bytes (once per prompt)
-size_t xattn_pack_bytes(int B, int C);
+// K [B][n_ctx][C], V^T [B][C][vt_ld] (f16) -> operand-order image of xattn_pack_bytes(B, C, n_ctx) bytes (once per prompt): per (entry, head)
+// ceil(n_ctx / 96) blocks of 24 fragments -- up to 96 keys one block, the bytes and layout the pipe epilogues read
+size_t xattn_pack_bytes(int B, int C, int n_ctx);
 void launch_xattn_pack(const void* K, const void* Vt, void* out, int B, int C, int n_ctx, int vt_ld, hipStream_t s);
 int igemm_splitk_slices(const IgemmParams& p);                       // 1 or 3: depends on one batch entry's shape only
 size_t igemm_splitk_ws_bytes(int batch, int rows_per_entry, int n_max);   // slab bytes a plan must provide

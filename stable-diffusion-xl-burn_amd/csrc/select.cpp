@@ -47,6 +47,7 @@ SelectKnobs select_knobs_snapshot() {
 // ---------------------------------------------------------------------------------------------------------
 // GEMM
 namespace {
+bool xattn_forced_pipe(int v) { return v == 35 || v == 36 || v == 44 || v == 45; }      // forced numbers that keep a fused cross-attention on a pipe tile
 bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 bool is_linear(const IgemmParams& p) { return p.ksize == 1 && p.stride == 1 && p.up == 0; }
 
@@ -183,7 +184,11 @@ bool wreg_takes(const IgemmParams& p, const SelectKnobs& k, bool xa) {
   if (p.N % 128 != 0 || p.Cin != p.K || p.K != p.Kpad || p.Kpad % 64 != 0 || p.Kpad < 128) return false;
   if (p.act != 0 || p.n_split < p.N || p.gn_part || p.acc_scale || p.ebias) return false;
   if ((p.lda & 7) != 0 || misaligned16(p.A) || (p.ldc & 7) != 0 || misaligned16(p.C)) return false;
-  if (xa) return !p.stat_out && !p.R && !p.shadow && p.rpb > 0 && p.rpb % 64 == 0 && p.M % p.rpb == 0 && p.xa_nctx >= 1 && p.xa_nctx <= 96;
+  if (xa) {
+    if (p.stat_out || p.R || p.shadow || p.rpb <= 0 || p.rpb % 64 != 0 || p.M % p.rpb != 0 || p.xa_nctx < 1) return false;
+    // more than one 96-key block (xattn_unit_long): the rule the plan asked before it packed the blocked image -- one predicate for both
+    return p.xa_nctx <= 96 || igemm_xattn_ok(p.a_dt, p.c_dt, p.M, p.N, p.K, p.rpb, p.xa_nctx, k, true);
+  }
   if (p.ln_stat || (p.R && ((p.ldr & 7) != 0 || misaligned16(p.R)))) return false;
   // f16 shadow of an fp32 output (+ the fp32 rows' statistics): whole 16-byte pieces
   if (p.shadow && (p.c_dt != DT_F32 || !p.shadow_gamma || (p.shadow_ld & (p.shadow_lo_scale < 0.f ? 15 : 7)) != 0 || misaligned16(p.shadow))) return false;
@@ -236,7 +241,8 @@ IgemmChoice from_tile(int number, int elem, const IgemmParams& p) {
 }
 IgemmChoice wreg_choice(int bm, int depth, int mode, bool xa, const IgemmParams& p) {
   IgemmChoice c{};
-  c.family = IG_WREG; c.bm = bm; c.bn = 128; c.ns = depth; c.nw = 8; c.mode = mode; c.xa = xa; c.elem = c.a_elem = DT_F16; c.splitk = 1;
+  c.family = IG_WREG; c.bm = bm; c.bn = 128; c.ns = depth; c.nw = 8; c.mode = mode; c.elem = c.a_elem = DT_F16; c.splitk = 1;
+  c.xa = xa ? (p.xa_nctx + 95) / 96 : 0;      // the context's 96-key blocks: 1 = the form with the block in registers, 2 .. 4 = the long form
   set_geometry(c, p);
   return c;
 }
@@ -268,10 +274,13 @@ bool select_f16(const IgemmParams& p, int v, const SelectKnobs& k, IgemmChoice& 
   if (p.xa_k) {
     // fused cross-attention: wave tiles of 64 columns only, chosen by the same cost model
     if (p.act != 0 || p.n_split < p.N || p.stat_out || p.R || p.ebias ||
-        !igemm_xattn_ok(p.a_dt, p.c_dt, p.M, p.N, p.K, p.rpb, p.xa_nctx))
+        !igemm_xattn_ok(p.a_dt, p.c_dt, p.M, p.N, p.K, p.rpb, p.xa_nctx, k, p.Wf && !p.xa_k_lo))
       throw std::runtime_error("igemm: fused cross-attention needs a plain f16 projection (no residual / split outputs)");
     if (!p.xa_k_lo && p.c_dt != DT_F16) throw std::runtime_error("igemm: the f16 fused cross-attention writes f16 rows");
-    const bool forced_pipe = v == 35 || v == 36 || v == 44 || v == 45;     // forced pipe tiles stay forced
+    const bool forced_pipe = xattn_forced_pipe(v);     // forced pipe tiles stay forced
+    // (above 96 keys igemm_xattn_ok has just answered for the weights-in-registers form: the pipe epilogues hold one block)
+    if (p.xa_nctx > 96 && (forced_pipe || !igemm_wreg_xattn_selected(p, k)))
+      throw std::runtime_error("igemm: fused cross-attention over more than 96 keys needs the weights-in-registers kernel");
     if (p.xa_k_lo) {     // split precision: the one-MFMA-row tiles only (128x128 / 96x128)
       c = from_tile(pick_tile(p, {36, 45}) == 45 ? 45 : 36, DT_F16, p);
       c.xh = 1;
@@ -480,10 +489,20 @@ bool igemm_gn_part_ok(const IgemmParams& p, const SelectKnobs& k) {
   return p.N % 160 != 0 || tile_cost(q, nk, 35) - tile_cost(q, nk, 49) < 6000.0;
 }
 
-bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx) {
+bool igemm_xattn_ok(int a_dt, int c_dt, int M, int N, int K, int rpb, int n_ctx, const SelectKnobs& k, bool wreg_form) {
   // (c_dt: f16 rows; HL16 rows for the split-precision form behind an fp32-class out-projection -- the row / staged epilogues store either)
-  return a_dt == DT_F16 && (c_dt == DT_F16 || c_dt == DT_HL) && M > 0 && N % 64 == 0 && K % 64 == 0 && rpb > 0 && rpb % 64 == 0 && M % rpb == 0 &&
-         n_ctx >= 1 && n_ctx <= 96;
+  if (!(a_dt == DT_F16 && (c_dt == DT_F16 || c_dt == DT_HL) && M > 0 && N % 64 == 0 && K % 64 == 0 && rpb > 0 && rpb % 64 == 0 && M % rpb == 0 && n_ctx >= 1))
+    return false;
+  if (n_ctx <= 96) return true;      // one block: every epilogue form; neither the knobs nor the weights' forms are read
+  // 97 .. 384 keys: only the weights-in-registers XA form walks blocks (xattn_unit_long).  Everything of wreg_takes / igemm_wreg_xattn_selected that a
+  // shape, the knobs or the operands' forms decide is decided HERE, so that the plan (UNet::set_context packs the blocked image,
+  // spatial_transformer sets xa_k) and the selection cannot disagree: 128-column tiles, whole k-tiles, f16 rows, the pair's grid in one round,
+  // the two A/B knobs, no forced pipe tile.  xattn_long_max_blocks: the last block count the fused form is kept for.
+  if (!wreg_form || n_ctx > 96 * xattn_long_max_blocks || c_dt != DT_F16 || N % 128 != 0 || K < 128) return false;
+  if (!k.zero_page || !k.igemm_wreg || !k.wreg_xattn || k.igemm_variant < 0 || xattn_forced_pipe(k.igemm_variant)) return false;
+  IgemmParams q{};
+  q.M = M; q.N = N; q.rpb = rpb;
+  return wreg_pair_grid_fits(q);
 }
 bool igemm_phase_ok(const IgemmParams& p, int compute_dt, const SelectKnobs& k) {
   if (k.igemm_variant < 0 || !phase_shape_ok(p, compute_dt == DT_HL ? 32 : 64)) return false;

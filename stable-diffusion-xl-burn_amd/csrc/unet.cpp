@@ -224,6 +224,8 @@ static std::atomic<int> g_mix_classes{-1};     // A/B / debugging knob (sdxl_deb
 void unet_set_mix_classes(int v) { g_mix_classes = v; }
 static std::atomic<int> g_hl_demote{0};
 void unet_set_hl_demote(int mask) { g_hl_demote = mask; }
+static std::atomic<int> g_xattn_long{1};
+void unet_set_xattn_long(int v) { g_xattn_long = v; }
 int unet_hl_demote() { return g_hl_demote.load(); }
 
 // the exact-f16 flag (acc_scale[1]) of every packed matrix of a demoted class reads 1 -- the kernel then leaves its w_lo MFMAs out --
@@ -362,14 +364,24 @@ void UNet::set_context(const float* context, int n_ctx, const float* label, int 
   // (MIX_XATTN_SPLIT: TWO images -- the hi and the lo halves of the fp32-class projection -- for the split-precision form of that epilogue)
   bool pack_xs = false, pack_xa = false;
   for (const STW* st : st_list_) { pack_xs = pack_xs || st->plan.xattn == XA_SPLIT; pack_xa = pack_xa || st->plan.xattn != XA_LAUNCH; }
-  pack_xs = pack_xs && n_ctx <= 96; pack_xa = pack_xa && n_ctx <= 96;
+  // more than 96 keys (a prompt of two to four 77-token chunks): the blocked image, where the weights-in-registers form of the fused launch will take
+  // a transformer's width (igemm_xattn_ok -- the predicate spatial_transformer and the selection ask; rows per entry are not known here: one 64-row
+  // entry stands in, the forward asks again with its own) and the knob "xattn_long" allows it; the split-precision form keeps its 96 keys
+  bool long_ok = false;
+  if (n_ctx > 96 && g_xattn_long.load()) {
+    const SelectKnobs knobs = igemm_launch_knobs();
+    for (const STW* st : st_list_)
+      if (!st->blocks.empty())
+        long_ok = long_ok || igemm_xattn_ok(DT_F16, DT_F16, 64, st->C, st->C, 64, n_ctx, knobs, st->blocks[0].q2.wf || st->blocks[0].q2_sh.wf);
+  }
+  pack_xs = pack_xs && n_ctx <= 96; pack_xa = pack_xa && (n_ctx <= 96 || long_ok);
   const int kvdt = attn_dt();                           // dtype of the K / V^T caches (fp32 in the split-operand mode)
   const int emb = 4 * cfg_.model_channels;
   {   // precision-frontier instrument: the demoted classes take effect from here (weights now, activations in every forward after)
     const int dm = cdt_ == DT_HL ? unet_hl_demote() : 0;
     if (dm != demote_mask_ || (dm && demote_flags_.empty())) { demote_mask_ = dm; apply_demote_weights(s); }
   }
-  if (B != ctx_B_ || n_ctx != n_ctx_) {
+  if (B != ctx_B_ || n_ctx != n_ctx_ || pack_xa != ctx_xa_) {
     // (re)allocate the caches; captured graphs hold these addresses
     if (graph_) { (void)hipGraphExecDestroy(graph_); graph_ = nullptr; plan_runs_ = 0; }
     // the recorded warming schedule holds raw pointers into ctx_arena_ (the packed context of the fused cross-attention
@@ -380,7 +392,7 @@ void UNet::set_context(const float* context, int n_ctx, const float* label, int 
     for (const STW* st : st_list_)
       bytes += st->blocks.size() * (round_up((size_t)B * n_ctx * st->C * dt_size(kvdt), 256) +
                                     round_up((size_t)B * st->C * vt_ld * dt_size(kvdt), 256) +
-                                    (pack_xa ? round_up(xattn_pack_bytes(B, st->C), 256) : 0) + (pack_xs ? round_up(xattn_pack_bytes(B, st->C), 256) : 0) + 768);
+                                    (pack_xa ? round_up(xattn_pack_bytes(B, st->C, n_ctx), 256) : 0) + (pack_xs ? round_up(xattn_pack_bytes(B, st->C, n_ctx), 256) : 0) + 768);
     bytes += 3 * round_up((size_t)B * emb * sizeof(float), 256);
     if (cdt_ == DT_HL) bytes += round_up((size_t)B * n_ctx * cfg_.context_dim * 4, 256) + 256;   // HL16 copy of the context
     if (cdt_ == DT_HL) {   // fp32 scratch of one block's K / V^T projection: the caches themselves are HL16 (what the attention kernel reads)
@@ -398,14 +410,14 @@ void UNet::set_context(const float* context, int n_ctx, const float* label, int 
         KV kv;
         kv.k = ctx_arena_.alloc((size_t)B * n_ctx * st->C * dt_size(kvdt));
         kv.vt = ctx_arena_.alloc((size_t)B * st->C * vt_ld * dt_size(kvdt));
-        if (pack_xa) kv.xa = ctx_arena_.alloc(xattn_pack_bytes(B, st->C));
-        if (pack_xs) kv.xa_lo = ctx_arena_.alloc(xattn_pack_bytes(B, st->C));
+        if (pack_xa) kv.xa = ctx_arena_.alloc(xattn_pack_bytes(B, st->C, n_ctx));
+        if (pack_xs) kv.xa_lo = ctx_arena_.alloc(xattn_pack_bytes(B, st->C, n_ctx));
         v.push_back(kv);
       }
       kv_.push_back(v);
     }
     label_emb_ = (float*)ctx_arena_.alloc((size_t)B * emb * sizeof(float));
-    ctx_B_ = B; n_ctx_ = n_ctx; vt_ld_ctx_ = vt_ld;
+    ctx_B_ = B; n_ctx_ = n_ctx; vt_ld_ctx_ = vt_ld; ctx_xa_ = pack_xa;
   }
   Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &ctx_arena_; ex.demote = demote_mask_;
   const size_t m0 = ctx_arena_.mark();
@@ -504,15 +516,18 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   // cross-attention caches of this run's batch entries (dry runs carry null caches)
   const int adt = attn_dt();      // q / k / V^T / attention output: the compute dtype, fp32 in the split-operand mode
   auto kv_k = [&](int s_, size_t j) { char* k = (char*)kv_[s_][j].k; return (void*)(k ? k + (size_t)ex.b0 * n_ctx_ * C * dt_size(adt) : k); };
-  auto kv_xa = [&](int s_, size_t j) { char* v = (char*)kv_[s_][j].xa; return (const void*)(v ? v + xattn_pack_bytes(ex.b0, C) : v); };
-  auto kv_xa_lo = [&](int s_, size_t j) { char* v = (char*)kv_[s_][j].xa_lo; return (const void*)(v ? v + xattn_pack_bytes(ex.b0, C) : v); };
+  auto kv_xa = [&](int s_, size_t j) { char* v = (char*)kv_[s_][j].xa; return (const void*)(v ? v + xattn_pack_bytes(ex.b0, C, n_ctx_) : v); };
+  auto kv_xa_lo = [&](int s_, size_t j) { char* v = (char*)kv_[s_][j].xa_lo; return (const void*)(v ? v + xattn_pack_bytes(ex.b0, C, n_ctx_) : v); };
   auto kv_vt = [&](int s_, size_t j) { char* v = (char*)kv_[s_][j].vt; return (const void*)(v ? v + (size_t)ex.b0 * C * vt_ld_ctx_ * dt_size(adt) : v); };
   Act gn = ex.alloc(M, C, ex.cdt);
   run_groupnorm(ex, w.norm, x, B, HW, gn, false);
   demote_lo(ex, DM_CONV_PROJ, gn, M, C);
   Act t = ex.alloc(M, C, ex.sdt);
-  // cross-attention fused into the query projection (f16 operands, <= 96 context tokens; igemm_xattn_ok)
-  const bool xattn = plan_xattn_ && igemm_xattn_ok(fuse_ln_ ? ex.sdt : ex.cdt, ex.cdt, (int)M, C, C, HW, n_ctx_);
+  // cross-attention fused into the query projection (f16 operands; igemm_xattn_ok: up to 96 context tokens in every form, up to 384 where the
+  // weights-in-registers form takes the launch and set_context packed the blocked image)
+  const SelectKnobs xknobs = igemm_launch_knobs();
+  const bool xa_img = n_ctx_ <= 96 || ctx_xa_;
+  const bool xattn = plan_xattn_ && xa_img && igemm_xattn_ok(fuse_ln_ ? ex.sdt : ex.cdt, ex.cdt, (int)M, C, C, HW, n_ctx_, xknobs, !w.blocks.empty() && w.blocks[0].q2.wf);
   // folded LayerNorms: two ping-pong [M][C/64][2] partial-sum buffers -- each is written by one GEMM and read by the next
   float* stbuf[2] = {nullptr, nullptr};
   if (fuse_ln_) for (int i = 0; i < 2; ++i) stbuf[i] = (float*)ex.act->alloc(M * (size_t)(C / 64) * 2 * sizeof(float));
@@ -557,7 +572,8 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
   if (pl.q2 == LF_F16 && !q2_widen) q32 = ex.alloc(M, C, DT_F32);
   // cross-attention inside the query projection's epilogue (the context images of set_context): q never reaches memory, no attention launch
   const bool xa_fused = pl.xattn != XA_LAUNCH && plan_xattn_ && !w.blocks.empty() && (pl.xattn == XA_SPLIT ? kv_[si][0].xa_lo : kv_[si][0].xa) &&
-                        igemm_xattn_ok(DT_F16, ao2.dt, (int)M, C, pl.q2 == LF_X2 ? 2 * C : C, HW, n_ctx_);
+                        igemm_xattn_ok(DT_F16, ao2.dt, (int)M, C, pl.q2 == LF_X2 ? 2 * C : C, HW, n_ctx_, xknobs,
+                                       pl.xattn == XA_F16 && w.blocks[0].q2.wf && (!pl.q2_sh || w.blocks[0].q2_sh.wf));      // (ln_input picks either weight)
   auto want_shadow = [&](Epi& e, bool sh, LinForm f, const NormW& n) { want_ln_shadow(lo, e, sh, f, n); };
   auto ln_in = [&](const Lin& plain, const Lin& sh, LinForm f, const NormW& n, int cls) { return ln_input(ex, lo, plain, sh, f, n, t, cls); };
   const auto x2op = x2_operand;

@@ -552,7 +552,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     if (igemm_phase_ok(q, wdt_, knobs)) { p = q; wbytes_f16 = 4 * (size_t)w.Npad * q.Kpad * 2; }
   }
   if (e.fold_done) *e.fold_done = p.ph_rows != 0;
-  SDXL_REQUIRE(!e.xa_k || igemm_xattn_ok(a.dt, out.dt, p.M, p.N, p.K, p.rpb, e.xa_nctx), "fused cross-attention: unsupported shape");
+  SDXL_REQUIRE(!e.xa_k || igemm_xattn_ok(a.dt, out.dt, p.M, p.N, p.K, p.rpb, e.xa_nctx, knobs, p.Wf && !p.xa_k_lo), "fused cross-attention: unsupported shape");
   SDXL_REQUIRE(!e.ln_stat || (w.ln_k ? w.ln_k : w.K) % 64 == 0, "LayerNorm-folded GEMM needs K % 64 == 0");
   SDXL_REQUIRE(!e.stat_out || (w.N % 64 == 0 && (e.n_split < 0 || e.n_split >= w.N) && e.act == 0), "row statistics need a plain N % 64 == 0 output");
   SDXL_REQUIRE(!e.ln_stat || w.cs, "ln_stat given but the weight is not LayerNorm-folded");
@@ -579,7 +579,7 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     }
     if (ws.recording) {
       // (a fused cross-attention projection also reads the packed context of its batch entries: a target of its own in front of it)
-      if (p.xa_k) ws.seq.push_back(WarmSeq::Item{p.xa_k, (unsigned)xattn_pack_bytes(p.M / p.rpb, p.N), false, 0u, {nullptr, nullptr, nullptr}, {0u, 0u, 0u}});
+      if (p.xa_k) ws.seq.push_back(WarmSeq::Item{p.xa_k, (unsigned)xattn_pack_bytes(p.M / p.rpb, p.N, p.xa_nctx), false, 0u, {nullptr, nullptr, nullptr}, {0u, 0u, 0u}});
       // what a host can carry without outliving its own tiles: its >= 36 warmers pull ~30 GB/s each, the shortest host runs 13 us
       const unsigned budget = host ? 14u << 20 : 0u;
       ws.seq.push_back(WarmSeq::Item{lo, (unsigned)(hi - lo), host, budget, {nullptr, nullptr, nullptr}, {0u, 0u, 0u}});

@@ -152,3 +152,23 @@ def tokenize_text(text: str, tokenizer: _BpeTokenizer, seq_len: int) -> List[int
     ids = tokenizer.encode(text, True, True)
     ids = ids[:seq_len] + [tokenizer.padding_token()] * max(0, seq_len - len(ids))
     return ids
+
+
+MAX_PROMPT_CHUNKS = 4      # 4 x 77 = 308 context tokens: what the UNet's fused cross-attention walks (up to 384 keys)
+
+
+def tokenize_text_chunks(text: str, tokenizer: _BpeTokenizer, seq_len: int, max_chunks: int) -> List[List[int]]:
+    """A prompt longer than one context window as several windows (the reference has one: text beyond it is cut off).  The text is
+    encoded without sot / eot and cut into pieces of seq_len - 2 ids; each piece becomes [sot] + piece + [eot], padded to seq_len
+    with the tokenizer's pad id.  At least one chunk (the empty prompt is [sot, eot, pad ...]); text beyond max_chunks chunks is
+    dropped.  max_chunks = 1 is tokenize_text itself, id for id -- including its truncation, which keeps seq_len - 1 ids of the
+    text and no eot."""
+    if max_chunks < 1:
+        raise ValueError("max_chunks must be at least 1")
+    if max_chunks == 1:
+        return [tokenize_text(text, tokenizer, seq_len)]
+    ids = tokenizer.encode(text, False, False)
+    n = seq_len - 2
+    pieces = [ids[i:i + n] for i in range(0, len(ids), n)][:max_chunks] or [[]]
+    pad = tokenizer.padding_token()
+    return [[tokenizer.start_of_text_token()] + p + [tokenizer.end_of_text_token()] + [pad] * (n - len(p)) for p in pieces]
