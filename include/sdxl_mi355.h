@@ -321,6 +321,26 @@ int sdxl_diffuser_get_guidance(sdxl_diffuser* d, sdxl_guidance* out);
  * the result reproducible -- 64 merges at 1024 x 1024, and a cost that grows with HW */
 int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int n, int HW, const float* scales, float rescale,
                              float* factors_out);
+/* the trajectory without the UNet (a test seam: what pins the bits of the per-step kernel): every launch a trajectory call makes between two
+ * UNet forwards -- the coefficient table, the initial launch, per iteration the rescale factors and the update -- with the noise predictions
+ * given.  iterations = sdxl_step_count(n_steps, step_start, n_train_steps), B = n where single != 0, else 2n.  Host: alphas_cumprod_host
+ * [n_train_steps], guidance (NULL: the default), seeds [n] (NULL: explicit noise, eta must be 0).  Device inputs: eps [iterations, B, h*w, 4]
+ * fp32 (cond entries first), latent0 [n,4,h,w], and optionally reference [n,4,h,w] + mask uint8 [n,4,h,w] (inpainting; with explicit noise
+ * step_noise [iterations, n,4,h,w] too).  Device outputs, all fp32: latents_out [iterations+1, n,4,h,w] (after the initial launch and after
+ * every update), hist_out [n,4,h,w] (the x0 history after the last update; SDXL_SOLVER_DPMPP_2M only, else untouched, may be NULL),
+ * unet_in_out [B, h*w, 4] (the UNet input after the last launch, kept as f16 in between where input_f16 != 0), timesteps_out [iterations+1].
+ * SDXL_ERR_INVALID before anything is launched: a NULL required pointer, n outside 1..8, h*w outside 1..2^22, a solver, eta, schedule or
+ * alphas sdxl_solver_coefficients refuses, mask without reference (or the reverse), explicit-noise inpainting without step_noise, eta != 0
+ * without seeds, options sdxl_guidance_check refuses (single != 0 takes the default or SDXL_GUIDANCE_OFF only), n_scales != 0 && != n. */
+typedef struct {
+  const float* alphas_cumprod_host; int32_t n_train_steps, n_steps, step_start;
+  int32_t solver; double eta; double unconditional_guidance_scale;
+  const sdxl_guidance* guidance; int32_t single;
+  int32_t n, h, w; int32_t input_f16;
+  const float* eps; const float* latent0; const float* reference; const uint8_t* mask; const float* step_noise; const uint64_t* seeds;
+  float* latents_out; float* hist_out; float* unet_in_out; float* timesteps_out;
+} sdxl_step_replay_args;
+int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

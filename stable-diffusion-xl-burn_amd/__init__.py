@@ -108,6 +108,7 @@ ABI_SYMBOLS = [
     "sdxl_gen_noise", "sdxl_sample_latent_seeded", "sdxl_sample_latent_with_inpainting_seeded", "sdxl_refine_latent_seeded",
     "sdxl_diffuser_set_solver", "sdxl_diffuser_get_solver", "sdxl_solver_coefficients",
     "sdxl_guidance_default", "sdxl_guidance_check", "sdxl_diffuser_set_guidance", "sdxl_diffuser_get_guidance", "sdxl_cfg_rescale_factors",
+    "sdxl_sampler_step_replay",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -162,6 +163,8 @@ def lib() -> ctypes.CDLL:
             l.sdxl_diffuser_get_guidance.argtypes = [ctypes.c_void_p, ctypes.POINTER(Guidance)]
             l.sdxl_cfg_rescale_factors.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_float, ctypes.c_void_p]
+        if hasattr(l, "sdxl_sampler_step_replay"):
+            l.sdxl_sampler_step_replay.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = l
     return _lib
 
@@ -845,6 +848,47 @@ def cfg_rescale_factors(ctx: Context, eps, scales, rescale: float):
     out = torch.empty((n,), dtype=torch.float32, device="cuda")
     _check_invalid(lib().sdxl_cfg_rescale_factors(ctx.h, _stream(), pe, n, HW, (ctypes.c_float * max(n, 1))(*v), ctypes.c_float(rescale),
                                                   ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
+class _StepReplayArgsC(ctypes.Structure):
+    _fields_ = [("alphas_cumprod_host", _c_p), ("n_train_steps", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("step_start", ctypes.c_int32),
+                ("solver", ctypes.c_int32), ("eta", ctypes.c_double), ("unconditional_guidance_scale", ctypes.c_double),
+                ("guidance", ctypes.POINTER(Guidance)), ("single", ctypes.c_int32),
+                ("n", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("input_f16", ctypes.c_int32),
+                ("eps", _f_p), ("latent0", _f_p), ("reference", _f_p), ("mask", _f_p), ("step_noise", _f_p), ("seeds", _c_p),
+                ("latents_out", _f_p), ("hist_out", _f_p), ("unet_in_out", _f_p), ("timesteps_out", _f_p)]
+
+
+def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps, latent0, solver="ddim", eta: float = 0.0,
+                        cfg_scale: float = 7.5, guidance: Optional[Guidance] = None, single: bool = False, input_f16: bool = False,
+                        reference=None, mask=None, step_noise=None, seeds=None):
+    """sdxl_sampler_step_replay, the trajectory without the UNet (a test seam): eps [iterations, B, h*w, 4] and latent0 [n, 4, h, w] float32
+    CUDA tensors, B = n where single (or guidance mode "off"), else 2n.  Returns float32 CUDA tensors (latents [iterations + 1, n, 4, h, w],
+    hist [n, 4, h, w] -- zeros under DDIM --, unet_in [B, h*w, 4], timesteps [iterations + 1]).  Nothing is checked here but the shapes the
+    outputs are sized by: the engine reports what it refuses (InvalidArgument)."""
+    torch = _torch()
+    a = np.ascontiguousarray(alphas, dtype=np.float32)
+    eps, pe = _dev(eps)
+    latent0, pl = _dev(latent0)
+    n, h, w = int(latent0.shape[0]), int(latent0.shape[2]), int(latent0.shape[3])
+    iters = int(eps.shape[0])
+    B = n if single or (guidance is not None and guidance.mode == GUIDANCE_OFF) else 2 * n
+    want = step_count(n_steps, step_start, int(a.shape[0])) if n_steps >= 1 else -1
+    if (want >= 0 and iters != want) or tuple(eps.shape[1:]) != (B, h * w, 4) or latent0.shape[1] != 4:
+        raise InvalidArgument(f"eps must be [{want}, {B}, {h * w}, 4] and latent0 [n, 4, h, w]")
+    for t, lead in ((reference, ()), (mask, ()), (step_noise, (iters,))):
+        if t is not None and tuple(t.shape) != lead + (n, 4, h, w):
+            raise InvalidArgument(f"reference / mask must be [{n}, 4, {h}, {w}], step_noise [{iters}, {n}, 4, {h}, {w}]")
+    keep = [_dev(t, torch.uint8 if t is mask else None) if t is not None else (None, None) for t in (reference, mask, step_noise)]
+    out = (torch.zeros((iters + 1, n, 4, h, w), device="cuda"), torch.zeros((n, 4, h, w), device="cuda"),
+           torch.zeros((B, h * w, 4), device="cuda"), torch.zeros((iters + 1,), device="cuda"))
+    sd = _seeds(seeds, n)
+    args = _StepReplayArgsC(a.ctypes.data_as(_c_p), int(a.shape[0]), n_steps, step_start, _solver(solver), float(eta), float(cfg_scale),
+                            ctypes.pointer(guidance) if guidance is not None else None, int(single), n, h, w, int(input_f16),
+                            pe, pl, keep[0][1], keep[1][1], keep[2][1], ctypes.cast(sd, _c_p) if sd is not None else None,
+                            *[ctypes.c_void_p(t.data_ptr()) for t in out])
+    _check_invalid(lib().sdxl_sampler_step_replay(ctx.h, _stream(), ctypes.byref(args)))
     return out
 
 

@@ -648,17 +648,26 @@ int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out) {
   return SDXL_OK;
 }
 // host logic of the sampler's coefficient table -- no device needed; the function Diffuser::diffuse fills its DPM-Solver++(2M) table from
+static const char* schedule_args_error(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta) {
+  if (!alphas_cumprod_host) return "null argument";
+  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)";
+  if (!(eta >= 0.0 && eta <= 1.0)) return "eta must be a finite value in [0, 1]";
+  if (n_train_steps < 1 || n_steps < 1 || n_steps > n_train_steps) return "n_steps out of range (1..n_train_steps)";
+  if (step_start < 0 || step_start >= n_train_steps) return "step_start out of range (0..n_train_steps-1)";
+  return nullptr;
+}
+static const char* alphas_error(const float* alphas_cumprod_host, int n_train_steps) {
+  for (int i = 0; i < n_train_steps; ++i)
+    if (!(alphas_cumprod_host[i] > 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
+  return nullptr;
+}
 int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta,
                              double* out, int capacity_steps) {
-  if (!alphas_cumprod_host || !out) return fail(SDXL_ERR_INVALID, "null argument");
-  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return fail(SDXL_ERR_INVALID, "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)");
-  if (!(eta >= 0.0 && eta <= 1.0)) return fail(SDXL_ERR_INVALID, "eta must be a finite value in [0, 1]");
-  if (n_train_steps < 1 || n_steps < 1 || n_steps > n_train_steps) return fail(SDXL_ERR_INVALID, "n_steps out of range (1..n_train_steps)");
-  if (step_start < 0 || step_start >= n_train_steps) return fail(SDXL_ERR_INVALID, "step_start out of range (0..n_train_steps-1)");
+  if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = schedule_args_error(alphas_cumprod_host, n_train_steps, n_steps, step_start, solver, eta)) return fail(SDXL_ERR_INVALID, m);
   const int iters = (int)Diffuser::step_schedule(n_steps, step_start, n_train_steps).size();
   if (capacity_steps < iters) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than sdxl_step_count");
-  for (int i = 0; i < n_train_steps; ++i)
-    if (!(alphas_cumprod_host[i] > 0.f && alphas_cumprod_host[i] < 1.f)) return fail(SDXL_ERR_INVALID, "alphas_cumprod outside (0, 1)");
+  if (const char* m = alphas_error(alphas_cumprod_host, n_train_steps)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
   std::vector<double> rows((size_t)4 * iters);
@@ -714,6 +723,45 @@ int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int 
   float* partials = (float*)tmp.get(cfg_moments_floats(n, HW) * sizeof(float));
   launch_cfg_rescale_factors(eps, DT_F32, 4, n, HW, k, rescale, partials, factors_out, s);
   SDXL_HIP(hipStreamSynchronize(s));     // the scratch goes away with this call
+  API_END
+}
+// the trajectory without the UNet: a StepLoop of its own, driven as Diffuser::diffuse drives its one, with eps where the UNet's output would be
+int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a) {
+  if (!ctx || !a || !a->eps || !a->latent0 || !a->latents_out || !a->unet_in_out || !a->timesteps_out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (a->n < 1 || a->n > kMaxSeeds || a->h < 1 || a->w < 1 || (int64_t)a->h * a->w > 1 << 22)
+    return fail(SDXL_ERR_INVALID, "step_replay: n (1..8) or h * w (1..2^22) out of range");
+  if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = alphas_error(a->alphas_cumprod_host, a->n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  if ((a->mask != nullptr) != (a->reference != nullptr)) return fail(SDXL_ERR_INVALID, "inpainting needs reference and mask");
+  if (a->mask && !a->seeds && !a->step_noise) return fail(SDXL_ERR_INVALID, "inpainting with explicit noise needs step_noise");
+  if (!a->seeds && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "eta needs seeds: explicit noise carries none for the sigma term");
+  const Guidance g = to_guidance(a->guidance);
+  if (const char* m = Diffuser::guidance_error(g, a->single != 0)) return fail(SDXL_ERR_INVALID, m);
+  if (g.n_scales != 0 && g.n_scales != a->n) return fail(SDXL_ERR_INVALID, "guidance: n_scales differs from the batch (n)");
+  API_BEGIN
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  const bool single = a->single != 0 || g.mode == kGuidanceOff;
+  const int n = a->n, HW = a->h * a->w, B = single ? n : 2 * n;
+  const size_t elems = (size_t)n * 4 * HW, bytes = elems * sizeof(float);
+  const int in_dt = a->input_f16 ? DT_F16 : DT_F32;
+  const std::vector<double> alphas(a->alphas_cumprod_host, a->alphas_cumprod_host + a->n_train_steps);   // elem -> f64 as the Diffuser holds them
+  Tmp tmp;
+  StepIo io{};
+  io.latent = (float*)tmp.get(bytes);
+  io.unet_in = tmp.get((size_t)B * HW * 4 * sizeof(float)); io.in_dt = in_dt;
+  io.reference = a->reference; io.mask = a->mask; io.step_noise = a->step_noise; io.seeds = a->seeds;
+  SDXL_HIP(hipMemcpyAsync(io.latent, a->latent0, bytes, hipMemcpyDeviceToDevice, s));
+  StepLoop loop;
+  const int iters = loop.begin(alphas, a->n_steps, a->step_start, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s);
+  for (int i = 0; i <= iters; ++i) {
+    if (i > 0) loop.after_forward(i - 1, a->eps + (size_t)(i - 1) * B * HW * 4, s);
+    SDXL_HIP(hipMemcpyAsync(a->latents_out + (size_t)i * elems, io.latent, bytes, hipMemcpyDeviceToDevice, s));
+    SDXL_HIP(hipMemcpyAsync(a->timesteps_out + i, loop.t_dev(), sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  if (a->solver == SDXL_SOLVER_DPMPP_2M && a->hist_out) SDXL_HIP(hipMemcpyAsync(a->hist_out, loop.hist(), bytes, hipMemcpyDeviceToDevice, s));
+  launch_copy_rows(io.unet_in, in_dt, 4, a->unet_in_out, DT_F32, 4, B * HW, 4, s);
+  SDXL_HIP(hipStreamSynchronize(s));     // the loop and the scratch go away with this call
   API_END
 }
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled) {

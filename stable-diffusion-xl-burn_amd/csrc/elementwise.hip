@@ -559,7 +559,7 @@ void launch_causal_mask(float* out, int n, hipStream_t s) {
 // 64-bit seed (low, high), counter = (hw, draw, 0, 0).  One call is the four channel values of one latent pixel: two
 // Box-Muller pairs from the four output words.  Both uniforms are 24-bit fractions, exact in fp32; ua is in (0, 1] so the
 // logarithm is finite and |z| <= sqrt(48 ln 2).  Contraction is off so the stand-alone fill and the in-register draw of
-// ddim_kernel round every product alike.
+// step_kernel round every product alike.
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t out[4]) {
 #pragma unroll
@@ -608,16 +608,23 @@ void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// CFG combine + DDIM update + inpaint blend + next-UNet-input refresh, one thread per latent pixel.
-// stablediffusion/mod.rs:423-428 (update), :539-540 (CFG), :463-465 (mask_where blend).
-// SEEDED = false: explicit noise, eta = 0 (step_noise tensor, sigma never read).  SEEDED = true: the blend noise of :463 and the
-// gen_noise() * sigma term of :427 are drawn in registers from the entry's seed; z is drawn only where sigma != 0.
-// Every rounding is written out (contraction off, fmaf where a product is fused) so that both instantiations round alike and the
-// explicit one keeps the bits the committed fixtures were produced with: e = fma(ec - eu, cfg, eu), x0 = fma(-e, sqrt_1ma, x) / sqrt_a,
-// then x = x0 sqrt_ap + e sqrt_1map with the first product fused into the sum on channels 2 and 3 only (channels 0 and 1 round both
-// products: that is how the update was first compiled, and a trajectory amplifies a last-bit change); the blend rounds both products.
-template <bool SEEDED>
-__global__ void ddim_kernel(const DdimParams p, int do_update) {
+// The per-step kernel: CFG combine + DDIM or DPM-Solver++(2M) update + sigma noise + inpaint blend + next-UNet-input refresh, one thread per
+// latent pixel.  stablediffusion/mod.rs:423-428 (update), :539-540 (CFG), :463-465 (mask_where blend).
+// SEEDED = false: explicit noise, eta = 0 (step_noise tensor; sigma / c_z never read).  SEEDED = true: the blend noise of :463 and the
+// gen_noise() * sigma term of :427 are drawn in registers from the entry's seed (never stored); z is drawn only where its coefficient != 0.
+// Every rounding is written out -- contraction off, fmaf where a product is fused, correctly rounded division -- so the bits do not depend on
+// how the text is compiled; tests/test_gpu_sampler_step.py replays a recorded matrix of cases and demands them:
+//     e   = fma(ec - eu, scales[b], eu), then e * factors[b] under CFG rescale; e = ec without CFG and on an inactive iteration
+//     x0  = fma(-e, sqrt_1ma, x) / sqrt_a
+//   kSolverDdim:     x = x0 sqrt_ap + e sqrt_1map with the first product fused into the sum on channels 2 and 3 only (channels 0 and 1 round
+//                    both products: that is how the update was first compiled, and a trajectory amplifies a last-bit change)
+//   kSolverDpmpp2M:  acc = c_1 * x0p      (p.hist, read only where c_1 != 0: a first-order row never looks at the history, whatever it holds)
+//                    acc = fma(x0, c_0, acc);  x = fma(x, c_x, acc);  p.hist = x0 -- with inpainting the one computed from the blended state.
+//                    The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.
+//     x   = fma(z, sigma or c_z, x)       (SEEDED, coefficient != 0; z = seeded_normal4(seed, hw, draw_sigma(idx)))
+//   the blend rounds both products.
+template <int SOLVER, bool SEEDED>
+__global__ void step_kernel(const StepParams p, int do_update) {
 #pragma clang fp contract(off)
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)p.n * p.HW) return;
@@ -630,95 +637,48 @@ __global__ void ddim_kernel(const DdimParams p, int do_update) {
   for (int c = 0; c < 4; ++c) x[c] = p.latent[((size_t)b * 4 + c) * p.HW + hw];
   if (do_update) {
     const StepCoef k = p.table[idx];
+    const bool active = p.use_cfg && (!p.active || p.active[idx] != 0);     // uniform over the launch, as is whether p.factors is set
+    // b is per lane (an entry boundary falls inside a wave wherever HW % 64 != 0).  The scale is selected from the eight argument words, which
+    // arrive through scalar loads with the other arguments; indexing the by-value array with b made it a vector load from the argument
+    // segment in front of the CFG line
+    float sb = p.scales.v[0];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-      float e = ec;
-      if (p.use_cfg) {
-        const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-        e = __builtin_fmaf(ec - eu, k.cfg, eu);
-      }
-      const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
-      const float en = e * k.sqrt_1map;
-      x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
-    }
-    if constexpr (SEEDED) {
-      if (k.sigma != 0.f) {
-        float z[4];
-        seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], k.sigma, x[c]);
-      }
-    }
-  }
-  if (p.mask && next < p.n_steps_total) {
-    const StepCoef kn = p.table[next];
-    float z[4];
-    if constexpr (SEEDED) seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_blend((uint32_t)next), z);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const size_t e = ((size_t)b * 4 + c) * p.HW + hw;
-      if (!p.mask[e]) {
-        float zn;
-        if constexpr (SEEDED) zn = z[c]; else zn = p.step_noise[(size_t)next * p.n * 4 * p.HW + e];
-        x[c] = p.ref[e] * kn.sqrt_a + zn * kn.sqrt_1ma;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) p.latent[((size_t)b * 4 + c) * p.HW + hw] = x[c];
-  for (int r = 0; r < p.in_rep; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) st_f(p.unet_in, ((size_t)(r * p.n + b) * p.HW + hw) * p.in_ld + c, p.in_dt, x[c]);
-}
-// DPM-Solver++(2M) (SDE form where c_z != 0) in the same place: the table holds the 2M layout of StepCoef, p.hist the data prediction of the
-// previous iteration.  e and x0 exactly as in ddim_kernel; x0 is what the history keeps -- with inpainting the one computed from the blended
-// state.  The update, the same on all four channels, one rounding per line:
-//     acc = c_1 * x0p                (x0p read only where c_1 != 0: a first-order row never looks at the history, whatever it holds)
-//     acc = fma(x0, c_0, acc)
-//     acc = fma(x,  c_x, acc)
-//     acc = fma(z,  c_z, acc)        (SEEDED and c_z != 0 only; z = seeded_normal4(seed, hw, draw_sigma(idx)), never stored)
-// The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.  Load, CFG, blend and store restate ddim_kernel's lines
-// instead of sharing them through a helper: ddim_kernel stays the text it was compiled from when the fixtures were produced.
-template <bool SEEDED>
-__global__ void dpmpp2m_kernel(const DdimParams p, int do_update) {
-#pragma clang fp contract(off)
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)p.n * p.HW) return;
-  const int b = i / p.HW;
-  const int hw = i - (size_t)b * p.HW;
-  const int idx = *p.step_idx;
-  const int next = do_update ? idx + 1 : 0;
-  float x[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) x[c] = p.latent[((size_t)b * 4 + c) * p.HW + hw];
-  if (do_update) {
-    const StepCoef k = p.table[idx];
+    for (int j = 1; j < kMaxSeeds; ++j) sb = b == j ? p.scales.v[j] : sb;
+    const float fb = active && p.factors ? p.factors[b] : 1.f;
     float x0p[4] = {0.f, 0.f, 0.f, 0.f};
-    if (k.c_1 != 0.f) {
+    if constexpr (SOLVER == kSolverDpmpp2M) {
+      if (k.c_1 != 0.f) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
+        for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
+      }
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
       float e = ec;
-      if (p.use_cfg) {
+      if (active) {
         const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-        e = __builtin_fmaf(ec - eu, k.cfg, eu);
+        e = __builtin_fmaf(ec - eu, sb, eu);
+        if (p.factors) e = e * fb;
       }
       const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
-      p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
-      float acc = k.c_1 * x0p[c];
-      acc = __builtin_fmaf(x0, k.c_0, acc);
-      x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+      if constexpr (SOLVER == kSolverDpmpp2M) {
+        p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
+        float acc = k.c_1 * x0p[c];
+        acc = __builtin_fmaf(x0, k.c_0, acc);
+        x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+      } else {
+        const float en = e * k.sqrt_1map;
+        x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
+      }
     }
     if constexpr (SEEDED) {
-      if (k.c_z != 0.f) {
+      const float cz = SOLVER == kSolverDpmpp2M ? k.c_z : k.sigma;
+      if (cz != 0.f) {
         float z[4];
         seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], k.c_z, x[c]);
+        for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], cz, x[c]);
       }
     }
   }
@@ -747,21 +707,21 @@ __global__ void ddim_advance_kernel(const StepCoef* table, int* step_idx, float*
   *step_idx = next;
   *t_out = table[next].t;     // table carries one sentinel entry past the last step
 }
-void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s) {
+void launch_step(const StepParams& p, int do_update, hipStream_t s) {
   const size_t total = (size_t)p.n * p.HW;
   const dim3 grid((total + 255) / 256), block(256);
   if (p.solver == kSolverDpmpp2M) {
-    if (p.seeded) hipLaunchKernelGGL(dpmpp2m_kernel<true>, grid, block, 0, s, p, do_update);
-    else hipLaunchKernelGGL(dpmpp2m_kernel<false>, grid, block, 0, s, p, do_update);
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, true>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, false>), grid, block, 0, s, p, do_update);
   } else {
-    if (p.seeded) hipLaunchKernelGGL(ddim_kernel<true>, grid, block, 0, s, p, do_update);
-    else hipLaunchKernelGGL(ddim_kernel<false>, grid, block, 0, s, p, do_update);
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDdim, true>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverDdim, false>), grid, block, 0, s, p, do_update);
   }
   hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, do_update);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Guidance options (kernels.h GuidedParams): CFG rescale factors, then the per-step kernel with the guidance lines.
+// CFG rescale factors (kernels.h launch_cfg_rescale_factors): what the sampler runs in front of the per-step kernel where rescale is on.
 // Chan merge of (nb, mb, M2b) into (na, ma, M2a), as in norm.hip
 __device__ __forceinline__ void moments_merge(float& na, float& ma, float& m2a, float nb, float mb, float m2b) {
   if (nb == 0.f) return;
@@ -855,95 +815,6 @@ void launch_cfg_rescale_factors(const void* eps, int eps_dt, int eps_ld, int n, 
   const int blocks = cfg_moments_blocks(HW);
   hipLaunchKernelGGL(cfg_moments_kernel, dim3(blocks, n), dim3(kCfgMomentsBlock), 0, s, eps, eps_dt, eps_ld, n, HW, scales, partials);
   hipLaunchKernelGGL(cfg_factor_kernel, dim3(n), dim3(64), 0, s, (const float*)partials, blocks, phi, factors);
-}
-// The update launch of a handle with guidance options: ddim_kernel (SOLVER = kSolverDdim) or dpmpp2m_kernel (kSolverDpmpp2M) at do_update = 1
-// and use_cfg = 1, line for line -- the channel-0/1 rounding of the DDIM update included -- except the one CFG line, which becomes
-//     active iteration (g.active[idx]):  e = fma(ec - eu, g.scales.v[b], eu);  e = e * g.factors[b] where g.factors != nullptr
-//     inactive iteration:                e = ec   (eu is not read)
-// With scales all equal to the call's scalar, no factors and every iteration active this is the default kernel's arithmetic bit for bit.
-template <int SOLVER, bool SEEDED>
-__global__ void guided_step_kernel(const DdimParams p, const GuidedParams g) {
-#pragma clang fp contract(off)
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)p.n * p.HW) return;
-  const int b = i / p.HW;
-  const int hw = i - (size_t)b * p.HW;
-  const int idx = *p.step_idx;
-  const int next = idx + 1;
-  const bool active = g.active[idx] != 0;
-  const float sb = g.scales.v[b];
-  const float fb = active && g.factors ? g.factors[b] : 1.f;
-  float x[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) x[c] = p.latent[((size_t)b * 4 + c) * p.HW + hw];
-  const StepCoef k = p.table[idx];
-  float x0p[4] = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (SOLVER == kSolverDpmpp2M) {
-    if (k.c_1 != 0.f) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-    float e = ec;
-    if (active) {
-      const float eu = ld_f(p.eps, ((size_t)(p.n + b) * p.HW + hw) * p.eps_ld + c, p.eps_dt);
-      e = __builtin_fmaf(ec - eu, sb, eu);
-      if (g.factors) e = e * fb;
-    }
-    const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
-    if constexpr (SOLVER == kSolverDpmpp2M) {
-      p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
-      float acc = k.c_1 * x0p[c];
-      acc = __builtin_fmaf(x0, k.c_0, acc);
-      x[c] = __builtin_fmaf(x[c], k.c_x, acc);
-    } else {
-      const float en = e * k.sqrt_1map;
-      x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
-    }
-  }
-  if constexpr (SEEDED) {
-    const float cz = SOLVER == kSolverDpmpp2M ? k.c_z : k.sigma;
-    if (cz != 0.f) {
-      float z[4];
-      seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) x[c] = __builtin_fmaf(z[c], cz, x[c]);
-    }
-  }
-  if (p.mask && next < p.n_steps_total) {
-    const StepCoef kn = p.table[next];
-    float z[4];
-    if constexpr (SEEDED) seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_blend((uint32_t)next), z);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const size_t e = ((size_t)b * 4 + c) * p.HW + hw;
-      if (!p.mask[e]) {
-        float zn;
-        if constexpr (SEEDED) zn = z[c]; else zn = p.step_noise[(size_t)next * p.n * 4 * p.HW + e];
-        x[c] = p.ref[e] * kn.sqrt_a + zn * kn.sqrt_1ma;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) p.latent[((size_t)b * 4 + c) * p.HW + hw] = x[c];
-  for (int r = 0; r < p.in_rep; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) st_f(p.unet_in, ((size_t)(r * p.n + b) * p.HW + hw) * p.in_ld + c, p.in_dt, x[c]);
-}
-void launch_guided_step(const DdimParams& p, const GuidedParams& g, hipStream_t s) {
-  const size_t total = (size_t)p.n * p.HW;
-  const dim3 grid((total + 255) / 256), block(256);
-  if (p.solver == kSolverDpmpp2M) {
-    if (p.seeded) hipLaunchKernelGGL((guided_step_kernel<kSolverDpmpp2M, true>), grid, block, 0, s, p, g);
-    else hipLaunchKernelGGL((guided_step_kernel<kSolverDpmpp2M, false>), grid, block, 0, s, p, g);
-  } else {
-    if (p.seeded) hipLaunchKernelGGL((guided_step_kernel<kSolverDdim, true>), grid, block, 0, s, p, g);
-    else hipLaunchKernelGGL((guided_step_kernel<kSolverDdim, false>), grid, block, 0, s, p, g);
-  }
-  hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, 1);
 }
 __global__ void axpby_kernel(float* dst, const float* a, float sa, const float* b, float sb, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

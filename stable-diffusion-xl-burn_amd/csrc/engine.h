@@ -598,6 +598,46 @@ struct Guidance {
   bool plain() const { return mode == kGuidanceCfg && rescale == 0.f && n_scales == 0 && t_lo == 0 && t_hi == 0x7fffffff; }
 };
 
+// The trajectory minus the UNet: the coefficient table, the guidance interval and the launches between two UNet forwards.  Diffuser::diffuse
+// drives one with the UNet's output; sdxl_sampler_step_replay (the op-level test seam) drives one with given noise predictions.
+struct StepIo {                       // device buffers of one trajectory (seeds: host array [n], nullptr = explicit noise)
+  float* latent = nullptr;            // [n][4][HW] fp32, updated in place
+  int eps_ld = 4;                     // row stride of the noise predictions handed to after_forward
+  void* unet_in = nullptr; int in_dt = DT_F32; int in_ld = 4;     // next UNet input NHWC [B][HW][in_ld], B = n (single) or 2n
+  const float* reference = nullptr; const unsigned char* mask = nullptr; const float* step_noise = nullptr;
+  const uint64_t* seeds = nullptr;
+};
+class StepLoop {
+ public:
+  StepLoop();
+  ~StepLoop();
+  StepLoop(const StepLoop&) = delete;
+  StepLoop& operator=(const StepLoop&) = delete;
+  // Builds the StepCoef table (host f64 -> f32) and the active-iteration array of one trajectory, uploads them and runs the do_update = 0
+  // launch: *step_idx = 0, the step-0 inpainting blend, the first UNet input and timestep.  `single`: one branch, no CFG (B = n).  Returns the
+  // number of iterations.  alphas: the n_train alphas_cumprod values as f64.
+  int begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale, const Guidance& g,
+            bool single, int n, int HW, const StepIo& io, hipStream_t s);
+  // behind the UNet forward of iteration i: eps [B][HW][eps_ld] fp32 (cond entries first) -> the CFG rescale factors where rescale is on and
+  // the iteration active, then the update + advance launches
+  void after_forward(int i, const float* eps, hipStream_t s);
+  float* t_dev() const { return t_dev_; }       // device scalar: the timestep of the next UNet call
+  const float* hist() const { return hist_; }   // kSolverDpmpp2M: x0 of the previous iteration [n][4][HW]
+
+ private:
+  StepCoef* table_ = nullptr; int table_cap_ = 0;
+  // the per-iteration active flags next to the table (uploaded where an interval leaves an iteration out), the CFG rescale partials and the n factors
+  int* active_ = nullptr; int active_cap_ = 0;
+  float* moments_ = nullptr; size_t moments_cap_ = 0;
+  float* factors_ = nullptr;
+  int* step_idx_ = nullptr; float* t_dev_ = nullptr;
+  float* hist_ = nullptr; size_t hist_cap_ = 0;
+  // the trajectory begin() set up
+  StepParams p_{};
+  float rescale_ = 0.f;
+  std::vector<int> act_;           // host copy of the active flags: which iterations run the rescale launches
+};
+
 class Diffuser {
  public:
   Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, const float* alphas_host, int n_train,
@@ -630,8 +670,8 @@ class Diffuser {
   void set_solver(int solver);
   int solver() const { return solver_; }
   // guidance options, a per-handle choice like the solver.  guidance_error: host logic only -- the first complaint about `g` (for a refiner
-  // handle: anything but the default or kGuidanceOff), nullptr where it is valid.  set_guidance requires a valid `g`.  A handle with
-  // Guidance{} launches exactly what it launched before the options existed; kGuidanceOff runs the conditional branch alone (batch n).
+  // handle: anything but the default or kGuidanceOff), nullptr where it is valid.  set_guidance requires a valid `g`.  Guidance{} is
+  // the call's scalar as every entry's scale on every iteration (the reference's line); kGuidanceOff runs the conditional branch alone (batch n).
   static const char* guidance_error(const Guidance& g, bool is_refiner);
   void set_guidance(const Guidance& g);
   const Guidance& guidance() const { return guidance_; }
@@ -643,7 +683,15 @@ class Diffuser {
   float* trace = nullptr; int trace_cap = 0;
 
  private:
-  void ensure_state(size_t elems);   // latent_ (and hist_ under kSolverDpmpp2M) hold a trajectory of `elems` values
+  // what the six public calls share: latent_ sized, its start (noise, the seeded fill, or `renoise` re-noised to step_start), diffuse, copy out
+  struct Trajectory {
+    const float* noise = nullptr;                             // explicit start (or re-noise) tensor; nullptr with seeds
+    const float* renoise = nullptr; int step_start = 0;       // refine_latent: the finished latent and where to re-noise it to
+    const float* reference = nullptr; const unsigned char* mask = nullptr; const float* step_noise = nullptr;      // inpainting
+    const uint64_t* seeds = nullptr; double eta = 0.0;        // seeded noise
+  };
+  void trajectory(const Conditioning& c, double cfg_scale, int n_steps, const Trajectory& t, float* out, hipStream_t s);
+  // context setup, then StepLoop::begin and one UNet forward + StepLoop::after_forward per iteration
   void diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale, const float* reference,
                const unsigned char* mask, const float* step_noise, hipStream_t s, const uint64_t* seeds = nullptr, double eta = 0.0);
   std::unique_ptr<UNet> unet_;
@@ -653,15 +701,9 @@ class Diffuser {
   // device state
   float* latent_ = nullptr; size_t latent_cap_ = 0;
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
-  float* hist_ = nullptr; size_t hist_cap_ = 0;       // kSolverDpmpp2M: x0 of the previous iteration [n,4,h,w], allocated with the latent
   int solver_ = kSolverDdim;
   Guidance guidance_;
-  // non-default guidance only: the per-iteration active flags next to the table, the CFG rescale partials and the n factors
-  int* active_ = nullptr; int active_cap_ = 0;
-  float* moments_ = nullptr; size_t moments_cap_ = 0;
-  float* factors_ = nullptr;
-  StepCoef* table_ = nullptr; int table_cap_ = 0;
-  int* step_idx_ = nullptr; float* t_dev_ = nullptr;
+  StepLoop loop_;
   float* ctx_buf_ = nullptr; size_t ctx_cap_ = 0;     // [2n][77][ctx] cond then uncond
   float* y_buf_ = nullptr; size_t y_cap_ = 0;
   const void* cached_ctx_key_[4] = {nullptr, nullptr, nullptr, nullptr}; int cached_n_ = 0;

@@ -334,16 +334,16 @@ void launch_causal_mask(float* out, int n, hipStream_t s);
 // conditioning_embedding (unet/mod.rs:41-57): out[n][E + w*dim] = [pooled | sinusoidal embedding of each of the w ints]
 void launch_conditioning_embedding(const float* pooled, int E, const int* vals, int w, int dim, float* out, int n, hipStream_t s);
 
-// DDIM step table entry (host f64 -> f32): stablediffusion/mod.rs:407-428
+// Step table entry (host f64 -> f32): stablediffusion/mod.rs:407-428
 // sigma: the DDIM eta term of :427 (0 on every explicit-noise trajectory; then sqrt_1map = sqrt(1 - ap), else sqrt(1 - ap - sigma^2))
-// The DPM-Solver++(2M) table (kSolverDpmpp2M) is the second layout of the same 32 bytes: t, sqrt_a, sqrt_1ma and cfg as in the DDIM one
+// The DPM-Solver++(2M) table (kSolverDpmpp2M) is the second layout of the same 32 bytes: t, sqrt_a and sqrt_1ma as in the DDIM one
 // (x0, the inpainting blend and ddim_advance_kernel read them alike), and the four coefficients of x' = c_x x + c_0 x0 + c_1 x0p + c_z z
 // (include/sdxl_mi355.h, sdxl_solver_coefficients) where the DDIM layout keeps its three update terms and its padding.
 struct StepCoef {
   float t; float sqrt_a; float sqrt_1ma;
   union { float sqrt_ap; float c_0; };
   union { float sqrt_1map; float c_x; };
-  float cfg;
+  float pad;     // (held the guidance scale until it became StepParams::scales)
   union { float sigma; float c_z; };
   float c_1;     // padding of the DDIM layout (0)
 };
@@ -355,14 +355,22 @@ constexpr uint32_t draw_blend(uint32_t i) { return 1u + 2u * i; }
 constexpr uint32_t draw_sigma(uint32_t i) { return 2u + 2u * i; }
 constexpr int kMaxSeeds = 8;   // batch entries of one trajectory (Diffuser::diffuse: B <= 8)
 struct DdimSeeds { uint64_t v[kMaxSeeds]; };   // per-entry seeds, passed by value in the kernel arguments
-// eps = u + (c-u)*cfg (or c when !use_cfg); x0 = (x - eps*sqrt_1ma)/sqrt_a; x = x0*sqrt_ap + eps*sqrt_1map
-// eps_nhwc: UNet output [Bu][HW][4] fp32-or-T rows; latent NCHW fp32 [n][4][HW].  Also refreshes the UNet input
-// (NHWC, replicated for cond/uncond) and advances *step_idx.
-struct DdimParams {
+struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, passed by value in the kernel arguments like the seeds
+// The per-step kernel, one thread per latent pixel (step_kernel<SOLVER, SEEDED>, elementwise.hip, where every rounding is written out):
+//   e  = ec                                  where !use_cfg, or on an inactive iteration (active != nullptr && !active[*step_idx]); eu is not read
+//   e  = fma(ec - eu, scales[b], eu)         otherwise; times factors[b] where factors != nullptr (CFG rescale)
+//   x0 = (x - e sqrt_1ma) / sqrt_a;  x = x0 sqrt_ap + e sqrt_1map (+ z sigma)   or, kSolverDpmpp2M,   x = c_x x + c_0 x0 + c_1 x0p (+ c_z z)
+// then the inpainting blend for the next iteration and the refresh of the UNet input (NHWC, once per branch).
+// eps: UNet output [Bu][HW][eps_ld] fp32-or-T rows; latent NCHW fp32 [n][4][HW].
+struct StepParams {
   float* latent;             // [n][4][HW] fp32 NCHW (state)
   const void* eps; int eps_dt; int eps_ld;   // UNet output NHWC rows: cond batch entries [0,n), uncond [n,2n)
   const StepCoef* table; int* step_idx;
   int n, HW; int use_cfg;
+  // guidance (include/sdxl_mi355.h, sdxl_guidance).  The default is the call's scalar in every scales[b], active = factors = nullptr.
+  CfgScales scales;
+  const int* active;         // device [iterations] or nullptr (every iteration active): 1 where guidance is on at that iteration's timestep
+  const float* factors;      // device [n] or nullptr (no rescale): f_b of this iteration, left by launch_cfg_rescale_factors on the same stream
   // inpainting (optional): before the *next* UNet call latent = mask ? latent : ref*sqrt_a(next)+noise*sqrt_1ma(next)
   const float* ref; const unsigned char* mask; const float* step_noise; int n_steps_total;
   // seeded mode: the blend noise (draw_blend(next)) and the sigma noise (draw_sigma(idx)) are drawn in the thread from
@@ -375,19 +383,8 @@ struct DdimParams {
   int solver; float* hist;
 };
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
-// input and timestep.  do_update=1: DDIM (or, p.solver, DPM-Solver++(2M)) update with table[*step_idx], blend for the next step, then advances.
-void launch_ddim_step(const DdimParams& p, int do_update, hipStream_t s);
-// Guidance options (include/sdxl_mi355.h, sdxl_guidance): what a handle with non-default options runs in place of the update launch of
-// launch_ddim_step.  On an active iteration e = fma(ec - eu, scales[b], eu), times factors[b] where factors != nullptr (CFG rescale);
-// on an inactive one e = ec.  Everything behind e is the text of ddim_kernel / dpmpp2m_kernel.
-struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, passed by value in the kernel arguments like the seeds
-struct GuidedParams {
-  CfgScales scales;
-  const int* active;         // device [iterations]: 1 where guidance is on at that iteration's timestep (read at *step_idx)
-  const float* factors;      // device [n]: f_b of this iteration, left by launch_cfg_rescale_factors on the same stream; nullptr = no rescale
-};
-// the do_update = 1 launch pair of launch_ddim_step (update kernel + advance) with the guidance lines; p.use_cfg must be 1
-void launch_guided_step(const DdimParams& p, const GuidedParams& g, hipStream_t s);
+// input and timestep.  do_update=1: the update with table[*step_idx], blend for the next step, then advances.
+void launch_step(const StepParams& p, int do_update, hipStream_t s);
 // CFG rescale (Lin et al. 2023, section 3.4): factors[b] = fma(phi, sqrt(M2(ec_b) / M2(ecfg_b)), 1 - phi), M2 the centred sum of squares over the
 // 4 * HW values of entry b, ecfg = fma(ec - eu, scales[b], eu); M2(ecfg_b) == 0 gives 1.  eps: rows [2n][HW][eps_ld] of eps_dt, cond entries
 // first.  Two launches: per-block (count, mean, M2) partials, grid (cfg_moments_blocks(HW), n), then one block per entry that merges them in
@@ -398,7 +395,7 @@ inline size_t cfg_moments_floats(int n, int HW) { return (size_t)n * cfg_moments
 void launch_cfg_rescale_factors(const void* eps, int eps_dt, int eps_ld, int n, int HW, const CfgScales& scales, float phi, float* partials,
                                 float* factors, hipStream_t s);
 // gen_noise (:378-388) with a seed: out [n][4][HW] fp32, entry b from seeds[b] (host array, n <= kMaxSeeds per launch), the
-// same values the seeded ddim kernel draws in registers for (seed, hw, draw)
+// same values the seeded per-step kernel draws in registers for (seed, hw, draw)
 void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n, int HW, hipStream_t s);
 // noised = latent*sa + noise*sb   (refine_latent :363-367)
 void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb, size_t n, hipStream_t s);

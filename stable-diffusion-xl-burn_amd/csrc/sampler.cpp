@@ -13,8 +13,9 @@
 //   * the update itself is a per-handle choice (set_solver): the reference's DDIM, or DPM-Solver++(2M) on the same schedule, same table
 //     mechanism and same fused kernel position, with one more latent-sized buffer for the previous data prediction.
 //   * how the pair becomes e is a per-handle choice too (set_guidance): the reference's one line by default; the conditional branch alone as a
-//     batch-n forward; or per-entry scales, a timestep interval and CFG rescale, run by launch_guided_step in the per-step kernel's place with
-//     two small launches in front of it where rescale is on.  A handle with default options launches what it always launched.
+//     batch-n forward; or per-entry scales, a timestep interval and CFG rescale -- arguments of the same per-step kernel, with two small launches
+//     in front of it where rescale is on.  The default options are the call's scalar as every entry's scale.
+// StepLoop is everything between two UNet forwards; Diffuser::diffuse is context setup and the loop around UNet::forward.
 #include "engine.h"
 
 #include <algorithm>
@@ -37,12 +38,9 @@ Diffuser::Diffuser(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSour
   unet_.reset(new UNet(cfg, compute_dt, stream_dt, src, st, mix));
   alphas_.resize(n_train);
   for (int i = 0; i < n_train; ++i) alphas_[i] = (double)alphas_host[i];   // get_alpha :485-492 (elem -> f64)
-  SDXL_HIP(hipMalloc((void**)&step_idx_, sizeof(int)));
-  SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
 }
 Diffuser::~Diffuser() {
-  for (void* p : {(void*)latent_, (void*)noise_, (void*)hist_, (void*)table_, (void*)step_idx_, (void*)t_dev_, (void*)ctx_buf_, (void*)y_buf_,
-                  (void*)active_, (void*)moments_, (void*)factors_})
+  for (void* p : {(void*)latent_, (void*)noise_, (void*)ctx_buf_, (void*)y_buf_})
     if (p) (void)hipFree(p);
 }
 
@@ -125,14 +123,106 @@ bool g_debug_no_cfg = false;
 static constexpr bool g_debug_no_cfg = false;
 #endif
 
-static void ensure_latent(float*& buf, size_t& cap, size_t elems) {
-  if (elems > cap) {
+template <class T, class N>
+static void ensure_device(T*& buf, N& cap, size_t elems) {     // a device buffer of at least `elems` values; grows, never shrinks
+  if (elems > (size_t)cap) {
     if (buf) SDXL_HIP(hipFree(buf));
-    SDXL_HIP(hipMalloc((void**)&buf, elems * sizeof(float)));
-    cap = elems;
+    buf = nullptr;
+    SDXL_HIP(hipMalloc((void**)&buf, elems * sizeof(T)));
+    cap = (N)elems;
   }
 }
 
+// ------------------------------------------------------------------------------------------ StepLoop
+StepLoop::StepLoop() {
+  SDXL_HIP(hipMalloc((void**)&step_idx_, sizeof(int)));
+  SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
+}
+StepLoop::~StepLoop() {
+  for (void* p : {(void*)table_, (void*)active_, (void*)moments_, (void*)factors_, (void*)step_idx_, (void*)t_dev_, (void*)hist_})
+    if (p) (void)hipFree(p);
+}
+
+int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale,
+                    const Guidance& go, bool single, int n, int HW, const StepIo& io, hipStream_t s) {
+  const int n_train = (int)alphas.size();
+  SDXL_REQUIRE(n >= 1 && n <= kMaxSeeds, "batch out of range");
+  SDXL_REQUIRE(single || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
+  // --- coefficient table (host f64, exactly the reference's scalar arithmetic :407-414, :423-426)
+  const std::vector<int> ts = Diffuser::step_schedule(n_steps, step_start, n_train);
+  const int iters = (int)ts.size();
+  const int step_size = n_train / n_steps;
+  std::vector<StepCoef> tab(iters + 1);
+  act_.assign(iters, 1);                               // guidance interval: iteration i is active where t_lo <= t_i <= t_hi
+  std::vector<double> c2m;
+  if (solver == kSolverDpmpp2M) {
+    c2m.resize((size_t)4 * iters);
+    Diffuser::solver_coefficients(alphas.data(), n_train, n_steps, step_start, solver, eta, c2m.data());
+  }
+  for (int i = 0; i < iters; ++i) {
+    const int t = ts[i];
+    const double a = alphas[t];
+    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+    StepCoef k{};
+    k.t = (float)t;
+    k.sqrt_a = (float)std::sqrt(a);
+    k.sqrt_1ma = (float)std::sqrt(1.0 - a);
+    if (solver == kSolverDpmpp2M) {
+      k.c_x = (float)c2m[4 * i]; k.c_0 = (float)c2m[4 * i + 1]; k.c_1 = (float)c2m[4 * i + 2]; k.c_z = (float)c2m[4 * i + 3];
+    } else {
+      double sqrt_ap, sqrt_1map, sigma;
+      ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma);
+      k.sqrt_ap = (float)sqrt_ap;
+      k.sqrt_1map = (float)sqrt_1map;
+      k.sigma = (float)sigma;
+    }
+    tab[i] = k;
+    if (!single) act_[i] = t >= go.t_lo && t <= go.t_hi;
+  }
+  tab[iters] = StepCoef{};
+  ensure_device(table_, table_cap_, (size_t)iters + 1);
+  SDXL_HIP(hipMemcpyAsync(table_, tab.data(), (size_t)(iters + 1) * sizeof(StepCoef), hipMemcpyHostToDevice, s));
+  p_ = StepParams{};
+  rescale_ = single ? 0.f : go.rescale;
+  // the default options are the call's scalar for every entry -- the float the kernel always multiplied by -- no interval array, no factors
+  for (int b = 0; b < n; ++b) p_.scales.v[b] = !single && go.n_scales ? go.scales[b] : (float)cfg_scale;
+  if (std::find(act_.begin(), act_.end(), 0) != act_.end()) {
+    ensure_device(active_, active_cap_, (size_t)iters);
+    SDXL_HIP(hipMemcpyAsync(active_, act_.data(), (size_t)iters * sizeof(int), hipMemcpyHostToDevice, s));
+    p_.active = active_;
+  }
+  if (rescale_ > 0.f) {
+    ensure_device(moments_, moments_cap_, cfg_moments_floats(n, HW));
+    if (!factors_) SDXL_HIP(hipMalloc((void**)&factors_, kMaxSeeds * sizeof(float)));
+    p_.factors = factors_;
+  }
+  if (solver == kSolverDpmpp2M) ensure_device(hist_, hist_cap_, (size_t)n * 4 * HW);
+  SDXL_HIP(hipStreamSynchronize(s));   // tab is a stack-owned host buffer
+
+  p_.latent = io.latent;
+  p_.eps_dt = DT_F32; p_.eps_ld = io.eps_ld;
+  p_.table = table_; p_.step_idx = step_idx_;
+  p_.n = n; p_.HW = HW; p_.use_cfg = single ? 0 : 1;
+  p_.ref = io.reference; p_.mask = io.mask; p_.step_noise = io.step_noise; p_.n_steps_total = iters;
+  p_.unet_in = io.unet_in; p_.in_dt = io.in_dt; p_.in_ld = io.in_ld; p_.in_rep = single ? 1 : 2;
+  p_.t_out = t_dev_;
+  p_.solver = solver; p_.hist = hist_;
+  if (io.seeds) {
+    p_.seeded = 1;
+    for (int b = 0; b < n; ++b) p_.seeds.v[b] = io.seeds[b];
+  }
+  launch_step(p_, 0, s);
+  return iters;
+}
+
+void StepLoop::after_forward(int i, const float* eps, hipStream_t s) {
+  p_.eps = eps;
+  // CFG rescale: moments and factor in front of the step on an active iteration
+  if (p_.factors && act_[i]) launch_cfg_rescale_factors(eps, p_.eps_dt, p_.eps_ld, p_.n, p_.HW, p_.scales, rescale_, moments_, factors_, s);
+  launch_step(p_, 1, s);
+}
+
+// ------------------------------------------------------------------------------------------ Diffuser
 void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale,
                        const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s,
                        const uint64_t* seeds, double eta) {
@@ -142,9 +232,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   const Guidance& go = guidance_;
   // kGuidanceOff: conditional branch only, as for a refiner (debug knob: the same for concurrency experiments)
   const bool single = is_refiner_ || go.mode == kGuidanceOff || g_debug_no_cfg;
-  const bool guided = !single && !go.plain();          // non-default options: the update launch is launch_guided_step
   const int n = c.n, B = single ? n : 2 * n;
-  SDXL_REQUIRE(!guided || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
   SDXL_REQUIRE(n >= 1 && B <= 8, "batch out of range");
   static_assert(kMaxSeeds >= 8, "one seed per batch entry");
   const int h = c.height / 8, w = c.width / 8, HW = h * w;
@@ -157,16 +245,8 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   SDXL_REQUIRE(ctx && y, "conditioning tensors missing");
   SDXL_REQUIRE(single || (uctx && uy), "unconditional conditioning tensors missing");
   const size_t ctx_elems = (size_t)c.n_ctx * ctx_dim;
-  if ((size_t)B * ctx_elems > ctx_cap_) {
-    if (ctx_buf_) SDXL_HIP(hipFree(ctx_buf_));
-    SDXL_HIP(hipMalloc((void**)&ctx_buf_, (size_t)B * ctx_elems * sizeof(float)));
-    ctx_cap_ = (size_t)B * ctx_elems;
-  }
-  if ((size_t)B * adm > y_cap_) {
-    if (y_buf_) SDXL_HIP(hipFree(y_buf_));
-    SDXL_HIP(hipMalloc((void**)&y_buf_, (size_t)B * adm * sizeof(float)));
-    y_cap_ = (size_t)B * adm;
-  }
+  ensure_device(ctx_buf_, ctx_cap_, (size_t)B * ctx_elems);
+  ensure_device(y_buf_, y_cap_, (size_t)B * adm);
   SDXL_HIP(hipMemcpyAsync(ctx_buf_, ctx, (size_t)n * ctx_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
   SDXL_HIP(hipMemcpyAsync(y_buf_, y, (size_t)n * adm * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (!single)
@@ -174,82 +254,13 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
       SDXL_HIP(hipMemcpyAsync(ctx_buf_ + (size_t)(n + i) * ctx_elems, uctx, ctx_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
       SDXL_HIP(hipMemcpyAsync(y_buf_ + (size_t)(n + i) * adm, uy, adm * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-  void* unet_in = u.unet_in(B, h, w);
+  StepIo io{};
+  io.latent = latent; io.eps_ld = uc.out_channels;
+  io.unet_in = u.unet_in(B, h, w); io.in_dt = u.input_dt(); io.in_ld = uc.in_channels;
+  io.reference = reference; io.mask = mask; io.step_noise = step_noise; io.seeds = seeds;
   u.set_context(ctx_buf_, c.n_ctx, y_buf_, B, s);
 
-  // --- coefficient table (host f64, exactly the reference's scalar arithmetic :407-414, :423-426)
-  const std::vector<int> ts = step_schedule(n_steps, step_start, n_train_);
-  const int iters = (int)ts.size();
-  const int step_size = n_train_ / n_steps;
-  std::vector<StepCoef> tab(iters + 1);
-  std::vector<int> act(guided ? iters : 0);            // guidance interval: iteration i is active where t_lo <= t_i <= t_hi
-  std::vector<double> c2m;
-  if (solver_ == kSolverDpmpp2M) {
-    c2m.resize((size_t)4 * iters);
-    solver_coefficients(alphas_.data(), n_train_, n_steps, step_start, solver_, eta, c2m.data());
-  }
-  for (int i = 0; i < iters; ++i) {
-    const int t = ts[i];
-    const double a = alphas_[t];
-    const double ap = t >= step_size ? alphas_[t - step_size] : 1.0;
-    StepCoef k{};
-    k.t = (float)t;
-    k.sqrt_a = (float)std::sqrt(a);
-    k.sqrt_1ma = (float)std::sqrt(1.0 - a);
-    k.cfg = (float)cfg_scale;
-    if (solver_ == kSolverDpmpp2M) {
-      k.c_x = (float)c2m[4 * i]; k.c_0 = (float)c2m[4 * i + 1]; k.c_1 = (float)c2m[4 * i + 2]; k.c_z = (float)c2m[4 * i + 3];
-    } else {
-      double sqrt_ap, sqrt_1map, sigma;
-      ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma);
-      k.sqrt_ap = (float)sqrt_ap;
-      k.sqrt_1map = (float)sqrt_1map;
-      k.sigma = (float)sigma;
-    }
-    tab[i] = k;
-    if (guided) act[i] = t >= go.t_lo && t <= go.t_hi;
-  }
-  tab[iters] = StepCoef{};
-  if (iters + 1 > table_cap_) {
-    if (table_) SDXL_HIP(hipFree(table_));
-    SDXL_HIP(hipMalloc((void**)&table_, (size_t)(iters + 1) * sizeof(StepCoef)));
-    table_cap_ = iters + 1;
-  }
-  SDXL_HIP(hipMemcpyAsync(table_, tab.data(), (size_t)(iters + 1) * sizeof(StepCoef), hipMemcpyHostToDevice, s));
-  GuidedParams gp{};
-  if (guided) {
-    if (iters > active_cap_) {
-      if (active_) SDXL_HIP(hipFree(active_));
-      active_ = nullptr;
-      SDXL_HIP(hipMalloc((void**)&active_, (size_t)iters * sizeof(int)));
-      active_cap_ = iters;
-    }
-    SDXL_HIP(hipMemcpyAsync(active_, act.data(), (size_t)iters * sizeof(int), hipMemcpyHostToDevice, s));
-    for (int b = 0; b < n; ++b) gp.scales.v[b] = go.n_scales ? go.scales[b] : (float)cfg_scale;
-    gp.active = active_;
-    if (go.rescale > 0.f) {
-      ensure_latent(moments_, moments_cap_, cfg_moments_floats(n, HW));
-      if (!factors_) SDXL_HIP(hipMalloc((void**)&factors_, kMaxSeeds * sizeof(float)));
-      gp.factors = factors_;
-    }
-  }
-  SDXL_HIP(hipStreamSynchronize(s));   // tab is a stack-owned host buffer
-
-  DdimParams p{};
-  p.latent = latent;
-  p.eps = u.eps_out(); p.eps_dt = DT_F32; p.eps_ld = uc.out_channels;
-  p.table = table_; p.step_idx = step_idx_;
-  p.n = n; p.HW = HW; p.use_cfg = single ? 0 : 1;
-  p.ref = reference; p.mask = mask; p.step_noise = step_noise; p.n_steps_total = iters;
-  p.unet_in = unet_in; p.in_dt = u.input_dt(); p.in_ld = uc.in_channels; p.in_rep = single ? 1 : 2;
-  p.t_out = t_dev_;
-  p.solver = solver_; p.hist = hist_;
-  if (seeds) {
-    p.seeded = 1;
-    for (int b = 0; b < n; ++b) p.seeds.v[b] = seeds[b];
-  }
-  launch_ddim_step(p, 0, s);
-
+  const int iters = loop_.begin(alphas_, n_steps, step_start, solver_, eta, cfg_scale, go, single, n, HW, io, s);
   std::vector<hipEvent_t> ev;
   if (time_steps) {
     ev.resize(iters + 1);
@@ -257,13 +268,8 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
     SDXL_HIP(hipEventRecord(ev[0], s));
   }
   for (int i = 0; i < iters; ++i) {
-    u.forward(B, h, w, t_dev_, 0, s);     // one timestep shared by every batch entry (:416)
-    if (guided) {     // moments, factor, step on an active iteration with rescale; the step kernel alone otherwise
-      if (gp.factors && act[i]) launch_cfg_rescale_factors(p.eps, p.eps_dt, p.eps_ld, n, HW, gp.scales, go.rescale, moments_, factors_, s);
-      launch_guided_step(p, gp, s);
-    } else {
-      launch_ddim_step(p, 1, s);
-    }
+    u.forward(B, h, w, loop_.t_dev(), 0, s);     // one timestep shared by every batch entry (:416)
+    loop_.after_forward(i, (const float*)u.eps_out(), s);
     if (trace && i < trace_cap)
       SDXL_HIP(hipMemcpyAsync(trace + (size_t)i * n * 4 * HW, latent, (size_t)n * 4 * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (time_steps) SDXL_HIP(hipEventRecord(ev[i + 1], s));
@@ -276,81 +282,71 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   }
 }
 
-void Diffuser::ensure_state(size_t elems) {
-  ensure_latent(latent_, latent_cap_, elems);
-  if (solver_ == kSolverDpmpp2M) ensure_latent(hist_, hist_cap_, elems);
+// Prologue and epilogue of the six trajectory calls.  The trajectory starts from t.noise (seeds: the kDrawInitial tensor of the entries' seeds)
+// or, where t.renoise is given, from that latent re-noised to t = n_train - step_start (:355-376); then diffuse and the copy out.
+void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, const Trajectory& t, float* out, hipStream_t s) {
+  SDXL_REQUIRE(!t.renoise || (t.step_start >= 1 && t.step_start <= n_train_), "step_start out of range");
+  SDXL_REQUIRE(!t.seeds || c.n <= kMaxSeeds, "batch out of range");
+  const int HW = (c.height / 8) * (c.width / 8);
+  const size_t elems = (size_t)c.n * 4 * HW;
+  ensure_device(latent_, latent_cap_, elems);
+  if (t.renoise) {
+    const float* noise = t.noise;
+    if (t.seeds) {
+      ensure_device(noise_, noise_cap_, elems);
+      launch_seeded_noise(noise_, t.seeds, kDrawInitial, c.n, HW, s);
+      noise = noise_;
+    }
+    const double a = alphas_[n_train_ - t.step_start];
+    launch_axpby(latent_, t.renoise, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
+  } else if (t.seeds) {
+    launch_seeded_noise(latent_, t.seeds, kDrawInitial, c.n, HW, s);
+  } else {
+    SDXL_HIP(hipMemcpyAsync(latent_, t.noise, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  diffuse(latent_, c, t.step_start, n_steps, cfg_scale, t.reference, t.mask, t.step_noise, s, t.seeds, t.eta);
+  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
 void Diffuser::sample_latent(const Conditioning& c, double cfg_scale, int n_steps, const float* noise0, float* out,
                              hipStream_t s) {
-  const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_state(elems);
-  SDXL_HIP(hipMemcpyAsync(latent_, noise0, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-  diffuse(latent_, c, 0, n_steps, cfg_scale, nullptr, nullptr, nullptr, s);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.noise = noise0;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 void Diffuser::sample_latent_inpaint(const Conditioning& c, double cfg_scale, int n_steps, const float* reference,
                                      const unsigned char* mask, const float* noise0, const float* step_noise, float* out,
                                      hipStream_t s) {
   SDXL_REQUIRE(reference && mask && step_noise, "inpainting needs reference, mask and per-step noise");
-  const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_state(elems);
-  SDXL_HIP(hipMemcpyAsync(latent_, noise0, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-  diffuse(latent_, c, 0, n_steps, cfg_scale, reference, mask, step_noise, s);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.noise = noise0; t.reference = reference; t.mask = mask; t.step_noise = step_noise;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 void Diffuser::refine_latent(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                              const float* noise, float* out, hipStream_t s) {
-  // :355-376: re-noise the finished latent to t = n_train - step_start, then denoise from there
-  SDXL_REQUIRE(step_start >= 1 && step_start <= n_train_, "step_start out of range");
-  const size_t elems = (size_t)c.n * 4 * (c.height / 8) * (c.width / 8);
-  ensure_state(elems);
-  const double a = alphas_[n_train_ - step_start];
-  launch_axpby(latent_, latent, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
-  diffuse(latent_, c, step_start, n_steps, cfg_scale, nullptr, nullptr, nullptr, s);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.renoise = latent; t.step_start = step_start; t.noise = noise;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 // The seeded forms: same trajectories, noise from launch_seeded_noise / the seeded per-step kernel.
 void Diffuser::sample_latent_seeded(const Conditioning& c, double cfg_scale, int n_steps, const uint64_t* seeds, double eta,
                                     float* out, hipStream_t s) {
-  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
-  const int HW = (c.height / 8) * (c.width / 8);
-  const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_state(elems);
-  launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
-  diffuse(latent_, c, 0, n_steps, cfg_scale, nullptr, nullptr, nullptr, s, seeds, eta);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.seeds = seeds; t.eta = eta;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 void Diffuser::sample_latent_inpaint_seeded(const Conditioning& c, double cfg_scale, int n_steps, const float* reference,
                                             const unsigned char* mask, const uint64_t* seeds, double eta, float* out,
                                             hipStream_t s) {
   SDXL_REQUIRE(reference && mask, "inpainting needs reference and mask");
-  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
-  const int HW = (c.height / 8) * (c.width / 8);
-  const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_state(elems);
-  launch_seeded_noise(latent_, seeds, kDrawInitial, c.n, HW, s);
-  diffuse(latent_, c, 0, n_steps, cfg_scale, reference, mask, nullptr, s, seeds, eta);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.seeds = seeds; t.eta = eta; t.reference = reference; t.mask = mask;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 void Diffuser::refine_latent_seeded(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                                     const uint64_t* seeds, double eta, float* out, hipStream_t s) {
-  SDXL_REQUIRE(step_start >= 1 && step_start <= n_train_, "step_start out of range");
-  SDXL_REQUIRE(c.n <= kMaxSeeds, "batch out of range");
-  const int HW = (c.height / 8) * (c.width / 8);
-  const size_t elems = (size_t)c.n * 4 * HW;
-  ensure_state(elems);
-  ensure_latent(noise_, noise_cap_, elems);
-  launch_seeded_noise(noise_, seeds, kDrawInitial, c.n, HW, s);
-  const double a = alphas_[n_train_ - step_start];
-  launch_axpby(latent_, latent, (float)std::sqrt(a), noise_, (float)std::sqrt(1.0 - a), elems, s);
-  diffuse(latent_, c, step_start, n_steps, cfg_scale, nullptr, nullptr, nullptr, s, seeds, eta);
-  SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+  Trajectory t; t.renoise = latent; t.step_start = step_start; t.seeds = seeds; t.eta = eta;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
 }  // namespace sdxl

@@ -1,4 +1,4 @@
-"""Rows of a rocprofv3 kernel trace by ordinal inside one replayed UNet step (the 256x160 f16 pipe-kernel launches between two ddim_kernel rows) or inside one
+"""Rows of a rocprofv3 kernel trace by ordinal inside one replayed UNet step (the 256x160 f16 pipe-kernel launches between two step_kernel rows) or inside one
 VAE decode (launches over 300 us between two to_u8_kernel rows) -- for library A/Bs of single launches (profiles/upsample_fold_ab.txt).
 usage: trace_launch_rows.py step|decode <rocprofv3 output dir>"""
 import csv, glob, sys
@@ -9,7 +9,7 @@ for r in csv.DictReader(open(f)):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0], r.get("Grid_Size_X", r.get("Grid_Size", ""))))
 rows.sort()
 if mode == "step":
-    idx = [i for i, r in enumerate(rows) if r[2].split("<")[0].endswith("ddim_kernel")]
+    idx = [i for i, r in enumerate(rows) if r[2].split("<")[0].endswith("step_kernel")]
     for a, b in ((idx[-4], idx[-3]), (idx[-3], idx[-2])):
         seg = rows[a + 1:b + 1]
         print("step span %.3f ms, %d dispatches" % ((seg[-1][1] - rows[a][1]) / 1e6, len(seg)))

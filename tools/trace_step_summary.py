@@ -1,4 +1,4 @@
-"""Per-kernel duration summary of ONE replayed UNet step (between two ddim_kernel dispatches) from a rocprofv3 kernel trace.
+"""Per-kernel duration summary of ONE replayed UNet step (between two step_kernel dispatches) from a rocprofv3 kernel trace.
 usage: trace_step_summary.py <kernel_trace.csv>"""
 import csv, sys
 from collections import defaultdict
@@ -6,7 +6,7 @@ rows = []
 for r in csv.DictReader(open(sys.argv[1])):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0], r.get("Grid_Size_X", "")))
 rows.sort()
-idx = [i for i, r in enumerate(rows) if r[2].split("<")[0].endswith("ddim_kernel")]      # (a template since the seeded-noise form: ddim_kernel<false>)
+idx = [i for i, r in enumerate(rows) if r[2].split("<")[0].endswith("step_kernel")]      # (a template: step_kernel<0, false>)
 a, b = idx[-3], idx[-2]
 seg = rows[a + 1:b + 1]
 print("step span %.3f ms, %d dispatches" % ((seg[-1][1] - rows[a][1]) / 1e6, len(seg)))
