@@ -531,6 +531,19 @@ int sdxl_gemv(sdxl_ctx* ctx, void* stream, const float* x, const float* weight, 
 /* timestep_embedding (unet/mod.rs:21-39) of n fp32 device timesteps: out [n,dim] = [cos(t f) | sin(t f)], f_j = exp(j * -ln(10000) / (dim / 2));
  * dim even */
 int sdxl_timestep_embedding(sdxl_ctx* ctx, void* stream, const float* t, int n, int dim, float* out);
+/* The two blocks of the autoencoder on their own, through the code the LatentDecoder's decoder and encoder run (parity tests).  NCHW fp32 device tensors
+ * in and out; convolution weights [Cout,Cin,k,k], biases [Cout] or NULL; dtype as sdxl_vae_create takes it, one of SDXL_DTYPE_F32, SDXL_DTYPE_F16,
+ * SDXL_DTYPE_F32_SPLIT (channel counts % 32 == 0), mapped to compute / stream dtypes as a VAE handle maps it; channel counts divisible by n_group and by 8.
+ * sdxl_vae_attn_block: ConvSelfAttentionBlock::forward (autoencoder/mod.rs:550-586): out = x + proj_out(attention(q, k, v of GroupNorm(x))), one head of C
+ *   channels, softmax(q k^T / sqrt(C)); wq / wk / wv / wo [C,C,1,1].  C a multiple of the k-tile (64 in f16, else 32).
+ * sdxl_vae_res_block: ResnetBlock::forward (:500-516): out = shortcut(x) + conv2(silu(GN2(conv1(silu(GN1(x)))))), w1 [Cout,Cin,3,3], w2 [Cout,Cout,3,3],
+ *   w_nin [Cout,Cin,1,1] (NULL only where Cin == Cout: the shortcut is x itself). */
+int sdxl_vae_attn_block(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps, const float* wq, const float* bq,
+                        const float* wk, const float* bk, const float* wv, const float* bv, const float* wo, const float* bo, int B, int C, int H, int W,
+                        int n_group, int dtype, float* out);
+int sdxl_vae_res_block(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma1, const float* beta1, float eps1, const float* w1, const float* b1,
+                       const float* gamma2, const float* beta2, float eps2, const float* w2, const float* b2, const float* w_nin, const float* b_nin, int B,
+                       int Cin, int Cout, int H, int W, int n_group, int dtype, float* out);
 /* LayerNorm::forward (layernorm/mod.rs:34-49) followed by nn::Linear, as TransformerBlock::forward pairs them
  * (unet/mod.rs:885-891): y = LN(x[M,K]; gamma, beta, eps) @ W[K,N] + b (bias may be NULL), optional GEGLU.  Runs the path
  * the UNet runs in that dtype: SDXL_DTYPE_F16 = LayerNorm folded into the GEMM (row statistics from the producer's

@@ -113,7 +113,7 @@ ABI_SYMBOLS = [
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
     "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
-    "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_gemv", "sdxl_timestep_embedding", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
+    "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_gemv", "sdxl_timestep_embedding", "sdxl_vae_attn_block", "sdxl_vae_res_block", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
     "sdxl_clip_config_clip_l", "sdxl_clip_config_open_clip_bigg", "sdxl_clip_param_count", "sdxl_clip_param_spec",
@@ -1293,6 +1293,43 @@ def timestep_embedding(ctx: Context, t, dim: int):
     n = int(t.numel())
     out = torch.empty((n, dim), device=t.device, dtype=torch.float32)
     _check(lib().sdxl_timestep_embedding(ctx.h, _stream(), pt, n, int(dim), ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
+def _opt(t):
+    """(tensor kept alive, device pointer) of an optional fp32 CUDA tensor (None -> a null pointer)"""
+    return (None, None) if t is None else _dev(t)
+
+
+def vae_attn_block(ctx: Context, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, n_group: int = 32, eps: float = 1e-5, dtype: int = DTYPE_F32_SPLIT):
+    """ConvSelfAttentionBlock::forward (autoencoder/mod.rs:550-586) on x [B,C,H,W] through the code the LatentDecoder's mid block runs: GroupNorm, the 1x1
+    convolutions wq / wk / wv [C,C,1,1] (biases [C] or None), one head of C channels, wo + residual.  dtype: DTYPE_F32, DTYPE_F16 or DTYPE_F32_SPLIT."""
+    torch = _torch()
+    keep = [_opt(t) for t in (x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo)]
+    px, pg, pbe, pwq, pbq, pwk, pbk, pwv, pbv, pwo, pbo = [k[1] for k in keep]
+    if x is None or x.dim() != 4:
+        raise EngineError("vae_attn_block: x must be [B, C, H, W]")
+    B, C, H, W = (int(v) for v in x.shape)
+    out = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32)
+    _check(lib().sdxl_vae_attn_block(ctx.h, _stream(), px, pg, pbe, ctypes.c_float(eps), pwq, pbq, pwk, pbk, pwv, pbv, pwo, pbo, B, C, H, W, int(n_group),
+                                     int(dtype), ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
+def vae_res_block(ctx: Context, x, gamma1, beta1, w1, b1, gamma2, beta2, w2, b2, w_nin=None, b_nin=None, n_group: int = 32, eps1: float = 1e-5,
+                  eps2: float = 1e-5, dtype: int = DTYPE_F32_SPLIT):
+    """ResnetBlock::forward (autoencoder/mod.rs:500-516) on x [B,Cin,H,W] through the code every block of the LatentDecoder runs: w1 [Cout,Cin,3,3],
+    w2 [Cout,Cout,3,3], w_nin [Cout,Cin,1,1] or None where Cin == Cout (biases [Cout] or None).  dtype: DTYPE_F32, DTYPE_F16 or DTYPE_F32_SPLIT."""
+    torch = _torch()
+    keep = [_opt(t) for t in (x, gamma1, beta1, w1, b1, gamma2, beta2, w2, b2, w_nin, b_nin)]
+    px, pg1, pbe1, pw1, pb1, pg2, pbe2, pw2, pb2, pwn, pbn = [k[1] for k in keep]
+    if x is None or x.dim() != 4:
+        raise EngineError("vae_res_block: x must be [B, Cin, H, W]")
+    B, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(w2.shape[0]) if w2 is not None else Cin      # (a missing w2 is the library's error to report)
+    out = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32)
+    _check(lib().sdxl_vae_res_block(ctx.h, _stream(), px, pg1, pbe1, ctypes.c_float(eps1), pw1, pb1, pg2, pbe2, ctypes.c_float(eps2), pw2, pb2, pwn, pbn,
+                                    B, Cin, Cout, H, W, int(n_group), int(dtype), ctypes.c_void_p(out.data_ptr())))
     return out
 
 

@@ -122,6 +122,30 @@ template <class F> float time_launches(hipStream_t s, int warmup, int iters, F f
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   return ms / iters;
 }
+// A block of the autoencoder run the way Vae runs it (Vae's constructor and its two-pass execution): compute dtype of the mode with the stream in io_dt()
+// (fp32 under the split-operand mode), a builder without fragment-order images, and an activation arena sized by a dry run of the block with the GroupNorm
+// workspace of the batch at its head.  body(ex) allocates from ex.act and launches (helpers skip their launches on the dry pass).
+void vae_block_dtypes(int dtype, int& cdt, int& sdt) {
+  SDXL_REQUIRE(dtype == SDXL_DTYPE_F32 || dtype == SDXL_DTYPE_F16 || dtype == SDXL_DTYPE_F32_SPLIT,
+               "the VAE block entries take SDXL_DTYPE_F32, SDXL_DTYPE_F16 or SDXL_DTYPE_F32_SPLIT");
+  vae_dtype(dtype, cdt);
+  sdt = cdt == DT_HL ? DT_F32 : cdt;
+}
+void vae_block_shape(int B, int C, int H, int W, int n_group, int cdt) {
+  SDXL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (size_t)B * H * W * (size_t)(C > 0 ? C : 1) < ((size_t)1 << 31), "VAE block: B, H, W >= 1 and fewer than 2^31 elements");
+  SDXL_REQUIRE(n_group >= 1 && n_group <= 256, "n_group out of range (1..256)");
+  SDXL_REQUIRE(C > 0 && C % n_group == 0 && C % 8 == 0, "The number of channels must be divisible by the number of groups (and by 8)");
+  SDXL_REQUIRE(cdt != DT_HL || C % 32 == 0, "SDXL_DTYPE_F32_SPLIT blocks need channel counts that are multiples of 32");
+}
+template <class F> void vae_block_run(DeviceArena& act, int cdt, int sdt, int B, int n_group, hipStream_t s, F body) {
+  Exec ex; ex.s = s; ex.cdt = cdt; ex.sdt = sdt; ex.act = &act;
+  for (int pass = 0; pass < 2; ++pass) {
+    act.dry = ex.dry = pass == 0; act.off = 0; act.peak = 0;
+    ex.gn_partial = (float*)act.alloc(groupnorm_workspace_floats(B, n_group) * sizeof(float));
+    body(ex);
+    if (pass == 0) act.reserve(act.peak + 4096);
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -711,6 +735,74 @@ int sdxl_conv2d_group_norm(sdxl_ctx* ctx, void* stream, const float* x, const fl
   if (fused_taken) *fused_taken = took ? 1 : 0;
   run_groupnorm(ex, n, h, B, HW, Act(yo, Cout, cdt), silu != 0, n_group);
   launch_nhwc_to_nchw(yo, cdt, Cout, out, B, Cout, HW, 1.0f, s);
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
+
+// ---------------------------------------------------------------------------------------------- VAE blocks
+// ConvSelfAttentionBlock::forward (autoencoder/mod.rs:550-586) through vae_attn_block, the code Vae::mid runs: GroupNorm, 1x1 q / k / v, one head of C
+// channels (f16 with C = 512: the flash kernel; else score GEMM -> row softmax -> P V GEMM in passes of 8192 queries), proj_out + residual
+int sdxl_vae_attn_block(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps, const float* wq, const float* bq,
+                        const float* wk, const float* bk, const float* wv, const float* bv, const float* wo, const float* bo, int B, int C, int H, int W,
+                        int n_group, int dtype, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(ctx && x && gamma && beta && wq && wk && wv && wo && out, "null argument");
+  int cdt, sdt; vae_block_dtypes(dtype, cdt, sdt);
+  vae_block_shape(B, C, H, W, n_group, cdt);
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  Operands ops;
+  add_norm(ops, "attn.norm", C, gamma, beta, eps);
+  add_conv(ops, "attn.q", C, C, 1, wq, bq); add_conv(ops, "attn.k", C, C, 1, wk, bk); add_conv(ops, "attn.v", C, C, 1, wv, bv);
+  add_conv(ops, "attn.proj_out", C, C, 1, wo, bo);
+  Packed pk(ops, cdt, s);
+  pk.wb.wfrag = false;
+  VaeMidW w; w.C = C;
+  vae_load_attn(pk.wb, "attn", w);
+  DeviceArena act;
+  const int HW = H * W;
+  vae_block_run(act, cdt, sdt, B, n_group, s, [&](Exec& ex) {
+    Act y = ex.alloc((size_t)B * HW, C, sdt);
+    if (!ex.dry) launch_nchw_to_nhwc(x, C * HW, y.p, sdt, B, C, HW, C, 1.0f, s);
+    vae_attn_block(ex, w, y, B, H, W, n_group);
+    if (!ex.dry) launch_nhwc_to_nchw(y.p, sdt, C, out, B, C, HW, 1.0f, s);
+  });
+  SDXL_HIP(hipGetLastError());
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
+// ResnetBlock::forward (autoencoder/mod.rs:500-516) through vae_res_block, the code every block of Vae runs: GroupNorm + SiLU, conv 3x3, GroupNorm + SiLU,
+// conv 3x3 + shortcut (x, or the 1x1 nin_shortcut of x -- split-operand mode: on the HL16 copy scaled per batch entry from the maxima norm1's statistics pass leaves)
+int sdxl_vae_res_block(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma1, const float* beta1, float eps1, const float* w1, const float* b1,
+                       const float* gamma2, const float* beta2, float eps2, const float* w2, const float* b2, const float* w_nin, const float* b_nin, int B,
+                       int Cin, int Cout, int H, int W, int n_group, int dtype, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(ctx && x && gamma1 && beta1 && w1 && gamma2 && beta2 && w2 && out, "null argument");
+  SDXL_REQUIRE(w_nin || Cin == Cout, "a ResnetBlock that changes the channel count needs its nin_shortcut weight");
+  SDXL_REQUIRE(w_nin || !b_nin, "nin_shortcut bias without its weight");
+  int cdt, sdt; vae_block_dtypes(dtype, cdt, sdt);
+  vae_block_shape(B, Cin, H, W, n_group, cdt);
+  vae_block_shape(B, Cout, H, W, n_group, cdt);
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  Operands ops;
+  add_norm(ops, "res.norm1", Cin, gamma1, beta1, eps1);
+  add_conv(ops, "res.conv1", Cout, Cin, 3, w1, b1);
+  add_norm(ops, "res.norm2", Cout, gamma2, beta2, eps2);
+  add_conv(ops, "res.conv2", Cout, Cout, 3, w2, b2);
+  if (w_nin) add_conv(ops, "res.nin_shortcut", Cout, Cin, 1, w_nin, b_nin);
+  Packed pk(ops, cdt, s);
+  pk.wb.wfrag = false;
+  const VaeResW w = vae_load_res(pk.wb, "res", Cin, Cout);
+  DeviceArena act;
+  const int HW = H * W;
+  vae_block_run(act, cdt, sdt, B, n_group, s, [&](Exec& ex) {
+    Act xi = ex.alloc((size_t)B * HW, Cin, sdt), yo = ex.alloc((size_t)B * HW, Cout, sdt);
+    if (!ex.dry) launch_nchw_to_nhwc(x, Cin * HW, xi.p, sdt, B, Cin, HW, Cin, 1.0f, s);
+    vae_res_block(ex, w, xi, B, H, W, yo, n_group);
+    if (!ex.dry) launch_nhwc_to_nchw(yo.p, sdt, Cout, out, B, Cout, HW, 1.0f, s);
+  });
+  SDXL_HIP(hipGetLastError());
   SDXL_HIP(hipStreamSynchronize(s));
   API_END
 }

@@ -486,6 +486,14 @@ class UNet {
 // ------------------------------------------------------------------------------------------ VAE
 struct VaeResW { NormW n1, n2; Lin c1, c2, nin; bool has_nin = false; int cin = 0, cout = 0; };
 struct VaeMidW { VaeResW b1, b2; NormW an; Lin q, k, v, proj; int C = 0; };
+// The two blocks of the autoencoder that exist as single-op entries too (sdxl_vae_res_block / sdxl_vae_attn_block): free functions over a WeightBuilder and an
+// Exec, so that the entries run the code Vae runs.  vae_load_res: p.norm1 / conv1 / norm2 / conv2 (+ p.nin_shortcut where the parameters have one);
+// vae_load_attn: p.norm / q / k / v / proj_out into m (m.C set by the caller).  vae_res_block: ResnetBlock::forward x -> out; vae_attn_block:
+// ConvSelfAttentionBlock::forward in place on the stream tensor y (the f16 C = 512 flash kernel, else QK^T GEMM -> row softmax -> P V GEMM in query passes).
+VaeResW vae_load_res(WeightBuilder& wb, const std::string& p, int cin, int cout);
+void vae_load_attn(WeightBuilder& wb, const std::string& p, VaeMidW& m);
+void vae_res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int W, const Act& out, int n_group);
+void vae_attn_block(Exec& ex, const VaeMidW& w, const Act& y, int B, int H, int W, int n_group);
 
 class Vae {
  public:
@@ -508,7 +516,6 @@ class Vae {
   void mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W);
   void run_decode(Exec& ex, const Act& in, int n, int h, int w, const Act& out);
   void run_encode(Exec& ex, const Act& in, int n, int H, int W, const Act& out);
-  VaeResW load_res(WeightBuilder& wb, const std::string& p, int cin, int cout);
   VaeMidW load_mid(WeightBuilder& wb, const std::string& p, int c);
 
   VaeCfg cfg_;

@@ -9,7 +9,7 @@
 
 namespace sdxl {
 
-VaeResW Vae::load_res(WeightBuilder& wb, const std::string& p, int cin, int cout) {
+VaeResW vae_load_res(WeightBuilder& wb, const std::string& p, int cin, int cout) {
   VaeResW r; r.cin = cin; r.cout = cout;
   r.n1 = wb.norm(p + ".norm1"); r.c1 = wb.conv(p + ".conv1");
   r.n2 = wb.norm(p + ".norm2"); r.c2 = wb.conv(p + ".conv2");
@@ -17,13 +17,16 @@ VaeResW Vae::load_res(WeightBuilder& wb, const std::string& p, int cin, int cout
   if (r.has_nin) r.nin = wb.conv(p + ".nin_shortcut");
   return r;
 }
+void vae_load_attn(WeightBuilder& wb, const std::string& p, VaeMidW& m) {
+  m.an = wb.norm(p + ".norm");
+  m.q = wb.conv(p + ".q"); m.k = wb.conv(p + ".k"); m.v = wb.conv(p + ".v");
+  m.proj = wb.conv(p + ".proj_out");
+}
 VaeMidW Vae::load_mid(WeightBuilder& wb, const std::string& p, int c) {
   VaeMidW m; m.C = c;
-  m.b1 = load_res(wb, p + ".block_1", c, c);
-  m.an = wb.norm(p + ".attn.norm");
-  m.q = wb.conv(p + ".attn.q"); m.k = wb.conv(p + ".attn.k"); m.v = wb.conv(p + ".attn.v");
-  m.proj = wb.conv(p + ".attn.proj_out");
-  m.b2 = load_res(wb, p + ".block_2", c, c);
+  m.b1 = vae_load_res(wb, p + ".block_1", c, c);
+  vae_load_attn(wb, p + ".attn", m);
+  m.b2 = vae_load_res(wb, p + ".block_2", c, c);
   return m;
 }
 
@@ -44,9 +47,9 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
     for (size_t i = 0; i < cfg_.dec.size(); ++i) {
       const std::string p = "decoder.blocks." + std::to_string(i);
       DecBlk b;
-      b.r[0] = load_res(wb, p + ".res1", cfg_.dec[i].first, cfg_.dec[i].second);
-      b.r[1] = load_res(wb, p + ".res2", cfg_.dec[i].second, cfg_.dec[i].second);
-      b.r[2] = load_res(wb, p + ".res3", cfg_.dec[i].second, cfg_.dec[i].second);
+      b.r[0] = vae_load_res(wb, p + ".res1", cfg_.dec[i].first, cfg_.dec[i].second);
+      b.r[1] = vae_load_res(wb, p + ".res2", cfg_.dec[i].second, cfg_.dec[i].second);
+      b.r[2] = vae_load_res(wb, p + ".res3", cfg_.dec[i].second, cfg_.dec[i].second);
       b.has_up = i + 1 != cfg_.dec.size();
       if (b.has_up) b.up = wb.conv(p + ".upsampler", cdt_ == DT_HL);      // split-operand decoder: + the folded phase matrices (Lin::w_fold)
       d_blocks_.push_back(b);
@@ -63,8 +66,8 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
     for (size_t i = 0; i < cfg_.enc.size(); ++i) {
       const std::string p = "encoder.blocks." + std::to_string(i);
       EncBlk b;
-      b.r[0] = load_res(wb, p + ".res1", cfg_.enc[i].first, cfg_.enc[i].second);
-      b.r[1] = load_res(wb, p + ".res2", cfg_.enc[i].second, cfg_.enc[i].second);
+      b.r[0] = vae_load_res(wb, p + ".res1", cfg_.enc[i].first, cfg_.enc[i].second);
+      b.r[1] = vae_load_res(wb, p + ".res2", cfg_.enc[i].second, cfg_.enc[i].second);
       b.has_down = i + 1 != cfg_.enc.size();
       if (b.has_down) b.down = wb.conv(p + ".downsampler");
       e_blocks_.push_back(b);
@@ -79,7 +82,7 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
 }
 Vae::~Vae() {}
 
-void Vae::res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int W, const Act& out) {
+void vae_res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int W, const Act& out, int n_group) {
   // ResnetBlock::forward autoencoder/mod.rs:500-516
   const size_t mk = ex.act->mark();
   const size_t M = (size_t)B * H * W;
@@ -92,11 +95,11 @@ void Vae::res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int 
   float* nin_max = nullptr;
   if (w.has_nin && ex.cdt == DT_HL && x.dt == DT_F32 && w.nin.dt != DT_F32 && !x.gn_part && M % (size_t)B == 0)
     nin_max = (float*)ex.act->alloc(hl_scale_floats(B) * sizeof(float));
-  run_groupnorm(ex, w.n1, x, B, H * W, gn1, true, cfg_.n_group, nin_max);
+  run_groupnorm(ex, w.n1, x, B, H * W, gn1, true, n_group, nin_max);
   Act h = ex.alloc(M, w.cout, ex.sdt);          // (read by a GroupNorm only: stays in the stream dtype)
   run_conv(ex, w.c1, gn1, w.cin, g3, h);
   Act gn2 = ex.alloc(M, w.cout, ex.cdt);
-  run_groupnorm(ex, w.n2, h, B, H * W, gn2, true, cfg_.n_group);
+  run_groupnorm(ex, w.n2, h, B, H * W, gn2, true, n_group);
   Epi e;
   if (w.has_nin) { run_conv(ex, w.nin, hl_operand(ex, w.nin, x, M, w.cin, B, nin_max), w.cin, g1, out); e.R = out; }
   else e.R = x;
@@ -104,14 +107,16 @@ void Vae::res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int 
   ex.act->reset(mk);
 }
 
-void Vae::mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W) {
-  // Mid::forward :443-449 (in place on x); ConvSelfAttentionBlock::forward :550-586
+void Vae::res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int W, const Act& out) {
+  vae_res_block(ex, w, x, B, H, W, out, cfg_.n_group);
+}
+
+void vae_attn_block(Exec& ex, const VaeMidW& w, const Act& y, int B, int H, int W, int n_group) {
+  // ConvSelfAttentionBlock::forward :550-586, in place on y (the residual stream)
   const size_t mk = ex.act->mark();
   const int HW = H * W, C = w.C;
   const size_t M = (size_t)B * HW;
   const ConvGeom g1{B, H, W, H, W, 1, 1, 0, 0};
-  Act y = ex.alloc(M, C, ex.sdt);
-  res_block(ex, w.b1, x, B, H, W, y);
   {
     const int kt = ex.cdt == DT_F16 ? 64 : 32;
     const int kpad = (int)round_up(HW, kt);        // K padding of the P V product
@@ -119,7 +124,7 @@ void Vae::mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W) {
     const int rows_v = (int)round_up(C, 128);
     SDXL_REQUIRE(C % kt == 0, "VAE attention channel count must be a multiple of the k-tile");
     Act hn = ex.alloc(M, C, ex.cdt);
-    run_groupnorm(ex, w.an, y, B, HW, hn, false, cfg_.n_group);
+    run_groupnorm(ex, w.an, y, B, HW, hn, false, n_group);
     const float scale = (float)(1.0 / std::sqrt((double)C));   // (d^-0.25)^2, backend.rs:98
     if (ex.cdt == DT_F16 && C == 512) {
       // one head of 512 channels: the flash kernel (attn_hd_kernel) -- scores never materialised.  q | k from the 1x1 convs as
@@ -142,7 +147,6 @@ void Vae::mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W) {
       }
       Epi ep; ep.R = y;
       run_conv(ex, w.proj, o, C, g1, y, ep);
-      res_block(ex, w.b2, y, B, H, W, x);
       ex.act->reset(mk);
       return;
     }
@@ -198,6 +202,15 @@ void Vae::mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W) {
     Epi ep; ep.R = y;
     run_conv(ex, w.proj, o, C, g1, y, ep);
   }
+  ex.act->reset(mk);
+}
+
+void Vae::mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W) {
+  // Mid::forward :443-449 (in place on x)
+  const size_t mk = ex.act->mark();
+  Act y = ex.alloc((size_t)B * H * W, w.C, ex.sdt);
+  res_block(ex, w.b1, x, B, H, W, y);
+  vae_attn_block(ex, w, y, B, H, W, cfg_.n_group);
   res_block(ex, w.b2, y, B, H, W, x);
   ex.act->reset(mk);
 }
