@@ -283,6 +283,35 @@ int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out);
  * 0..n_train_steps-1, capacity_steps too small, an unknown solver, alphas outside (0, 1): SDXL_ERR_INVALID, out untouched. */
 int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver,
                              double eta, double* out, int capacity_steps);
+/* ---- prediction type: what the UNet's output means, a per-handle option (refiner handles too) all six trajectory calls above honour, with
+ * both solvers, explicit and seeded noise, eta, inpainting, refine_latent and every guidance option.  SDXL_PREDICTION_EPSILON (default) is
+ * the reference's reading, the noise e, and a handle that never calls the setter runs exactly what it ran before the option existed.
+ * SDXL_PREDICTION_V reads v = alpha e - sigma x0 (Salimans & Ho 2022), what checkpoints trained on a zero-terminal-SNR schedule predict
+ * (Lin et al. 2023).  The two branches of an iteration are combined by the guidance lines below as they stand, on v (v = vc; v =
+ * fma(vc - vu, s_b, vu), then v f_b: CFG rescale sees the network's raw output rows whatever they mean, under v the moments of vc and vcfg).  Then
+ *     x0 = fma(x, alpha, -(v sigma))        no division: finite at alpha == 0, where x0 = -v
+ *     e  = fma(v, alpha, x sigma)           SDXL_SOLVER_DDIM only; SDXL_SOLVER_DPMPP_2M never forms e
+ * and everything behind x0 and e -- the DDIM / 2M update, the sigma noise, the inpainting blend -- is unchanged: the rows (c_x, c_0, c_1,
+ * c_z) do not depend on the prediction type.
+ * Zero terminal SNR: with a = alphas_cumprod at an iteration's own timestep, a == 0 is admitted under SDXL_PREDICTION_V (ap == 0 and
+ * a >= 1 stay refused), and such a table can be handed to sdxl_diffuser_create* as it is.  There alpha = 0, sigma = 1, lambda = -inf and
+ * h = +inf, and the rows are the limits: DDIM's expressions are finite as they stand (sigma_t = eta sqrt(1 - ap)); the 2M row is first
+ * order, (sigma', alpha', 0, 0) at eta == 0 and (0, alpha', 0, sigma') at eta > 0, and the iteration behind it (r = h_prev / h = inf) is first
+ * order too, like iteration 0.  Under SDXL_PREDICTION_EPSILON a trajectory, replay or coefficient call whose schedule touches a timestep
+ * with a == 0 returns SDXL_ERR_INVALID before anything is launched (x0 would divide by alpha == 0); the message names v-prediction. */
+enum { SDXL_PREDICTION_EPSILON = 0, SDXL_PREDICTION_V = 1 };   /* (x0 / "sample" and EDM parameterisations: not offered, values 2.. are free) */
+/* unknown value: SDXL_ERR_INVALID ("prediction" in sdxl_last_error), the handle keeps its own */
+int sdxl_diffuser_set_prediction(sdxl_diffuser* d, int prediction);
+int sdxl_diffuser_get_prediction(sdxl_diffuser* d, int* prediction_out);
+/* host logic only: Lin et al. 2023, Algorithm 1 on s = sqrt(alphas_cumprod) in f64:
+ * s <- (s - s[T-1]) * s[0] / (s[0] - s[T-1]);  out = (float)(s * s).  out[T-1] is exactly 0, out[0] == in[0] as a float.
+ * n < 2, NULL, an input outside (0, 1) or not strictly decreasing: SDXL_ERR_INVALID, out untouched.  in == out allowed. */
+int sdxl_rescale_zero_terminal_snr(const float* alphas_cumprod_in, int n_train_steps, float* alphas_cumprod_out);
+/* sdxl_solver_coefficients under a prediction type: the same rows, and with SDXL_PREDICTION_V the a == 0 rows above.  An unknown prediction,
+ * or SDXL_PREDICTION_EPSILON with a == 0 at an iteration's timestep: SDXL_ERR_INVALID, out untouched.  sdxl_solver_coefficients is this
+ * entry with SDXL_PREDICTION_EPSILON. */
+int sdxl_solver_coefficients_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver,
+                                  int prediction, double eta, double* out, int capacity_steps);
 /* ---- guidance: how the two UNet branches of an iteration become the noise prediction e, a per-handle option all six trajectory
  * calls above honour, with both solvers, explicit and seeded noise, and inpainting.  The default is the reference's line (:539-540),
  * e = eu + (ec - eu) s with the call's scalar s on every iteration, and a handle with default options runs exactly what it ran before
@@ -341,6 +370,9 @@ typedef struct {
   float* latents_out; float* hist_out; float* unet_in_out; float* timesteps_out;
 } sdxl_step_replay_args;
 int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args);
+/* the same replay with eps read under `prediction` (SDXL_PREDICTION_V: the rows are v); sdxl_sampler_step_replay is this entry with
+ * SDXL_PREDICTION_EPSILON.  The struct is shared.  Refuses what sdxl_solver_coefficients_pred refuses. */
+int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args, int prediction);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

@@ -392,6 +392,23 @@ pub enum Solver {
     /// DPM-Solver++(2M) on the same schedule, with `eta > 0` its SDE form: second order at one UNet evaluation per iteration
     Dpmpp2M = ffi::SDXL_SOLVER_DPMPP_2M as isize,
 }
+/// what the UNet's output means (`SDXL_PREDICTION_*`): a per-handle option all trajectory methods honour
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Prediction {
+    /// the noise `e`, the reference's reading and the default
+    Epsilon = ffi::SDXL_PREDICTION_EPSILON as isize,
+    /// `v = alpha e - sigma x0`: checkpoints trained on a zero-terminal-SNR schedule (Lin et al. 2023); admits `alphas_cumprod == 0` at
+    /// an iteration's own timestep
+    V = ffi::SDXL_PREDICTION_V as isize,
+}
+/// `sdxl_rescale_zero_terminal_snr` (host logic, no device): the `alphas_cumprod` table shifted and scaled in sqrt-space so that its last
+/// value is exactly 0 and its first unchanged (Lin et al. 2023, Algorithm 1).  A table with fewer than two values, a value outside (0, 1)
+/// or one that is not strictly decreasing is an `Err` with the engine's message.
+pub fn rescale_zero_terminal_snr(alphas_cumprod: &[f32]) -> Result<Vec<f32>, Box<dyn std::error::Error>> {
+    let mut out = vec![0f32; alphas_cumprod.len()];
+    try_check(unsafe { ffi::sdxl_rescale_zero_terminal_snr(alphas_cumprod.as_ptr(), alphas_cumprod.len() as c_int, out.as_mut_ptr()) })?;
+    Ok(out)
+}
 /// how the two UNet branches of an iteration become the noise prediction (`sdxl_guidance`): a per-handle option all trajectory methods
 /// honour.  `Guidance::default()` is the reference's line, one scalar scale on every iteration.
 #[derive(Clone, Debug, PartialEq)]
@@ -521,6 +538,15 @@ impl<B: BurnBackend> Diffuser<B> {
         let mut v: c_int = 0;
         check(unsafe { ffi::sdxl_diffuser_get_solver(self.raw, &mut v) });
         if v == Solver::Dpmpp2M as c_int { Solver::Dpmpp2M } else { Solver::Ddim }
+    }
+    /// every following trajectory of this handle reads the UNet's output as `prediction` (`sdxl_diffuser_set_prediction`)
+    pub fn set_prediction(&self, prediction: Prediction) {
+        check(unsafe { ffi::sdxl_diffuser_set_prediction(self.raw, prediction as c_int) });
+    }
+    pub fn prediction(&self) -> Prediction {
+        let mut v: c_int = 0;
+        check(unsafe { ffi::sdxl_diffuser_get_prediction(self.raw, &mut v) });
+        if v == Prediction::V as c_int { Prediction::V } else { Prediction::Epsilon }
     }
     /// every following trajectory of this handle runs `guidance` (`sdxl_diffuser_set_guidance`); options the engine refuses
     /// (`sdxl_guidance_check`: values out of range, anything but the default or `off` on a refiner) are an `Err` with its message and

@@ -109,6 +109,8 @@ ABI_SYMBOLS = [
     "sdxl_diffuser_set_solver", "sdxl_diffuser_get_solver", "sdxl_solver_coefficients",
     "sdxl_guidance_default", "sdxl_guidance_check", "sdxl_diffuser_set_guidance", "sdxl_diffuser_get_guidance", "sdxl_cfg_rescale_factors",
     "sdxl_sampler_step_replay",
+    "sdxl_diffuser_set_prediction", "sdxl_diffuser_get_prediction", "sdxl_rescale_zero_terminal_snr", "sdxl_solver_coefficients_pred",
+    "sdxl_sampler_step_replay_pred",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -165,6 +167,13 @@ def lib() -> ctypes.CDLL:
                                                    ctypes.c_float, ctypes.c_void_p]
         if hasattr(l, "sdxl_sampler_step_replay"):
             l.sdxl_sampler_step_replay.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        if hasattr(l, "sdxl_solver_coefficients_pred"):
+            l.sdxl_diffuser_set_prediction.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_diffuser_get_prediction.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+            l.sdxl_rescale_zero_terminal_snr.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+            l.sdxl_solver_coefficients_pred.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_sampler_step_replay_pred.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         _lib = l
     return _lib
 
@@ -791,14 +800,42 @@ def _solver(solver) -> int:
     return int(solver)
 
 
-def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp_2m", eta: float = 0.0) -> np.ndarray:
+PREDICTION_EPSILON = 0  # SDXL_PREDICTION_EPSILON: the UNet's output is the noise e (default, the reference's reading)
+PREDICTION_V = 1        # SDXL_PREDICTION_V: it is v = alpha e - sigma x0 (checkpoints trained on a zero-terminal-SNR schedule)
+_PREDICTION_NAMES = {"epsilon": PREDICTION_EPSILON, "v": PREDICTION_V}
+
+
+def _prediction(prediction) -> int:
+    """a name of _PREDICTION_NAMES or an SDXL_PREDICTION_* value (an unknown value travels on: the engine reports it)"""
+    if isinstance(prediction, str):
+        if prediction not in _PREDICTION_NAMES:
+            raise InvalidArgument(f"unknown prediction {prediction!r}: one of {sorted(_PREDICTION_NAMES)}")
+        return _PREDICTION_NAMES[prediction]
+    return int(prediction)
+
+
+def rescale_zero_terminal_snr(alphas) -> np.ndarray:
+    """sdxl_rescale_zero_terminal_snr (host logic: no GPU needed): the alphas_cumprod table shifted and scaled in sqrt-space so that its last
+    value is exactly 0 and its first unchanged (Lin et al. 2023, Algorithm 1) -> float32 array; a table it refuses raises InvalidArgument"""
+    a = np.ascontiguousarray(alphas, dtype=np.float32)
+    out = np.empty_like(a)
+    _check_invalid(lib().sdxl_rescale_zero_terminal_snr(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp_2m", eta: float = 0.0, prediction="epsilon") -> np.ndarray:
     """sdxl_solver_coefficients: float64 [iterations, 4] rows (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z, the
-    table the sampler runs (host logic: no GPU needed)"""
+    table the sampler runs (host logic: no GPU needed).  prediction "v" (sdxl_solver_coefficients_pred) admits a zero-terminal-SNR table."""
     a = np.ascontiguousarray(alphas, dtype=np.float32)
     iters = max(step_count(n_steps, step_start, int(a.shape[0])), 0) if n_steps >= 1 else 0
     out = np.zeros((iters, 4), dtype=np.float64)
-    _check(lib().sdxl_solver_coefficients(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), n_steps, step_start, _solver(solver),
-                                         float(eta), out.ctypes.data_as(ctypes.c_void_p), iters))
+    if _prediction(prediction) == PREDICTION_EPSILON:      # the entry every build has
+        _check_invalid(lib().sdxl_solver_coefficients(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), n_steps, step_start, _solver(solver),
+                                                     float(eta), out.ctypes.data_as(ctypes.c_void_p), iters))
+    else:
+        _check_invalid(lib().sdxl_solver_coefficients_pred(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), n_steps, step_start,
+                                                           _solver(solver), _prediction(prediction), float(eta),
+                                                           out.ctypes.data_as(ctypes.c_void_p), iters))
     return out
 
 
@@ -862,12 +899,14 @@ class _StepReplayArgsC(ctypes.Structure):
 
 def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps, latent0, solver="ddim", eta: float = 0.0,
                         cfg_scale: float = 7.5, guidance: Optional[Guidance] = None, single: bool = False, input_f16: bool = False,
-                        reference=None, mask=None, step_noise=None, seeds=None):
+                        reference=None, mask=None, step_noise=None, seeds=None, prediction="epsilon"):
     """sdxl_sampler_step_replay, the trajectory without the UNet (a test seam): eps [iterations, B, h*w, 4] and latent0 [n, 4, h, w] float32
     CUDA tensors, B = n where single (or guidance mode "off"), else 2n.  Returns float32 CUDA tensors (latents [iterations + 1, n, 4, h, w],
     hist [n, 4, h, w] -- zeros under DDIM --, unet_in [B, h*w, 4], timesteps [iterations + 1]).  Nothing is checked here but the shapes the
-    outputs are sized by: the engine reports what it refuses (InvalidArgument)."""
+    outputs are sized by: the engine reports what it refuses (InvalidArgument).  prediction "v" (sdxl_sampler_step_replay_pred): the rows
+    of eps are v."""
     torch = _torch()
+    pred = _prediction(prediction)
     a = np.ascontiguousarray(alphas, dtype=np.float32)
     eps, pe = _dev(eps)
     latent0, pl = _dev(latent0)
@@ -888,7 +927,10 @@ def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps
                             ctypes.pointer(guidance) if guidance is not None else None, int(single), n, h, w, int(input_f16),
                             pe, pl, keep[0][1], keep[1][1], keep[2][1], ctypes.cast(sd, _c_p) if sd is not None else None,
                             *[ctypes.c_void_p(t.data_ptr()) for t in out])
-    _check_invalid(lib().sdxl_sampler_step_replay(ctx.h, _stream(), ctypes.byref(args)))
+    if pred == PREDICTION_EPSILON:      # the entry every build has
+        _check_invalid(lib().sdxl_sampler_step_replay(ctx.h, _stream(), ctypes.byref(args)))
+    else:
+        _check_invalid(lib().sdxl_sampler_step_replay_pred(ctx.h, _stream(), ctypes.byref(args), pred))
     return out
 
 
@@ -1030,6 +1072,16 @@ class Diffuser:
         v = ctypes.c_int(-1)
         _check(lib().sdxl_diffuser_get_solver(self.h, ctypes.byref(v)))
         return {v: k for k, v in _SOLVER_NAMES.items()}[v.value]
+
+    def set_prediction(self, prediction):
+        """"epsilon" (default) or "v" (or the PREDICTION_* value): what the UNet's output means to every following trajectory of this
+        handle.  An unknown value raises InvalidArgument and the handle keeps its own."""
+        _check_invalid(lib().sdxl_diffuser_set_prediction(self.h, _prediction(prediction)))
+
+    def get_prediction(self) -> str:
+        v = ctypes.c_int(-1)
+        _check(lib().sdxl_diffuser_get_prediction(self.h, ctypes.byref(v)))
+        return {v: k for k, v in _PREDICTION_NAMES.items()}[v.value]
 
     def set_guidance(self, guidance: Optional[Guidance] = None, **options):
         """sdxl_diffuser_set_guidance: the guidance options every following trajectory of this handle runs -- a Guidance, or the keywords of

@@ -661,19 +661,63 @@ static const char* alphas_error(const float* alphas_cumprod_host, int n_train_st
     if (!(alphas_cumprod_host[i] > 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
   return nullptr;
 }
-int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta,
-                             double* out, int capacity_steps) {
+// the table under a prediction type (valid schedule arguments): SDXL_PREDICTION_V admits 0 in it, and the schedule decides where it may stand;
+// under SDXL_PREDICTION_EPSILON a 0 at a sampled timestep gets the message that names the remedy, any other value outside (0, 1) the old one
+static const char* alphas_error_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int prediction) {
+  if (prediction != SDXL_PREDICTION_EPSILON && prediction != SDXL_PREDICTION_V) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
+  for (int i = 0; i < n_train_steps; ++i)
+    if (!(alphas_cumprod_host[i] >= 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
+  const std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);
+  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train_steps, n_steps, step_start, prediction)) return m;
+  return prediction == SDXL_PREDICTION_EPSILON ? alphas_error(alphas_cumprod_host, n_train_steps) : nullptr;
+}
+int sdxl_solver_coefficients_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, int prediction,
+                                  double eta, double* out, int capacity_steps) {
   if (!out) return fail(SDXL_ERR_INVALID, "null argument");
   if (const char* m = schedule_args_error(alphas_cumprod_host, n_train_steps, n_steps, step_start, solver, eta)) return fail(SDXL_ERR_INVALID, m);
   const int iters = (int)Diffuser::step_schedule(n_steps, step_start, n_train_steps).size();
   if (capacity_steps < iters) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than sdxl_step_count");
-  if (const char* m = alphas_error(alphas_cumprod_host, n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = alphas_error_pred(alphas_cumprod_host, n_train_steps, n_steps, step_start, prediction)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
   std::vector<double> rows((size_t)4 * iters);
-  Diffuser::solver_coefficients(alphas.data(), n_train_steps, n_steps, step_start, solver, eta, rows.data());
+  Diffuser::solver_coefficients(alphas.data(), n_train_steps, n_steps, step_start, solver, eta, rows.data(), prediction);
   std::copy(rows.begin(), rows.end(), out);
   API_END
+}
+int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta,
+                             double* out, int capacity_steps) {
+  return sdxl_solver_coefficients_pred(alphas_cumprod_host, n_train_steps, n_steps, step_start, solver, SDXL_PREDICTION_EPSILON, eta, out,
+                                       capacity_steps);
+}
+// prediction: a per-handle option like the solver; an unknown value is an argument error and leaves the handle as it was
+int sdxl_diffuser_set_prediction(sdxl_diffuser* d, int prediction) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  if (prediction != SDXL_PREDICTION_EPSILON && prediction != SDXL_PREDICTION_V)
+    return fail(SDXL_ERR_INVALID, "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)");
+  API_BEGIN
+  d->d->set_prediction(prediction);
+  API_END
+}
+int sdxl_diffuser_get_prediction(sdxl_diffuser* d, int* prediction_out) {
+  if (!d || !prediction_out) return fail(SDXL_ERR_INVALID, "null argument");
+  *prediction_out = d->d->prediction();
+  return SDXL_OK;
+}
+// Lin et al. 2023, Algorithm 1 on s = sqrt(alphas_cumprod), f64: shift so that s[T-1] = 0, scale so that s[0] keeps its value
+int sdxl_rescale_zero_terminal_snr(const float* alphas_cumprod_in, int n_train_steps, float* alphas_cumprod_out) {
+  if (!alphas_cumprod_in || !alphas_cumprod_out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (n_train_steps < 2) return fail(SDXL_ERR_INVALID, "rescale_zero_terminal_snr: n_train_steps must be at least 2");
+  for (int i = 0; i < n_train_steps; ++i) {
+    if (!(alphas_cumprod_in[i] > 0.f && alphas_cumprod_in[i] < 1.f)) return fail(SDXL_ERR_INVALID, "alphas_cumprod outside (0, 1)");
+    if (i > 0 && !(alphas_cumprod_in[i] < alphas_cumprod_in[i - 1])) return fail(SDXL_ERR_INVALID, "alphas_cumprod is not strictly decreasing");
+  }
+  const double s0 = std::sqrt((double)alphas_cumprod_in[0]), sT = std::sqrt((double)alphas_cumprod_in[n_train_steps - 1]);
+  for (int i = 0; i < n_train_steps; ++i) {     // in == out allowed: entry i is read before it is written, s0 and sT are held
+    const double s = (std::sqrt((double)alphas_cumprod_in[i]) - sT) * s0 / (s0 - sT);
+    alphas_cumprod_out[i] = (float)(s * s);
+  }
+  return SDXL_OK;
 }
 // guidance: a per-handle option; options the check refuses are an argument error and leave the handle as it was
 static Guidance to_guidance(const sdxl_guidance* g) {
@@ -727,11 +771,14 @@ int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int 
 }
 // the trajectory without the UNet: a StepLoop of its own, driven as Diffuser::diffuse drives its one, with eps where the UNet's output would be
 int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a) {
+  return sdxl_sampler_step_replay_pred(ctx, stream, a, SDXL_PREDICTION_EPSILON);
+}
+int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction) {
   if (!ctx || !a || !a->eps || !a->latent0 || !a->latents_out || !a->unet_in_out || !a->timesteps_out) return fail(SDXL_ERR_INVALID, "null argument");
   if (a->n < 1 || a->n > kMaxSeeds || a->h < 1 || a->w < 1 || (int64_t)a->h * a->w > 1 << 22)
     return fail(SDXL_ERR_INVALID, "step_replay: n (1..8) or h * w (1..2^22) out of range");
   if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
-  if (const char* m = alphas_error(a->alphas_cumprod_host, a->n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = alphas_error_pred(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, prediction)) return fail(SDXL_ERR_INVALID, m);
   if ((a->mask != nullptr) != (a->reference != nullptr)) return fail(SDXL_ERR_INVALID, "inpainting needs reference and mask");
   if (a->mask && !a->seeds && !a->step_noise) return fail(SDXL_ERR_INVALID, "inpainting with explicit noise needs step_noise");
   if (!a->seeds && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "eta needs seeds: explicit noise carries none for the sigma term");
@@ -753,7 +800,7 @@ int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay
   io.reference = a->reference; io.mask = a->mask; io.step_noise = a->step_noise; io.seeds = a->seeds;
   SDXL_HIP(hipMemcpyAsync(io.latent, a->latent0, bytes, hipMemcpyDeviceToDevice, s));
   StepLoop loop;
-  const int iters = loop.begin(alphas, a->n_steps, a->step_start, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s);
+  const int iters = loop.begin(alphas, a->n_steps, a->step_start, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s, prediction);
   for (int i = 0; i <= iters; ++i) {
     if (i > 0) loop.after_forward(i - 1, a->eps + (size_t)(i - 1) * B * HW * 4, s);
     SDXL_HIP(hipMemcpyAsync(a->latents_out + (size_t)i * elems, io.latent, bytes, hipMemcpyDeviceToDevice, s));

@@ -16,7 +16,8 @@ inline int fail(int code, const std::string& m) { g_err = m; return code; }
 #define API_BEGIN try {
 #define API_END                                                              \
   return SDXL_OK;                                                            \
-  } catch (const sdxl::Error& e) { return fail(SDXL_ERR_RUNTIME, e.what()); } \
+  } catch (const sdxl::InvalidArgumentError& e) { return fail(SDXL_ERR_INVALID, e.what()); } \
+  catch (const sdxl::Error& e) { return fail(SDXL_ERR_RUNTIME, e.what()); } \
   catch (const std::exception& e) { return fail(SDXL_ERR_RUNTIME, e.what()); } \
   catch (...) { return fail(SDXL_ERR_RUNTIME, "unknown error"); }
 

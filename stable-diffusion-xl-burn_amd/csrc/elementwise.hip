@@ -623,7 +623,12 @@ void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n
 //                    The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.
 //     x   = fma(z, sigma or c_z, x)       (SEEDED, coefficient != 0; z = seeded_normal4(seed, hw, draw_sigma(idx)))
 //   the blend rounds both products.
-template <int SOLVER, bool SEEDED>
+// PRED = kPredictionV: the network's rows are v = alpha e - sigma x0.  The two guidance lines above combine them as they combine e (v = vc;
+// v = fma(vc - vu, scales[b], vu), then v * factors[b]), and the x0 line is replaced by
+//     x0  = fma(x, sqrt_a, -(v * sqrt_1ma))           no division: finite at sqrt_a == 0 (zero terminal SNR), where x0 = -v
+//     e   = fma(v, sqrt_a, x * sqrt_1ma)              kSolverDdim only; kSolverDpmpp2M never forms e
+// with everything behind x0 and e the text of that solver.  The kPredictionEpsilon instantiations compile from the lines they always had.
+template <int SOLVER, bool SEEDED, int PRED>
 __global__ void step_kernel(const StepParams p, int do_update) {
 #pragma clang fp contract(off)
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -661,7 +666,14 @@ __global__ void step_kernel(const StepParams p, int do_update) {
         e = __builtin_fmaf(ec - eu, sb, eu);
         if (p.factors) e = e * fb;
       }
-      const float x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
+      float x0;
+      if constexpr (PRED == kPredictionV) {      // e holds v up to here
+        const float v = e;
+        x0 = __builtin_fmaf(x[c], k.sqrt_a, -(v * k.sqrt_1ma));
+        if constexpr (SOLVER == kSolverDdim) e = __builtin_fmaf(v, k.sqrt_a, x[c] * k.sqrt_1ma);
+      } else {
+        x0 = __builtin_fmaf(-e, k.sqrt_1ma, x[c]) / k.sqrt_a;
+      }
       if constexpr (SOLVER == kSolverDpmpp2M) {
         p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
         float acc = k.c_1 * x0p[c];
@@ -707,16 +719,21 @@ __global__ void ddim_advance_kernel(const StepCoef* table, int* step_idx, float*
   *step_idx = next;
   *t_out = table[next].t;     // table carries one sentinel entry past the last step
 }
+template <int PRED>
+static void launch_step_pred(const StepParams& p, int do_update, dim3 grid, dim3 block, hipStream_t s) {
+  if (p.solver == kSolverDpmpp2M) {
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, true, PRED>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, false, PRED>), grid, block, 0, s, p, do_update);
+  } else {
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDdim, true, PRED>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverDdim, false, PRED>), grid, block, 0, s, p, do_update);
+  }
+}
 void launch_step(const StepParams& p, int do_update, hipStream_t s) {
   const size_t total = (size_t)p.n * p.HW;
   const dim3 grid((total + 255) / 256), block(256);
-  if (p.solver == kSolverDpmpp2M) {
-    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, true>), grid, block, 0, s, p, do_update);
-    else hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, false>), grid, block, 0, s, p, do_update);
-  } else {
-    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDdim, true>), grid, block, 0, s, p, do_update);
-    else hipLaunchKernelGGL((step_kernel<kSolverDdim, false>), grid, block, 0, s, p, do_update);
-  }
+  if (p.prediction == kPredictionV) launch_step_pred<kPredictionV>(p, do_update, grid, block, s);
+  else launch_step_pred<kPredictionEpsilon>(p, do_update, grid, block, s);
   hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(1), 0, s, p.table, p.step_idx, p.t_out, do_update);
 }
 

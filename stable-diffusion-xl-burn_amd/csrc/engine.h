@@ -16,6 +16,9 @@ namespace sdxl {
 struct Error : std::runtime_error {
   explicit Error(const std::string& m) : std::runtime_error(m) {}
 };
+struct InvalidArgumentError : Error {     // an argument the call refuses before anything is launched: SDXL_ERR_INVALID at the C ABI
+  explicit InvalidArgumentError(const std::string& m) : Error(m) {}
+};
 #define SDXL_HIP(x)                                                                                   \
   do {                                                                                                \
     hipError_t e__ = (x);                                                                             \
@@ -623,8 +626,10 @@ class StepLoop {
   // Builds the StepCoef table (host f64 -> f32) and the active-iteration array of one trajectory, uploads them and runs the do_update = 0
   // launch: *step_idx = 0, the step-0 inpainting blend, the first UNet input and timestep.  `single`: one branch, no CFG (B = n).  Returns the
   // number of iterations.  alphas: the n_train alphas_cumprod values as f64.
+  // prediction: kPredictionEpsilon or kPredictionV, what the rows handed to after_forward mean.  A schedule Diffuser::schedule_error refuses
+  // (alphas_cumprod == 0 at an iteration's timestep under kPredictionEpsilon) throws InvalidArgumentError before anything is launched.
   int begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale, const Guidance& g,
-            bool single, int n, int HW, const StepIo& io, hipStream_t s);
+            bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction = kPredictionEpsilon);
   // behind the UNet forward of iteration i: eps [B][HW][eps_ld] fp32 (cond entries first) -> the CFG rescale factors where rescale is on and
   // the iteration active, then the update + advance launches
   void after_forward(int i, const float* eps, hipStream_t s);
@@ -671,8 +676,18 @@ class Diffuser {
   static std::vector<int> step_schedule(int n_steps, int step_start, int n_train);
   // (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z per iteration of step_schedule, f64, out[4 * i ..] (host logic only;
   // formulas in include/sdxl_mi355.h, sdxl_solver_coefficients).  kSolverDpmpp2M: what diffuse() rounds into its table.  kSolverDdim: the
-  // DDIM update folded into the same four numbers.  alphas: n_train values in (0, 1).
-  static void solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out);
+  // DDIM update folded into the same four numbers.  alphas: n_train values in (0, 1).  The rows do not depend on the prediction type; it
+  // decides only whether a == 0 at an iteration's timestep (zero terminal SNR) is admitted: kPredictionV writes that row as the limit
+  // lambda -> -inf, kPredictionEpsilon throws InvalidArgumentError.
+  static void solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out,
+                                  int prediction = kPredictionEpsilon);
+  // host logic only: the first complaint about the (a, ap) pairs of step_schedule under `prediction`, nullptr where the trajectory can run.
+  // kPredictionEpsilon: a == 0 on an iteration (x0 would divide by it) -- the message names v-prediction.  kPredictionV: a outside [0, 1)
+  // or ap outside (0, 1].
+  static const char* schedule_error(const double* alphas, int n_train, int n_steps, int step_start, int prediction);
+  // kPredictionEpsilon (default) or kPredictionV: what the UNet's output means to every following trajectory of this handle
+  void set_prediction(int prediction);
+  int prediction() const { return prediction_; }
   // kSolverDdim (default) or kSolverDpmpp2M: the update every following trajectory of this handle runs
   void set_solver(int solver);
   int solver() const { return solver_; }
@@ -709,6 +724,7 @@ class Diffuser {
   float* latent_ = nullptr; size_t latent_cap_ = 0;
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
   int solver_ = kSolverDdim;
+  int prediction_ = kPredictionEpsilon;
   Guidance guidance_;
   StepLoop loop_;
   float* ctx_buf_ = nullptr; size_t ctx_cap_ = 0;     // [2n][77][ctx] cond then uncond

@@ -349,6 +349,7 @@ struct StepCoef {
 };
 static_assert(sizeof(StepCoef) == 32, "one table entry is eight floats in both layouts");
 constexpr int kSolverDdim = 0, kSolverDpmpp2M = 1;   // SDXL_SOLVER_* of the public header
+constexpr int kPredictionEpsilon = 0, kPredictionV = 1;   // SDXL_PREDICTION_* of the public header: what the UNet's output rows mean
 // draw numbers of the seeded noise (counter word 1 of the generator); the public header carries the same values as SDXL_DRAW_*
 constexpr uint32_t kDrawInitial = 0;
 constexpr uint32_t draw_blend(uint32_t i) { return 1u + 2u * i; }
@@ -356,10 +357,13 @@ constexpr uint32_t draw_sigma(uint32_t i) { return 2u + 2u * i; }
 constexpr int kMaxSeeds = 8;   // batch entries of one trajectory (Diffuser::diffuse: B <= 8)
 struct DdimSeeds { uint64_t v[kMaxSeeds]; };   // per-entry seeds, passed by value in the kernel arguments
 struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, passed by value in the kernel arguments like the seeds
-// The per-step kernel, one thread per latent pixel (step_kernel<SOLVER, SEEDED>, elementwise.hip, where every rounding is written out):
+// The per-step kernel, one thread per latent pixel (step_kernel<SOLVER, SEEDED, PRED>, elementwise.hip, where every rounding is written out):
 //   e  = ec                                  where !use_cfg, or on an inactive iteration (active != nullptr && !active[*step_idx]); eu is not read
 //   e  = fma(ec - eu, scales[b], eu)         otherwise; times factors[b] where factors != nullptr (CFG rescale)
 //   x0 = (x - e sqrt_1ma) / sqrt_a;  x = x0 sqrt_ap + e sqrt_1map (+ z sigma)   or, kSolverDpmpp2M,   x = c_x x + c_0 x0 + c_1 x0p (+ c_z z)
+// kPredictionV: the rows are v = alpha e - sigma x0, combined by the same two guidance lines (v, vc, vu for e, ec, eu), and then
+//   x0 = x sqrt_a - v sqrt_1ma               no division: finite at sqrt_a == 0 (zero terminal SNR), where x0 = -v
+//   e  = v sqrt_a + x sqrt_1ma               kSolverDdim only; the update lines behind x0 and e are those above
 // then the inpainting blend for the next iteration and the refresh of the UNet input (NHWC, once per branch).
 // eps: UNet output [Bu][HW][eps_ld] fp32-or-T rows; latent NCHW fp32 [n][4][HW].
 struct StepParams {
@@ -380,7 +384,8 @@ struct StepParams {
   float* t_out;              // device scalar(s): timestep for the next UNet call
   // kSolverDpmpp2M: table holds the 2M layout and hist [n][4][HW] fp32 the x0 of the previous iteration (read where c_1 != 0, written by
   // every update); kSolverDdim reads neither
-  int solver; float* hist;
+  // prediction: kPredictionEpsilon or kPredictionV (sits in the padding between solver and hist: no other member moves)
+  int solver; int prediction; float* hist;
 };
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
 // input and timestep.  do_update=1: the update with table[*step_idx], blend for the next step, then advances.
@@ -389,6 +394,7 @@ void launch_step(const StepParams& p, int do_update, hipStream_t s);
 // 4 * HW values of entry b, ecfg = fma(ec - eu, scales[b], eu); M2(ecfg_b) == 0 gives 1.  eps: rows [2n][HW][eps_ld] of eps_dt, cond entries
 // first.  Two launches: per-block (count, mean, M2) partials, grid (cfg_moments_blocks(HW), n), then one block per entry that merges them in
 // block-index order.  partials: device scratch of cfg_moments_floats(n, HW) floats.  No atomics: an entry's factor has the same bits alone and batched.
+// The op sees the network's raw output rows whatever they mean: under kPredictionV the moments are those of vc and vcfg (what Lin et al. rescale).
 constexpr int kCfgMomentsBlock = 256;
 inline int cfg_moments_blocks(int HW) { return (HW + kCfgMomentsBlock - 1) / kCfgMomentsBlock; }
 inline size_t cfg_moments_floats(int n, int HW) { return (size_t)n * cfg_moments_blocks(HW) * 6; }

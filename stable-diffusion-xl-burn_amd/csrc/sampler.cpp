@@ -15,6 +15,9 @@
 //   * how the pair becomes e is a per-handle choice too (set_guidance): the reference's one line by default; the conditional branch alone as a
 //     batch-n forward; or per-entry scales, a timestep interval and CFG rescale -- arguments of the same per-step kernel, with two small launches
 //     in front of it where rescale is on.  The default options are the call's scalar as every entry's scale.
+//   * what the UNet's output means is a per-handle choice as well (set_prediction): the noise e, or v = alpha e - sigma x0, in further instantiations
+//     of the same kernel (x0 = alpha x - sigma v, no division).  With v a schedule may hold alphas_cumprod == 0 at an iteration's timestep (zero
+//     terminal SNR); the table's row there is written as the limit lambda -> -inf, and under e such a schedule is refused before anything is launched.
 // StepLoop is everything between two UNet forwards; Diffuser::diffuse is context setup and the loop around UNet::forward.
 #include "engine.h"
 
@@ -75,8 +78,33 @@ void Diffuser::set_guidance(const Guidance& g) {
   guidance_ = g;
 }
 
-void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out) {
+void Diffuser::set_prediction(int prediction) {
+  SDXL_REQUIRE(prediction == kPredictionEpsilon || prediction == kPredictionV, "unknown prediction");
+  prediction_ = prediction;
+}
+
+const char* Diffuser::schedule_error(const double* alphas, int n_train, int n_steps, int step_start, int prediction) {
+  if (prediction != kPredictionEpsilon && prediction != kPredictionV) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
+  const std::vector<int> ts = step_schedule(n_steps, step_start, n_train);
+  const int step_size = n_train / n_steps;
+  for (int t : ts) {
+    const double a = alphas[t];
+    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+    if (prediction == kPredictionEpsilon) {
+      if (a == 0.0)
+        return "alphas_cumprod is 0 at a sampled timestep (zero terminal SNR): x0 = (x - sigma e) / alpha has no value there under the "
+               "epsilon prediction; such a schedule needs v-prediction (SDXL_PREDICTION_V)";
+    } else if (!(a >= 0.0 && a < 1.0 && ap > 0.0 && ap <= 1.0)) {
+      return "prediction v: alphas_cumprod outside [0, 1) at a sampled timestep, or 0 at the timestep a step lands on";
+    }
+  }
+  return nullptr;
+}
+
+void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out,
+                                   int prediction) {
   SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
+  if (const char* m = schedule_error(alphas, n_train, n_steps, step_start, prediction)) throw InvalidArgumentError(m);
   const std::vector<int> ts = step_schedule(n_steps, step_start, n_train);
   const int step_size = n_train / n_steps;
   double h_prev = 0.0;
@@ -85,7 +113,7 @@ void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_step
     const int t = ts[i];
     const double a = alphas[t];
     const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
-    SDXL_REQUIRE(a > 0.0 && a < 1.0 && ap > 0.0 && ap <= 1.0, "alphas_cumprod outside (0, 1)");
+    SDXL_REQUIRE((a > 0.0 || (a == 0.0 && prediction == kPredictionV)) && a < 1.0 && ap > 0.0 && ap <= 1.0, "alphas_cumprod outside (0, 1)");
     const double alpha = std::sqrt(a), sigma = std::sqrt(1.0 - a);
     double* c = out + 4 * i;     // c_x, c_0, c_1, c_z
     if (solver == kSolverDdim) {
@@ -100,6 +128,12 @@ void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_step
       continue;
     }
     const double alpha_p = std::sqrt(ap), sigma_p = std::sqrt(1.0 - ap);
+    if (a == 0.0) {              // alpha = 0, sigma = 1, lambda = -inf, h = +inf: the limits of the first-order row, written out (the formulas
+                                 // below would evaluate exp(-0 * inf)).  A -> 1; eta == 0: c_x = sigma'; eta > 0: c_x -> 0, c_z -> sigma'
+      c[0] = eta == 0.0 ? sigma_p : 0.0; c[1] = alpha_p; c[2] = 0.0; c[3] = eta == 0.0 ? 0.0 : sigma_p;
+      have_prev = false;         // the next iteration has r = h_prev / h = inf: first order, as iteration 0
+      continue;
+    }
     const double h = std::log(alpha_p / sigma_p) - std::log(alpha / sigma);
     const double A = -std::expm1(-(1.0 + eta) * h);
     c[0] = (sigma_p / sigma) * std::exp(-eta * h);
@@ -144,9 +178,11 @@ StepLoop::~StepLoop() {
 }
 
 int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale,
-                    const Guidance& go, bool single, int n, int HW, const StepIo& io, hipStream_t s) {
+                    const Guidance& go, bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction) {
   const int n_train = (int)alphas.size();
   SDXL_REQUIRE(n >= 1 && n <= kMaxSeeds, "batch out of range");
+  // a == 0 on an iteration: x0 = -v under kPredictionV; under kPredictionEpsilon the first update would divide by sqrt_a == 0
+  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train, n_steps, step_start, prediction)) throw InvalidArgumentError(m);
   SDXL_REQUIRE(single || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
   // --- coefficient table (host f64, exactly the reference's scalar arithmetic :407-414, :423-426)
   const std::vector<int> ts = Diffuser::step_schedule(n_steps, step_start, n_train);
@@ -157,7 +193,7 @@ int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_sta
   std::vector<double> c2m;
   if (solver == kSolverDpmpp2M) {
     c2m.resize((size_t)4 * iters);
-    Diffuser::solver_coefficients(alphas.data(), n_train, n_steps, step_start, solver, eta, c2m.data());
+    Diffuser::solver_coefficients(alphas.data(), n_train, n_steps, step_start, solver, eta, c2m.data(), prediction);
   }
   for (int i = 0; i < iters; ++i) {
     const int t = ts[i];
@@ -206,7 +242,7 @@ int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_sta
   p_.ref = io.reference; p_.mask = io.mask; p_.step_noise = io.step_noise; p_.n_steps_total = iters;
   p_.unet_in = io.unet_in; p_.in_dt = io.in_dt; p_.in_ld = io.in_ld; p_.in_rep = single ? 1 : 2;
   p_.t_out = t_dev_;
-  p_.solver = solver; p_.hist = hist_;
+  p_.solver = solver; p_.prediction = prediction; p_.hist = hist_;
   if (io.seeds) {
     p_.seeded = 1;
     for (int b = 0; b < n; ++b) p_.seeds.v[b] = io.seeds[b];
@@ -260,7 +296,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   io.reference = reference; io.mask = mask; io.step_noise = step_noise; io.seeds = seeds;
   u.set_context(ctx_buf_, c.n_ctx, y_buf_, B, s);
 
-  const int iters = loop_.begin(alphas_, n_steps, step_start, solver_, eta, cfg_scale, go, single, n, HW, io, s);
+  const int iters = loop_.begin(alphas_, n_steps, step_start, solver_, eta, cfg_scale, go, single, n, HW, io, s, prediction_);
   std::vector<hipEvent_t> ev;
   if (time_steps) {
     ev.resize(iters + 1);
@@ -287,6 +323,8 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
 void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, const Trajectory& t, float* out, hipStream_t s) {
   SDXL_REQUIRE(!t.renoise || (t.step_start >= 1 && t.step_start <= n_train_), "step_start out of range");
   SDXL_REQUIRE(!t.seeds || c.n <= kMaxSeeds, "batch out of range");
+  // what StepLoop::begin refuses, before the start latent is written: nothing is launched
+  if (const char* m = schedule_error(alphas_.data(), n_train_, n_steps, t.step_start, prediction_)) throw InvalidArgumentError(m);
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
   ensure_device(latent_, latent_cap_, elems);

@@ -6,6 +6,8 @@ every repeat.
 
     --solver NAME[:ETA]   repeatable; NAME ddim | dpmpp_2m.  Without ETA the explicit-noise call (noise0 as a tensor), with
                           ETA the seeded call.  Default: --solver ddim
+    --prediction NAME     epsilon (default) | v: the handle's prediction type for every run of this process (DESIGN 3.7,
+                          profiles/prediction_step_times.txt); "v" also hands the handle the zero-terminal-SNR table
     --e2e                 afterwards, whole sample_latent calls under a host clock (ends in a synchronise), step timing off:
                           DDIM at 30 steps, 2M at 20 and at 15 -- latents/s of the sampler alone, a step-count comparison
                           at unmeasured image quality
@@ -15,6 +17,7 @@ only), so an A/B is
 
     SDXL_LIB_PATH=<parent .so> python tools/solver_step_times.py --solver ddim
     python tools/solver_step_times.py --solver ddim --solver dpmpp_2m:0 --solver dpmpp_2m:1 --e2e
+    python tools/solver_step_times.py --prediction v --solver ddim --solver dpmpp_2m
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solver", action="append", default=None, metavar="NAME[:ETA]")
+    ap.add_argument("--prediction", default="epsilon", choices=["epsilon", "v"])
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
@@ -51,7 +55,11 @@ def main():
                             unconditional_context_full=r(77, cfg.context_dim).cuda(),
                             unconditional_channel_context=r(cfg.adm_in_channels).cuda(), resolution=(1024, 1024))
     noise0 = r(1, 4, 128, 128).cuda()
-    d = pkg.Diffuser(ctx, cfg, pkg.DTYPE_F16, seed=0)
+    v_pred = args.prediction == "v"      # a library that knows epsilon only is never asked
+    d = pkg.Diffuser(ctx, cfg, pkg.DTYPE_F16, seed=0,
+                     alphas_cumprod=pkg.rescale_zero_terminal_snr(pkg.default_alphas_cumprod()) if v_pred else None)
+    if v_pred:
+        d.set_prediction("v")
     current = ["ddim"]
 
     def run(name, eta, n_steps):
@@ -73,7 +81,7 @@ def main():
             run(name, eta, 30)
             torch.cuda.synchronize()
             ms = d.step_times_ms()
-            print(json.dumps({"lib": lib, "mode": label, "repeat": rep, "iterations": len(ms), "step_ms_p50": round(statistics.median(ms), 4),
+            print(json.dumps({"lib": lib, "prediction": args.prediction, "mode": label, "repeat": rep, "iterations": len(ms), "step_ms_p50": round(statistics.median(ms), 4),
                               "step_ms_min": round(min(ms), 4), "step_ms_max": round(max(ms), 4)}), flush=True)
     if args.e2e:
         d.enable_step_timing(False)
