@@ -47,7 +47,9 @@ The old bars (test_gpu_ops.py: 4e-3 GEMM/norm, 8e-3 GEGLU, 6e-3 attention, relat
 oracle) sit 10x-400x above these.
 
 Out of scope: the f16-store epilogues no op entry reaches (the f16 output of a plain linear / conv2d with a residual as the UNet runs
-them, the QKV projection's transposed V^T store); the UNet-level tests cover them.
+them, the QKV projection's transposed V^T store); the UNet-level tests cover them, and tests/test_gpu_clip_layer.py holds both to an fp64
+reference at the CLIP encoders' real widths: the V^T store at 77 rows per entry (every row tile straddles batch entries) and the in-place residual
+epilogue on an f16 and on an fp32 stream.
 
 Dispatch (launch_attention_d64, attention.hip): base 64^2 (10 heads, 4096 queries) runs attn_d64_mix_kernel level 0 (4/5 of the heads in
 128-query blocks, the rest key-split); base 32^2 (20 heads, 1024) level 2 (the last fifth as key halves merged across workgroups);
