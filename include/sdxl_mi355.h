@@ -504,6 +504,11 @@ int sdxl_debug_warm_schedule(int n, const unsigned* bytes, const unsigned char* 
  * 2a + b of output pixel (2i + a, 2j + b), W_ab[dy][dx] = the taps of row set R_a(dy) x column set R_b(dx) summed in fp32, ky major, kx minor
  * (R_0(0) = {0}, R_0(1) = {1, 2}, R_1(0) = {0, 1}, R_1(1) = {2}) */
 int sdxl_debug_upsample_fold(const float* weight, int cout, int cin, float* out);
+/* the layout pass of a model's weight arena (no device needed; tests): *bytes receives what the model's weight arena holds -- sdxl_*_weight_arena of the
+ * created model, the size of its weight broadcast.  Exactly one of unet / vae / clip is non-NULL.  option: UNet -- the MixClass bits in force, -1 =
+ * the dtype's own (a model created on parameters that are not f16 values falls back to other classes: pass what sdxl_unet_mix_classes reports);
+ * VAE -- 0 = decoder only, 1 = with the encoder; CLIP -- 0 */
+int sdxl_debug_weight_layout(const sdxl_unet_config* unet, const sdxl_vae_config* vae, const sdxl_clip_config* clip, int dtype, int option, size_t* bytes);
 /* the kernel selection on a described launch (no device needed, no process-wide state read or written; tests): which kernel instantiation, grid and LDS
  * bytes a GEMM / a head-dim-64 attention call with these integer fields, optional operands and knob values would launch.  Optional operands are named by
  * the SDXL_SEL_* bits of `present`; `misaligned` != 0 puts every operand 8 bytes off a 16-byte boundary.  A status != 0 (text in sdxl_last_error())

@@ -114,7 +114,7 @@ ABI_SYMBOLS = [
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
-    "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
+    "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_debug_weight_layout", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
     "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_gemv", "sdxl_timestep_embedding", "sdxl_vae_attn_block", "sdxl_vae_res_block", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
@@ -750,6 +750,18 @@ def arena_as_tensor(ptr: int, nbytes: int, device_id: int = 0):
 
 def debug_set(key: str, value: int):
     _check(lib().sdxl_debug_set(key.encode(), int(value)))
+
+
+def weight_layout_bytes(cfg, dtype: int, option: int = -1) -> int:
+    """sdxl_debug_weight_layout: the bytes the weight arena of a model of this config (UNetConfig, VAEConfig or CLIPConfig) and dtype holds, from the
+    layout pass alone -- no GPU needed.  option: UNet -- the MixClass bits in force (-1: the dtype's own); VAE -- with_encoder; CLIP -- unused"""
+    c = cfg.to_c()
+    slots = [ctypes.byref(c) if isinstance(cfg, k) else None for k in (UNetConfig, VAEConfig, CLIPConfig)]
+    if not any(s is not None for s in slots):
+        raise EngineError("weight_layout_bytes: a UNetConfig, VAEConfig or CLIPConfig")
+    n = ctypes.c_size_t(0)
+    _check(lib().sdxl_debug_weight_layout(slots[0], slots[1], slots[2], int(dtype), 0 if isinstance(cfg, CLIPConfig) else int(option), ctypes.byref(n)))
+    return int(n.value)
 
 
 def bench_igemm(ctx: "Context", B: int, H: int, W: int, Cin: int, Cout: int, ksize: int = 1, geglu: bool = False,

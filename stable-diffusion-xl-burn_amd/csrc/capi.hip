@@ -175,6 +175,23 @@ int sdxl_debug_upsample_fold(const float* weight, int cout, int cin, float* out)
   fold_upsample_weights(weight, out, (size_t)cout, (size_t)cin);
   API_END
 }
+// the layout pass of a model's weight arena (the loader over a dry arena and an empty source) -- no device needed
+int sdxl_debug_weight_layout(const sdxl_unet_config* unet, const sdxl_vae_config* vae, const sdxl_clip_config* clip, int dtype, int option, size_t* bytes) {
+  API_BEGIN
+  SDXL_REQUIRE(bytes && (unet != nullptr) + (vae != nullptr) + (clip != nullptr) == 1, "weight layout: exactly one model description and a result");
+  int cdt, sdt;
+  if (unet) {
+    dtypes(dtype, cdt, sdt);
+    *bytes = UNet::weight_layout_bytes(to_cfg(unet), cdt, sdt, option < 0 ? mix_of(dtype) : option);
+  } else if (vae) {
+    vae_dtype(dtype, cdt);
+    *bytes = Vae::weight_layout_bytes(to_vcfg(vae), cdt, true, option != 0);
+  } else {
+    no_mix(dtype); dtypes(dtype, cdt, sdt); no_split(cdt, "the CLIP text encoders");
+    *bytes = ClipText::weight_layout_bytes(to_ccfg(clip), cdt);
+  }
+  API_END
+}
 // the kernel selection (select.cpp) on a described launch -- no device needed, the knobs come with the call
 int sdxl_debug_igemm_select(const sdxl_igemm_case* c, const sdxl_select_knobs* knobs, sdxl_igemm_choice* out) {
   API_BEGIN

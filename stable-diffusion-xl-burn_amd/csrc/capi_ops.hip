@@ -36,6 +36,18 @@ void add_conv(Operands& o, const std::string& n, int Cout, int Cin, int ksize, c
 void add_norm(Operands& o, const std::string& n, int C, const float* gamma, const float* beta, float eps) {
   o.push_back({n + ".gamma", {C}, PK_GAMMA, gamma}); o.push_back({n + ".beta", {C}, PK_BETA, beta}); o.push_back({n + ".eps", {1}, PK_EPS, nullptr, eps});
 }
+// An entry packs a handful of operands lazily, in forms it chooses after this bound is taken: a coarse upper bound on what WeightBuilder can allocate for them
+// (the models size their arenas by a layout pass instead).  Per matrix: padded weights (twice: the widest forms double K, the folded upsample phases hold
+// 16/9 of a 3x3 kernel) + their fragment-order image + bias, column sums, plain-twin bias and the scalars; per vector its padded length.
+size_t operand_bound(const std::vector<ParamSpec>& specs, int dt) {
+  size_t total = 1 << 20;
+  for (const ParamSpec& p : specs) {
+    if (p.kind != PK_LINEAR_W && p.kind != PK_CONV_W) { total += round_up(p.numel(), 128) * sizeof(float) + 256; continue; }
+    const size_t n = round_up(p.kind == PK_LINEAR_W ? p.shape[1] : p.shape[0], 128), k = round_up(p.numel() / (p.kind == PK_LINEAR_W ? p.shape[1] : p.shape[0]), 64);
+    total += 2 * (n * k * dt_size(dt) + n * k * 2 + 3 * (n * 4 + 256) + 4 * 256);
+  }
+  return total;
+}
 // the parameters of an entry as a model holds them: spec list, flat device buffer, source, arena and the WeightBuilder over them
 struct Packed {
   std::vector<ParamSpec> specs;
@@ -44,7 +56,7 @@ struct Packed {
   DeviceArena arena;
   WeightBuilder wb;
   Packed(const Operands& ops, int cdt, hipStream_t s)
-      : specs(specs_of(ops)), src(stage(ops, specs, tmp, s), specs), wb(specs, src, reserved(arena, 2 * WeightBuilder::arena_bound(specs, cdt) + (1 << 20)), cdt, s) {}
+      : specs(specs_of(ops)), src(stage(ops, specs, tmp, s), specs), wb(specs, src, reserved(arena, operand_bound(specs, cdt)), cdt, s) {}
   static std::vector<ParamSpec> specs_of(const Operands& ops) {
     std::vector<ParamSpec> v;
     for (const Operand& o : ops) v.push_back(ParamSpec{o.name, o.shape, o.kind, 0.f, 0.f});
@@ -515,7 +527,8 @@ int sdxl_layer_norm_linear(sdxl_ctx* ctx, void* stream, const float* x, const fl
     // f16 mode of the UNet: the consumer applies the LayerNorm in its epilogue, from the statistics the stream's producer left
     const F16Stream xs = identity_producer(ex, tmp, x, M, K, s);
     e.ln_stat = xs.stat;
-    run_linear(ex, pk.wb.linear_ln("lin", geglu != 0, "norm"), Act(xs.rows, K, DT_F16), M, o, e);
+    Proj d; d.names = {"lin"}; d.geglu = geglu != 0; d.ln = LN_FOLD; d.norm = "norm";
+    run_linear(ex, pk.wb.pack(d), Act(xs.rows, K, DT_F16), M, o, e);
   } else {
     const NormW n = pk.wb.norm("norm");
     void* xi = tmp.get((size_t)M * K * dt_size(sdt));
@@ -551,7 +564,8 @@ int sdxl_ln_query_cross_attention(sdxl_ctx* ctx, void* stream, const float* x, c
   Tmp tmp;
   Exec ex; ex.s = s; ex.cdt = DT_F16; ex.sdt = DT_F16;
   // beta W is folded into the packed bias; attn2.query has none of its own, so fold with beta as given (zero beta -> no bias)
-  const Lin l = pk.wb.linear_ln("lin", false, "norm", true);
+  Proj d; d.names = {"lin"}; d.ln = LN_FOLD; d.norm = "norm"; d.wfrag_folded = true;
+  const Lin l = pk.wb.pack(d);
   const F16Stream xs = identity_producer(ex, tmp, x, M, C, s);
   const Act xi(xs.rows, C, DT_F16);
   void* od = tmp.get((size_t)M * C * 2);
@@ -603,7 +617,7 @@ int sdxl_transformer_projection(sdxl_ctx* ctx, void* stream, int B, int rows_per
                                 const float* r, int Kp, int producer_form, const float* gamma, const float* beta, float eps, const float* w,
                                 const float* b, int N, int proj, int form, int shadow, float* t_out, float* out, int* shadow_taken) {
   // one LayerNorm-fed projection of a split-operand UNet's transformer block in a named form (plan_transformer), through the code
-  // UNet::spatial_transformer runs: pack_proj, alloc_ln_operands, want_ln_shadow, ln_input.  The producer (an out-projection / FF-out) adds into the
+  // UNet::spatial_transformer runs: WeightBuilder::pack, alloc_ln_operands, want_ln_shadow, ln_input.  The producer (an out-projection / FF-out) adds into the
   // fp32 stream t in place and, with `shadow`, is asked for the shadow of LayerNorm(t) exactly as the UNet asks it.
   API_BEGIN
   SDXL_REQUIRE(ctx && r && gamma && beta && w && out, "null argument");
@@ -642,9 +656,12 @@ int sdxl_transformer_projection(sdxl_ctx* ctx, void* stream, int B, int rows_per
   if ((f == LF_F16_AHILO || f == LF_X2) && !wb.all_f16_exact(wnames)) return fail(SDXL_ERR_INVALID, "transformer projection: AHILO / X2 need f16-valued weights");
   if (has_p && pf == LF_X2 && !wb.all_f16_exact({"prod.weight"})) return fail(SDXL_ERR_INVALID, "transformer projection: an X2 producer needs f16-valued weights");
   const NormW n = wb.norm("norm");
-  Lin plain, sh;
-  plain = pack_proj(wb, f, names, geglu, shadow ? &sh : nullptr, "norm");
-  const Lin lp = has_p ? pack_proj(wb, pf, {"prod"}, false) : Lin();
+  Lin sh;
+  Proj d; d.names = names; d.geglu = geglu; d.form = f;
+  if (shadow) { d.ln = LN_SHADOW; d.norm = "norm"; d.shadow = &sh; }
+  const Lin plain = wb.pack(d);
+  Proj dp; dp.names = {"prod"}; dp.form = pf;
+  const Lin lp = has_p ? wb.pack(dp) : Lin();
   // the UNet's plan for this one projection: its form (+ shadow twin) in its slot
   StPlan pl;
   LinForm& slot = proj == SDXL_PROJ_QKV ? pl.qkv : proj == SDXL_PROJ_QUERY ? pl.q2 : pl.geglu;

@@ -11,16 +11,29 @@
 
 namespace sdxl {
 
-ClipText::ClipText(const ClipCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st)
-    : cfg_(cfg), cdt_(compute_dt), sdt_(stream_dt) {
+ClipText::ClipText(const ClipCfg& cfg, int compute_dt, int stream_dt) : cfg_(cfg), cdt_(compute_dt), sdt_(stream_dt) {
   SDXL_REQUIRE(!(compute_dt == DT_F32 && stream_dt != DT_F32), "f32 compute implies an f32 residual stream");
+}
+ClipText::ClipText(const ClipCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st) : ClipText(cfg, compute_dt, stream_dt) {
+  warena_.reserve(weight_layout_bytes(cfg, compute_dt));
+  load_weights(warena_, src, st);
+  SDXL_HIP(hipStreamSynchronize(st));
+}
+size_t ClipText::weight_layout_bytes(const ClipCfg& cfg, int compute_dt) {
+  DeviceArena dry; dry.dry = true;
+  NullSource none;
+  ClipText c(cfg, compute_dt, DT_F32);
+  c.load_weights(dry, none, nullptr);
+  return dry.peak;
+}
+void ClipText::load_weights(DeviceArena& arena, WeightSource& src, hipStream_t st) {
   const std::vector<ParamSpec> specs = clip_param_specs(cfg_);
-  warena_.reserve(WeightBuilder::arena_bound(specs, cdt_));
-  WeightBuilder wb(specs, src, warena_, cdt_, st);
+  WeightBuilder wb(specs, src, arena, cdt_, st);
+  blocks_.clear();
   const int C = cfg_.n_state;
   // embedding tables in the compute dtype, row-major as the reference stores them
-  void* tok = warena_.alloc((size_t)cfg_.n_vocab * C * dt_size(cdt_));
-  void* pos = warena_.alloc((size_t)cfg_.n_ctx * C * dt_size(cdt_));
+  void* tok = arena.alloc((size_t)cfg_.n_vocab * C * dt_size(cdt_));
+  void* pos = arena.alloc((size_t)cfg_.n_ctx * C * dt_size(cdt_));
   if (!src.empty()) {
     launch_copy_rows(wb.fetch("token_embedding.weight"), DT_F32, C, tok, cdt_, C, cfg_.n_vocab, C, st);
     launch_copy_rows(wb.fetch("position_embedding"), DT_F32, C, pos, cdt_, C, cfg_.n_ctx, C, st);
@@ -43,12 +56,11 @@ ClipText::ClipText(const ClipCfg& cfg, int compute_dt, int stream_dt, WeightSour
     const ParamSpec& sp = wb.spec("text_projection");
     Lin l; l.K = sp.shape[0]; l.N = sp.shape[1]; l.ksize = 1; l.cin = l.K;
     l.Kpad = (int)round_up(l.K, cdt_ == DT_F16 ? 64 : 32); l.Npad = (int)round_up(l.N, 128);
-    void* w = warena_.alloc((size_t)l.Npad * l.Kpad * dt_size(cdt_));
+    void* w = arena.alloc((size_t)l.Npad * l.Kpad * dt_size(cdt_));
     l.w = w; l.b = nullptr;
     if (!src.empty()) launch_pack_linear(wb.fetch("text_projection"), w, cdt_, l.K, l.N, l.Kpad, l.Npad, 0, 0, st);
     proj_ = l;
   }
-  SDXL_HIP(hipStreamSynchronize(st));
 }
 
 void ClipText::block(Exec& ex, const ClipBlockW& w, const Act& x, int B, int S, const Act& ln, const Act& qk, void* vt, int npad,

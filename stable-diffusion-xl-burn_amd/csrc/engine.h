@@ -92,7 +92,7 @@ struct NullSource : WeightSource {   // replica ranks: same arena layout, conten
   void fetch(const ParamSpec&, size_t, float*, hipStream_t) override {}
   bool empty() const override { return true; }
 };
-constexpr float kHiLoScale = 256.0f;    // lo halves of WeightBuilder::linear_hilo travel times 2^8 (out of the f16 subnormals), the A operand's second copy times 2^-8
+constexpr float kHiLoScale = 256.0f;    // lo halves of the LF_F16_WHILO packing travel times 2^8 (out of the f16 subnormals), the A operand's second copy times 2^-8
 constexpr uint64_t kSeedF16Weights = 1ull << 63;   // seed flag (C ABI: SDXL_SEED_F16_WEIGHTS): synthetic parameters rounded to f16
 struct SyntheticSource : WeightSource {
   uint64_t seed;
@@ -144,12 +144,12 @@ struct Lin {        // packed dense weight: [Npad][Kpad] compute dtype + fp32 bi
   const void* w = nullptr; const float* b = nullptr;
   const void* wf = nullptr;        // f16 linear layers / 1x1 convs with N % 128 == 0: the same weights in MFMA fragment order (igemm_wreg.hip)
   int N = 0, K = 0, Kpad = 0, Npad = 0, ksize = 1, cin = 0;
-  // LayerNorm folded in (linear_ln / fused_linear_ln): w = diag(gamma) W, b = beta W + bias, cs = column sums of the
-  // packed rows; the GEMM then takes the RAW rows plus their per-64-column (mean, M2) statistics -- see IgemmParams::ln_stat
+  // a LayerNorm in front (LnMode): cs = column sums of the packed rows (LN_FOLD) or gamma W over them (LN_SHADOW), b = beta W + bias; the GEMM
+  // then takes the RAW rows plus their per-64-column (mean, M2) statistics -- see IgemmParams::ln_stat
   const float* cs = nullptr;
   const float* ln_eps = nullptr;   // device scalar: eps of the folded LayerNorm
   int ln_k = 0;                    // folded LayerNorm over ln_k columns (0: K) -- the (hi | lo) shadow form packs K = 2 ln_k
-  int k_form = 0;                  // 0 plain; 1: K doubled as two HALVES, weight (hi | lo s) or (w | w / s) against [a | a / s] or [a_hi | a_lo s] (linear_hilo); 2: K doubled in the HL16
+  int k_form = 0;                  // 0 plain; 1: K doubled as two HALVES, weight (hi | lo s) or (w | w / s) against [a | a / s] or [a_hi | a_lo s] (LF_F16_WHILO / _AHILO); 2: K doubled in the HL16
                                    // interleave, the weight twice per 16-channel group: the A operand is an un-scaled HL16 tensor read as f16 (MIX_LINEAR_F16X2)
   int dt = -1;                     // dtype the weight was packed in when it differs from the model's compute dtype (-1: the model's):
                                    // a DT_HL model packs the layers its pipeline cannot take (Cin % 32 != 0) as fp32
@@ -163,6 +163,37 @@ struct Lin {        // packed dense weight: [Npad][Kpad] compute dtype + fp32 bi
 // host-side copy, and a checkpoint's per-norm eps (groupnorm/load.rs:19, layernorm/load.rs:17) travels with the weights
 struct NormW { const float* gamma = nullptr; const float* beta = nullptr; const float* eps = nullptr; int C = 0; };
 
+// Form of a transformer projection on a split-operand model (StPlan): what it packs and which operand it reads
+enum LinForm {
+  LF_NATIVE,      // split-operand (HL16) weights, fp32-class (fp32 where K % 32 != 0)
+  LF_F16,         // plain f16 weights x f16 operand
+  LF_F16_WHILO,   // (hi | lo 2^8) weight halves along a doubled K against [a | a 2^-8] (MIX_GEGLU_HILO; k_form 1)
+  LF_F16_AHILO,   // (w | w 2^-8) against (hi | lo 2^8) activation halves (MIX_GEGLU_AHILO; k_form 1)
+  LF_X2           // the weight twice in the HL16 interleave against an HL16 operand read as f16 (MIX_LINEAR_F16X2; k_form 2)
+};
+inline bool packs_f16_values(LinForm f) { return f == LF_F16 || f == LF_F16_AHILO || f == LF_X2; }   // the packed weights are the parameter rounded to f16
+// How a preceding LayerNorm(gamma, beta) enters a projection:  LN(x) W + b = rstd (x - mu) (diag(gamma) W) + (beta W + b)
+//   = rstd * (x W') - rstd * mu * colsum(W') + b'   -- the GEMM takes the RAW rows plus their row statistics (IgemmParams::ln_stat)
+enum LnMode {
+  LN_NONE,        // not at all: the projection reads the output of a LayerNorm launch (or no LayerNorm)
+  LN_FOLD,        // folded into the weight (the f16 engine): W' = diag(gamma) W packed (rounded to the compute dtype) FIRST, cs = column sums over the
+                  // rounded values -- the identity holds exactly for what the MFMA multiplies --, b = beta W + bias
+  LN_SHADOW       // shadow form (split-operand models, MIX_LN_SHADOW): the weight stays UN-folded in f16 (an f16-valued parameter stays exact), gamma rides on
+                  // the A operand -- the shadow f16(x o gamma) the producer of the fp32 stream leaves (IgemmParams::shadow) --, cs = gamma W over the packed
+                  // values, b = beta W + bias; a plain twin shares the packed matrix and has the canonical bias (the LayerNorm-launch path)
+};
+// One [K,N] projection, or several fused along N, as WeightBuilder::pack takes it
+struct Proj {
+  std::vector<std::string> names;       // name.weight [K,N] (+ name.bias); several: concatenated along N (same K), ONE DT_HL scale for the matrix
+  bool geglu = false;                   // columns interleaved (16 x | 16 gate) for the GEGLU epilogue; a single projection
+  int dt = -1;                          // packed dtype whatever the model's (the GEMV weights of a split-operand model stay fp32); -1: the model's
+  LinForm form = LF_NATIVE;             // LF_NATIVE: plain, in the model's dtype or `dt`; LF_F16: plain f16; the doubled-K forms are f16 and need K % 32 == 0
+  LnMode ln = LN_NONE; std::string norm;      // the LayerNorm in front (its parameter prefix)
+  bool wfrag_folded = false;            // LN_FOLD: also the fragment-order image (the attn2 query projection: the weights-in-registers kernel applies the
+                                        // folded affine in its fused cross-attention form alone)
+  Lin* shadow = nullptr;                // LN_SHADOW: receives the shadow form (.cs set); pack() returns its plain twin
+};
+
 // dt_override of the M <= 8 GEMV weights (time / label MLPs, the hoisted lin_embed) for a model of compute dtype cdt: a split-operand model packs them
 // fp32 (gemv_kernel reads f16 or fp32 rows, not HL16), every other model in its own dtype (-1).  One rule for UNet's constructor and sdxl_gemv.
 inline int gemv_weight_dt(int cdt) { return cdt == DT_HL ? DT_F32 : -1; }
@@ -174,43 +205,42 @@ struct WeightBuilder {
   DeviceArena& arena;
   int dt;
   hipStream_t st;
-  float* tmp = nullptr; size_t tmp_numel = 0;
+  float* tmp = nullptr; size_t tmp_numel = 0;      // staging buffer of fetch(), allocated on the first one (a layout pass makes no device call)
   std::string last_fetched;      // name of the tensor `tmp` holds (fetch() of the same name again is free)
   WeightBuilder(const std::vector<ParamSpec>& sp, WeightSource& s, DeviceArena& a, int dtype, hipStream_t stream);
   ~WeightBuilder();
-  // wfrag: the model keeps fragment-order images of its plain f16 linear / 1x1 weights (attach_wfrag) -- only the UNet's layers can be
+  // wfrag: the model keeps fragment-order images of its plain f16 linear / 1x1 weights (alloc_wfrag) -- only the UNet's layers can be
   // routed to the weights-in-registers kernel, so the CLIP towers and the VAE leave it off (half the arena / broadcast bytes for those layers)
   bool wfrag = true;
-  static size_t arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag = true, bool fold_up = false);   // fold_up: the model builds its upsample convolutions with conv(name, true)
   const ParamSpec& spec(const std::string& name, size_t* idx = nullptr) const;
   bool has(const std::string& name) const { return index.count(name) != 0; }
   const float* fetch(const std::string& name);            // canonical fp32 tensor in tmp
-  // dt_override >= 0: pack in that dtype whatever the model's (the GEMV weights of a split-operand model stay fp32)
-  Lin linear(const std::string& name, bool geglu = false, int dt_override = -1);   // name.weight [K,N] (+ name.bias)
-  Lin fused_linear(const std::vector<std::string>& names, int dt_override = -1);   // concatenated along N (same K)
-  Lin linear_hilo(const std::string& name, bool geglu, bool dup = false, bool hl_interleave = false);   // hl_interleave: the weight twice in the HL16 interleave (launch_pack_linear_hilo mode 2; + fragment-order image)
-  //     // dup: (w | w / kHiLoScale) for an A operand of (hi | lo * kHiLoScale) ACTIVATION halves
-      // f16 GEMM on (hi | lo * kHiLoScale) weight halves along a doubled K: un-rounded weights (MIX_GEGLU_HILO)
-  float hl_scale(Lin& l, const std::vector<std::string>& weight_names);     // DT_HL packing: power-of-two factor, inverse into the arena
-  float hl_scale_of(const float* dev, size_t n, const float*& acc_scale);   // the same for one device tensor that is not a parameter (folded weights)
-  // the same with the preceding LayerNorm(gamma, beta) folded into weight / bias / column sums
-  // xattn_query: the attn2 query projection -- also packed in fragment order, for the weights-in-registers form of the fused cross-attention
-  Lin linear_ln(const std::string& name, bool geglu, const std::string& norm, bool xattn_query = false);
-  Lin fused_linear_ln(const std::vector<std::string>& names, const std::string& norm);
-  // dt_override / shadow / plain: the SHADOW form (round 6, split-operand models): the weights are packed UN-folded in dt_override (f16) -- gamma rides on
-  // the A operand, an f16 shadow  f16(x o gamma)  the producer of the fp32 stream leaves (IgemmParams::shadow) -- with cs = gamma W over the packed values
-  // and b = beta W + bias; *plain receives the same packed matrix with the canonical bias (for the LayerNorm-launch path where no shadow exists)
-  Lin fold_ln(const std::vector<std::string>& names, const std::string& norm, bool geglu, int dt_override = -1, bool shadow = false, Lin* plain = nullptr, bool hilo_dup = false,
-              bool hl_interleave = false);   // hl_interleave: the weights twice in the HL16 interleave (K = 2 x, k_form 2) for an HL16 shadow (shadow form only; any number of fused names)   // hilo_dup: (w | w / kHiLoScale) along a doubled K for a (hi | lo) shadow
+  // Every routine below has two phases in one body.  LAYOUT runs always: every arena.alloc of the layer, in one fixed order.  FILL is skipped as a
+  // whole when src.empty().  So an empty source lays out the identical arena -- replica ranks receive rank 0's by broadcast -- and over a dry
+  // arena it is the pass that sizes the reservation (UNet / Vae / ClipText run their loader twice).
+  // pack: the one routine for projections.  Allocation order (run_conv's weight warming extends a launch's cold region over these neighbours):
+  //   packed weights [Npad][Kpad], bias [Npad], [DT_HL: scale + exactness flag], [LN_FOLD / LN_SHADOW: column sums [Npad], eps],
+  //   [LN_SHADOW: the plain twin's bias [Npad]], [fragment-order image]
+  // Fragment image: never for a fused matrix, a GEGLU projection or a shadow pair; a doubled-K form only LF_X2; a folded weight only with
+  // wfrag_folded; and then only where alloc_wfrag's shape rule holds.  DT_HL falls back to fp32 where K % 32 != 0; k-tiles of 64 (f16) / 32.
+  Lin pack(const Proj& p);
+  Lin linear(const std::string& name, bool geglu = false, int dt_override = -1) { Proj p; p.names = {name}; p.geglu = geglu; p.dt = dt_override; return pack(p); }
+  Lin fused_linear(const std::vector<std::string>& names, int dt_override = -1) { Proj p; p.names = names; p.dt = dt_override; return pack(p); }
   // AND of "every value of these tensors is exactly one f16" (device flag read back): what SDXL_DTYPE_F32_SPLIT_MIX_F16W asks of the classes it moves to f16
   bool all_f16_exact(const std::vector<std::string>& names);
-  float* tmp2 = nullptr; size_t tmp2_numel = 0;   // scratch for folded biases (device)
-  // fold_up: a 3x3 conv that runs behind a nearest-2x upsample also gets its folded phase matrices (Lin::w_fold) -- f16 and split-operand packings
-  // with whole k-tiles per tap; folded from the fetched tensor, i.e. after any adapter merge; allocated on empty replicas too (identical arena layout)
-  Lin conv(const std::string& name, bool fold_up = false);                  // name.weight [Cout,Cin,k,k] + bias
-  static bool folds_upsample(const ParamSpec& p, int dt);                   // the rule of fold_up for an upsample.conv / upsampler parameter (arena_bound)
-  void attach_wfrag(Lin& l, bool fill, bool folded = false);    // second image of a plain f16 linear / 1x1 weight in fragment order (arena; no-op for other layers)
-  NormW norm(const std::string& name);
+  float* tmp2 = nullptr; size_t tmp2_numel = 0;   // scratch for folded biases / folded upsample weights (device)
+  // name.weight [Cout,Cin,k,k] + bias.  fold_up: a 3x3 conv that runs behind a nearest-2x upsample also gets its folded phase matrices (Lin::w_fold) where
+  // folds_upsample holds; folded from the fetched tensor, i.e. after any adapter merge.
+  // Allocation order: packed weights, bias, [DT_HL: scale], [phase matrices], [DT_HL: their scale], [fragment-order image (1x1)]
+  Lin conv(const std::string& name, bool fold_up = false);
+  static bool folds_upsample(const ParamSpec& p, int dt);     // f16 and split-operand packings of a 3x3 kernel with whole k-tiles per tap
+  NormW norm(const std::string& name);                       // gamma [C], beta [C], eps
+ private:
+  float* need_tmp2(size_t numel);
+  // DT_HL packing: two arena floats -- [0] 1 / (power-of-two factor of the packed weights), [1] "every weight is one f16" --, filled by hl_scale (-> the factor)
+  // over every tensor `each` visits
+  template <typename Each> float hl_scale(float* sc, Each each);
+  bool alloc_wfrag(Lin& l, bool folded = false);    // layout of the second image of a plain f16 linear / 1x1 weight in fragment order (no-op for other layers)
 };
 
 // activation view: rows of `ld` elements
@@ -342,15 +372,6 @@ void run_layernorm(Exec& ex, const NormW& n, const Act& x, int rows, const Act& 
 struct ResBlockW { NormW norm_in, norm_out; Lin conv_in, conv_out, skip; bool has_skip = false; int emb_off = 0, cin = 0, cout = 0; };
 struct TBlockW { NormW n1, n2, n3; Lin qkv, out1, q2, kv2, out2, geglu, ff;
                  Lin qkv_sh, q2_sh, geglu_sh; };   // *_sh: shadow forms (MIX_LN_SHADOW; .cs set) sharing the packed matrix of their plain twin
-// Form of a transformer projection on a split-operand model (StPlan): what it packs and which operand it reads
-enum LinForm {
-  LF_NATIVE,      // split-operand (HL16) weights, fp32-class (fp32 where K % 32 != 0)
-  LF_F16,         // plain f16 weights x f16 operand
-  LF_F16_WHILO,   // (hi | lo 2^8) weight halves along a doubled K against [a | a 2^-8] (MIX_GEGLU_HILO; k_form 1)
-  LF_F16_AHILO,   // (w | w 2^-8) against (hi | lo 2^8) activation halves (MIX_GEGLU_AHILO; k_form 1)
-  LF_X2           // the weight twice in the HL16 interleave against an HL16 operand read as f16 (MIX_LINEAR_F16X2; k_form 2)
-};
-inline bool packs_f16_values(LinForm f) { return f == LF_F16 || f == LF_F16_AHILO || f == LF_X2; }   // the packed weights are the parameter rounded to f16
 enum XattnForm { XA_LAUNCH, XA_F16, XA_SPLIT };   // cross-attention: its own launch / in the query projection's epilogue on f16 (the f16 engines'
                                                   // fused launch; MIX_XATTN_F16) / there at split precision (MIX_XATTN_SPLIT)
 // how one spatial transformer runs (UNet plan_transformer): the only reading of the MixClass bits besides the fallback and mix_classes()
@@ -362,9 +383,7 @@ struct StPlan {
 };
 struct STW { NormW norm; Lin proj_in, proj_out; std::vector<TBlockW> blocks; int C = 0, heads = 0; StPlan plan; };
 // The LayerNorm-fed projections of a transformer block, shared by UNet::spatial_transformer and the op entry that runs one of them
-// (sdxl_transformer_projection), so that both go through the same packing, operands and shadow hand-off.
-// projection `names` packed in form f; with `sh` also its shadow twin (behind LayerNorm `norm`), which shares the packed matrix
-Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh = nullptr, const std::string& norm = "");
+// (sdxl_transformer_projection), so that both go through the same packing (WeightBuilder::pack), operands and shadow hand-off.
 inline bool reads_f16(LinForm f) { return f == LF_F16 || f == LF_F16_WHILO || f == LF_F16_AHILO; }   // the projection reads f16 activations
 // X2: an un-scaled HL16 operand of C logical channels handed to an f16 GEMM whose weight is packed twice in the HL16 interleave (K = 2 C)
 inline Act x2_operand(LinForm f, const Act& a) { return f == LF_X2 ? Act(a.p, 2 * a.ld, DT_F16) : a; }
@@ -430,9 +449,17 @@ class UNet {
   float eager_ms(int B, int H, int W, hipStream_t s);     // the chain profile() runs, without the per-launch events (best of three)
   size_t weight_bytes() const { return warena_.off; }
   void* weight_base() const { return warena_.base; }
+  // weight_bytes() of a model with these MixClass bits in force, from the layout pass alone (no device call, no source)
+  static size_t weight_layout_bytes(const UNetCfg& cfg, int compute_dt, int stream_dt, int mix);
 
  private:
+  UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, int mix);      // everything but the weights
+  // build_weights: plans (+ the f16-exactness guard on the source), then load_weights twice -- over a dry arena and an empty source to size the
+  // reservation (layout_weights), then for real
   void build_weights(WeightSource& src, hipStream_t st);
+  std::vector<StPlan> plan_transformers(const std::vector<ParamSpec>& specs, std::vector<std::string>* f16_names) const;
+  size_t layout_weights(const std::vector<ParamSpec>& specs, const std::vector<StPlan>& plans);
+  void load_weights(WeightBuilder& wb, const std::vector<StPlan>& plans);
   void ensure_plan(int B, int H, int W);
   void run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb);
   const float* res_block(Exec& ex, const ResBlockW& w, const Act& x, int B, int H, int W, const Act& out, float* out_gn_part = nullptr);
@@ -513,8 +540,12 @@ class Vae {
   void image_to_latent(const unsigned char* img_hwc, int n, int H, int W, float* latent_out, hipStream_t s);
   size_t weight_bytes() const { return warena_.off; }
   void* weight_base() const { return warena_.base; }
+  static size_t weight_layout_bytes(const VaeCfg& cfg, int compute_dt, bool decoder, bool encoder);      // weight_bytes() from the layout pass alone (no device call)
 
  private:
+  Vae(const VaeCfg& cfg, int compute_dt) : cfg_(cfg), cdt_(compute_dt) {}
+  // the loader: decoder and / or encoder (null: left out) into `arena`; run over a dry arena and empty sources first to size the reservation
+  void load_weights(DeviceArena& arena, WeightSource* dec_src, WeightSource* enc_src, hipStream_t st);
   void res_block(Exec& ex, const VaeResW& w, const Act& x, int B, int H, int W, const Act& out);
   void mid(Exec& ex, const VaeMidW& w, const Act& x, int B, int H, int W);
   void run_decode(Exec& ex, const Act& in, int n, int h, int w, const Act& out);
@@ -563,8 +594,11 @@ class ClipText {
   void forward_hidden_pooled(const int* ids, int B, int S, int hidden_idx, float* hidden, float* pooled, hipStream_t s);
   size_t weight_bytes() const { return warena_.off; }
   void* weight_base() const { return warena_.base; }
+  static size_t weight_layout_bytes(const ClipCfg& cfg, int compute_dt);      // weight_bytes() from the layout pass alone (no device call)
 
  private:
+  ClipText(const ClipCfg& cfg, int compute_dt, int stream_dt);
+  void load_weights(DeviceArena& arena, WeightSource& src, hipStream_t st);      // run over a dry arena and an empty source first to size the reservation
   void run(const int* ids, int B, int S, int n_blocks, int tap, float* hidden, float* pooled, hipStream_t s);
   void block(Exec& ex, const ClipBlockW& w, const Act& x, int B, int S, const Act& ln, const Act& qk, void* vt, int npad,
              const Act& ao, const Act& h);

@@ -84,19 +84,6 @@ void f16_valued_weights(const StPlan& s, const std::string& q, std::vector<std::
   for (const std::string& n : kQkv) add(s.qkv, n.c_str());
   add(s.out1, kOut1); add(s.q2, kQ2); add(s.out2, kOut2); add(s.geglu, kGeglu); add(s.ff, kFf);
 }
-}  // namespace
-Lin pack_proj(WeightBuilder& wb, LinForm f, const std::vector<std::string>& names, bool geglu, Lin* sh, const std::string& norm) {
-  Lin l;
-  if (sh) { *sh = wb.fold_ln(names, norm, geglu, DT_F16, true, &l, f == LF_F16_AHILO, f == LF_X2); return l; }
-  switch (f) {
-    case LF_F16: return names.size() > 1 ? wb.fused_linear(names, DT_F16) : wb.linear(names[0], geglu, DT_F16);
-    case LF_F16_WHILO: return wb.linear_hilo(names[0], geglu);
-    case LF_F16_AHILO: return wb.linear_hilo(names[0], geglu, true);
-    case LF_X2: return wb.linear_hilo(names[0], geglu, false, true);
-    default: return names.size() > 1 ? wb.fused_linear(names) : wb.linear(names[0], geglu);
-  }
-}
-namespace {
 STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth, bool fuse_ln, const StPlan& plan) {
   STW s;
   s.C = C; s.heads = heads; s.plan = plan;
@@ -106,29 +93,24 @@ STW load_st(WeightBuilder& wb, const std::string& p, int C, int heads, int depth
     const std::string q = p + ".blocks." + std::to_string(j);
     const std::vector<std::string> qkv = {q + kQkv[0], q + kQkv[1], q + kQkv[2]};
     TBlockW t;
-    if (fuse_ln) {
-      // the three LayerNorms of TransformerBlock::forward (unet/mod.rs:885-891) are folded into the projections that
-      // consume them; their row statistics come out of the epilogue of the GEMM that produced the residual stream
-      t.qkv = wb.fused_linear_ln(qkv, q + ".norm1");
-      t.out1 = wb.linear(q + kOut1);
-      t.q2 = wb.linear_ln(q + kQ2, false, q + ".norm2", true);
-      t.kv2 = wb.fused_linear({q + ".attn2.key", q + ".attn2.value"});
-      t.out2 = wb.linear(q + kOut2);
-      t.geglu = wb.linear_ln(q + kGeglu, true, q + ".norm3");
-      t.ff = wb.linear(q + kFf);
-      s.blocks.push_back(t);
-      continue;
-    }
-    t.n1 = wb.norm(q + ".norm1");
-    t.qkv = pack_proj(wb, plan.qkv, qkv, false, plan.qkv_sh ? &t.qkv_sh : nullptr, q + ".norm1");
-    t.out1 = pack_proj(wb, plan.out1, {q + kOut1}, false);
-    t.n2 = wb.norm(q + ".norm2");
-    t.q2 = pack_proj(wb, plan.q2, {q + kQ2}, false, plan.q2_sh ? &t.q2_sh : nullptr, q + ".norm2");
+    // a projection in its planned form; behind LayerNorm `norm`: folded (f16 engine), or with its shadow twin `sh` where the plan has one
+    auto proj = [&](LinForm f, const std::vector<std::string>& names, bool geglu = false, const char* norm = nullptr, Lin* sh = nullptr, bool xattn_query = false) {
+      Proj d; d.names = names; d.geglu = geglu; d.form = f;
+      if (norm && (fuse_ln || sh)) { d.ln = fuse_ln ? LN_FOLD : LN_SHADOW; d.norm = q + norm; d.shadow = sh; d.wfrag_folded = xattn_query; }
+      return wb.pack(d);
+    };
+    // f16 engine: the three LayerNorms of TransformerBlock::forward (unet/mod.rs:885-891) are folded into the projections that
+    // consume them; their row statistics come out of the epilogue of the GEMM that produced the residual stream
+    if (!fuse_ln) t.n1 = wb.norm(q + ".norm1");
+    t.qkv = proj(plan.qkv, qkv, false, ".norm1", plan.qkv_sh ? &t.qkv_sh : nullptr);
+    t.out1 = proj(plan.out1, {q + kOut1});
+    if (!fuse_ln) t.n2 = wb.norm(q + ".norm2");
+    t.q2 = proj(plan.q2, {q + kQ2}, false, ".norm2", plan.q2_sh ? &t.q2_sh : nullptr, true);
     t.kv2 = wb.fused_linear({q + ".attn2.key", q + ".attn2.value"});
-    t.out2 = pack_proj(wb, plan.out2, {q + kOut2}, false);
-    t.n3 = wb.norm(q + ".norm3");
-    t.geglu = pack_proj(wb, plan.geglu, {q + kGeglu}, true, plan.geglu_sh ? &t.geglu_sh : nullptr, q + ".norm3");
-    t.ff = pack_proj(wb, plan.ff, {q + kFf}, false);
+    t.out2 = proj(plan.out2, {q + kOut2});
+    if (!fuse_ln) t.n3 = wb.norm(q + ".norm3");
+    t.geglu = proj(plan.geglu, {q + kGeglu}, true, ".norm3", plan.geglu_sh ? &t.geglu_sh : nullptr);
+    t.ff = proj(plan.ff, {q + kFf});
     s.blocks.push_back(t);
   }
   s.proj_out = wb.linear(p + ".proj_out");
@@ -260,14 +242,21 @@ void UNet::apply_demote_weights(hipStream_t s) {
   SDXL_HIP(hipStreamSynchronize(s));     // (vals is host memory of this frame)
 }
 
-UNet::UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st, int mix)
-    : cfg_(cfg), cdt_(compute_dt), sdt_(stream_dt), mix_(compute_dt == DT_HL ? (mix && g_mix_classes.load() >= 0 ? g_mix_classes.load() : mix) : 0),
-      mix_knob_(compute_dt == DT_HL && mix && g_mix_classes.load() >= 0) {
+UNet::UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, int mix) : cfg_(cfg), cdt_(compute_dt), sdt_(stream_dt), mix_(compute_dt == DT_HL ? mix : 0) {
   SDXL_REQUIRE(cfg.n_head_channels == 64, "this engine's fused attention kernel is specialised for 64 channels per head");
   SDXL_REQUIRE(!((compute_dt == DT_F32 || compute_dt == DT_HL) && stream_dt != DT_F32), "f32 / split-operand compute implies an f32 residual stream");
   SDXL_REQUIRE(cfg.model_channels % 32 == 0, "GroupNorm(32) needs model_channels % 32 == 0");
   fuse_ln_ = compute_dt == DT_F16 && stream_dt == DT_F16;
+}
+UNet::UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st, int mix)
+    : UNet(cfg, compute_dt, stream_dt, mix && g_mix_classes.load() >= 0 ? g_mix_classes.load() : mix) {
+  mix_knob_ = compute_dt == DT_HL && mix && g_mix_classes.load() >= 0;
   build_weights(src, st);
+}
+size_t UNet::weight_layout_bytes(const UNetCfg& cfg, int compute_dt, int stream_dt, int mix) {
+  UNet u(cfg, compute_dt, stream_dt, mix);
+  const std::vector<ParamSpec> specs = unet_param_specs(cfg);
+  return u.layout_weights(specs, u.plan_transformers(specs, nullptr));
 }
 UNet::~UNet() {
   if (graph_) (void)hipGraphExecDestroy(graph_);
@@ -276,26 +265,35 @@ UNet::~UNet() {
   if (s2_) (void)hipStreamDestroy(s2_);
 }
 
-void UNet::build_weights(WeightSource& src, hipStream_t st) {
-  const std::vector<ParamSpec> specs = unet_param_specs(cfg_);
+// the plans of the spatial transformers in build order (input blocks, middle block, output blocks) for the classes in force; f16_names: + the weights
+// those plans pack as f16 values
+std::vector<StPlan> UNet::plan_transformers(const std::vector<ParamSpec>& specs, std::vector<std::string>* f16_names) const {
   std::vector<BlockDesc> inp, out; BlockDesc mid;
   unet_block_plan(cfg_, inp, mid, out);
-  // the spatial transformers in build order (parameter prefix, depth) and their plans
-  std::vector<std::pair<std::string, int>> sts;
-  auto has_st = [](const BlockDesc& d) { return d.kind == BK_REST || d.kind == BK_RESTU; };
-  for (size_t i = 0; i < inp.size(); ++i) if (has_st(inp[i])) sts.push_back({"input_blocks." + std::to_string(i) + ".transformer", inp[i].depth});
-  sts.push_back({"middle_block.transformer", mid.depth});
-  for (size_t i = 0; i < out.size(); ++i) if (has_st(out[i])) sts.push_back({"output_blocks." + std::to_string(i) + ".transformer", out[i].depth});
   std::vector<StPlan> plans;
-  std::vector<std::string> f16_names;      // weights the plans pack as f16 values
-  auto plan_all = [&]() {
-    plans.clear(); f16_names.clear();
-    for (const auto& t : sts) {
-      plans.push_back(plan_transformer(mix_, cdt_, specs, t.first));
-      for (int j = 0; j < t.second; ++j) f16_valued_weights(plans.back(), t.first + ".blocks." + std::to_string(j), f16_names);
-    }
+  auto add = [&](const std::string& p, const BlockDesc& d, bool has_st) {
+    if (!has_st) return;
+    plans.push_back(plan_transformer(mix_, cdt_, specs, p + ".transformer"));
+    for (int j = 0; f16_names && j < d.depth; ++j) f16_valued_weights(plans.back(), p + ".transformer.blocks." + std::to_string(j), *f16_names);
   };
-  plan_all();
+  auto has_st = [](const BlockDesc& d) { return d.kind == BK_REST || d.kind == BK_RESTU; };
+  for (size_t i = 0; i < inp.size(); ++i) add("input_blocks." + std::to_string(i), inp[i], has_st(inp[i]));
+  add("middle_block", mid, true);
+  for (size_t i = 0; i < out.size(); ++i) add("output_blocks." + std::to_string(i), out[i], has_st(out[i]));
+  return plans;
+}
+// the arena bytes load_weights allocates: the loader over a dry arena and an empty source (no device call)
+size_t UNet::layout_weights(const std::vector<ParamSpec>& specs, const std::vector<StPlan>& plans) {
+  DeviceArena dry; dry.dry = true;
+  NullSource none;
+  WeightBuilder wb(specs, none, dry, cdt_, nullptr);
+  load_weights(wb, plans);
+  return dry.peak;
+}
+void UNet::build_weights(WeightSource& src, hipStream_t st) {
+  const std::vector<ParamSpec> specs = unet_param_specs(cfg_);
+  std::vector<std::string> f16_names;
+  std::vector<StPlan> plans = plan_transformers(specs, &f16_names);
   WeightBuilder wb(specs, src, warena_, cdt_, st);
   // A form that packs a parameter's values as f16 (StPlan) must get f16 values (the reference's records are, src/bin/sample/main.rs:37): on other
   // parameters it would round the weights as well and leave the mode's error bound (0.029 against 0.0212).  Checked here on exactly those
@@ -305,19 +303,21 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
   // source (they receive rank 0's arena: the caller compares rank 0's mix_classes() with the mode before the broadcast, bench.py does).
   if (!mix_knob_ && !wb.all_f16_exact(f16_names)) {
     mix_ = (mix_ & (MIX_ATTN_F16 | MIX_GEGLU_F16)) ? (MIX_ATTN_F16 | MIX_GEGLU_F16 | MIX_GEGLU_HILO) : 0;
-    plan_all();
+    f16_names.clear();
+    plans = plan_transformers(specs, &f16_names);
     SDXL_REQUIRE(f16_names.empty(), "the fallback classes pack no parameter as f16 values");
   }
-  bool x2 = false;
+  // the plans are final: size the arena by a layout pass of the loader, then run it for real
+  warena_.reserve(layout_weights(specs, plans));
+  load_weights(wb, plans);
+  SDXL_HIP(hipStreamSynchronize(st));
+}
+void UNet::load_weights(WeightBuilder& wb, const std::vector<StPlan>& plans) {
+  std::vector<BlockDesc> inp, out; BlockDesc mid;
+  unet_block_plan(cfg_, inp, mid, out);
+  inp_.clear(); out_.clear(); st_list_.clear();
   attn16_ = cdt_ == DT_F16;
-  for (const StPlan& pl : plans) {
-    x2 = x2 || pl.qkv == LF_X2 || pl.out1 == LF_X2 || pl.q2 == LF_X2 || pl.out2 == LF_X2 || pl.geglu == LF_X2 || pl.ff == LF_X2;
-    attn16_ = attn16_ || pl.attn_f16;
-  }
-  size_t bound = WeightBuilder::arena_bound(specs, cdt_, true, fuse_ln_);
-  if (x2)      // f16 x 2 K images carry a fragment-order twin the split-operand bound does not count
-    for (const ParamSpec& ps : specs) if (ps.kind == PK_LINEAR_W) bound += round_up(ps.shape[1], 128) * round_up((size_t)ps.shape[0], 64) * 4 + 256;
-  warena_.reserve(bound);
+  for (const StPlan& pl : plans) attn16_ = attn16_ || pl.attn_f16;
   const int gv = gemv_weight_dt(cdt_);     // the M <= 8 GEMV weights of a split-operand model are packed fp32
   lin1_t_ = wb.linear("lin1_time_embed", false, gv);
   lin2_t_ = wb.linear("lin2_time_embed", false, gv);
@@ -349,7 +349,6 @@ void UNet::build_weights(WeightSource& src, hipStream_t st) {
   conv_out_ = wb.conv("conv_out");
   embcat_ = wb.fused_linear(emb_names, gv);
   emb_total_ = emb_off;
-  SDXL_HIP(hipStreamSynchronize(st));
   // execution order of the spatial transformers (for the K/V caches)
   for (BlockW& b : inp_) if (!b.st.blocks.empty()) st_list_.push_back(&b.st);
   st_list_.push_back(&mid_res1_.st);

@@ -30,16 +30,24 @@ VaeMidW Vae::load_mid(WeightBuilder& wb, const std::string& p, int c) {
   return m;
 }
 
-Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource* enc_src, hipStream_t st)
-    : cfg_(cfg), cdt_(compute_dt) {
+Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource* enc_src, hipStream_t st) : Vae(cfg, compute_dt) {
+  warena_.reserve(weight_layout_bytes(cfg, compute_dt, dec_src != nullptr, enc_src != nullptr));
+  load_weights(warena_, dec_src, enc_src, st);
+  SDXL_HIP(hipStreamSynchronize(st));
+}
+size_t Vae::weight_layout_bytes(const VaeCfg& cfg, int compute_dt, bool decoder, bool encoder) {
+  DeviceArena dry; dry.dry = true;
+  NullSource none;
+  Vae v(cfg, compute_dt);
+  v.load_weights(dry, decoder ? &none : nullptr, encoder ? &none : nullptr, nullptr);
+  return dry.peak;
+}
+void Vae::load_weights(DeviceArena& arena, WeightSource* dec_src, WeightSource* enc_src, hipStream_t st) {
   const std::vector<ParamSpec> dspecs = vae_decoder_param_specs(cfg_), especs = vae_encoder_param_specs(cfg_);
-  size_t bound = 0;
+  d_blocks_.clear(); e_blocks_.clear();
   // (no fragment-order weight images: the VAE's 1x1 convs run on >= 4096 rows per entry, never on the weights-in-registers kernel)
-  if (dec_src) bound += WeightBuilder::arena_bound(dspecs, cdt_, false, cdt_ == DT_HL);
-  if (enc_src) bound += WeightBuilder::arena_bound(especs, cdt_, false);
-  warena_.reserve(bound + 4096);
   if (dec_src) {
-    WeightBuilder wb(dspecs, *dec_src, warena_, cdt_, st);
+    WeightBuilder wb(dspecs, *dec_src, arena, cdt_, st);
     wb.wfrag = false;
     post_quant_ = wb.conv("post_quant_conv");
     d_conv_in_ = wb.conv("decoder.conv_in");
@@ -56,11 +64,10 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
     }
     d_norm_out_ = wb.norm("decoder.norm_out");
     d_conv_out_ = wb.conv("decoder.conv_out");
-    SDXL_HIP(hipStreamSynchronize(st));
     has_dec_ = true;
   }
   if (enc_src) {
-    WeightBuilder wb(especs, *enc_src, warena_, cdt_, st);
+    WeightBuilder wb(especs, *enc_src, arena, cdt_, st);
     wb.wfrag = false;
     e_conv_in_ = wb.conv("encoder.conv_in");
     for (size_t i = 0; i < cfg_.enc.size(); ++i) {
@@ -76,7 +83,6 @@ Vae::Vae(const VaeCfg& cfg, int compute_dt, WeightSource* dec_src, WeightSource*
     e_norm_out_ = wb.norm("encoder.norm_out");
     e_conv_out_ = wb.conv("encoder.conv_out");
     quant_ = wb.conv("quant_conv");
-    SDXL_HIP(hipStreamSynchronize(st));
     has_enc_ = true;
   }
 }

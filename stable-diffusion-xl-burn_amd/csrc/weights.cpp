@@ -159,29 +159,9 @@ WeightBuilder::WeightBuilder(const std::vector<ParamSpec>& sp, WeightSource& s, 
     index[specs[i].name] = i;
     if (specs[i].numel() > tmp_numel) tmp_numel = specs[i].numel();
   }
-  SDXL_HIP(hipMalloc((void**)&tmp, tmp_numel * sizeof(float)));
 }
 WeightBuilder::~WeightBuilder() { if (tmp) (void)hipFree(tmp); if (tmp2) (void)hipFree(tmp2); }
 
-size_t WeightBuilder::arena_bound(const std::vector<ParamSpec>& specs, int dt, bool wfrag, bool fold_up) {
-  size_t total = 1 << 20;
-  for (const ParamSpec& p : specs) {
-    if (p.kind == PK_LINEAR_W) total += round_up(p.shape[1], 128) * round_up(p.shape[0], 64) * dt_size(dt) + 768;   // (+ the DT_HL scale scalar)
-    else if (p.kind == PK_CONV_W)
-      total += round_up(p.shape[0], 128) * round_up((size_t)p.shape[1] * p.shape[2] * p.shape[3], 64) * dt_size(dt) + 768;   // (+ the DT_HL scale scalar)
-    else total += round_up(p.numel(), 128) * sizeof(float) + 256;
-    if (p.kind == PK_LINEAR_W || p.kind == PK_CONV_W) total += round_up(p.kind == PK_LINEAR_W ? p.shape[1] : p.shape[0], 128) * 4 + 256;
-    if (p.kind == PK_LINEAR_W) total += round_up(p.shape[1], 128) * 4 + 256;   // column sums of LayerNorm-folded projections
-    // fragment-order image of the f16 linear / 1x1 weights (attach_wfrag)
-    if (wfrag && dt == DT_F16 && p.kind == PK_LINEAR_W) total += round_up(p.shape[1], 128) * round_up(p.shape[0], 64) * 2 + 256;
-    if (wfrag && dt == DT_F16 && p.kind == PK_CONV_W && p.shape[2] == 1) total += round_up(p.shape[0], 128) * round_up((size_t)p.shape[1], 64) * 2 + 256;
-    // folded phase matrices of the upsample convolutions (conv fold_up): 4 x [Npad][4 cin] (+ their DT_HL scale scalar)
-    auto ends_with = [&](const char* t) { const size_t n = std::strlen(t); return p.name.size() >= n && p.name.compare(p.name.size() - n, n, t) == 0; };
-    if (fold_up && (ends_with(".upsample.conv.weight") || ends_with(".upsampler.weight")) && folds_upsample(p, dt))
-      total += 4 * round_up(p.shape[0], 128) * 4 * (size_t)p.shape[1] * dt_size(dt) + 768;
-  }
-  return total;
-}
 const ParamSpec& WeightBuilder::spec(const std::string& name, size_t* idx) const {
   auto it = index.find(name);
   if (it == index.end()) throw Error("unknown parameter '" + name + "'");
@@ -192,22 +172,27 @@ const float* WeightBuilder::fetch(const std::string& name) {
   // (the split-operand packing asks for a weight three times in a row -- absmax, exactness flag, packer: the staging buffer still holds
   //  it, and a host-backed source would otherwise pay three H2D copies of up to 26 MB per layer)
   if (name == last_fetched) return tmp;
+  if (!tmp) SDXL_HIP(hipMalloc((void**)&tmp, tmp_numel * sizeof(float)));
   size_t i; const ParamSpec& s = spec(name, &i);
   src.fetch(s, i, tmp, st);
   last_fetched = name;
   return tmp;
 }
+float* WeightBuilder::need_tmp2(size_t numel) {
+  if (numel > tmp2_numel) {
+    if (tmp2) { SDXL_HIP(hipFree(tmp2)); tmp2 = nullptr; tmp2_numel = 0; }
+    SDXL_HIP(hipMalloc((void**)&tmp2, numel * sizeof(float)));
+    tmp2_numel = numel;
+  }
+  return tmp2;
+}
 // Split-operand packing (DT_HL): hi = f16(w * 2^e), lo = f16(w * 2^e - hi).  With 2^e * max|w| in [2^13, 2^14) both halves of every
 // weight down to 2^-11 of the largest stay f16-normal (22 significand bits); unscaled, |w| ~ 0.02 would push every lo into the
 // subnormals (~20 bits).  The factor is exact, a function of the tensor(s) only, and the GEMM epilogue undoes it with the device
-// scalar this returns through l.acc_scale (it lives in the arena, so replicas receive it with the weights).
+// scalar sc[0] (Lin::acc_scale; it lives in the arena, so replicas receive it with the weights).
 // (each(f): calls f(device tensor, numel) for every tensor of the matrix; called twice -- range, then exactness at the chosen factor)
 template <typename Each>
-static float hl_scale_over(WeightBuilder& wb, const float*& acc_scale, Each each) {
-  float* sc = (float*)wb.arena.alloc(2 * sizeof(float));     // [0] 1 / factor, [1] "every weight is one f16" (allocated on empty replicas too: identical arena layout)
-  acc_scale = sc;
-  if (wb.src.empty()) return 1.f;
-  hipStream_t st = wb.st;
+float WeightBuilder::hl_scale(float* sc, Each each) {
   SDXL_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(float), st));
   each([&](const float* t, size_t n) { launch_absmax(t, n, sc, st, true); });
   float h = 0.f;
@@ -225,118 +210,98 @@ static float hl_scale_over(WeightBuilder& wb, const float*& acc_scale, Each each
   each([&](const float* t, size_t n) { launch_f16_exact(t, n, wscale, sc + 1, st, !first); first = false; });
   return wscale;
 }
-float WeightBuilder::hl_scale(Lin& l, const std::vector<std::string>& weight_names) {
-  return hl_scale_over(*this, l.acc_scale, [&](auto f) { for (const std::string& n : weight_names) f(fetch(n), spec(n).numel()); });
-}
-float WeightBuilder::hl_scale_of(const float* dev, size_t n, const float*& acc_scale) {
-  return hl_scale_over(*this, acc_scale, [&](auto f) { f(dev, n); });
-}
 
 // Plain f16 linear layers / 1x1 convolutions whose width is a multiple of 128 keep a second image of the packed weights in MFMA
 // fragment order: the weights-in-registers GEMM (igemm_wreg.hip) streams it straight into VGPRs.  Same bytes, same arena (so a
-// replica receives it with the weight broadcast); allocated on empty replicas too (identical arena layout).
-// (folded: a LayerNorm-folded weight -- only the attn2 query projection asks for it: the weights-in-registers kernel applies the folded
-// affine in its fused cross-attention form alone, every other LayerNorm-fed linear stays on the pipe kernels.)
-void WeightBuilder::attach_wfrag(Lin& l, bool fill, bool folded) {
+// replica receives it with the weight broadcast).  The fill is launch_repack_wfrag(l.w, l.wf, ...) behind the packing.
+bool WeightBuilder::alloc_wfrag(Lin& l, bool folded) {
   const int wdt = l.dt >= 0 ? l.dt : dt;
-  if (!wfrag) return;
-  if (wdt != DT_F16 || l.ksize != 1 || l.N % 128 != 0 || l.K != l.Kpad || l.Kpad % 64 != 0 || l.Kpad < 128 || (l.cs && !folded) || l.acc_scale) return;
-  void* wf = arena.alloc((size_t)l.Npad * l.Kpad * 2);
-  l.wf = wf;
-  if (fill) launch_repack_wfrag(l.w, wf, l.Npad, l.Kpad, st);
+  if (!wfrag) return false;
+  if (wdt != DT_F16 || l.ksize != 1 || l.N % 128 != 0 || l.K != l.Kpad || l.Kpad % 64 != 0 || l.Kpad < 128 || (l.cs && !folded) || l.acc_scale) return false;
+  l.wf = arena.alloc((size_t)l.Npad * l.Kpad * 2);
+  return true;
 }
-Lin WeightBuilder::linear(const std::string& name, bool geglu, int dt_override) {
-  const ParamSpec& s = spec(name + ".weight");
-  Lin l; l.K = s.shape[0]; l.N = s.shape[1]; l.ksize = 1; l.cin = l.K;
-  // dt_override: the GEMV weights of a split-operand model stay fp32; K % 32 != 0 cannot go through the HL pipeline either
-  const int wdt = dt_override >= 0 ? dt_override : ((dt == DT_HL && l.K % 32 != 0) ? DT_F32 : dt);
-  if (wdt != dt) l.dt = wdt;
-  const int kt = wdt == DT_F16 ? 64 : 32;
-  l.Kpad = (int)round_up(l.K, kt); l.Npad = (int)round_up(l.N, 128);
-  void* w = arena.alloc((size_t)l.Npad * l.Kpad * dt_size(wdt));
-  float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  l.w = w; l.b = b;
-  const float wscale = wdt == DT_HL ? hl_scale(l, {name + ".weight"}) : 1.f;
-  if (src.empty()) { if (!geglu) attach_wfrag(l, false); return l; }
-  launch_pack_linear(fetch(name + ".weight"), w, wdt, l.K, l.N, l.Kpad, l.Npad, geglu ? 1 : 0, 0, st, nullptr, wscale);
-  const float* bsrc = has(name + ".bias") ? fetch(name + ".bias") : nullptr;
-  launch_pack_bias(bsrc, b, l.N, l.Npad, geglu ? 1 : 0, 0, st);
-  if (!geglu) attach_wfrag(l, true);
-  return l;
-}
-// f16 GEMM with UN-ROUNDED weights (round 6, SDXL_DTYPE_F32_SPLIT_MIX's GEGLU projection): every weight as (hi, lo) f16 values along a doubled K --
-// dst[n] = [f16(w) | f16((w - hi) * kHiLoScale)] -- against the A operand [a | a / kHiLoScale] (run_layernorm dup_scale): two MFMAs per product,
-// the activations rounded once, the weights not at all.  An f16 Lin of K = 2 K0.
-Lin WeightBuilder::linear_hilo(const std::string& name, bool geglu, bool dup, bool hl_interleave) {
-  const ParamSpec& s = spec(name + ".weight");
-  const int K0 = s.shape[0];
-  SDXL_REQUIRE(K0 % 32 == 0, "linear_hilo: K % 32 == 0");
-  Lin l; l.K = 2 * K0; l.N = s.shape[1]; l.ksize = 1; l.cin = l.K; l.dt = DT_F16; l.k_form = hl_interleave ? 2 : 1;
-  l.Kpad = l.K; l.Npad = (int)round_up(l.N, 128);
-  void* w = arena.alloc((size_t)l.Npad * l.Kpad * 2);
-  float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  l.w = w; l.b = b;
-  if (src.empty()) { if (hl_interleave && !geglu) attach_wfrag(l, false); return l; }
-  launch_pack_linear_hilo(fetch(name + ".weight"), w, K0, l.N, l.Npad, geglu ? 1 : 0, kHiLoScale, st, hl_interleave ? 2 : dup ? 1 : 0);
-  const float* bsrc = has(name + ".bias") ? fetch(name + ".bias") : nullptr;
-  launch_pack_bias(bsrc, b, l.N, l.Npad, geglu ? 1 : 0, 0, st);
-  if (hl_interleave && !geglu) attach_wfrag(l, true);
-  return l;
-}
-Lin WeightBuilder::fused_linear(const std::vector<std::string>& names, int dt_override) {
+Lin WeightBuilder::pack(const Proj& p) {
+  // ---- layout
+  const bool fused = p.names.size() > 1;
+  // doubled-K forms (round 6): 1 = two HALVES along K -- (hi | lo kHiLoScale) weight halves against [a | a / kHiLoScale] (WHILO: un-rounded weights, the
+  // activations rounded once), or (w | w / kHiLoScale) against (hi | lo kHiLoScale) activation halves (AHILO); 2 = the weight twice in the HL16 interleave (X2)
+  const int kf = (p.form == LF_F16_WHILO || p.form == LF_F16_AHILO) ? 1 : p.form == LF_X2 ? 2 : 0;
+  SDXL_REQUIRE(!p.names.empty() && (!p.geglu || !fused), "GEGLU packing applies to a single projection");
+  SDXL_REQUIRE((p.ln == LN_SHADOW) == (p.shadow != nullptr) && (p.ln == LN_NONE || !p.norm.empty()), "pack: a LayerNorm mode names its norm, the shadow form its twin");
+  SDXL_REQUIRE(p.ln != LN_SHADOW || p.form == LF_F16 || p.form == LF_F16_AHILO || p.form == LF_X2, "pack: the shadow form is an f16 projection (F16, AHILO, X2)");
+  SDXL_REQUIRE(p.ln != LN_FOLD || kf == 0, "pack: a doubled-K form takes its LayerNorm as a shadow");
+  SDXL_REQUIRE(kf != 1 || !fused, "pack: the (hi | lo) forms are single projections");
   Lin l; l.ksize = 1;
-  int ntot = 0;
-  for (const std::string& n : names) {
+  int K0 = 0;                               // columns of the parameter (and of the LayerNorm)
+  for (const std::string& n : p.names) {
     const ParamSpec& s = spec(n + ".weight");
-    if (l.K == 0) l.K = s.shape[0];
-    SDXL_REQUIRE(l.K == s.shape[0], "fused_linear: K mismatch");
-    ntot += s.shape[1];
+    if (K0 == 0) K0 = s.shape[0];
+    SDXL_REQUIRE(K0 == s.shape[0], "pack: K mismatch between fused projections");
+    l.N += s.shape[1];
   }
-  l.N = ntot; l.cin = l.K;
-  const int wdt = dt_override >= 0 ? dt_override : ((dt == DT_HL && l.K % 32 != 0) ? DT_F32 : dt);
+  SDXL_REQUIRE(kf == 0 || K0 % 32 == 0, "pack: a doubled-K form needs K % 32 == 0");
+  // K % 32 != 0 cannot go through the HL pipeline: fp32 on the generic kernel
+  const int wdt = (kf || p.form == LF_F16) ? DT_F16 : p.dt >= 0 ? p.dt : (dt == DT_HL && K0 % 32 != 0) ? DT_F32 : dt;
+  SDXL_REQUIRE(p.ln == LN_NONE || wdt != DT_HL, "pack: a LayerNorm enters f16 / fp32 weights only");
   if (wdt != dt) l.dt = wdt;
-  const int kt = wdt == DT_F16 ? 64 : 32;
-  l.Kpad = (int)round_up(l.K, kt); l.Npad = (int)round_up(l.N, 128);
-  char* w = (char*)arena.alloc((size_t)l.Npad * l.Kpad * dt_size(wdt));
-  float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  l.w = w; l.b = b;
-  float wscale = 1.f;
-  if (wdt == DT_HL) {     // ONE factor for the concatenated matrix (one accumulator scale per GEMM)
-    std::vector<std::string> wn;
-    for (const std::string& n : names) wn.push_back(n + ".weight");
-    wscale = hl_scale(l, wn);
-  }
+  l.K = kf ? 2 * K0 : K0; l.cin = l.K; l.k_form = kf;
+  if (kf && p.ln != LN_NONE) l.ln_k = K0;
+  l.Kpad = (int)round_up(l.K, wdt == DT_F16 ? 64 : 32); l.Npad = (int)round_up(l.N, 128);
+  const size_t wbytes = (size_t)l.Npad * l.Kpad * dt_size(wdt), vbytes = (size_t)l.Npad * sizeof(float);
+  char* w = (char*)arena.alloc(wbytes);
+  float* b = (float*)arena.alloc(vbytes);
+  float* sc = wdt == DT_HL ? (float*)arena.alloc(2 * sizeof(float)) : nullptr;      // ONE factor for a fused matrix (one accumulator scale per GEMM)
+  float* cs = p.ln != LN_NONE ? (float*)arena.alloc(vbytes) : nullptr;
+  float* leps = p.ln != LN_NONE ? (float*)arena.alloc(sizeof(float)) : nullptr;
+  float* bplain = p.ln == LN_SHADOW ? (float*)arena.alloc(vbytes) : nullptr;
+  l.w = w; l.b = b; l.acc_scale = sc; l.cs = cs; l.ln_eps = leps;
+  if (p.shadow) { *p.shadow = l; l.b = bplain; l.cs = nullptr; l.ln_eps = nullptr; }      // from here on l is the plain twin
+  const bool wf = !fused && !p.geglu && !p.shadow && kf != 1 && (p.ln == LN_NONE || p.wfrag_folded) && alloc_wfrag(l, p.ln == LN_FOLD);
   if (src.empty()) return l;
-  SDXL_HIP(hipMemsetAsync(w, 0, (size_t)l.Npad * l.Kpad * dt_size(wdt), st));
-  SDXL_HIP(hipMemsetAsync(b, 0, (size_t)l.Npad * sizeof(float), st));
+  // ---- fill
+  float wscale = 1.f;
+  if (sc) wscale = hl_scale(sc, [&](auto f) { for (const std::string& n : p.names) f(fetch(n + ".weight"), spec(n + ".weight").numel()); });
+  SDXL_HIP(hipMemsetAsync(w, 0, wbytes, st));
+  SDXL_HIP(hipMemsetAsync(b, 0, vbytes, st));
+  float *gamma = nullptr, *beta = nullptr, *bsrc = nullptr, *bfold = nullptr;
+  if (p.ln != LN_NONE) {
+    SDXL_REQUIRE(spec(p.norm + ".gamma").shape[0] == K0, "pack: norm width mismatch");
+    gamma = need_tmp2(3 * (size_t)l.Npad + 2 * (size_t)l.K + 64);      // [K0]
+    beta = gamma + l.K;            // [K0]
+    bsrc = beta + l.K;             // [Npad] canonical bias of the current projection
+    bfold = bsrc + l.Npad;         // [Npad] beta W + bias, canonical order
+    SDXL_HIP(hipMemcpyAsync(leps, fetch(p.norm + ".eps"), sizeof(float), hipMemcpyDeviceToDevice, st));
+    SDXL_HIP(hipMemcpyAsync(gamma, fetch(p.norm + ".gamma"), K0 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SDXL_HIP(hipMemcpyAsync(beta, fetch(p.norm + ".beta"), K0 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (bplain) SDXL_HIP(hipMemsetAsync(bplain, 0, vbytes, st));
+  }
+  const int g = p.geglu ? 1 : 0;
   int off = 0;
-  for (const std::string& n : names) {
-    const ParamSpec& s = spec(n + ".weight");
-    const int N = s.shape[1];
-    launch_pack_linear(fetch(n + ".weight"), w, wdt, l.K, N, l.Kpad, N, 0, off, st, nullptr, wscale);   // exactly N rows at row offset
-    const float* bsrc = has(n + ".bias") ? fetch(n + ".bias") : nullptr;
-    launch_pack_bias(bsrc, b, N, N, 0, off, st);
+  for (const std::string& n : p.names) {
+    const int N = spec(n + ".weight").shape[1], rows = fused ? N : l.Npad;      // a fused part packs exactly its N rows at row offset `off`
+    const bool hb = has(n + ".bias");
+    if (hb && p.ln != LN_NONE) SDXL_HIP(hipMemcpyAsync(bsrc, fetch(n + ".bias"), N * sizeof(float), hipMemcpyDeviceToDevice, st));      // (the staging buffer holds one tensor)
+    const float* wsrc = fetch(n + ".weight");
+    if (kf) launch_pack_linear_hilo(wsrc, w, K0, N, rows, g, kHiLoScale, st, p.form == LF_X2 ? 2 : p.form == LF_F16_AHILO ? 1 : 0, off);
+    else launch_pack_linear(wsrc, w, wdt, l.K, N, l.Kpad, rows, g, off, st, p.ln == LN_FOLD ? gamma : nullptr, wscale);
+    if (p.ln == LN_NONE) launch_pack_bias(hb ? fetch(n + ".bias") : nullptr, b, N, rows, g, off, st);
+    else {
+      launch_beta_dot(wsrc, beta, hb ? bsrc : nullptr, bfold, K0, N, st);
+      launch_pack_bias(bfold, b, N, rows, g, off, st);
+      if (bplain) launch_pack_bias(hb ? bsrc : nullptr, bplain, N, rows, g, off, st);
+    }
     off += N;
   }
-  l.w = w; l.b = b;
+  // column sums over the packed (rounded) values; shadow form: cs[n] = sum_k gamma[k] W[k][n]
+  if (p.ln == LN_SHADOW) launch_colsum_packed(w, wdt, l.Kpad, l.Npad, cs, st, gamma, K0, kf == 2 ? 1 : 0);
+  else if (p.ln == LN_FOLD) launch_colsum_packed(w, wdt, l.Kpad, l.Npad, cs, st);
+  if (wf) launch_repack_wfrag(l.w, const_cast<void*>(l.wf), l.Npad, l.Kpad, st);
   return l;
-}
-// LayerNorm(gamma, beta) followed by Linear(W, b):  LN(x) W + b = rstd (x - mu) (diag(gamma) W) + (beta W + b)
-//   = rstd * (x W') - rstd * mu * colsum(W') + b'   -- W' is packed (rounded to the compute dtype) FIRST and the column sums
-// are taken over the rounded values, so the identity holds exactly for what the MFMA multiplies.
-Lin WeightBuilder::linear_ln(const std::string& name, bool geglu, const std::string& norm, bool xattn_query) {
-  Lin l = fold_ln({name}, norm, geglu);
-  // (after everything fold_ln allocates, filled or not: replicas keep the arena layout)
-  if (xattn_query && !geglu && !l.k_form) attach_wfrag(l, !src.empty(), true);
-  return l;
-}
-Lin WeightBuilder::fused_linear_ln(const std::vector<std::string>& names, const std::string& norm) {
-  return fold_ln(names, norm, false);
 }
 bool WeightBuilder::all_f16_exact(const std::vector<std::string>& names) {
   if (src.empty() || names.empty()) return true;      // (replica ranks receive rank 0's arena: its decision is theirs -- see UNet::build_weights)
-  float* flag = (float*)tmp2;
-  if (tmp2_numel < 4) { if (tmp2) SDXL_HIP(hipFree(tmp2)); SDXL_HIP(hipMalloc((void**)&tmp2, 64 * sizeof(float))); tmp2_numel = 64; flag = tmp2; }
+  float* flag = need_tmp2(64);
   bool first = true;
   for (const std::string& n : names) { launch_f16_exact(fetch(n), spec(n).numel(), 1.0f, flag, st, !first); first = false; }
   float h = 0.f;
@@ -344,77 +309,11 @@ bool WeightBuilder::all_f16_exact(const std::vector<std::string>& names) {
   SDXL_HIP(hipStreamSynchronize(st));
   return h != 0.f;
 }
-Lin WeightBuilder::fold_ln(const std::vector<std::string>& names, const std::string& norm, bool geglu, int dt_override, bool shadow, Lin* plain, bool hilo_dup, bool hl_interleave) {
-  SDXL_REQUIRE(!geglu || names.size() == 1, "GEGLU packing applies to a single projection");
-  const int mdt = dt;                       // the model's dtype
-  const int dt = dt_override >= 0 ? dt_override : mdt;      // (shadows the member below: the dtype THIS matrix is packed in)
-  Lin l; l.ksize = 1;
-  if (dt != mdt) l.dt = dt;
-  int ntot = 0;
-  for (const std::string& n : names) {
-    const ParamSpec& s = spec(n + ".weight");
-    if (l.K == 0) l.K = s.shape[0];
-    SDXL_REQUIRE(l.K == s.shape[0], "fused_linear_ln: K mismatch");
-    ntot += s.shape[1];
-  }
-  SDXL_REQUIRE(!hilo_dup || (shadow && names.size() == 1 && dt == DT_F16 && l.K % 32 == 0), "fold_ln: the (hi | lo) form is a single f16 shadow-form projection");
-  const int K0 = l.K;                       // columns of the LayerNorm
-  SDXL_REQUIRE(!hl_interleave || (shadow && !hilo_dup && dt == DT_F16 && l.K % 32 == 0), "fold_ln: the HL16-interleaved form is an f16 shadow-form projection");
-  if (hilo_dup) { l.ln_k = K0; l.K = 2 * K0; l.k_form = 1; }
-  if (hl_interleave) { l.ln_k = K0; l.K = 2 * K0; l.k_form = 2; }
-  l.N = ntot; l.cin = l.K;
-  const int kt = dt == DT_F16 ? 64 : 32;
-  l.Kpad = (int)round_up(l.K, kt); l.Npad = (int)round_up(l.N, 128);
-  char* w = (char*)arena.alloc((size_t)l.Npad * l.Kpad * dt_size(dt));
-  float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  float* cs = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  float* leps = (float*)arena.alloc(sizeof(float));
-  l.w = w; l.b = b; l.cs = cs; l.ln_eps = leps;
-  float* bplain = plain ? (float*)arena.alloc((size_t)l.Npad * sizeof(float)) : nullptr;
-  if (plain) { *plain = l; plain->b = bplain; plain->cs = nullptr; plain->ln_eps = nullptr; }
-  if (src.empty()) return l;
-  SDXL_HIP(hipMemcpyAsync(leps, fetch(norm + ".eps"), sizeof(float), hipMemcpyDeviceToDevice, st));
-  const size_t need = 3 * (size_t)l.Npad + 2 * (size_t)l.K + 64;
-  if (need > tmp2_numel) {
-    if (tmp2) SDXL_HIP(hipFree(tmp2));
-    SDXL_HIP(hipMalloc((void**)&tmp2, need * sizeof(float)));
-    tmp2_numel = need;
-  }
-  float* gamma = tmp2;                 // [K]
-  float* beta = tmp2 + l.K;            // [K]
-  float* bsrc = beta + l.K;            // [Npad] canonical bias of the current projection
-  float* bfold = bsrc + l.Npad;        // [Npad] beta W + bias, canonical order
-  SDXL_REQUIRE(spec(norm + ".gamma").shape[0] == K0, "fused_linear_ln: norm width mismatch");
-  SDXL_HIP(hipMemcpyAsync(gamma, fetch(norm + ".gamma"), K0 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  SDXL_HIP(hipMemcpyAsync(beta, fetch(norm + ".beta"), K0 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  SDXL_HIP(hipMemsetAsync(w, 0, (size_t)l.Npad * l.Kpad * dt_size(dt), st));
-  SDXL_HIP(hipMemsetAsync(b, 0, (size_t)l.Npad * sizeof(float), st));
-  if (bplain) SDXL_HIP(hipMemsetAsync(bplain, 0, (size_t)l.Npad * sizeof(float), st));
-  int off = 0;
-  for (const std::string& n : names) {
-    const ParamSpec& s = spec(n + ".weight");
-    const int N = s.shape[1];
-    const bool hb = has(n + ".bias");
-    if (hb) SDXL_HIP(hipMemcpyAsync(bsrc, fetch(n + ".bias"), N * sizeof(float), hipMemcpyDeviceToDevice, st));
-    const float* wsrc = fetch(n + ".weight");
-    // (shadow form: the matrix stays W -- an f16-representable parameter stays exact -- and gamma multiplies the A operand instead)
-    if (hl_interleave) launch_pack_linear_hilo(wsrc, w, K0, N, names.size() == 1 ? l.Npad : N, geglu ? 1 : 0, kHiLoScale, st, 2, off);      // the weight twice per 16-channel group
-    else if (hilo_dup) launch_pack_linear_hilo(wsrc, w, K0, N, l.Npad, geglu ? 1 : 0, kHiLoScale, st, 1);      // (w | w / kHiLoScale): the (hi | lo) shadow's partner
-    else if (names.size() == 1) launch_pack_linear(wsrc, w, dt, l.K, N, l.Kpad, l.Npad, geglu ? 1 : 0, 0, st, shadow ? nullptr : gamma);
-    else launch_pack_linear(wsrc, w, dt, l.K, N, l.Kpad, N, 0, off, st, shadow ? nullptr : gamma);
-    launch_beta_dot(wsrc, beta, hb ? bsrc : nullptr, bfold, K0, N, st);
-    launch_pack_bias(bfold, b, N, names.size() == 1 ? l.Npad : N, geglu ? 1 : 0, off, st);
-    if (bplain) launch_pack_bias(hb ? bsrc : nullptr, bplain, N, names.size() == 1 ? l.Npad : N, geglu ? 1 : 0, off, st);
-    off += N;
-  }
-  if (shadow) launch_colsum_packed(w, dt, l.Kpad, l.Npad, cs, st, gamma, K0, hl_interleave ? 1 : 0);      // cs[n] = sum_k gamma[k] W[k][n] over the packed (rounded) values
-  else launch_colsum_packed(w, dt, l.Kpad, l.Npad, cs, st);
-  return l;
-}
 bool WeightBuilder::folds_upsample(const ParamSpec& p, int dt) {
   return p.kind == PK_CONV_W && p.shape[2] == 3 && p.shape[3] == 3 && ((dt == DT_F16 && p.shape[1] % 64 == 0) || (dt == DT_HL && p.shape[1] % 32 == 0));
 }
 Lin WeightBuilder::conv(const std::string& name, bool fold_up) {
+  // ---- layout
   const ParamSpec& s = spec(name + ".weight");
   Lin l; l.N = s.shape[0]; l.cin = s.shape[1]; l.ksize = s.shape[2];
   l.K = l.cin * l.ksize * l.ksize;
@@ -422,31 +321,32 @@ Lin WeightBuilder::conv(const std::string& name, bool fold_up) {
   // 8-channel ends of the VAE) are packed and run as plain fp32 on the generic kernel
   const int wdt = (dt == DT_HL && l.cin % 32 != 0) ? DT_F32 : dt;
   if (wdt != dt) l.dt = wdt;
-  const int kt = wdt == DT_F16 ? 64 : 32;
-  l.Kpad = (int)round_up(l.K, kt); l.Npad = (int)round_up(l.N, 128);
+  l.Kpad = (int)round_up(l.K, wdt == DT_F16 ? 64 : 32); l.Npad = (int)round_up(l.N, 128);
   void* w = arena.alloc((size_t)l.Npad * l.Kpad * dt_size(wdt));
   float* b = (float*)arena.alloc((size_t)l.Npad * sizeof(float));
-  l.w = w; l.b = b;
-  const float wscale = wdt == DT_HL ? hl_scale(l, {name + ".weight"}) : 1.f;
-  // nearest-2x upsample + this conv as four 2x2-tap phase convolutions (upsample_fold.h): fp32 sums of the fetched taps first, then the packing of
-  // w -- one f16 rounding, or the (hi, lo) split at a factor of the SUMS' own range
+  float* sc = wdt == DT_HL ? (float*)arena.alloc(2 * sizeof(float)) : nullptr;
+  // nearest-2x upsample + this conv as four 2x2-tap phase convolutions (upsample_fold.h): [4][Npad][4 cin] packed like w, with a scale of their own
   const bool fold = fold_up && folds_upsample(s, wdt);
   const size_t fold_numel = 16 * (size_t)l.N * l.cin, fold_kpad = 4 * (size_t)l.cin;      // (cin is a multiple of the k-tile: no padding along K)
   char* wfold = fold ? (char*)arena.alloc(4 * l.Npad * fold_kpad * dt_size(wdt)) : nullptr;
-  l.w_fold = wfold;
-  if (fold && !src.empty() && fold_numel > tmp2_numel) {
-    if (tmp2) SDXL_HIP(hipFree(tmp2));
-    SDXL_HIP(hipMalloc((void**)&tmp2, fold_numel * sizeof(float)));
-    tmp2_numel = fold_numel;
+  float* fsc = fold && wdt == DT_HL ? (float*)arena.alloc(2 * sizeof(float)) : nullptr;
+  l.w = w; l.b = b; l.acc_scale = sc; l.w_fold = wfold; l.fold_acc_scale = fsc;
+  const bool wf = alloc_wfrag(l);
+  if (src.empty()) return l;
+  // ---- fill
+  const float* wsrc = fetch(name + ".weight");
+  const float wscale = sc ? hl_scale(sc, [&](auto f) { f(wsrc, s.numel()); }) : 1.f;
+  launch_pack_conv(wsrc, w, wdt, l.N, l.cin, l.ksize, l.Kpad, l.Npad, st, wscale);
+  if (fold) {
+    // fp32 sums of the fetched taps first, then the packing of w -- one f16 rounding, or the (hi, lo) split at a factor of the SUMS' own range
+    float* folded = need_tmp2(fold_numel);
+    launch_fold_upsample(wsrc, folded, l.N, l.cin, st);
+    const float fscale = fsc ? hl_scale(fsc, [&](auto f) { f(folded, fold_numel); }) : 1.f;
+    for (int ph = 0; ph < 4; ++ph)
+      launch_pack_conv(folded + (size_t)ph * 4 * l.N * l.cin, wfold + (size_t)ph * l.Npad * fold_kpad * dt_size(wdt), wdt, l.N, l.cin, 2, (int)fold_kpad, l.Npad, st, fscale);
   }
-  if (fold && !src.empty()) launch_fold_upsample(fetch(name + ".weight"), tmp2, l.N, l.cin, st);
-  const float fscale = fold && wdt == DT_HL ? hl_scale_of(tmp2, fold_numel, l.fold_acc_scale) : 1.f;
-  if (src.empty()) { attach_wfrag(l, false); return l; }
-  launch_pack_conv(fetch(name + ".weight"), w, wdt, l.N, l.cin, l.ksize, l.Kpad, l.Npad, st, wscale);
-  for (int ph = 0; fold && ph < 4; ++ph)
-    launch_pack_conv(tmp2 + (size_t)ph * 4 * l.N * l.cin, wfold + (size_t)ph * l.Npad * fold_kpad * dt_size(wdt), wdt, l.N, l.cin, 2, (int)fold_kpad, l.Npad, st, fscale);
   launch_pack_bias(fetch(name + ".bias"), b, l.N, l.Npad, 0, 0, st);
-  attach_wfrag(l, true);
+  if (wf) launch_repack_wfrag(l.w, const_cast<void*>(l.wf), l.Npad, l.Kpad, st);
   return l;
 }
 NormW WeightBuilder::norm(const std::string& name) {
@@ -563,8 +463,8 @@ bool run_conv(Exec& ex, const Lin& w, const Act& a, int cin, const ConvGeom& g, 
     // weight warming: the plan's first forward records which weights every launch reads and whether its kernel has idle CUs to host
     // warming workgroups; later forwards hand launch i the weights of a later launch (WarmSeq::finish)
     WarmSeq& ws = *ex.warm;
-    // the region the launch reads cold: its weights and the per-column vectors next to them in the arena (allocation order: packed
-    // weights, bias, [column sums, eps of a folded LayerNorm], [fragment-order image])
+    // the region the launch reads cold: its weights and the per-column vectors next to them in the arena -- bias, column sums and eps follow the
+    // packed weights and precede the fragment-order image (the allocation order WeightBuilder::pack / conv document and keep, engine.h)
     const bool host = igemm_wreg_selected(p, knobs) || igemm_wreg_xattn_selected(p, knobs);
     const size_t wbytes = wbytes_f16;
     const char* lo; const char* hi;

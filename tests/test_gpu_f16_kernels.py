@@ -8,7 +8,7 @@ rounding the kernels perform is emulated or bounded per element (DESIGN 5.1 list
   * f16 operands on entry: copy_rows / nchw_to_nhwc (csrc/elementwise.hip:20-25 st_f) at dtype 1; the generic kernel's A load
     (csrc/igemm.hip:53-65 load_chunk, :161 the gather) at dtype 2; the packed weights (elementwise.hip:636-649 pack_linear_kernel,
     pack_conv_kernel).  All are round-to-nearest-even: test_*_conversion_* check them bit for bit.
-  * fold_ln (csrc/weights.cpp:284-350): W' = f16(fp32(gamma_k W_kn)) (pack_linear_kernel with kscale), cs_n = sum_k W'_kn in fp32
+  * WeightBuilder::pack, LN_FOLD (csrc/weights.cpp): W' = f16(fp32(gamma_k W_kn)) (pack_linear_kernel with kscale), cs_n = sum_k W'_kn in fp32
     over the packed values (colsum_packed_kernel), b'_n = sum_k beta_k W_kn + b_n in fp32 from the unrounded W (beta_dot_kernel); the
     epilogue forms rstd (x W') - rstd mu cs + b' (igemm_common.h:211-219) with (mu, rstd) of the f16 rows (the identity GEMM's stat_out).
     Emulated exactly in fp64 (W' bit-exact on the host).

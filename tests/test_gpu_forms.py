@@ -1,7 +1,7 @@
 """The transformer projection forms of the split-operand UNet (csrc/unet.cpp plan_transformer, csrc/engine.h LinForm) against fp64, op by op.
 
 Every case runs ONE LayerNorm-fed projection through sdxl_transformer_projection, which calls the code UNet::spatial_transformer runs
-(pack_proj, alloc_ln_operands, want_ln_shadow, ln_input): a producer (out-projection / FF-out, form NATIVE, F16 or X2) adds into the
+(WeightBuilder::pack, alloc_ln_operands, want_ln_shadow, ln_input): a producer (out-projection / FF-out, form NATIVE, F16 or X2) adds into the
 fp32 stream t, then LayerNorm(t) feeds the consumer in its form -- through the LayerNorm launch ("ln") or through the shadow the producer
 left ("sh", MIX_LN_SHADOW).  The consumer is checked against the engine's own fp32 t (returned by the entry), so a bar measures the
 consumer alone; the producer is checked against fp64 on its own.
