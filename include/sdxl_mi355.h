@@ -581,6 +581,22 @@ int sdxl_vae_attn_block(sdxl_ctx* ctx, void* stream, const float* x, const float
 int sdxl_vae_res_block(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma1, const float* beta1, float eps1, const float* w1, const float* b1,
                        const float* gamma2, const float* beta2, float eps2, const float* w2, const float* b2, const float* w_nin, const float* b_nin, int B,
                        int Cin, int Cout, int H, int W, int n_group, int dtype, float* out);
+/* One entry of a UNet's block plan on its own, through the code sdxl_unet_forward runs for it (parity tests): section 0 = input_blocks[index] (Conv, Res,
+ * Res + SpatialTransformer, Down), 1 = the middle block (res1, transformer, res2; index 0), 2 = output_blocks[index] (Res, optionally + SpatialTransformer,
+ * optionally + the upsample convolution), 3 = norm_out + SiLU + conv_out (index 0).  NCHW fp32 device tensors: x [B,c_in,h,w] at the entry's OWN resolution
+ * (c_in: the concat width for output entries), emb [B,4*model_channels] = t_emb + l_emb (what every ResBlock's lin_embed(silu(emb)) consumes), context
+ * [B,n_ctx,context_dim], out [B,c_out,h_out,w_out] (h_out = (h - 1) / 2 + 1 for a Down entry, 2h behind an upsample convolution, else h).
+ * The entry is run as inside a forward of the top-level size its level implies (h, w times 2^level): x is laid out with the row stride its source has
+ * there (the previous entry's slice of a concat buffer; the whole buffer for output entries), the result is written at the row stride and column offset
+ * its destination has there, the time-embedding bias is the entry's slice of the one GEMV over all ResBlocks, the cross-attention caches are the entry's
+ * own among all transformers'.  The per-handle options (sdxl_unet_set_fused_cross_attention, sdxl_unet_set_gn_from_producer) apply.
+ * out_shape (may be NULL) receives {B, c_out, h_out, w_out}; out == NULL: only that, nothing is launched.
+ * SDXL_ERR_INVALID, nothing launched: an index outside the plan, c_in not the entry's width, a size no forward has at that level (top-level height and
+ * width must be divisible by 2^(levels-1)), B outside 1..8, a top-level height or width above 256, a NULL x / emb / context with out != NULL.
+ * Replaces the handle's context and leaves no label embedding: sdxl_unet_forward sets its own again; a Diffuser whose UNet handle ran an entry refuses
+ * (SDXL_ERR_RUNTIME) to step until its conditioning is set again. */
+int sdxl_unet_block(sdxl_unet* u, void* stream, int section, int index, const float* x, const float* emb, const float* context, int B, int c_in, int h,
+                    int w, int n_ctx, float* out, int64_t out_shape[4]);
 /* LayerNorm::forward (layernorm/mod.rs:34-49) followed by nn::Linear, as TransformerBlock::forward pairs them
  * (unet/mod.rs:885-891): y = LN(x[M,K]; gamma, beta, eps) @ W[K,N] + b (bias may be NULL), optional GEGLU.  Runs the path
  * the UNet runs in that dtype: SDXL_DTYPE_F16 = LayerNorm folded into the GEMM (row statistics from the producer's

@@ -100,7 +100,7 @@ ABI_SYMBOLS = [
     "sdxl_last_error", "sdxl_build_info", "sdxl_ctx_create", "sdxl_ctx_destroy", "sdxl_ctx_synchronize",
     "sdxl_unet_config_base", "sdxl_unet_config_refiner", "sdxl_vae_config_default",
     "sdxl_unet_param_count", "sdxl_unet_param_spec", "sdxl_vae_param_count", "sdxl_vae_param_spec",
-    "sdxl_unet_create", "sdxl_unet_create_synthetic", "sdxl_unet_destroy", "sdxl_unet_forward", "sdxl_unet_set_graph", "sdxl_unet_set_split_cfg", "sdxl_unet_set_fused_cross_attention", "sdxl_unet_set_gn_from_producer", "sdxl_unet_mix_classes",
+    "sdxl_unet_create", "sdxl_unet_create_synthetic", "sdxl_unet_destroy", "sdxl_unet_forward", "sdxl_unet_set_graph", "sdxl_unet_set_split_cfg", "sdxl_unet_set_fused_cross_attention", "sdxl_unet_set_gn_from_producer", "sdxl_unet_mix_classes", "sdxl_unet_block",
     "sdxl_qkv_attention", "sdxl_attn_decoder_mask",
     "sdxl_diffuser_create", "sdxl_diffuser_create_synthetic", "sdxl_diffuser_destroy", "sdxl_diffuser_unet",
     "sdxl_sample_latent", "sdxl_sample_latent_with_inpainting", "sdxl_refine_latent", "sdxl_step_count",
@@ -515,6 +515,31 @@ class UNet:
         out = torch.empty((B, self.cfg.out_channels, H, W), device=x.device, dtype=torch.float32)
         _check(lib().sdxl_unet_forward(self.h, _stream(), px, pt, pc, pl, B, H, W, int(context.shape[1]),
                                       ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    BLOCK_SECTIONS = {"input": 0, "middle": 1, "output": 2, "head": 3}
+
+    def run_block(self, section: str, index: int, x, emb, context):
+        """one entry of the block plan through the code forward runs for it (sdxl_unet_block): section "input" / "middle" / "output" / "head";
+        x [B,c_in,h,w] at the entry's own resolution (the concat width for output entries), emb [B,4*model_channels] = t_emb + l_emb,
+        context [B,n_ctx,ctx] -> [B,c_out,h_out,w_out].  Replaces the handle's context."""
+        torch = _torch()
+        sec = self.BLOCK_SECTIONS.get(section)
+        if sec is None:
+            raise InvalidArgument(f"run_block: unknown section {section!r}")
+        if x is None or emb is None or context is None or x.dim() != 4 or emb.dim() != 2 or context.dim() != 3:
+            raise InvalidArgument("run_block: x must be [B,c_in,h,w], emb [B,4*model_channels], context [B,n_ctx,ctx]")
+        x, px = _dev(x)
+        emb, pe = _dev(emb)
+        context, pc = _dev(context)
+        B, c_in, h, w = x.shape
+        if tuple(emb.shape) != (B, 4 * self.cfg.model_channels) or context.shape[0] != B or context.shape[2] != self.cfg.context_dim:
+            raise InvalidArgument("run_block: emb must be [B,4*model_channels] and context [B,n_ctx,context_dim] for x's B")
+        shape = (ctypes.c_int64 * 4)()
+        call = lambda out: _check_invalid(lib().sdxl_unet_block(self.h, _stream(), sec, int(index), px, pe, pc, B, c_in, h, w, int(context.shape[1]), out, shape))      # noqa: E731
+        call(ctypes.c_void_p(None))      # the entry's output shape (and the refusal of an entry / size outside the plan) before anything is allocated
+        out = torch.empty(tuple(int(v) for v in shape), device=x.device, dtype=torch.float32)
+        call(ctypes.c_void_p(out.data_ptr()))
         return out
 
     def set_split_cfg(self, enabled: bool, release_offset: int = 0):

@@ -354,6 +354,14 @@ int sdxl_unet_forward(sdxl_unet* u, void* stream, const float* x, const int32_t*
   u->u->forward_nchw(x, timesteps, context, n_ctx, label, B, H, W, out, pick(u->ctx, stream));
   API_END
 }
+int sdxl_unet_block(sdxl_unet* u, void* stream, int section, int index, const float* x, const float* emb, const float* context, int B, int c_in, int h,
+                    int w, int n_ctx, float* out, int64_t out_shape[4]) {
+  API_BEGIN
+  if (!u) throw InvalidArgumentError("unet block: null handle");
+  use(u->ctx);
+  u->u->run_block(section, index, x, emb, context, n_ctx, B, c_in, h, w, out, out_shape, pick(u->ctx, stream));
+  API_END
+}
 int sdxl_unet_set_graph(sdxl_unet* u, int enabled) {
   API_BEGIN
   SDXL_REQUIRE(u != nullptr, "null argument");

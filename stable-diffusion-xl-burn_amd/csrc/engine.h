@@ -429,6 +429,14 @@ class UNet {
   // reference-shaped entry (unet/mod.rs:450-456): NCHW fp32 in/out, int32 device timesteps
   void forward_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label,
                     int B, int H, int W, float* out, hipStream_t s);
+  // one entry of the block plan on caller tensors (sdxl_unet_block): x NCHW fp32 [B][c_in][h][w] at the entry's own resolution is laid out as the entry's
+  // source is in a forward of the top-level size its level implies (row stride of the concat slice / buffer it reads there), the entry runs through
+  // run_entry with the ebias slice of the one embcat_ GEMV over emb [B][4 mc] and the caches set_context leaves for context, and its destination (row stride
+  // and column offset as in the forward) comes back as NCHW fp32.  out == nullptr: only out_shape {B, C, h, w} is filled, nothing is launched.
+  // Replaces the handle's context (label embedding included: the next forward sets its own).  Indices / shapes outside the plan: InvalidArgumentError.
+  enum Section { SEC_INPUT = 0, SEC_MIDDLE = 1, SEC_OUTPUT = 2, SEC_HEAD = 3 };
+  void run_block(int section, int index, const float* x, const float* emb, const float* context, int n_ctx, int B, int c_in, int h, int w, float* out,
+                 int64_t out_shape[4], hipStream_t s);
   void* unet_in(int B, int H, int W);     // ensures the plan exists
   float* eps_out() { return eps_; }
   int compute_dt() const { return cdt_; }
@@ -462,6 +470,9 @@ class UNet {
   void load_weights(WeightBuilder& wb, const std::vector<StPlan>& plans);
   void ensure_plan(int B, int H, int W);
   void run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb);
+  struct Skips { std::vector<Act> cat; std::vector<int> cx, hs_h, hs_w; };      // concat buffers, the column where each one's skip half starts, resolution after every input entry
+  void alloc_skips(Exec& ex, int B, int H, int W, Skips& k);
+  void run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si);      // the body of one plan entry (run's loops, run_block)
   const float* res_block(Exec& ex, const ResBlockW& w, const Act& x, int B, int H, int W, const Act& out, float* out_gn_part = nullptr);
   void spatial_transformer(Exec& ex, const STW& w, int st_index, const Act& x, int B, int H, int W);
 
@@ -484,6 +495,7 @@ class UNet {
   int ctx_B_ = 0, n_ctx_ = 0, vt_ld_ctx_ = 0;
   bool ctx_xa_ = false;      // set_context packed the operand-order context image (kv_[..].xa) for this n_ctx_
   float* label_emb_ = nullptr;           // [B][4mc]
+  bool label_valid_ = false;             // the last set_context computed label_emb_ (run_block sets the context without a label)
   // plan
   int pB_ = 0, pH_ = 0, pW_ = 0;
   DeviceArena act_;

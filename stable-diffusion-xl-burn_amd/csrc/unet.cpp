@@ -464,6 +464,8 @@ void UNet::set_context(const float* context, int n_ctx, const float* label, int 
   }
   ctx_arena_.reset(m0);
   // label embedding MLP (unet/mod.rs:464-466); scratch after the caches
+  label_valid_ = label != nullptr;
+  if (!label) return;      // (run_block: its caller hands in t_emb + l_emb; forward refuses to run on what is left in label_emb_)
   const size_t m = ctx_arena_.mark();
   float* l1 = (float*)ctx_arena_.alloc((size_t)B * emb * sizeof(float));
   gemv(ex, lin1_l_, label, cfg_.adm_in_channels, l1, emb, B, false, true);
@@ -675,6 +677,95 @@ void UNet::spatial_transformer(Exec& ex, const STW& w, int si, const Act& x, int
 }
 
 // ------------------------------------------------------------------------------------------ forward
+// the skip / concat buffers of a run at top-level size H x W: every input entry writes the slice [cx, cx + C_skip) of the buffer its matching output entry
+// reads, the previous output entry (the middle block for cat[0]) the slice [0, cx)
+void UNet::alloc_skips(Exec& ex, int B, int H, int W, Skips& k) {
+  const int n_in = (int)inp_.size(), n_out = (int)out_.size();
+  SDXL_REQUIRE(n_in == n_out, "input/output block count mismatch");
+  k.hs_h.assign(n_in, 0); k.hs_w.assign(n_in, 0);
+  std::vector<int> hs_c(n_in);
+  {
+    int h = H, w = W;
+    for (int i = 0; i < n_in; ++i) {
+      const BlockDesc& d = inp_[i].d;
+      if (d.kind == BK_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+      k.hs_h[i] = h; k.hs_w[i] = w; hs_c[i] = d.c_out;
+    }
+  }
+  k.cat.assign(n_out, Act());
+  k.cx.assign(n_out, 0);
+  for (int j = 0; j < n_out; ++j) {
+    const int i = n_in - 1 - j;
+    k.cx[j] = out_[j].d.c_in - hs_c[i];
+    SDXL_REQUIRE(k.cx[j] > 0, "bad concat geometry");
+    k.cat[j] = ex.alloc((size_t)B * k.hs_h[i] * k.hs_w[i], out_[j].d.c_in, ex.sdt);
+  }
+}
+
+// one entry of the block plan, src -> dst, at the entry's own input resolution h x w (a Down entry writes (h - 1) / 2 + 1, an entry with an upsample
+// convolution 2h x 2w); si: the index of its spatial transformer in execution order (st_list_ / kv_)
+void UNet::run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si) {
+  if (section == SEC_INPUT) {
+    const BlockW& b = inp_[index];
+    const int cur_c = b.d.c_in;
+    switch (b.d.kind) {
+      case BK_CONV: run_conv(ex, b.conv, hl_op(ex, b.conv, src, (size_t)B * h * w, cur_c, DM_CONV_IO, B), cur_c, ConvGeom{B, h, w, h, w, 3, 1, 1, 0}, dst, tag_epi(DM_CONV_IO)); break;
+      case BK_DOWN: {
+        const int h2 = (h - 1) / 2 + 1, w2 = (w - 1) / 2 + 1;
+        run_conv(ex, b.conv, hl_op(ex, b.conv, src, (size_t)B * h * w, cur_c, DM_CONV_UPDOWN, B), cur_c, ConvGeom{B, h, w, h2, w2, 3, 2, 1, 0}, dst, tag_epi(DM_CONV_UPDOWN));
+        break;
+      }
+      case BK_RES: res_block(ex, b.res, src, B, h, w, dst); break;
+      case BK_REST: {
+        Act d = dst;      // statistics of the ResBlock output for the transformer's GroupNorm (scratch outlives both calls)
+        const size_t mkp = ex.act->mark();
+        float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * b.d.c_out * 2 * sizeof(float) + 256);
+        d.gn_part = res_block(ex, b.res, src, B, h, w, dst, part); d.gn_rt = h * w / 256;
+        spatial_transformer(ex, b.st, si, d, B, h, w);
+        ex.act->reset(mkp);
+        break;
+      }
+      default: throw Error("unexpected input block kind");
+    }
+  } else if (section == SEC_MIDDLE) {      // (:480, :713-719)
+    const size_t mk = ex.act->mark();
+    Act m1 = ex.alloc((size_t)B * h * w, mid_res1_.d.c_out, ex.sdt);
+    float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * mid_res1_.d.c_out * 2 * sizeof(float) + 256);
+    m1.gn_part = res_block(ex, mid_res1_.res, src, B, h, w, m1, part); m1.gn_rt = h * w / 256;
+    spatial_transformer(ex, mid_res1_.st, si, m1, B, h, w);
+    m1.gn_part = nullptr;                 // the transformer rewrote m1 in place
+    res_block(ex, mid_res2_.res, m1, B, h, w, dst);
+    ex.act->reset(mk);
+  } else if (section == SEC_OUTPUT) {
+    const BlockW& b = out_[index];
+    const bool up = b.d.kind == BK_RESTU || b.d.kind == BK_RESU;
+    const size_t mk = ex.act->mark();
+    Act dest = up ? ex.alloc((size_t)B * h * w, b.d.c_out, ex.sdt) : dst;
+    if (b.d.kind == BK_REST || b.d.kind == BK_RESTU) {
+      float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * b.d.c_out * 2 * sizeof(float) + 256);
+      Act d = dest;
+      d.gn_part = res_block(ex, b.res, src, B, h, w, dest, part); d.gn_rt = h * w / 256;
+      spatial_transformer(ex, b.st, si, d, B, h, w);
+    } else {
+      res_block(ex, b.res, src, B, h, w, dest);
+    }
+    if (up) {   // Upsample::forward :742-752 -- nearest 2x folded into the conv weights (four 2x2-tap phase convolutions) or, where the shape has no such launch, fused into the conv gather
+      Epi up_epi = tag_epi(DM_CONV_UPDOWN);
+      up_epi.fold = true;      // (run_conv: only layers that carry folded weights -- the f16 engine's)
+      run_conv(ex, b.conv, hl_op(ex, b.conv, dest, (size_t)B * h * w, b.d.c_out, DM_CONV_UPDOWN, B), b.d.c_out, ConvGeom{B, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, dst, up_epi);
+    }
+    ex.act->reset(mk);
+  } else {      // SEC_HEAD (:488-490)
+    const int mc = cfg_.model_channels;
+    const size_t mk = ex.act->mark();
+    Act gn = ex.alloc((size_t)B * h * w, mc, ex.cdt);
+    run_groupnorm(ex, norm_out_, src, B, h * w, gn, true);
+    demote_lo(ex, DM_CONV_IO, gn, (size_t)B * h * w, mc);
+    run_conv(ex, conv_out_, gn, mc, ConvGeom{B, h, w, h, w, 3, 1, 1, 0}, dst, tag_epi(DM_CONV_IO));
+    ex.act->reset(mk);
+  }
+}
+
 void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
   // batch entries [b0, b0 + nb) of the plan: every per-entry buffer is addressed through these views
   const int B = nb, H = pH_, W = pW_;
@@ -695,100 +786,35 @@ void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
   gemv(ex, embcat_, embv, emb, ebias, emb_total_, B, true, false);
 
   // --- geometry of the skip / concat buffers
+  Skips k;
+  alloc_skips(ex, B, H, W, k);
+  const std::vector<Act>& cat = k.cat;
+  const std::vector<int>& cx = k.cx;
   const int n_in = (int)inp_.size(), n_out = (int)out_.size();
-  SDXL_REQUIRE(n_in == n_out, "input/output block count mismatch");
-  std::vector<int> hs_h(n_in), hs_w(n_in), hs_c(n_in);
-  {
-    int h = H, w = W;
-    for (int i = 0; i < n_in; ++i) {
-      const BlockDesc& d = inp_[i].d;
-      if (d.kind == BK_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
-      hs_h[i] = h; hs_w[i] = w; hs_c[i] = d.c_out;
-    }
-  }
-  std::vector<Act> cat(n_out);
-  std::vector<int> cx(n_out);
-  for (int j = 0; j < n_out; ++j) {
-    const int i = n_in - 1 - j;
-    cx[j] = out_[j].d.c_in - hs_c[i];
-    SDXL_REQUIRE(cx[j] > 0, "bad concat geometry");
-    cat[j] = ex.alloc((size_t)B * hs_h[i] * hs_w[i], out_[j].d.c_in, ex.sdt);
-  }
+  auto has_st = [](const BlockW& b) { return b.d.kind == BK_REST || b.d.kind == BK_RESTU; };
   // --- input blocks (:474-477)
   Act cur(in, cfg_.in_channels, input_dt());
-  int h = H, w = W, cur_c = cfg_.in_channels;
+  int h = H, w = W;
   int si = 0;
   for (int i = 0; i < n_in; ++i) {
-    const BlockW& b = inp_[i];
-    const int j = n_in - 1 - i;
-    const Act dest = cat[j].cols(cx[j]);
-    switch (b.d.kind) {
-      case BK_CONV: run_conv(ex, b.conv, hl_op(ex, b.conv, cur, (size_t)B * h * w, cur_c, DM_CONV_IO, B), cur_c, ConvGeom{B, h, w, h, w, 3, 1, 1, 0}, dest, tag_epi(DM_CONV_IO)); break;
-      case BK_DOWN: {
-        const int h2 = (h - 1) / 2 + 1, w2 = (w - 1) / 2 + 1;
-        run_conv(ex, b.conv, hl_op(ex, b.conv, cur, (size_t)B * h * w, cur_c, DM_CONV_UPDOWN, B), cur_c, ConvGeom{B, h, w, h2, w2, 3, 2, 1, 0}, dest, tag_epi(DM_CONV_UPDOWN));
-        h = h2; w = w2;
-        break;
-      }
-      case BK_RES: res_block(ex, b.res, cur, B, h, w, dest); break;
-      case BK_REST: {
-        Act d = dest;      // statistics of the ResBlock output for the transformer's GroupNorm (scratch outlives both calls)
-        const size_t mkp = ex.act->mark();
-        float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * b.d.c_out * 2 * sizeof(float) + 256);
-        d.gn_part = res_block(ex, b.res, cur, B, h, w, dest, part); d.gn_rt = h * w / 256;
-        spatial_transformer(ex, b.st, si++, d, B, h, w);
-        ex.act->reset(mkp);
-        break;
-      }
-      default: throw Error("unexpected input block kind");
-    }
-    cur = dest; cur_c = b.d.c_out;
+    const Act dest = cat[n_in - 1 - i].cols(cx[n_in - 1 - i]);
+    run_entry(ex, SEC_INPUT, i, cur, dest, B, h, w, si);
+    if (has_st(inp_[i])) ++si;
+    if (inp_[i].d.kind == BK_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+    cur = dest;
   }
-  // --- middle block (:480, :713-719)
-  {
-    const size_t mk = ex.act->mark();
-    Act m1 = ex.alloc((size_t)B * h * w, mid_res1_.d.c_out, ex.sdt);
-    float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * mid_res1_.d.c_out * 2 * sizeof(float) + 256);
-    m1.gn_part = res_block(ex, mid_res1_.res, cur, B, h, w, m1, part); m1.gn_rt = h * w / 256;
-    spatial_transformer(ex, mid_res1_.st, si++, m1, B, h, w);
-    m1.gn_part = nullptr;                 // the transformer rewrote m1 in place
-    res_block(ex, mid_res2_.res, m1, B, h, w, cat[0].cols(0));
-    ex.act->reset(mk);
-  }
+  // --- middle block
+  run_entry(ex, SEC_MIDDLE, 0, cur, cat[0].cols(0), B, h, w, si++);
   // --- output blocks (:483-486)
   Act last = ex.alloc((size_t)B * H * W, mc, ex.sdt);
   for (int j = 0; j < n_out; ++j) {
-    const BlockW& b = out_[j];
-    const bool up = b.d.kind == BK_RESTU || b.d.kind == BK_RESU;
-    const Act next = j + 1 < n_out ? cat[j + 1].cols(0) : last;
-    const size_t mk = ex.act->mark();
-    Act dest = up ? ex.alloc((size_t)B * h * w, b.d.c_out, ex.sdt) : next;
-    if (b.d.kind == BK_REST || b.d.kind == BK_RESTU) {
-      float* part = (float*)ex.act->alloc((size_t)B * h * w / 256 * b.d.c_out * 2 * sizeof(float) + 256);
-      Act d = dest;
-      d.gn_part = res_block(ex, b.res, cat[j], B, h, w, dest, part); d.gn_rt = h * w / 256;
-      spatial_transformer(ex, b.st, si++, d, B, h, w);
-    } else {
-      res_block(ex, b.res, cat[j], B, h, w, dest);
-    }
-    if (up) {   // Upsample::forward :742-752 -- nearest 2x folded into the conv weights (four 2x2-tap phase convolutions) or, where the shape has no such launch, fused into the conv gather
-      Epi up_epi = tag_epi(DM_CONV_UPDOWN);
-      up_epi.fold = true;      // (run_conv: only layers that carry folded weights -- the f16 engine's)
-      run_conv(ex, b.conv, hl_op(ex, b.conv, dest, (size_t)B * h * w, b.d.c_out, DM_CONV_UPDOWN, B), b.d.c_out, ConvGeom{B, h, w, 2 * h, 2 * w, 3, 1, 1, 1}, next, up_epi);
-      h *= 2; w *= 2;
-    }
-    ex.act->reset(mk);
+    run_entry(ex, SEC_OUTPUT, j, cat[j], j + 1 < n_out ? cat[j + 1].cols(0) : last, B, h, w, si);
+    if (has_st(out_[j])) ++si;
+    if (out_[j].d.kind == BK_RESTU || out_[j].d.kind == BK_RESU) { h *= 2; w *= 2; }
   }
   SDXL_REQUIRE(h == H && w == W, "UNet input height/width must be divisible by 2^(levels-1)");
-  // --- out (:488-490)
-  {
-    const size_t mk = ex.act->mark();
-    Act gn = ex.alloc((size_t)B * H * W, mc, ex.cdt);
-    run_groupnorm(ex, norm_out_, last, B, H * W, gn, true);
-    demote_lo(ex, DM_CONV_IO, gn, (size_t)B * H * W, mc);
-    run_conv(ex, conv_out_, gn, mc, ConvGeom{B, H, W, H, W, 3, 1, 1, 0}, Act(eps, cfg_.out_channels, DT_F32), tag_epi(DM_CONV_IO));
-    ex.act->reset(mk);
-  }
+  // --- out
+  run_entry(ex, SEC_HEAD, 0, last, Act(eps, cfg_.out_channels, DT_F32), B, H, W, 0);
 }
 
 void UNet::ensure_plan(int B, int H, int W) {
@@ -882,6 +908,7 @@ void* UNet::unet_in(int B, int H, int W) { ensure_plan(B, H, W); return in_; }
 void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStream_t s) {
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before forward");
+  SDXL_REQUIRE(label_valid_, "set_context must be called again before forward: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
   Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.demote = demote_mask_;
   ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
   if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
@@ -940,6 +967,7 @@ void UNet::profile(int B, int H, int W, float ms[Profiler::NCLS], int launches[P
                    double flops[Profiler::NCLS], hipStream_t s) {
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before profile");
+  SDXL_REQUIRE(label_valid_, "set_context must be called again before profile: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
   const float t500[8] = {500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f};
   SDXL_HIP(hipMemcpyAsync(tconv_, t500, sizeof(t500), hipMemcpyHostToDevice, s));
   SDXL_HIP(hipStreamSynchronize(s));
@@ -958,6 +986,7 @@ void UNet::profile(int B, int H, int W, float ms[Profiler::NCLS], int launches[P
 float UNet::eager_ms(int B, int H, int W, hipStream_t s) {
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before eager_ms");
+  SDXL_REQUIRE(label_valid_, "set_context must be called again before eager_ms: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
   const float t500[8] = {500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f};
   SDXL_HIP(hipMemcpyAsync(tconv_, t500, sizeof(t500), hipMemcpyHostToDevice, s));
   SDXL_HIP(hipStreamSynchronize(s));
@@ -980,6 +1009,69 @@ float UNet::eager_ms(int B, int H, int W, hipStream_t s) {
   }
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   return best;
+}
+
+void UNet::run_block(int section, int index, const float* x, const float* emb, const float* context, int n_ctx, int B, int c_in, int h, int w, float* out,
+                     int64_t out_shape[4], hipStream_t s) {
+  auto require = [](bool ok, const char* msg) { if (!ok) throw InvalidArgumentError(std::string("unet block: ") + msg); };
+  constexpr int kMaxTop = 256;      // top-level latent height / width (a 2048-pixel image): larger plans are refused here, not by the arena
+  const int n_in = (int)inp_.size(), n_out = (int)out_.size(), mc = cfg_.model_channels;
+  require(section >= SEC_INPUT && section <= SEC_HEAD, "section must be 0 (input), 1 (middle), 2 (output) or 3 (head)");
+  require(index >= 0 && index < (section == SEC_INPUT ? n_in : section == SEC_OUTPUT ? n_out : 1), "index outside the block plan");
+  require(B >= 1 && B <= 8 && h >= 1 && w >= 1 && h <= kMaxTop && w <= kMaxTop && n_ctx >= 1, "batch must be in 1..8, h and w in 1..256");
+  auto has_st = [](const BlockW& b) { return b.d.kind == BK_REST || b.d.kind == BK_RESTU; };
+  // the entry's level (Down entries before it), its transformer's index and its widths in the plan
+  const int last_in = section == SEC_INPUT ? index : section == SEC_MIDDLE ? n_in : section == SEC_OUTPUT ? n_in - 1 - index : 0;      // input entries [0, last_in) run before the entry's source exists
+  int level = 0, si = 0;
+  for (int i = 0; i < n_in; ++i) {
+    if (i < (section == SEC_OUTPUT ? last_in + 1 : last_in) && inp_[i].d.kind == BK_DOWN) ++level;
+    if ((section != SEC_INPUT || i < index) && has_st(inp_[i])) ++si;
+  }
+  if (section == SEC_OUTPUT) { ++si; for (int j = 0; j < index; ++j) if (has_st(out_[j])) ++si; }
+  const BlockDesc& d = section == SEC_INPUT ? inp_[index].d : section == SEC_MIDDLE ? mid_res1_.d : out_[section == SEC_OUTPUT ? index : 0].d;
+  const int want_c = section == SEC_HEAD ? mc : d.c_in, c_out = section == SEC_HEAD ? cfg_.out_channels : d.c_out;
+  require(c_in == want_c, "c_in is not the entry's input width");
+  const int H = h << level, W = w << level;
+  const int div = 1 << (cfg_.channel_mults.size() - 1);
+  require(H <= kMaxTop && W <= kMaxTop, "the top-level size the entry's level implies exceeds 256 x 256");
+  require(H % div == 0 && W % div == 0, "no forward has this size at the entry's level (top-level height / width divisible by 2^(levels-1))");
+  int ho = h, wo = w;
+  if (section == SEC_INPUT && d.kind == BK_DOWN) { ho = (h - 1) / 2 + 1; wo = (w - 1) / 2 + 1; }
+  if (section == SEC_OUTPUT && (d.kind == BK_RESTU || d.kind == BK_RESU)) { ho = 2 * h; wo = 2 * w; }
+  if (out_shape) { out_shape[0] = B; out_shape[1] = c_out; out_shape[2] = ho; out_shape[3] = wo; }
+  if (!out) return;
+  require(x && emb && context, "null tensor");
+  ensure_plan(B, H, W);
+  set_context(context, n_ctx, nullptr, B, s);
+  Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.demote = demote_mask_;
+  ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
+  if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
+  ex.ebias = ebias_; ex.b0 = 0;
+  const size_t m = act_.mark();
+  try {
+    // every ResBlock's time-embedding bias, as run computes it: the entry reads its own emb_off slice
+    SDXL_HIP(hipMemcpyAsync(emb_, emb, (size_t)B * 4 * mc * sizeof(float), hipMemcpyDeviceToDevice, s));
+    gemv(ex, embcat_, emb_, 4 * mc, ebias_, emb_total_, B, true, false);
+    Skips k;
+    alloc_skips(ex, B, H, W, k);
+    const Act last = ex.alloc((size_t)B * H * W, mc, ex.sdt);
+    const int before = last_in - (section == SEC_OUTPUT ? 0 : 1);      // the input entry that leaves the resolution this entry runs at
+    SDXL_REQUIRE(section == SEC_HEAD || before < 0 || (k.hs_h[before] == h && k.hs_w[before] == w), "unet block: level geometry");
+    Act src, dst;
+    switch (section) {
+      case SEC_INPUT:
+        src = index == 0 ? Act(in_, cfg_.in_channels, input_dt()) : k.cat[n_in - index].cols(k.cx[n_in - index]);
+        dst = k.cat[n_in - 1 - index].cols(k.cx[n_in - 1 - index]);
+        break;
+      case SEC_MIDDLE: src = k.cat[0].cols(k.cx[0]); dst = k.cat[0].cols(0); break;
+      case SEC_OUTPUT: src = k.cat[index]; dst = index + 1 < n_out ? k.cat[index + 1].cols(0) : last; break;
+      default: src = last; dst = Act(eps_, cfg_.out_channels, DT_F32);
+    }
+    launch_nchw_to_nhwc(x, c_in * h * w, src.p, src.dt, B, c_in, h * w, src.ld, 1.0f, s);
+    run_entry(ex, section, index, src, dst, B, h, w, si);
+    launch_nhwc_to_nchw(dst.p, dst.dt, dst.ld, out, B, c_out, ho * wo, 1.0f, s);
+  } catch (...) { act_.reset(m); throw; }
+  act_.reset(m);
 }
 
 void UNet::forward_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, int B,
