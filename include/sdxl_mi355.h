@@ -597,6 +597,63 @@ int sdxl_vae_res_block(sdxl_ctx* ctx, void* stream, const float* x, const float*
  * (SDXL_ERR_RUNTIME) to step until its conditioning is set again. */
 int sdxl_unet_block(sdxl_unet* u, void* stream, int section, int index, const float* x, const float* emb, const float* context, int B, int c_in, int h,
                     int w, int n_ctx, float* out, int64_t out_shape[4]);
+/* ---- ControlNet skip residuals (Zhang et al. 2023; sgm ControlledUnetModel, diffusers down_block_additional_residuals / mid_block_additional_residual).
+ * A controlled forward runs the encoder unchanged, then  h = middle(h) + s r_mid  and every output block concatenates  hs.pop() + s r.pop().
+ * The residual tensors of a UNet are, in this order: one per input entry (the entry's output shape), then the middle block's.
+ * sdxl_unet_skip_count: their number, input entries + 1 (-1 with sdxl_last_error on a bad config).  sdxl_unet_skip_shape: {C, h, w} of tensor `index`
+ * for an H x W latent.  Both are host logic only.  SDXL_ERR_INVALID: an index outside 0 .. count - 1, H or W not a positive multiple of 2^(levels-1). */
+int sdxl_unet_skip_count(const sdxl_unet_config* cfg);
+int sdxl_unet_skip_shape(const sdxl_unet_config* cfg, int index, int H, int W, int64_t chw[3]);
+/* sdxl_unet_forward with residuals given by the caller: `residuals` holds all sdxl_unet_skip_count tensors back to back, each NCHW fp32
+ * [B,C,h,w] (device).  They are converted once into staging buffers of the handle in its stream dtype (fp32, or f16 for SDXL_DTYPE_F16), and ONE launch
+ * behind the middle block adds scale times each of them into the tensor the decoder reads (sdxl_skip_residual_add's kernel), in place.  The scale
+ * travels in device memory: calling again with another scale, or other residuals, replays the captured graph.  The handle keeps the residuals
+ * attached for later calls of this entry; residuals == NULL, or sdxl_unet_forward, detaches them (attaching and detaching re-capture the graph) and runs
+ * exactly the launches of a handle that never had any.
+ * SDXL_ERR_INVALID, nothing launched, the handle as it was: a non-finite scale; a handle with sdxl_unet_set_split_cfg enabled (split CFG and
+ * skip residuals cannot be combined); SDXL_DTYPE_F16_F32RES, the SDXL_DTYPE_F32_SPLIT_MIX* modes and SDXL_DTYPE_F32_SPLIT_F16W (no test covers them). */
+int sdxl_unet_forward_residuals(sdxl_unet* u, void* stream, const float* x, const int32_t* timesteps, const float* context, const float* label,
+                                int B, int H, int W, int n_ctx, const float* residuals, float scale, float* out);
+/* The per-step add on caller buffers: for each of the n_segments (1 .. 16) segments i, rows[i] rows of C[i] channels,
+ *   dst[i][r * dst_ld[i] + c] = round(fma(*scale_dev, src[i][r * C[i] + c], dst[i][r * dst_ld[i] + c]))      (fp32 fma, one rounding to the dtype)
+ * in ONE launch, in place.  dst / src are device buffers of the dtype (SDXL_DTYPE_F32: float, SDXL_DTYPE_F16: IEEE f16); src rows are dense, dst rows
+ * dst_ld[i] elements apart (a column slice of a wider buffer); scale_dev is a device float.  Segments must not overlap.
+ * SDXL_ERR_INVALID, nothing launched: n_segments outside 1 .. 16, another dtype, rows < 0, C <= 0 or C % 8 != 0, dst_ld < C, a dst / src pointer or a
+ * dst row pitch that is not 16-byte aligned. */
+int sdxl_skip_residual_add(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src,
+                           const int64_t* rows, const int32_t* C, const float* scale_dev, int dtype);
+/* ---- ControlNet: a second copy of the controlled UNet's encoder (embeddings, input entries, middle block: the UNet's own code, caches and packing),
+ * a hint embedder, one 1x1 convolution per residual tensor.  cfg.unet is the configuration of the UNet being controlled.
+ * Parameters (sdxl_controlnet_param_spec, conventions of sdxl_unet_param_spec): the UNet's lin1/lin2_time_embed, lin1/lin2_label_embed, input_blocks.{i},
+ * middle_block.{res1,transformer,res2} under their own names and in their order; input_hint_block.{0..7}: 3x3 pad-1 convolutions hint_in -> hc0 -> hc0
+ * -> hc1 -> hc1 -> hc2 -> hc2 -> hc3 -> model_channels, numbers 2, 4 and 6 with stride 2, SiLU behind each of the first seven; zero_convs.{i}: 1x1, c_i ->
+ * c_i for every input entry i; middle_block_out: 1x1.  (Checkpoints initialise zero_convs to zero; the synthetic ones are not zero.)
+ * Control forward: g = input_hint_block(hint), h = x; per input entry i: h = input_blocks[i](h, emb, context), h += g behind entry 0,
+ * r_i = zero_convs[i](h); then r_mid = middle_block_out(middle_block(h)).  hint is [n, hint_in, 8H, 8W] fp32 for an H x W latent; g does not depend
+ * on the timestep and is computed once per hint, never per step. */
+typedef struct sdxl_controlnet sdxl_controlnet;
+typedef struct {
+  sdxl_unet_config unet;
+  int32_t hint_in_channels;   /* 3 */
+  int32_t hint_channels[4];   /* 16, 32, 96, 256 */
+} sdxl_controlnet_config;
+void sdxl_controlnet_config_default(const sdxl_unet_config* unet, sdxl_controlnet_config* cfg);
+int sdxl_controlnet_param_count(const sdxl_controlnet_config* cfg);      /* host logic only; -1 with sdxl_last_error on a bad config */
+int sdxl_controlnet_param_spec(const sdxl_controlnet_config* cfg, int index, const char** name, int* ndim, int64_t shape[4], int* kind,
+                               float* synth_scale, float* synth_mean);
+/* dtype: SDXL_DTYPE_F32, SDXL_DTYPE_F16 or SDXL_DTYPE_F32_SPLIT -- every other mode is refused by name (SDXL_ERR_INVALID), as is a refiner
+ * configuration (unet.is_refiner != 0: there is no refiner ControlNet).  */
+int sdxl_controlnet_create(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, const float* weights_flat, sdxl_controlnet** out);
+int sdxl_controlnet_create_f16(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, const uint16_t* weights_flat_f16, sdxl_controlnet** out);
+int sdxl_controlnet_create_synthetic(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, uint64_t seed, sdxl_controlnet** out);
+void sdxl_controlnet_destroy(sdxl_controlnet* c);
+/* the hint embedder alone: hint [n, hint_in, H8, W8] -> out [n, model_channels, H8 / 8, W8 / 8], fp32 device tensors */
+int sdxl_controlnet_embed_hint(sdxl_controlnet* c, void* stream, const float* hint, int n, int H8, int W8, float* out);
+/* the control forward, reference-shaped like sdxl_unet_forward: x [B,in,H,W], timesteps int32 [B] (device), context [B,n_ctx,ctx_dim], label [B,adm],
+ * hint [B,hint_in,8H,8W]; residuals_out receives all sdxl_unet_skip_count tensors back to back, each NCHW fp32 [B,C,h,w] -- the layout
+ * sdxl_unet_forward_residuals takes */
+int sdxl_controlnet_forward(sdxl_controlnet* c, void* stream, const float* x, const int32_t* timesteps, const float* context, const float* label,
+                            const float* hint, int B, int H, int W, int n_ctx, float* residuals_out);
 /* LayerNorm::forward (layernorm/mod.rs:34-49) followed by nn::Linear, as TransformerBlock::forward pairs them
  * (unet/mod.rs:885-891): y = LN(x[M,K]; gamma, beta, eps) @ W[K,N] + b (bias may be NULL), optional GEGLU.  Runs the path
  * the UNet runs in that dtype: SDXL_DTYPE_F16 = LayerNorm folded into the GEMM (row statistics from the producer's

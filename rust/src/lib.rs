@@ -449,6 +449,92 @@ impl<B: BurnBackend> Drop for Diffuser<B> {
         unsafe { ffi::sdxl_diffuser_destroy(self.raw) };
     }
 }
+/// A ControlNet (`sdxl_controlnet`) for the UNet a `DiffuserConfig` describes: that UNet's encoder, a hint embedder and one 1x1 convolution per
+/// skip tensor.  `Precision::F32`, `F16` or `F32Split`.
+pub struct ControlNet {
+    raw: *mut ffi::sdxl_controlnet,
+}
+impl Drop for ControlNet {
+    fn drop(&mut self) {
+        unsafe { ffi::sdxl_controlnet_destroy(self.raw) };
+    }
+}
+impl ControlNet {
+    fn config(cfg: &DiffuserConfig) -> ffi::sdxl_controlnet_config {
+        let unet = cfg.to_c();
+        let mut c: ffi::sdxl_controlnet_config = unsafe { std::mem::zeroed() };
+        unsafe { ffi::sdxl_controlnet_config_default(&unet, &mut c) };
+        c
+    }
+    /// number of f32 values `from_flat` expects (`sdxl_controlnet_param_spec` order)
+    pub fn param_numel(cfg: &DiffuserConfig) -> usize {
+        let c = Self::config(cfg);
+        let n = unsafe { ffi::sdxl_controlnet_param_count(&c) };
+        assert!(n >= 0, "sdxl_mi355: {}", last_error());
+        let mut total = 0usize;
+        for i in 0..n {
+            let (mut ndim, mut shape): (c_int, [i64; 4]) = (0, [1; 4]);
+            check(unsafe {
+                ffi::sdxl_controlnet_param_spec(&c, i, ptr::null_mut(), &mut ndim, shape.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut())
+            });
+            total += shape.iter().take(ndim as usize).product::<i64>() as usize;
+        }
+        total
+    }
+    /// seeded synthetic weights (`sdxl_controlnet_create_synthetic`); a refiner configuration or another precision is an `Err`
+    pub fn synthetic(ctx: &Mi355Context, cfg: &DiffuserConfig, precision: Precision, seed: u64) -> Result<Self, Box<dyn std::error::Error>> {
+        let c = Self::config(cfg);
+        let mut raw = ptr::null_mut();
+        try_check(unsafe { ffi::sdxl_controlnet_create_synthetic(ctx.raw, &c, precision as c_int, seed, &mut raw) })?;
+        Ok(ControlNet { raw })
+    }
+    /// the control forward (`sdxl_controlnet_forward`): hint `[B, 3, 8h, 8w]` for the latent `x` `[B, 4, h, w]` -> the residual tensors
+    /// (`sdxl_unet_skip_shape` order: one per input entry, then the middle block's), what `Diffuser::unet_forward_residuals` takes
+    pub fn forward<B: BurnBackend>(&self, cfg: &DiffuserConfig, x: Tensor<B, 4>, timesteps: Tensor<B, 1, Int>, context: Tensor<B, 3>, label: Tensor<B, 2>,
+                                   hint: Tensor<B, 4>) -> Result<Vec<Tensor<B, 4>>, Box<dyn std::error::Error>> {
+        let device = x.device();
+        let [b, _, h, w] = x.dims();
+        let [_, n_ctx, _] = context.dims();
+        let uc = cfg.to_c();
+        let count = unsafe { ffi::sdxl_unet_skip_count(&uc) };
+        if count < 0 {
+            return Err(last_error().into());
+        }
+        let mut shapes = Vec::new();
+        for i in 0..count {
+            let mut chw = [0i64; 3];
+            try_check(unsafe { ffi::sdxl_unet_skip_shape(&uc, i, h as c_int, w as c_int, chw.as_mut_ptr()) })?;
+            shapes.push([b, chw[0] as usize, chw[1] as usize, chw[2] as usize]);
+        }
+        let total: usize = shapes.iter().map(|s| s.iter().product::<usize>()).sum();
+        let (d_x, (d_t, _), d_c, d_y, d_h) =
+            (bridge::upload(x), bridge::upload_int(timesteps), bridge::upload(context), bridge::upload(label), bridge::upload(hint));
+        let out = DeviceBuf::new(total * 4);
+        try_check(unsafe {
+            ffi::sdxl_controlnet_forward(self.raw, ptr::null_mut(), d_x.f32_ptr(), d_t.ptr as *const i32, d_c.f32_ptr(), d_y.f32_ptr(), d_h.f32_ptr(),
+                                         b as c_int, h as c_int, w as c_int, n_ctx as c_int, out.f32_mut())
+        })?;
+        let host = out.to_f32();
+        let mut res = Vec::new();
+        let mut o = 0usize;
+        for s in shapes {
+            let n: usize = s.iter().product();
+            res.push(Tensor::from_data(Data::new(host[o..o + n].to_vec(), Shape::new(s)).convert(), &device));
+            o += n;
+        }
+        Ok(res)
+    }
+    /// flat f32 weights in `sdxl_controlnet_param_spec` order (`sdxl_controlnet_create`)
+    pub fn from_flat(ctx: &Mi355Context, cfg: &DiffuserConfig, precision: Precision, weights: &[f32]) -> Result<Self, Box<dyn std::error::Error>> {
+        if weights.len() != Self::param_numel(cfg) {
+            return Err(format!("ControlNet::from_flat: {} values given, the configuration takes {}", weights.len(), Self::param_numel(cfg)).into());
+        }
+        let c = Self::config(cfg);
+        let mut raw = ptr::null_mut();
+        try_check(unsafe { ffi::sdxl_controlnet_create(ctx.raw, &c, precision as c_int, weights.as_ptr(), &mut raw) })?;
+        Ok(ControlNet { raw })
+    }
+}
 impl<B: BurnBackend> Diffuser<B> {
     /// reference signature (`:317-322`); noise = `gen_noise` (`:378-388`)
     pub fn sample_latent(&self, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize) -> Tensor<B, 4> {
@@ -636,6 +722,28 @@ impl<B: BurnBackend> Diffuser<B> {
                                    h as c_int, w as c_int, n_ctx as c_int, out.f32_mut())
         });
         bridge::download(&out, [b, c_in, h, w], &device)
+    }
+    /// `unet_forward` with ControlNet residuals (`ControlNet::forward`) added at `scale` behind the middle block: `sdxl_unet_forward_residuals`.
+    /// What the engine refuses (shapes that do not match, a non-finite scale, split CFG, a precision without a test) is an `Err`.
+    pub fn unet_forward_residuals(&self, x: Tensor<B, 4>, timesteps: Tensor<B, 1, Int>, context: Tensor<B, 3>, label: Tensor<B, 2>,
+                                  residuals: Vec<Tensor<B, 4>>, scale: f32) -> Result<Tensor<B, 4>, Box<dyn std::error::Error>> {
+        let device = x.device();
+        let [b, c_in, h, w] = x.dims();
+        let [_, n_ctx, _] = context.dims();
+        let unet = unsafe { ffi::sdxl_diffuser_unet(self.raw) };
+        let mut flat: Vec<f32> = Vec::new();
+        for r in residuals {
+            let data: Data<f32, 4> = r.into_data().convert();
+            flat.extend_from_slice(&data.value);
+        }
+        let d_r = DeviceBuf::from_f32(&flat);
+        let (d_x, (d_t, _), d_c, d_y) = (bridge::upload(x), bridge::upload_int(timesteps), bridge::upload(context), bridge::upload(label));
+        let out = DeviceBuf::new(b * c_in * h * w * 4);
+        try_check(unsafe {
+            ffi::sdxl_unet_forward_residuals(unet, ptr::null_mut(), d_x.f32_ptr(), d_t.ptr as *const i32, d_c.f32_ptr(), d_y.f32_ptr(), b as c_int,
+                                             h as c_int, w as c_int, n_ctx as c_int, d_r.f32_ptr(), scale, out.f32_mut())
+        })?;
+        Ok(bridge::download(&out, [b, c_in, h, w], &device))
     }
     /// Engine options of this handle's UNet (no reference counterpart; results stay within the same tolerance class):
     /// split-CFG = the CFG pair of `forward_diffuser` (`:523-537`) as two concurrent batch-1 chains; fused cross-attention

@@ -117,6 +117,9 @@ ABI_SYMBOLS = [
     "sdxl_unet_profile", "sdxl_unet_eager_forward_ms", "sdxl_bench_igemm", "sdxl_bench_attention", "sdxl_debug_set", "sdxl_debug_warm_schedule", "sdxl_debug_upsample_fold", "sdxl_debug_weight_layout", "sdxl_conv2d_upsample_folded", "sdxl_debug_igemm_select", "sdxl_debug_attn_select",
     "sdxl_group_norm", "sdxl_layer_norm", "sdxl_conv2d", "sdxl_linear", "sdxl_gemv", "sdxl_timestep_embedding", "sdxl_vae_attn_block", "sdxl_vae_res_block", "sdxl_layer_norm_linear", "sdxl_ln_query_cross_attention", "sdxl_conv2d_group_norm",
     "sdxl_transformer_projection",
+    "sdxl_unet_skip_count", "sdxl_unet_skip_shape", "sdxl_unet_forward_residuals", "sdxl_skip_residual_add",
+    "sdxl_controlnet_config_default", "sdxl_controlnet_param_count", "sdxl_controlnet_param_spec", "sdxl_controlnet_create", "sdxl_controlnet_create_f16",
+    "sdxl_controlnet_create_synthetic", "sdxl_controlnet_destroy", "sdxl_controlnet_embed_hint", "sdxl_controlnet_forward",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
     "sdxl_clip_config_clip_l", "sdxl_clip_config_open_clip_bigg", "sdxl_clip_param_count", "sdxl_clip_param_spec",
     "sdxl_clip_create", "sdxl_clip_create_synthetic", "sdxl_clip_destroy", "sdxl_clip_forward_hidden",
@@ -174,6 +177,13 @@ def lib() -> ctypes.CDLL:
             l.sdxl_solver_coefficients_pred.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
             l.sdxl_sampler_step_replay_pred.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(l, "sdxl_unet_forward_residuals"):
+            l.sdxl_unet_skip_shape.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+            l.sdxl_unet_forward_residuals.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
+            l.sdxl_skip_residual_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
+            l.sdxl_controlnet_destroy.restype = None
+            l.sdxl_controlnet_destroy.argtypes = [ctypes.c_void_p]
+            l.sdxl_controlnet_config_default.restype = None
         _lib = l
     return _lib
 
@@ -287,6 +297,35 @@ def unet_param_specs(cfg: UNetConfig) -> List[ParamSpec]:
     l = lib()
     return _specs(lambda: l.sdxl_unet_param_count(ctypes.byref(c)),
                   lambda i, *a: l.sdxl_unet_param_spec(ctypes.byref(c), i, *a))
+
+
+class _ControlNetConfigC(ctypes.Structure):
+    _fields_ = [("unet", _UNetConfigC), ("hint_in_channels", ctypes.c_int32), ("hint_channels", ctypes.c_int32 * 4)]
+
+
+@dataclass
+class ControlNetConfig:
+    """sdxl_controlnet_config: a ControlNet for the UNet `unet` -- that UNet's encoder, a hint embedder (hint_in_channels -> hint_channels ->
+    model_channels, 8x down) and one 1x1 convolution per residual tensor"""
+    unet: UNetConfig
+    hint_in_channels: int = 3
+    hint_channels: Tuple[int, int, int, int] = (16, 32, 96, 256)
+
+    def to_c(self) -> _ControlNetConfigC:
+        c = _ControlNetConfigC()
+        c.unet = self.unet.to_c()
+        c.hint_in_channels = int(self.hint_in_channels)
+        for i, v in enumerate(self.hint_channels):
+            c.hint_channels[i] = int(v)
+        return c
+
+
+def controlnet_param_specs(cfg: ControlNetConfig) -> List[ParamSpec]:
+    """host-only (no GPU needed): the order / layouts sdxl_controlnet_create expects its flat weight buffer in"""
+    c = cfg.to_c()
+    l = lib()
+    return _specs(lambda: l.sdxl_controlnet_param_count(ctypes.byref(c)),
+                  lambda i, *a: l.sdxl_controlnet_param_spec(ctypes.byref(c), i, *a))
 
 
 def vae_param_specs(cfg: VAEConfig, encoder: bool) -> List[ParamSpec]:
@@ -517,6 +556,28 @@ class UNet:
                                       ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def forward_residuals(self, x, timesteps, context, label, residuals, scale: float = 1.0):
+        """sdxl_unet_forward_residuals: forward with ControlNet skip residuals given by the caller -- a list of unet_skip_shapes(cfg, H, W) tensors
+        [B,C,h,w] (one per input entry, then the middle block's); scale * r is added into what the decoder reads, in one launch behind the middle
+        block.  The handle keeps them attached (another scale or other values replay the captured graph); residuals=None, or forward(), detaches."""
+        torch = _torch()
+        x, px = _dev(x)
+        ts, pt = _dev(timesteps, torch.int32)
+        context, pc = _dev(context)
+        label, pl = _dev(label)
+        B, _, H, W = x.shape
+        flat, pr = None, None
+        if residuals is not None:
+            shapes = unet_skip_shapes(self.cfg, H, W)
+            got = [tuple(r.shape) for r in residuals]
+            if got != [(B,) + s for s in shapes]:
+                raise InvalidArgument(f"forward_residuals: residuals must have the shapes {[(B,) + s for s in shapes]}, got {got}")
+            flat, pr = _dev(torch.cat([r.to(torch.float32).reshape(-1) for r in residuals]))
+        out = torch.empty((B, self.cfg.out_channels, H, W), device=x.device, dtype=torch.float32)
+        _check_invalid(lib().sdxl_unet_forward_residuals(self.h, _stream(), px, pt, pc, pl, B, H, W, int(context.shape[1]), pr, float(scale),
+                                                         ctypes.c_void_p(out.data_ptr())))
+        return out
+
     BLOCK_SECTIONS = {"input": 0, "middle": 1, "output": 2, "head": 3}
 
     def run_block(self, section: str, index: int, x, emb, context):
@@ -544,7 +605,7 @@ class UNet:
 
     def set_split_cfg(self, enabled: bool, release_offset: int = 0):
         """per-handle: run the CFG pair (batch-2 forward) as two concurrent batch-1 chains; bit-identical results"""
-        _check(lib().sdxl_unet_set_split_cfg(self.h, int(enabled), int(release_offset)))
+        _check_invalid(lib().sdxl_unet_set_split_cfg(self.h, int(enabled), int(release_offset)))      # (refused while skip residuals are attached)
 
     def set_fused_cross_attention(self, enabled: bool):
         """per-handle (default on): cross-attention inside the query projection's epilogue"""
@@ -590,6 +651,62 @@ class UNet:
         if getattr(self, "_owned", False) and getattr(self, "h", None) and _lib is not None:
             _lib.sdxl_unet_destroy(self.h)
             self.h = None
+
+
+class ControlNet:
+    """A ControlNet (Zhang et al. 2023; sgm ControlNet / diffusers ControlNetModel) for the UNet cfg.unet: DTYPE_F32, DTYPE_F16 or DTYPE_F32_SPLIT, its
+    residuals go to a UNet of the same configuration and dtype through UNet.forward_residuals.  weights: flat fp32 or f16 array in controlnet_param_specs order; None: the
+    synthetic seed."""
+
+    def __init__(self, ctx: Context, cfg: ControlNetConfig, dtype: int = DTYPE_F16, weights: Optional[np.ndarray] = None, seed: Optional[int] = None):
+        self.ctx, self.cfg, self.dtype = ctx, cfg, dtype
+        self.h = ctypes.c_void_p()
+        c = cfg.to_c()
+        if weights is None:
+            _check_invalid(lib().sdxl_controlnet_create_synthetic(ctx.h, ctypes.byref(c), dtype, ctypes.c_uint64(seed or 0), ctypes.byref(self.h)))
+        elif np.asarray(weights).dtype == np.float16:
+            w = np.ascontiguousarray(weights)
+            _check_invalid(lib().sdxl_controlnet_create_f16(ctx.h, ctypes.byref(c), dtype, w.ctypes.data_as(ctypes.c_void_p), ctypes.byref(self.h)))
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            _check_invalid(lib().sdxl_controlnet_create(ctx.h, ctypes.byref(c), dtype, w.ctypes.data_as(ctypes.c_void_p), ctypes.byref(self.h)))
+
+    def embed_hint(self, hint):
+        """input_hint_block: hint [n, hint_in, H8, W8] -> [n, model_channels, H8 / 8, W8 / 8]"""
+        torch = _torch()
+        hint, ph = _dev(hint)
+        n, _, H8, W8 = hint.shape
+        out = torch.empty((n, self.cfg.unet.model_channels, H8 // 8, W8 // 8), device=hint.device, dtype=torch.float32)
+        _check_invalid(lib().sdxl_controlnet_embed_hint(self.h, _stream(), ph, n, H8, W8, ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def forward(self, x, timesteps, context, label, hint):
+        """the control forward: x [B,4,H,W], timesteps [B] int, context [B,n_ctx,ctx], label [B,adm], hint [B,hint_in,8H,8W] -> the list of residual
+        tensors unet_skip_shapes(cfg.unet, H, W), what UNet.forward_residuals takes"""
+        torch = _torch()
+        x, px = _dev(x)
+        ts, pt = _dev(timesteps, torch.int32)
+        context, pc = _dev(context)
+        label, pl = _dev(label)
+        hint, ph = _dev(hint)
+        B, _, H, W = x.shape
+        if tuple(hint.shape) != (B, self.cfg.hint_in_channels, 8 * H, 8 * W):
+            raise InvalidArgument(f"ControlNet.forward: the hint must be {(B, self.cfg.hint_in_channels, 8 * H, 8 * W)}, got {tuple(hint.shape)}")
+        shapes = unet_skip_shapes(self.cfg.unet, H, W)
+        flat = torch.empty(sum(B * c * h * w for c, h, w in shapes), device=x.device, dtype=torch.float32)
+        _check_invalid(lib().sdxl_controlnet_forward(self.h, _stream(), px, pt, pc, pl, ph, B, H, W, int(context.shape[1]), ctypes.c_void_p(flat.data_ptr())))
+        out, o = [], 0
+        for c, h, w in shapes:
+            out.append(flat[o:o + B * c * h * w].view(B, c, h, w))
+            o += B * c * h * w
+        return out
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().sdxl_controlnet_destroy(self.h)
+        except Exception:
+            pass
 
 
 @dataclass
@@ -1383,6 +1500,51 @@ def timestep_embedding(ctx: Context, t, dim: int):
     out = torch.empty((n, dim), device=t.device, dtype=torch.float32)
     _check(lib().sdxl_timestep_embedding(ctx.h, _stream(), pt, n, int(dim), ctypes.c_void_p(out.data_ptr())))
     return out
+
+
+def unet_skip_shapes(cfg: UNetConfig, H: int, W: int) -> List[Tuple[int, int, int]]:
+    """(C, h, w) of every ControlNet residual tensor of a UNet on an H x W latent (sdxl_unet_skip_count / _skip_shape; host logic, no GPU needed):
+    one per input entry, then the middle block's"""
+    c = cfg.to_c()
+    n = lib().sdxl_unet_skip_count(ctypes.byref(c))
+    if n < 0:
+        raise EngineError(lib().sdxl_last_error().decode())
+    out = []
+    chw = (ctypes.c_int64 * 3)()
+    for i in range(n):
+        _check_invalid(lib().sdxl_unet_skip_shape(ctypes.byref(c), i, int(H), int(W), chw))
+        out.append((int(chw[0]), int(chw[1]), int(chw[2])))
+    return out
+
+
+def skip_residual_add(ctx: Context, segments, scale):
+    """sdxl_skip_residual_add, the UNet's per-step ControlNet add on caller tensors, in place and in ONE launch: for every (dst, src) of `segments`
+    (at most 16), dst[r, c] = round(fma(scale, src[r, c], dst[r, c])).  dst: a [rows, C] CUDA view whose columns are contiguous (a column slice of a
+    wider row-major buffer), src: a dense [rows, C] tensor; all float32 or all float16.  scale: a float or a one-element fp32 CUDA tensor.
+    InvalidArgument (nothing written): C % 8 != 0, a slice or a row pitch that is not 16-byte aligned."""
+    torch = _torch()
+    segments = list(segments)
+    n = len(segments)
+    if n < 1:
+        raise InvalidArgument("skip_residual_add: at least one segment")
+    dt = segments[0][0].dtype
+    if dt not in (torch.float32, torch.float16):
+        raise InvalidArgument("skip_residual_add: float32 or float16 tensors")
+    for d, s in segments:
+        if not (d.is_cuda and s.is_cuda) or d.dtype != dt or s.dtype != dt or d.dim() != 2 or tuple(s.shape) != tuple(d.shape) or not s.is_contiguous() \
+                or (d.shape[1] > 1 and d.stride(1) != 1) or d.stride(0) < d.shape[1]:
+            raise InvalidArgument("skip_residual_add: dst must be a [rows, C] view with contiguous columns and src a dense [rows, C] tensor, one dtype, on the GPU")
+    if not torch.is_tensor(scale):
+        scale = torch.tensor([float(scale)], dtype=torch.float32, device=segments[0][0].device)
+    scale, ps = _dev(scale)
+    ptrs = ctypes.c_void_p * n
+    i64 = ctypes.c_int64 * n
+    dst = ptrs(*[d.data_ptr() for d, _ in segments])
+    src = ptrs(*[s.data_ptr() for _, s in segments])
+    ld = i64(*[int(d.stride(0)) for d, _ in segments])
+    rows = i64(*[int(d.shape[0]) for d, _ in segments])
+    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
+    _check_invalid(lib().sdxl_skip_residual_add(ctx.h, _stream(), n, dst, ld, src, rows, cols, ps, DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
 
 
 def _opt(t):

@@ -354,6 +354,29 @@ int sdxl_unet_forward(sdxl_unet* u, void* stream, const float* x, const int32_t*
   u->u->forward_nchw(x, timesteps, context, n_ctx, label, B, H, W, out, pick(u->ctx, stream));
   API_END
 }
+int sdxl_unet_skip_count(const sdxl_unet_config* cfg) {
+  try {
+    std::vector<BlockDesc> inp, out; BlockDesc mid;
+    unet_block_plan(to_cfg(cfg), inp, mid, out);
+    return (int)inp.size() + 1;
+  } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int sdxl_unet_skip_shape(const sdxl_unet_config* cfg, int index, int H, int W, int64_t chw[3]) {
+  API_BEGIN
+  if (!cfg || !chw) throw InvalidArgumentError("skip shape: null argument");
+  const std::vector<UNet::SkipShape> sh = UNet::skip_shapes(to_cfg(cfg), H, W);
+  if (index < 0 || index >= (int)sh.size()) throw InvalidArgumentError("skip shape: index outside 0 .. sdxl_unet_skip_count - 1");
+  chw[0] = sh[index].C; chw[1] = sh[index].h; chw[2] = sh[index].w;
+  API_END
+}
+int sdxl_unet_forward_residuals(sdxl_unet* u, void* stream, const float* x, const int32_t* timesteps, const float* context, const float* label,
+                                int B, int H, int W, int n_ctx, const float* residuals, float scale, float* out) {
+  API_BEGIN
+  SDXL_REQUIRE(u && x && timesteps && context && label && out, "null argument");
+  use(u->ctx);
+  u->u->forward_residuals_nchw(x, timesteps, context, n_ctx, label, B, H, W, residuals, scale, out, pick(u->ctx, stream));
+  API_END
+}
 int sdxl_unet_block(sdxl_unet* u, void* stream, int section, int index, const float* x, const float* emb, const float* context, int B, int c_in, int h,
                     int w, int n_ctx, float* out, int64_t out_shape[4]) {
   API_BEGIN
@@ -777,6 +800,90 @@ int sdxl_diffuser_get_guidance(sdxl_diffuser* d, sdxl_guidance* out) {
   out->mode = o.mode; out->rescale = o.rescale; out->n_scales = o.n_scales; out->t_lo = o.t_lo; out->t_hi = o.t_hi;
   for (int b = 0; b < kMaxSeeds; ++b) out->scales[b] = o.scales[b];
   return SDXL_OK;
+}
+// ---------------------------------------------------------------------------------------------- ControlNet
+static ControlCfg to_ccfg_control(const sdxl_controlnet_config* c) {
+  SDXL_REQUIRE(c != nullptr, "null config");
+  ControlCfg k;
+  k.unet = to_cfg(&c->unet);
+  k.hint_in = c->hint_in_channels;
+  SDXL_REQUIRE(k.hint_in >= 1 && k.hint_in <= 64, "controlnet: hint_in_channels out of range (1..64)");
+  for (int i = 0; i < 4; ++i) {
+    k.hint_channels[i] = c->hint_channels[i];
+    SDXL_REQUIRE(k.hint_channels[i] >= 8 && k.hint_channels[i] % 8 == 0 && k.hint_channels[i] <= 4096, "controlnet: hint_channels must be multiples of 8 in 8..4096");
+  }
+  return k;
+}
+static int controlnet_create_impl(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, WeightSource& src, sdxl_controlnet** out) {
+  if (!ctx || !out || !cfg) throw InvalidArgumentError("controlnet: null argument");
+  if (dtype != SDXL_DTYPE_F32 && dtype != SDXL_DTYPE_F16 && dtype != SDXL_DTYPE_F32_SPLIT)
+    throw InvalidArgumentError("controlnet: dtype " + std::to_string(dtype) + " is not supported: a control net takes SDXL_DTYPE_F32, SDXL_DTYPE_F16 or SDXL_DTYPE_F32_SPLIT");
+  if (cfg->unet.is_refiner != 0) throw InvalidArgumentError("controlnet: there is no refiner ControlNet (unet.is_refiner != 0)");
+  use(ctx);
+  int cdt, sdt; dtypes(dtype, cdt, sdt);
+  const ControlCfg cc = to_ccfg_control(cfg);
+  create_handle(ctx, out, [&](sdxl_controlnet& h) { h.c = new UNet(cc, cdt, sdt, src, ctx->stream); });
+  return SDXL_OK;
+}
+void sdxl_controlnet_config_default(const sdxl_unet_config* unet, sdxl_controlnet_config* cfg) {
+  if (!cfg) return;
+  std::memset(cfg, 0, sizeof(*cfg));
+  if (unet) cfg->unet = *unet;
+  cfg->hint_in_channels = 3;
+  const int hc[4] = {16, 32, 96, 256};
+  for (int i = 0; i < 4; ++i) cfg->hint_channels[i] = hc[i];
+}
+int sdxl_controlnet_param_count(const sdxl_controlnet_config* cfg) {
+  try { return (int)controlnet_param_specs(to_ccfg_control(cfg)).size(); } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int sdxl_controlnet_param_spec(const sdxl_controlnet_config* cfg, int index, const char** name, int* ndim, int64_t shape[4], int* kind,
+                               float* sc, float* mean) {
+  API_BEGIN
+  SDXL_REQUIRE(cfg != nullptr, "null config");
+  static thread_local std::vector<ParamSpec> cache; static thread_local sdxl_controlnet_config key;
+  if (cache.empty() || std::memcmp(&key, cfg, sizeof(key)) != 0) { cache = controlnet_param_specs(to_ccfg_control(cfg)); key = *cfg; }
+  return spec_out(cache, index, name, ndim, shape, kind, sc, mean);
+  API_END
+}
+int sdxl_controlnet_create(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, const float* weights_flat, sdxl_controlnet** out) {
+  API_BEGIN
+  if (!weights_flat || !cfg) throw InvalidArgumentError("controlnet: null argument");
+  const std::vector<ParamSpec> specs = controlnet_param_specs(to_ccfg_control(cfg));
+  FlatSource src(weights_flat, specs);
+  return controlnet_create_impl(ctx, cfg, dtype, src, out);
+  API_END
+}
+int sdxl_controlnet_create_f16(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, const uint16_t* weights_flat_f16, sdxl_controlnet** out) {
+  API_BEGIN
+  if (!ctx || !weights_flat_f16 || !cfg) throw InvalidArgumentError("controlnet: null argument");
+  use(ctx);
+  const std::vector<ParamSpec> specs = controlnet_param_specs(to_ccfg_control(cfg));
+  FlatSourceF16 src(weights_flat_f16, specs);
+  return controlnet_create_impl(ctx, cfg, dtype, src, out);
+  API_END
+}
+int sdxl_controlnet_create_synthetic(sdxl_ctx* ctx, const sdxl_controlnet_config* cfg, int dtype, uint64_t seed, sdxl_controlnet** out) {
+  API_BEGIN
+  SyntheticSource src(seed);
+  return controlnet_create_impl(ctx, cfg, dtype, src, out);
+  API_END
+}
+void sdxl_controlnet_destroy(sdxl_controlnet* c) { delete c; }
+int sdxl_controlnet_embed_hint(sdxl_controlnet* c, void* stream, const float* hint, int n, int H8, int W8, float* out) {
+  API_BEGIN
+  if (!c || !hint || !out) throw InvalidArgumentError("controlnet: null argument");
+  if (n < 1 || n > 8 || H8 <= 0 || W8 <= 0 || H8 % 8 != 0 || W8 % 8 != 0) throw InvalidArgumentError("controlnet: n must be in 1..8 and the hint 8 x a valid latent size");
+  use(c->ctx);
+  c->c->embed_hint_nchw(hint, n, H8 / 8, W8 / 8, out, pick(c->ctx, stream));
+  API_END
+}
+int sdxl_controlnet_forward(sdxl_controlnet* c, void* stream, const float* x, const int32_t* timesteps, const float* context, const float* label,
+                            const float* hint, int B, int H, int W, int n_ctx, float* residuals_out) {
+  API_BEGIN
+  if (!c || !x || !timesteps || !context || !label || !hint || !residuals_out) throw InvalidArgumentError("controlnet: null argument");
+  use(c->ctx);
+  c->c->control_forward_nchw(x, timesteps, context, n_ctx, label, hint, B, H, W, residuals_out, pick(c->ctx, stream));
+  API_END
 }
 int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int n, int HW, const float* scales, float rescale,
                              float* factors_out) {

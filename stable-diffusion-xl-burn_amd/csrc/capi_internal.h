@@ -7,6 +7,7 @@
 struct sdxl_ctx { int device = 0; hipStream_t stream = nullptr; };
 struct sdxl_unet { sdxl_ctx* ctx = nullptr; sdxl::UNet* u = nullptr; bool owned = true; };
 struct sdxl_diffuser { sdxl_ctx* ctx = nullptr; sdxl::Diffuser* d = nullptr; sdxl_unet view; };
+struct sdxl_controlnet { sdxl_ctx* ctx = nullptr; sdxl::UNet* c = nullptr; ~sdxl_controlnet() { delete c; } };      // a UNet in control mode
 struct sdxl_vae { sdxl_ctx* ctx = nullptr; sdxl::Vae* v = nullptr; };
 struct sdxl_clip { sdxl_ctx* ctx = nullptr; sdxl::ClipText* c = nullptr; };
 

@@ -506,6 +506,33 @@ int sdxl_timestep_embedding(sdxl_ctx* ctx, void* stream, const float* t, int n, 
   SDXL_HIP(hipStreamSynchronize(s));
   API_END
 }
+// the per-step add of the ControlNet skip residuals (UNet::run behind the middle block) on caller buffers: the table is checked on the host, uploaded,
+// and the one launch walks it
+int sdxl_skip_residual_add(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src,
+                           const int64_t* rows, const int32_t* C, const float* scale_dev, int dtype) {
+  API_BEGIN
+  if (!ctx || !dst || !dst_ld || !src || !rows || !C || !scale_dev) throw InvalidArgumentError("skip residual add: null argument");
+  if (n_segments < 1 || n_segments > 16) throw InvalidArgumentError("skip residual add: n_segments must be in 1..16");
+  if (dtype != SDXL_DTYPE_F32 && dtype != SDXL_DTYPE_F16) throw InvalidArgumentError("skip residual add: the dtype must be SDXL_DTYPE_F32 or SDXL_DTYPE_F16");
+  const int dt = dtype == SDXL_DTYPE_F16 ? DT_F16 : DT_F32;
+  SkipSeg table[16];
+  for (int i = 0; i < n_segments; ++i) {
+    if (rows[i] < 0 || rows[i] > 0x7fffffff || dst_ld[i] < 0) throw InvalidArgumentError("skip residual add: rows must be in 0..2^31-1 and dst_ld >= C");
+    table[i] = SkipSeg{dst[i], src[i], (long long)dst_ld[i], (int)rows[i], (int)C[i], 0ull};
+  }
+  unsigned long long total = 0;
+  if (const char* bad = skip_table_check(table, n_segments, dt, &total)) throw InvalidArgumentError(bad);
+  use(ctx);
+  hipStream_t s = pick(ctx, stream);
+  Tmp tmp;
+  SkipSeg* table_dev = (SkipSeg*)tmp.get(sizeof(table));
+  SDXL_HIP(hipMemcpyAsync(table_dev, table, n_segments * sizeof(SkipSeg), hipMemcpyHostToDevice, s));
+  (void)hipGetLastError();
+  launch_skip_residual_add(table_dev, n_segments, total, scale_dev, dt, s);
+  SDXL_HIP(hipGetLastError());
+  SDXL_HIP(hipStreamSynchronize(s));
+  API_END
+}
 int sdxl_layer_norm_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps,
                            const float* weight, const float* bias, int M, int K, int N, int geglu, int dtype, float* out) {
   API_BEGIN

@@ -842,6 +842,72 @@ void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// ControlNet skip residuals: every segment of the table in one launch (kernels.h SkipSeg).  HBM-bound: one 16-byte chunk per lane and trip (8 halfs /
+// 4 floats), consecutive lanes on consecutive chunks of the flattened segment list, a grid capped at 2048 workgroups striding over the rest.  A lane's
+// chunk index only grows, so it walks the table forwards (a handful of uniform loads per segment change); one fp32 fma and one rounding per element.
+template <typename T>
+__global__ __launch_bounds__(256) void skip_residual_add_kernel(const SkipSeg* __restrict__ table, int n_seg, unsigned long long total,
+                                                                const float* __restrict__ scale_dev) {
+  constexpr int E = 16 / (int)sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(E)));
+  const float sc = *scale_dev;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  int si = 0;
+  SkipSeg g = table[0];
+  unsigned long long end = n_seg > 1 ? table[1].first : total;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    while (i >= end) {      // (i < total = the last segment's end: si stays inside the table)
+      ++si;
+      g = table[si];
+      end = si + 1 < n_seg ? table[si + 1].first : total;
+    }
+    const unsigned l = (unsigned)(i - g.first);      // (skip_table_check: a segment has fewer than 2^32 chunks -- a 32-bit division)
+    const unsigned cpr = (unsigned)g.C / E;
+    const unsigned row = l / cpr;
+    const unsigned cc = l - row * cpr;
+    vec_t* d = reinterpret_cast<vec_t*>(reinterpret_cast<T*>(g.dst) + (unsigned long long)row * (unsigned long long)g.dst_ld) + cc;
+    const vec_t a = reinterpret_cast<const vec_t*>(g.src)[l];
+    vec_t v = *d;
+#pragma unroll
+    for (int j = 0; j < E; ++j) v[j] = (T)fmaf(sc, (float)a[j], (float)v[j]);
+    *d = v;
+  }
+}
+// SiLU in place over a dense tensor (a control net's hint embedder, once per hint: off the per-step path and left plain)
+__global__ void silu_inplace_kernel(void* p, int dt, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) st_f(p, i, dt, silu_f(ld_f(p, i, dt)));
+}
+void launch_silu_inplace(void* p, int dt, size_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(silu_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, dt, n);
+}
+const char* skip_table_check(SkipSeg* t, int n_seg, int dt, unsigned long long* total_chunks) {
+  if (dt != DT_F32 && dt != DT_F16) return "skip residual add: the dtype must be fp32 or f16 (the stream dtype of the UNet)";
+  if (n_seg < 1 || !t) return "skip residual add: at least one segment";
+  const size_t es = dt_size(dt);
+  unsigned long long total = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (t[i].rows < 0 || t[i].C <= 0) return "skip residual add: rows must be >= 0 and C > 0";
+    if (t[i].C % 8 != 0) return "skip residual add: C must be a multiple of 8";
+    if (t[i].dst_ld < t[i].C) return "skip residual add: dst_ld must be >= C";
+    if (!t[i].dst || !t[i].src) return "skip residual add: null segment pointer";
+    if (((uintptr_t)t[i].dst | (uintptr_t)t[i].src | (uintptr_t)((size_t)t[i].dst_ld * es)) & 15) return "skip residual add: dst, src and the row pitch of dst must be 16-byte aligned";
+    const unsigned long long chunks = (unsigned long long)t[i].rows * (unsigned long long)((size_t)t[i].C * es / 16);
+    if (chunks >> 32) return "skip residual add: a segment must be smaller than 2^32 16-byte chunks";
+    t[i].first = total;
+    total += chunks;
+  }
+  if (total_chunks) *total_chunks = total;
+  return nullptr;
+}
+void launch_skip_residual_add(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scale_dev, int dt, hipStream_t s) {
+  if (!total_chunks) return;
+  const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
+  if (dt == DT_F16) hipLaunchKernelGGL(skip_residual_add_kernel<half_t>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scale_dev);
+  else hipLaunchKernelGGL(skip_residual_add_kernel<float>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scale_dev);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // image post-process, stablediffusion/mod.rs:210-230: ((x+1)/2)*255 -> clamp [0,255] -> truncating u8 cast
 __global__ void to_u8_kernel(const void* src, int dt, int lds_, unsigned char* dst, size_t pixels) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

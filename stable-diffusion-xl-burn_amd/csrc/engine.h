@@ -65,6 +65,9 @@ enum BlockKind { BK_CONV, BK_RES, BK_DOWN, BK_REST, BK_RESTU, BK_RESU };
 struct BlockDesc { int kind = 0, c_in = 0, c_emb = 0, c_out = 0, n_head = 0, depth = 0; };
 void unet_block_plan(const UNetCfg& cfg, std::vector<BlockDesc>& inp, BlockDesc& mid, std::vector<BlockDesc>& out);
 std::vector<ParamSpec> unet_param_specs(const UNetCfg& cfg);
+// a ControlNet for the UNet `unet` (sdxl_controlnet_config): that UNet's encoder + hint embedder + one 1x1 convolution per residual tensor
+struct ControlCfg { UNetCfg unet; int hint_in = 3; int hint_channels[4] = {16, 32, 96, 256}; };
+std::vector<ParamSpec> controlnet_param_specs(const ControlCfg& cfg);
 std::vector<ParamSpec> vae_decoder_param_specs(const VaeCfg& cfg);
 std::vector<ParamSpec> vae_encoder_param_specs(const VaeCfg& cfg);
 std::vector<ParamSpec> clip_param_specs(const ClipCfg& cfg);
@@ -437,6 +440,32 @@ class UNet {
   enum Section { SEC_INPUT = 0, SEC_MIDDLE = 1, SEC_OUTPUT = 2, SEC_HEAD = 3 };
   void run_block(int section, int index, const float* x, const float* emb, const float* context, int n_ctx, int B, int c_in, int h, int w, float* out,
                  int64_t out_shape[4], hipStream_t s);
+  // ControlNet skip residuals.  The residual tensors of a UNet: one per input entry (its output shape), then the middle block's.
+  struct SkipShape { int C = 0, h = 0, w = 0; };
+  static std::vector<SkipShape> skip_shapes(const UNetCfg& cfg, int H, int W);      // host logic only; a size no forward has: InvalidArgumentError
+  // nullptr where this handle can add residuals, else why not (split CFG on, a dtype mode without a test); host logic only
+  const char* residuals_refused() const;
+  // forward_nchw with residuals given by the caller: all skip_shapes tensors back to back, NCHW fp32 (device) -> staging buffers in the stream dtype,
+  // attached until clear_residuals / forward_nchw; residuals == nullptr: detached.  Refusals (InvalidArgumentError) come before any launch.
+  void forward_residuals_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, int B, int H, int W,
+                              const float* residuals, float scale, float* out, hipStream_t s);
+  void clear_residuals();
+  bool has_residuals() const { return res_key_ != 0; }
+  // A control net is this class in control mode: the embeddings, input entries and middle block through the same loaders, run_entry, set_context and
+  // K / V caches, no decoder; every entry's output (entry 0: + the hint features, the residual input of its convolution) goes through its 1x1
+  // convolution into a residual buffer that persists for the plan.  forward() then leaves the skip_shapes tensors in control_residuals().
+  UNet(const ControlCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st);
+  bool is_control() const { return control_; }
+  const ControlCfg& control_cfg() const { return ccfg_; }
+  // the hint embedder, once per hint: hint NCHW fp32 [n][hint_in][8H][8W] (device) -> features NHWC [B][H*W][mc] in the stream dtype for the plan
+  // (B, H, W); entry n + b of a batch B = 2n (the CFG pair) uses the hint of entry b.  Never per step.
+  void set_hint(const float* hint, int n, int B, int H, int W, hipStream_t s);
+  const void* hint_features() const { return hint_g_; }
+  const std::vector<void*>& control_residuals() const { return ctl_res_; }
+  // reference-shaped entries: hint -> features NCHW fp32 [n][mc][H][W]; the whole control forward -> all residual tensors back to back, NCHW fp32
+  void embed_hint_nchw(const float* hint, int n, int H, int W, float* out, hipStream_t s);
+  void control_forward_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, const float* hint, int B, int H, int W,
+                            float* residuals_out, hipStream_t s);
   void* unet_in(int B, int H, int W);     // ensures the plan exists
   float* eps_out() { return eps_; }
   int compute_dt() const { return cdt_; }
@@ -448,7 +477,10 @@ class UNet {
   void set_use_graph(bool g) { use_graph_ = g; }
   // per-handle option: run the two entries of a batch-2 forward (the CFG pair) as two concurrent batch-1 chains on two
   // streams, the second released after `release_offset` GEMM launches of the first; bit-identical results
-  void set_split_cfg(bool on, int release_offset) { split_cfg_ = on; split_offset_ = release_offset; }
+  void set_split_cfg(bool on, int release_offset) {
+    if (on && res_key_) throw InvalidArgumentError("set_split_cfg: split CFG cannot be combined with attached skip residuals (ControlNet); detach them first");
+    split_cfg_ = on; split_offset_ = release_offset;
+  }
   void set_fused_cross_attention(bool on) { fuse_xattn_ = on; }
   void set_gn_from_producer(bool on) { gn_from_producer_ = on; }   // re-plans (arena + graph) on the next forward, like the two options above
   // one eager forward of the current plan/context with hipEvents around every launch, summed per kernel class
@@ -472,7 +504,8 @@ class UNet {
   void run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb);
   struct Skips { std::vector<Act> cat; std::vector<int> cx, hs_h, hs_w; };      // concat buffers, the column where each one's skip half starts, resolution after every input entry
   void alloc_skips(Exec& ex, int B, int H, int W, Skips& k);
-  void run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si);      // the body of one plan entry (run's loops, run_block)
+  // the body of one plan entry (run's loops, run_block); add: a tensor of dst's shape added to the output of a Conv entry (a control net's hint features)
+  void run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si, const Act* add = nullptr);
   const float* res_block(Exec& ex, const ResBlockW& w, const Act& x, int B, int H, int W, const Act& out, float* out_gn_part = nullptr);
   void spatial_transformer(Exec& ex, const STW& w, int st_index, const Act& x, int B, int H, int W);
 
@@ -480,6 +513,7 @@ class UNet {
   int cdt_, sdt_;
   int mix_ = 0;                          // MixClass bits (split-operand engine): classes on plain f16 operands
   bool mix_knob_ = false;                // the bits came from sdxl_debug_set "mix_classes" (no f16-exactness fallback)
+  bool mix_mode_ = false;                // the handle was created in a SDXL_DTYPE_F32_SPLIT_MIX* / _F16W mode, whatever the fallback left in mix_
   bool attn16_ = false;                  // some transformer runs its self-attention on the f16 kernels (key-split workspace)
   DeviceArena warena_;
   std::vector<BlockW> inp_, out_;
@@ -523,6 +557,27 @@ class UNet {
   DeviceArena act2_;
   hipGraphExec_t graph_ = nullptr;
   const float* graph_t_ = nullptr; int graph_ts_ = 0; int plan_runs_ = 0;
+  // skip residuals: sources (dense NHWC rows in the stream dtype, one per skip_shapes entry) for the plan res_B_ x res_H_ x res_W_, the segment table
+  // run's one launch walks and the scale it reads, both in device memory.  res_key_: 0 = none attached, else a number that changes whenever the set of
+  // sources does -- part of the graph key (graph_res_key_), so attaching and detaching re-capture and a new scale or new values do not.
+  void stage_residuals(const float* residuals, int B, int H, int W, float scale, hipStream_t s);
+  void prepare_residuals();      // (re)builds the table for the current plan's concat buffers; outside any capture
+  int res_key_ = 0, res_serial_ = 0, graph_res_key_ = 0;
+  int res_B_ = 0, res_H_ = 0, res_W_ = 0;
+  DeviceArena res_arena_;
+  std::vector<const void*> res_src_;
+  SkipSeg* res_table_ = nullptr; float* res_scale_ = nullptr;
+  int res_segs_ = 0; unsigned long long res_chunks_ = 0; bool res_table_ok_ = false;
+  const void* res_dst_mid_ = nullptr;      // the table's last destination: run checks that its concat buffers are where the table says
+  // control mode
+  bool control_ = false;
+  ControlCfg ccfg_;
+  Lin hint_conv_[8]; std::vector<Lin> zero_; Lin mid_out_;
+  void run_control(Exec& ex, int B, int H, int W, void* in);
+  std::vector<void*> ctl_res_;             // persistent residual buffers of the plan (dense NHWC, stream dtype), skip_shapes order
+  DeviceArena hint_arena_;
+  void* hint_g_ = nullptr; int hint_n_ = 0, hint_B_ = 0, hint_H_ = 0, hint_W_ = 0;
+  const void* graph_hint_ = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------ VAE

@@ -405,6 +405,17 @@ void launch_cfg_rescale_factors(const void* eps, int eps_dt, int eps_ld, int n, 
 void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n, int HW, hipStream_t s);
 // noised = latent*sa + noise*sb   (refine_latent :363-367)
 void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb, size_t n, hipStream_t s);
+// ControlNet skip residuals: ONE launch adds every residual tensor of a step into the tensor the decoder reads -- the skip halves of the
+// concat buffers and the middle block's output.  A segment is `rows` rows of C channels: src dense [rows][C], dst rows of dst_ld elements, both in the
+// dtype `dt` (DT_F32 / DT_F16) of the launch;  dst = round_to_dt(fma(*scale_dev, (float)src, (float)dst)).  The table lives in device memory (fixed
+// address: a captured graph keeps it), the scale too (changing it re-captures nothing).  `first` = 16-byte chunks of the segments before this one
+// (filled by skip_table_check).  Segments must not overlap; the result does not depend on the grid.
+struct SkipSeg { void* dst; const void* src; long long dst_ld; int rows; int C; unsigned long long first; };
+// host logic only: nullptr where every segment can run -- rows >= 0, C > 0, C % 8 == 0, dst_ld >= C, dst / src / row pitch 16-byte aligned, fewer
+// than 2^32 chunks, dt is DT_F32 or DT_F16 --, else the complaint; fills SkipSeg::first and *total_chunks
+const char* skip_table_check(SkipSeg* table_host, int n_seg, int dt, unsigned long long* total_chunks);
+void launch_skip_residual_add(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scale_dev, int dt, hipStream_t s);
+void launch_silu_inplace(void* p, int dt, size_t n, hipStream_t s);      // p[i] = silu(p[i]), dense, DT_F32 / DT_F16
 // image post-process (stablediffusion/mod.rs:210-230): u8 = trunc(clamp(((x+1)/2)*255, 0, 255)), NHWC rows of 3
 void launch_to_u8_image(const void* src, int dt, int lds, unsigned char* dst, size_t pixels, hipStream_t s);
 // u8 HWC image -> NHWC activation (x/255)*2-1  (image_to_latent :239-255)

@@ -17,6 +17,7 @@ uint64_t fnv1a64(const std::string& s) {
 namespace {
 const double kSqrt12 = std::sqrt(12.0);
 const double kResGain = 0.5;   // synthetic-init gain of residual-branch output layers
+const double kHintGain = 1.5;  // ... of a ControlNet's hint convolutions
 
 struct Spec {
   std::vector<ParamSpec> items;
@@ -166,6 +167,31 @@ std::vector<ParamSpec> unet_param_specs(const UNetCfg& cfg) {
   for (size_t i = 0; i < out.size(); ++i) block_params(s, "output_blocks." + std::to_string(i), out[i], cfg.context_dim);
   s.norm("norm_out", mc);
   s.conv("conv_out", mc, cfg.out_channels, 3);
+  return s.items;
+}
+
+// ControlNet (sgm ControlNet / diffusers ControlNetModel): the UNet's embeddings, input entries and middle block under their own names, then the hint
+// embedder (eight 3x3 convolutions, numbers 2, 4 and 6 with stride 2), one 1x1 "zero" convolution per input entry and one behind the middle block.
+// Synthetic init: the hint convolutions carry gain 1.5 -- at 1.0 the seven SiLUs shrink the hint features until the hint no longer matters.
+std::vector<ParamSpec> controlnet_param_specs(const ControlCfg& cc) {
+  const UNetCfg& cfg = cc.unet;
+  Spec s;
+  const int mc = cfg.model_channels, emb = 4 * mc;
+  s.linear("lin1_time_embed", mc, emb);
+  s.linear("lin2_time_embed", emb, emb);
+  s.linear("lin1_label_embed", cfg.adm_in_channels, emb);
+  s.linear("lin2_label_embed", emb, emb);
+  std::vector<BlockDesc> inp, out; BlockDesc mid;
+  unet_block_plan(cfg, inp, mid, out);
+  for (size_t i = 0; i < inp.size(); ++i) block_params(s, "input_blocks." + std::to_string(i), inp[i], cfg.context_dim);
+  res_block(s, "middle_block.res1", mid.c_in, mid.c_emb, mid.c_out);
+  transformer(s, "middle_block.transformer", mid.c_out, cfg.context_dim, mid.depth);
+  res_block(s, "middle_block.res2", mid.c_in, mid.c_emb, mid.c_out);
+  const int* hc = cc.hint_channels;
+  const int ch[9] = {cc.hint_in, hc[0], hc[0], hc[1], hc[1], hc[2], hc[2], hc[3], mc};
+  for (int k = 0; k < 8; ++k) s.conv("input_hint_block." + std::to_string(k), ch[k], ch[k + 1], 3, kHintGain);
+  for (size_t i = 0; i < inp.size(); ++i) s.conv("zero_convs." + std::to_string(i), inp[i].c_out, inp[i].c_out, 1);
+  s.conv("middle_block_out", mid.c_out, mid.c_out, 1);
   return s.items;
 }
 

@@ -247,6 +247,7 @@ UNet::UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, int mix) : cfg_(cf
   SDXL_REQUIRE(!((compute_dt == DT_F32 || compute_dt == DT_HL) && stream_dt != DT_F32), "f32 / split-operand compute implies an f32 residual stream");
   SDXL_REQUIRE(cfg.model_channels % 32 == 0, "GroupNorm(32) needs model_channels % 32 == 0");
   fuse_ln_ = compute_dt == DT_F16 && stream_dt == DT_F16;
+  mix_mode_ = mix_ != 0;
 }
 UNet::UNet(const UNetCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st, int mix)
     : UNet(cfg, compute_dt, stream_dt, mix && g_mix_classes.load() >= 0 ? g_mix_classes.load() : mix) {
@@ -257,6 +258,11 @@ size_t UNet::weight_layout_bytes(const UNetCfg& cfg, int compute_dt, int stream_
   UNet u(cfg, compute_dt, stream_dt, mix);
   const std::vector<ParamSpec> specs = unet_param_specs(cfg);
   return u.layout_weights(specs, u.plan_transformers(specs, nullptr));
+}
+UNet::UNet(const ControlCfg& cfg, int compute_dt, int stream_dt, WeightSource& src, hipStream_t st) : UNet(cfg.unet, compute_dt, stream_dt, 0) {
+  control_ = true;
+  ccfg_ = cfg;
+  build_weights(src, st);
 }
 UNet::~UNet() {
   if (graph_) (void)hipGraphExecDestroy(graph_);
@@ -279,7 +285,7 @@ std::vector<StPlan> UNet::plan_transformers(const std::vector<ParamSpec>& specs,
   auto has_st = [](const BlockDesc& d) { return d.kind == BK_REST || d.kind == BK_RESTU; };
   for (size_t i = 0; i < inp.size(); ++i) add("input_blocks." + std::to_string(i), inp[i], has_st(inp[i]));
   add("middle_block", mid, true);
-  for (size_t i = 0; i < out.size(); ++i) add("output_blocks." + std::to_string(i), out[i], has_st(out[i]));
+  for (size_t i = 0; !control_ && i < out.size(); ++i) add("output_blocks." + std::to_string(i), out[i], has_st(out[i]));
   return plans;
 }
 // the arena bytes load_weights allocates: the loader over a dry arena and an empty source (no device call)
@@ -291,7 +297,7 @@ size_t UNet::layout_weights(const std::vector<ParamSpec>& specs, const std::vect
   return dry.peak;
 }
 void UNet::build_weights(WeightSource& src, hipStream_t st) {
-  const std::vector<ParamSpec> specs = unet_param_specs(cfg_);
+  const std::vector<ParamSpec> specs = control_ ? controlnet_param_specs(ccfg_) : unet_param_specs(cfg_);
   std::vector<std::string> f16_names;
   std::vector<StPlan> plans = plan_transformers(specs, &f16_names);
   WeightBuilder wb(specs, src, warena_, cdt_, st);
@@ -344,15 +350,22 @@ void UNet::load_weights(WeightBuilder& wb, const std::vector<StPlan>& plans) {
   mid_res1_.st = load_st(wb, "middle_block.transformer", mid.c_out, mid.n_head, mid.depth, fuse_ln_, plans[sti++]);
   mid_res2_.d = mid;
   mid_res2_.res = load_res(wb, "middle_block.res2", mid.c_in, mid.c_out, emb_names, emb_off);
-  for (size_t i = 0; i < out.size(); ++i) out_.push_back(load_block("output_blocks." + std::to_string(i), out[i]));
-  norm_out_ = wb.norm("norm_out");
-  conv_out_ = wb.conv("conv_out");
+  if (!control_) {
+    for (size_t i = 0; i < out.size(); ++i) out_.push_back(load_block("output_blocks." + std::to_string(i), out[i]));
+    norm_out_ = wb.norm("norm_out");
+    conv_out_ = wb.conv("conv_out");
+  } else {      // hint embedder, one 1x1 convolution per residual tensor
+    for (int k = 0; k < 8; ++k) hint_conv_[k] = wb.conv("input_hint_block." + std::to_string(k));
+    zero_.clear();
+    for (size_t i = 0; i < inp.size(); ++i) zero_.push_back(wb.conv("zero_convs." + std::to_string(i)));
+    mid_out_ = wb.conv("middle_block_out");
+  }
   embcat_ = wb.fused_linear(emb_names, gv);
   emb_total_ = emb_off;
   // execution order of the spatial transformers (for the K/V caches)
   for (BlockW& b : inp_) if (!b.st.blocks.empty()) st_list_.push_back(&b.st);
   st_list_.push_back(&mid_res1_.st);
-  for (BlockW& b : out_) if (!b.st.blocks.empty()) st_list_.push_back(&b.st);
+  for (BlockW& b : out_) if (!b.st.blocks.empty()) st_list_.push_back(&b.st);      // (none in control mode)
 }
 
 // ------------------------------------------------------------------------------------------ conditioning
@@ -704,12 +717,17 @@ void UNet::alloc_skips(Exec& ex, int B, int H, int W, Skips& k) {
 
 // one entry of the block plan, src -> dst, at the entry's own input resolution h x w (a Down entry writes (h - 1) / 2 + 1, an entry with an upsample
 // convolution 2h x 2w); si: the index of its spatial transformer in execution order (st_list_ / kv_)
-void UNet::run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si) {
+void UNet::run_entry(Exec& ex, int section, int index, const Act& src, const Act& dst, int B, int h, int w, int si, const Act* add) {
   if (section == SEC_INPUT) {
     const BlockW& b = inp_[index];
     const int cur_c = b.d.c_in;
     switch (b.d.kind) {
-      case BK_CONV: run_conv(ex, b.conv, hl_op(ex, b.conv, src, (size_t)B * h * w, cur_c, DM_CONV_IO, B), cur_c, ConvGeom{B, h, w, h, w, 3, 1, 1, 0}, dst, tag_epi(DM_CONV_IO)); break;
+      case BK_CONV: {
+        Epi e = tag_epi(DM_CONV_IO);
+        if (add) e.R = *add;
+        run_conv(ex, b.conv, hl_op(ex, b.conv, src, (size_t)B * h * w, cur_c, DM_CONV_IO, B), cur_c, ConvGeom{B, h, w, h, w, 3, 1, 1, 0}, dst, e);
+        break;
+      }
       case BK_DOWN: {
         const int h2 = (h - 1) / 2 + 1, w2 = (w - 1) / 2 + 1;
         run_conv(ex, b.conv, hl_op(ex, b.conv, src, (size_t)B * h * w, cur_c, DM_CONV_UPDOWN, B), cur_c, ConvGeom{B, h, w, h2, w2, 3, 2, 1, 0}, dst, tag_epi(DM_CONV_UPDOWN));
@@ -784,6 +802,7 @@ void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
   gemv(ex, lin1_t_, temb, mc, g1, emb, B, false, true);
   gemv(ex, lin2_t_, g1, emb, embv, emb, B, false, false, label_emb);
   gemv(ex, embcat_, embv, emb, ebias, emb_total_, B, true, false);
+  if (control_) { run_control(ex, B, H, W, in); return; }
 
   // --- geometry of the skip / concat buffers
   Skips k;
@@ -805,6 +824,13 @@ void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
   }
   // --- middle block
   run_entry(ex, SEC_MIDDLE, 0, cur, cat[0].cols(0), B, h, w, si++);
+  // --- skip residuals (ControlNet): scale * r into every skip half and the middle block's output, one launch over the plan's table
+  if (res_key_ && !ex.dry) {
+    SDXL_REQUIRE(res_table_ok_ && b0 == 0 && nb == pB_ && cat[0].p == res_dst_mid_, "skip residuals: the segment table does not describe this run");
+    if (ex.prof) ex.prof->begin(Profiler::OTHER, 0.0, ex.s);
+    launch_skip_residual_add(res_table_, res_segs_, res_chunks_, res_scale_, sdt_, ex.s);
+    if (ex.prof) ex.prof->end(ex.s);
+  }
   // --- output blocks (:483-486)
   Act last = ex.alloc((size_t)B * H * W, mc, ex.sdt);
   for (int j = 0; j < n_out; ++j) {
@@ -827,6 +853,8 @@ void UNet::ensure_plan(int B, int H, int W) {
   if (graph_) { (void)hipGraphExecDestroy(graph_); graph_ = nullptr; }
   plan_runs_ = 0;
   warm_ = WarmSeq();
+  res_table_ok_ = false;      // (the concat buffers move with the arena)
+  hint_g_ = nullptr;          // (control mode: the hint features belong to a plan)
   pB_ = B; pH_ = H; pW_ = W;
   const int mc = cfg_.model_channels, emb = 4 * mc;
   auto persist = [&]() {
@@ -838,6 +866,10 @@ void UNet::ensure_plan(int B, int H, int W) {
     ebias_ = (float*)act_.alloc((size_t)B * emb_total_ * sizeof(float));
     gn_partial_ = (float*)act_.alloc(groupnorm_workspace_floats(B, 32) * sizeof(float));
     tconv_ = (float*)act_.alloc(8 * sizeof(float));
+    if (control_) {      // the residual tensors: fixed addresses for the plan (the controlled UNet's segment table and both graphs hold them)
+      ctl_res_.clear();
+      for (const SkipShape& k : skip_shapes(cfg_, H, W)) ctl_res_.push_back(act_.alloc((size_t)B * k.C * k.h * k.w * dt_size(sdt_)));
+    }
     if (attn16_) {   // cross-workgroup key split of the (f16) self-attention: workspace + tickets per chain, sized for the largest level
       size_t wsb = 0, cnt = 0;
       { int h = H, w = W;
@@ -909,6 +941,7 @@ void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStr
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before forward");
   SDXL_REQUIRE(label_valid_, "set_context must be called again before forward: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
+  prepare_residuals();
   Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &act_; ex.gn_partial = gn_partial_; ex.demote = demote_mask_;
   ex.splitk_ws = skws_[0]; ex.splitk_ws_bytes = skws_bytes_; ex.splitk_cnt = skcnt_[0];
   if (attn16_) { ex.attn_xws = attn_xws_[0]; ex.attn_xcnt = attn_xcnt_[0]; }
@@ -934,7 +967,8 @@ void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStr
     SDXL_HIP(hipEventRecord(ev_join_, s2_));
     SDXL_HIP(hipStreamWaitEvent(s, ev_join_, 0));
   };
-  if (use_graph_ && graph_ && (graph_t_ != t_dev || graph_ts_ != t_stride || graph_off_ != split_offset_ || graph_warm_ != warming || graph_demote_ != demote_mask_)) {
+  if (use_graph_ && graph_ && (graph_t_ != t_dev || graph_ts_ != t_stride || graph_off_ != split_offset_ || graph_warm_ != warming || graph_demote_ != demote_mask_ ||
+                               graph_res_key_ != res_key_ || graph_hint_ != hint_g_)) {
     (void)hipGraphExecDestroy(graph_); graph_ = nullptr;
   }
   if (use_graph_ && !graph_ && plan_runs_ >= 1) {
@@ -951,7 +985,7 @@ void UNet::forward(int B, int H, int W, const float* t_dev, int t_stride, hipStr
     SDXL_HIP(hipStreamEndCapture(s, &g));
     SDXL_HIP(hipGraphInstantiate(&graph_, g, nullptr, nullptr, 0));
     SDXL_HIP(hipGraphDestroy(g));
-    graph_t_ = t_dev; graph_ts_ = t_stride; graph_off_ = split_offset_; graph_warm_ = warming; graph_demote_ = demote_mask_;
+    graph_t_ = t_dev; graph_ts_ = t_stride; graph_off_ = split_offset_; graph_warm_ = warming; graph_demote_ = demote_mask_; graph_res_key_ = res_key_; graph_hint_ = hint_g_;
     act_.reset(m);
   }
   if (use_graph_ && graph_) {
@@ -968,6 +1002,7 @@ void UNet::profile(int B, int H, int W, float ms[Profiler::NCLS], int launches[P
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before profile");
   SDXL_REQUIRE(label_valid_, "set_context must be called again before profile: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
+  prepare_residuals();
   const float t500[8] = {500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f};
   SDXL_HIP(hipMemcpyAsync(tconv_, t500, sizeof(t500), hipMemcpyHostToDevice, s));
   SDXL_HIP(hipStreamSynchronize(s));
@@ -987,6 +1022,7 @@ float UNet::eager_ms(int B, int H, int W, hipStream_t s) {
   ensure_plan(B, H, W);
   SDXL_REQUIRE(ctx_B_ == B && !kv_.empty(), "set_context must be called with the same batch before eager_ms");
   SDXL_REQUIRE(label_valid_, "set_context must be called again before eager_ms: a single-entry run (sdxl_unet_block) replaced the context and left no label embedding");
+  prepare_residuals();
   const float t500[8] = {500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f, 500.f};
   SDXL_HIP(hipMemcpyAsync(tconv_, t500, sizeof(t500), hipMemcpyHostToDevice, s));
   SDXL_HIP(hipStreamSynchronize(s));
@@ -1074,8 +1110,185 @@ void UNet::run_block(int section, int index, const float* x, const float* emb, c
   act_.reset(m);
 }
 
+// ------------------------------------------------------------------------------------------ skip residuals (ControlNet)
+std::vector<UNet::SkipShape> UNet::skip_shapes(const UNetCfg& cfg, int H, int W) {
+  std::vector<BlockDesc> inp, out; BlockDesc mid;
+  unet_block_plan(cfg, inp, mid, out);
+  const int div = 1 << (cfg.channel_mults.size() - 1);
+  if (H < div || W < div || H % div != 0 || W % div != 0)
+    throw InvalidArgumentError("skip residuals: the latent height and width must be positive multiples of 2^(levels-1)");
+  std::vector<SkipShape> v;
+  int h = H, w = W;
+  for (const BlockDesc& d : inp) {
+    if (d.kind == BK_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+    SkipShape s; s.C = d.c_out; s.h = h; s.w = w;
+    v.push_back(s);
+  }
+  SkipShape m; m.C = mid.c_out; m.h = h; m.w = w;
+  v.push_back(m);
+  return v;
+}
+const char* UNet::residuals_refused() const {
+  if (split_cfg_) return "skip residuals (ControlNet) cannot be combined with set_split_cfg: disable split CFG first";
+  if (mix_ != 0 || mix_mode_ || (cdt_ == DT_F16 && sdt_ != DT_F16))
+    return "skip residuals (ControlNet) take SDXL_DTYPE_F32, SDXL_DTYPE_F16 or SDXL_DTYPE_F32_SPLIT handles, not SDXL_DTYPE_F16_F32RES, the SDXL_DTYPE_F32_SPLIT_MIX* modes or SDXL_DTYPE_F32_SPLIT_F16W";
+  return nullptr;
+}
+void UNet::clear_residuals() { res_key_ = 0; res_table_ok_ = false; }
+void UNet::stage_residuals(const float* residuals, int B, int H, int W, float scale, hipStream_t s) {
+  const std::vector<SkipShape> sh = skip_shapes(cfg_, H, W);
+  const size_t es = dt_size(sdt_);
+  if (!(res_key_ && res_B_ == B && res_H_ == H && res_W_ == W)) {      // new buffers: a captured graph holds the old addresses -> new key
+    size_t bytes = 4096 + round_up(sh.size() * sizeof(SkipSeg), 256);
+    for (const SkipShape& k : sh) bytes += round_up((size_t)B * k.C * k.h * k.w * es, 256);
+    res_arena_.reserve(bytes);
+    res_arena_.off = 0;
+    res_scale_ = (float*)res_arena_.alloc(sizeof(float));
+    res_table_ = (SkipSeg*)res_arena_.alloc(sh.size() * sizeof(SkipSeg));
+    res_src_.clear();
+    for (const SkipShape& k : sh) res_src_.push_back(res_arena_.alloc((size_t)B * k.C * k.h * k.w * es));
+    res_B_ = B; res_H_ = H; res_W_ = W;
+    res_key_ = ++res_serial_;
+    res_table_ok_ = false;
+  }
+  const float* p = residuals;
+  for (size_t i = 0; i < sh.size(); ++i) {
+    const SkipShape& k = sh[i];
+    launch_nchw_to_nhwc(p, k.C * k.h * k.w, const_cast<void*>(res_src_[i]), sdt_, B, k.C, k.h * k.w, k.C, 1.0f, s);
+    p += (size_t)B * k.C * k.h * k.w;
+  }
+  unsigned bits; std::memcpy(&bits, &scale, sizeof(bits));
+  SDXL_HIP(hipMemsetD32Async((hipDeviceptr_t)res_scale_, (int)bits, 1, s));
+}
+void UNet::prepare_residuals() {
+  if (!res_key_ || res_table_ok_) return;
+  SDXL_REQUIRE(res_B_ == pB_ && res_H_ == pH_ && res_W_ == pW_ && !plan_split_, "skip residuals were attached for another plan");
+  Exec e; e.cdt = cdt_; e.sdt = sdt_; e.act = &act_;
+  Skips k;
+  const size_t m = act_.mark();      // run's first allocation: the same addresses every forward of this plan
+  alloc_skips(e, pB_, pH_, pW_, k);
+  act_.reset(m);
+  const int n_in = (int)inp_.size();
+  SDXL_REQUIRE((int)res_src_.size() == n_in + 1, "skip residuals: source count");
+  std::vector<SkipSeg> t(n_in + 1);
+  for (int i = 0; i < n_in; ++i) {
+    const int j = n_in - 1 - i;
+    const Act d = k.cat[j].cols(k.cx[j]);
+    t[i] = SkipSeg{d.p, res_src_[i], (long long)d.ld, pB_ * k.hs_h[i] * k.hs_w[i], inp_[i].d.c_out, 0ull};
+  }
+  t[n_in] = SkipSeg{k.cat[0].p, res_src_[n_in], (long long)k.cat[0].ld, pB_ * k.hs_h[n_in - 1] * k.hs_w[n_in - 1], mid_res1_.d.c_out, 0ull};
+  if (const char* bad = skip_table_check(t.data(), n_in + 1, sdt_, &res_chunks_)) throw InvalidArgumentError(bad);
+  SDXL_HIP(hipMemcpy(res_table_, t.data(), t.size() * sizeof(SkipSeg), hipMemcpyHostToDevice));
+  res_segs_ = n_in + 1;
+  res_dst_mid_ = k.cat[0].p;
+  res_table_ok_ = true;
+}
+void UNet::forward_residuals_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, int B, int H, int W,
+                                  const float* residuals, float scale, float* out, hipStream_t s) {
+  if (!residuals) { forward_nchw(x, timesteps, context, n_ctx, label, B, H, W, out, s); return; }
+  if (const char* bad = residuals_refused()) throw InvalidArgumentError(bad);
+  if (!std::isfinite(scale)) throw InvalidArgumentError("skip residuals: the scale must be finite");
+  if (B < 1 || B > 8) throw InvalidArgumentError("skip residuals: batch must be in 1..8");
+  (void)skip_shapes(cfg_, H, W);      // (the size check, before anything is planned)
+  ensure_plan(B, H, W);
+  stage_residuals(residuals, B, H, W, scale, s);
+  set_context(context, n_ctx, label, B, s);
+  launch_nchw_to_nhwc(x, cfg_.in_channels * H * W, in_, input_dt(), B, cfg_.in_channels, H * W, cfg_.in_channels, 1.0f, s);
+  launch_i32_to_f32(timesteps, tconv_, B, s);
+  forward(B, H, W, tconv_, 1, s);
+  launch_nhwc_to_nchw(eps_, DT_F32, cfg_.out_channels, out, B, cfg_.out_channels, H * W, 1.0f, s);
+}
+
+// ------------------------------------------------------------------------------------------ control net (a UNet in control mode)
+// control forward behind the embeddings: every input entry into a dense stream tensor of its own (entry 0: + the hint features, the residual input of
+// its convolution), its 1x1 convolution into the plan's residual buffer; then the middle block and its 1x1 convolution
+void UNet::run_control(Exec& ex, int B, int H, int W, void* in) {
+  SDXL_REQUIRE(ex.dry || hint_g_, "control net: set_hint must be called before forward");
+  const int n_in = (int)inp_.size(), mc = cfg_.model_channels;
+  SDXL_REQUIRE((int)zero_.size() == n_in && (int)ctl_res_.size() == n_in + 1, "control net: residual buffers");
+  const Act g(hint_g_, mc, ex.sdt);
+  Act cur(in, cfg_.in_channels, input_dt());
+  int h = H, w = W, si = 0;
+  const size_t mk = ex.act->mark();
+  auto one_by_one = [&](const Lin& l, const Act& x, int C, void* dst) {
+    run_conv(ex, l, hl_op(ex, l, x, (size_t)B * h * w, C, DM_CONV_SKIP, B), C, ConvGeom{B, h, w, h, w, 1, 1, 0, 0}, Act(dst, C, ex.sdt), tag_epi(DM_CONV_SKIP));
+  };
+  for (int i = 0; i < n_in; ++i) {
+    const BlockDesc& d = inp_[i].d;
+    const int ho = d.kind == BK_DOWN ? (h - 1) / 2 + 1 : h, wo = d.kind == BK_DOWN ? (w - 1) / 2 + 1 : w;
+    const Act dest = ex.alloc((size_t)B * ho * wo, d.c_out, ex.sdt);
+    run_entry(ex, SEC_INPUT, i, cur, dest, B, h, w, si, i == 0 ? &g : nullptr);
+    if (d.kind == BK_REST) ++si;
+    h = ho; w = wo;
+    one_by_one(zero_[i], dest, d.c_out, ctl_res_[i]);
+    cur = dest;
+  }
+  const Act m = ex.alloc((size_t)B * h * w, mid_res1_.d.c_out, ex.sdt);
+  run_entry(ex, SEC_MIDDLE, 0, cur, m, B, h, w, si);
+  one_by_one(mid_out_, m, mid_res1_.d.c_out, ctl_res_[n_in]);
+  ex.act->reset(mk);
+}
+void UNet::set_hint(const float* hint, int n, int B, int H, int W, hipStream_t s) {
+  SDXL_REQUIRE(control_, "set_hint: not a control net");
+  if (!hint || n < 1 || (B != n && B != 2 * n)) throw InvalidArgumentError("control net: the batch must be the hint's n or 2 n (the CFG pair)");
+  ensure_plan(B, H, W);
+  const int mc = cfg_.model_channels, H8 = 8 * H, W8 = 8 * W;
+  const int* hc = ccfg_.hint_channels;
+  const int ch[9] = {ccfg_.hint_in, hc[0], hc[0], hc[1], hc[1], hc[2], hc[2], hc[3], mc};
+  const size_t g_bytes = (size_t)n * H * W * mc * dt_size(sdt_);
+  // the eight convolutions with a SiLU launch between them, every layer's output kept: once over a dry arena for the size, then for real
+  auto pass = [&](Exec& ex) {
+    void* g = ex.act->alloc((B / n) * g_bytes);
+    Act x = ex.alloc((size_t)n * H8 * W8, ch[0], input_dt());
+    if (!ex.dry) launch_nchw_to_nhwc(hint, ch[0] * H8 * W8, x.p, x.dt, n, ch[0], H8 * W8, ch[0], 1.0f, s);
+    int h = H8, w = W8;
+    for (int k = 0; k < 8; ++k) {
+      const int st = (k == 2 || k == 4 || k == 6) ? 2 : 1, ho = (h - 1) / st + 1, wo = (w - 1) / st + 1;
+      const Act y = k == 7 ? Act(g, mc, ex.sdt) : ex.alloc((size_t)n * ho * wo, ch[k + 1], ex.sdt);
+      run_conv(ex, hint_conv_[k], hl_operand(ex, hint_conv_[k], x, (size_t)n * h * w, ch[k], n), ch[k], ConvGeom{n, h, w, ho, wo, 3, st, 1, 0}, y);
+      if (k < 7 && !ex.dry) launch_silu_inplace(y.p, y.dt, (size_t)n * ho * wo * ch[k + 1], s);
+      x = y; h = ho; w = wo;
+    }
+    SDXL_REQUIRE(h == H && w == W, "control net: the hint must be 8 x the latent size");
+    if (B == 2 * n && !ex.dry) SDXL_HIP(hipMemcpyAsync((char*)g + g_bytes, g, g_bytes, hipMemcpyDeviceToDevice, s));
+    return g;
+  };
+  DeviceArena dry; dry.dry = true;
+  Exec e0; e0.dry = true; e0.cdt = cdt_; e0.sdt = sdt_; e0.act = &dry;
+  (void)pass(e0);
+  hint_arena_.reserve(dry.peak + 4096);
+  hint_arena_.off = 0;
+  Exec ex; ex.s = s; ex.cdt = cdt_; ex.sdt = sdt_; ex.act = &hint_arena_;
+  hint_g_ = pass(ex);
+  hint_n_ = n; hint_B_ = B; hint_H_ = H; hint_W_ = W;
+  if (graph_ && graph_hint_ != hint_g_) { (void)hipGraphExecDestroy(graph_); graph_ = nullptr; }      // (the arena moved: the graph holds the old address)
+}
+void UNet::embed_hint_nchw(const float* hint, int n, int H, int W, float* out, hipStream_t s) {
+  if (!hint || !out) throw InvalidArgumentError("control net: null tensor");
+  (void)skip_shapes(cfg_, H, W);
+  set_hint(hint, n, n, H, W, s);
+  launch_nhwc_to_nchw(hint_g_, sdt_, cfg_.model_channels, out, n, cfg_.model_channels, H * W, 1.0f, s);
+}
+void UNet::control_forward_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, const float* hint, int B, int H,
+                                int W, float* residuals_out, hipStream_t s) {
+  SDXL_REQUIRE(control_, "control forward: not a control net");
+  if (B < 1 || B > 8) throw InvalidArgumentError("control net: batch must be in 1..8");
+  const std::vector<SkipShape> sh = skip_shapes(cfg_, H, W);
+  set_hint(hint, B, B, H, W, s);
+  set_context(context, n_ctx, label, B, s);
+  launch_nchw_to_nhwc(x, cfg_.in_channels * H * W, in_, input_dt(), B, cfg_.in_channels, H * W, cfg_.in_channels, 1.0f, s);
+  launch_i32_to_f32(timesteps, tconv_, B, s);
+  forward(B, H, W, tconv_, 1, s);
+  float* o = residuals_out;
+  for (size_t i = 0; i < sh.size(); ++i) {
+    launch_nhwc_to_nchw(ctl_res_[i], sdt_, sh[i].C, o, B, sh[i].C, sh[i].h * sh[i].w, 1.0f, s);
+    o += (size_t)B * sh[i].C * sh[i].h * sh[i].w;
+  }
+}
 void UNet::forward_nchw(const float* x, const int* timesteps, const float* context, int n_ctx, const float* label, int B,
                         int H, int W, float* out, hipStream_t s) {
+  SDXL_REQUIRE(!control_, "a control net has no UNet forward (sdxl_controlnet_forward)");
+  clear_residuals();      // the plain entry: exactly the launches of a handle that never had residuals
   ensure_plan(B, H, W);
   set_context(context, n_ctx, label, B, s);
   launch_nchw_to_nhwc(x, cfg_.in_channels * H * W, in_, input_dt(), B, cfg_.in_channels, H * W, cfg_.in_channels, 1.0f, s);
