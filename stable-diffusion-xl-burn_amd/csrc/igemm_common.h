@@ -72,6 +72,27 @@ __device__ __forceinline__ float gelu_erf2(float x) {
   const float e = poly * t * __builtin_amdgcn_exp2f(-z * z * 1.44269504088896340736f);
   return 0.5f * x * (x >= 0.f ? 2.0f - e : e);
 }
+// gelu_erf2 on a pair of outputs, for the direct GEGLU epilogue of the 256x320 kernel (a VALU-only tail: packed fp32 next to MFMAs
+// is slower, so this form stays out of every other epilogue).  The full-rate part is v_pk_mul / v_pk_fma / v_pk_add_f32, the v_rcp_f32
+// and the v_exp_f32 stay one per element.  Per element the operations and their order are gelu_erf2's as hipcc compiles it (nothing
+// in it contracts: contraction is off here so that stays true), so each half rounds like the scalar form: same bits.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ f32x2 gelu_erf2x2(f32x2 x) {
+#pragma clang fp contract(off)
+  const f32x2 z = __builtin_elementwise_abs(x) * 0.70710678118654752440f;
+  const f32x2 d = fma2(0.3275911f, z, 1.0f);
+  const f32x2 t = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+  f32x2 poly = fma2(1.061405429f, t, -1.453152027f);
+  poly = fma2(poly, t, 1.421413741f);
+  poly = fma2(poly, t, -0.284496736f);
+  poly = fma2(poly, t, 0.254829592f);
+  const f32x2 w = -z * z * 1.44269504088896340736f;
+  const f32x2 ex = {__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])};
+  const f32x2 e = poly * t * ex, f = 2.0f - e;
+  const f32x2 s = {x[0] >= 0.f ? f[0] : e[0], x[1] >= 0.f ? f[1] : e[1]};
+  return 0.5f * x * s;
+}
 
 // Kernel-argument prefetch.  hipcc loads kernel arguments lazily (s_load right before the first use of each field), and a struct
 // as large as IgemmParams spans five 64-byte lines: the s_memtime timeline of the production kernels (tools/timeline_probe.py,
@@ -844,6 +865,53 @@ __device__ __forceinline__ void igemm_epilogue_rows(const IgemmParams& p, const 
         }
       }
     }
+  }
+}
+
+// ---- direct GEGLU epilogue of the 256x320 kernel: one 32-row half of a wave tile, aligned f16 output, no residual / statistics / ebias
+// (every GEGLU projection of the UNet; launch_wide checks).  igemm_epilogue_rows<.., true> has the idea -- value and gate of a column sit
+// in one lane (groups q and q + 2), one half swap per dword leaves 8 consecutive f16 outputs = one 16-byte store -- but its residual,
+// ebias and statistics arrays on top of 160 accumulator registers spilled (profiles/r03_epilogue_ab.txt).  Here one 32x32 tile at a
+// time: 8 accumulator pairs -> affine -> gelu_erf2x2 -> product -> swap -> store; nothing but the accumulators outlives a tile.
+// cb / cc = the wave's 160 columns of the workgroup's bias / ln_cs vectors in LDS (zeros for an absent vector), read in the accumulator
+// layout.  Values: the staged path's operations in its order, as hipcc compiles `lna * acc + lnc * cz + bz + ez` there (the products
+// lna * acc rounded, lnc * cz fused into the sum, then the bias, then the zero page's ez -- kept as + 0.f: it turns a -0 into +0).
+template <int TN>
+__device__ __forceinline__ void igemm_epilogue_geglu_rows(const IgemmParams& p, const f32x16 (&acc)[1][TN], int mrow, int nwo, int lane,
+                                                          float lna, float lnc, const float* cb, const float* cc) {
+#pragma clang fp contract(off)
+  const int fr = lane & 31, fh = lane >> 5;
+  const bool mok = mrow + fr < p.M;           // (a ragged last row tile: its rows past M ran on zero-page operands)
+  half_t* crow = reinterpret_cast<half_t*>(p.C) + (size_t)(mrow + fr) * p.ldc + nwo + 8 * fh;
+  const f32x2 a2 = {lna, lna}, c2 = {lnc, lnc};
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    f32x4 v[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int nb = j * 32 + 8 * q + 4 * fh;
+      const f32x4 bz = *reinterpret_cast<const f32x4*>(cb + nb), gz = *reinterpret_cast<const f32x4*>(cb + nb + 16);
+      const f32x4 cz = *reinterpret_cast<const f32x4*>(cc + nb), gc = *reinterpret_cast<const f32x4*>(cc + nb + 16);
+#pragma unroll
+      for (int h = 0; h < 4; h += 2) {
+        const f32x2 x = {acc[0][j][q * 4 + h], acc[0][j][q * 4 + h + 1]}, xg = {acc[0][j][(q + 2) * 4 + h], acc[0][j][(q + 2) * 4 + h + 1]};
+        const f32x2 val = fma2(c2, f32x2{cz[h], cz[h + 1]}, a2 * x) + f32x2{bz[h], bz[h + 1]} + 0.f;
+        const f32x2 g = fma2(c2, f32x2{gc[h], gc[h + 1]}, a2 * xg) + f32x2{gz[h], gz[h + 1]};
+        const f32x2 o = val * gelu_erf2x2(g);
+        v[q][h] = o[0]; v[q][h + 1] = o[1];
+      }
+    }
+    // half swap of the group pair: lanes 0..31 keep group 0 and receive the partner's group 0, lanes 32..63 receive the partner's
+    // group 1 and keep their own -> 8 consecutive columns from nwo + 16 j + 8 fh
+    half8 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0][r]), __float_as_uint(v[1][r]), false, false);
+      o[r] = (half_t)__uint_as_float(sw[0]);
+      o[4 + r] = (half_t)__uint_as_float(sw[1]);
+    }
+    if (mok) *reinterpret_cast<half8*>(crow + j * 16) = o;
+    __builtin_amdgcn_sched_barrier(0);      // the next tile's vector reads stay behind this one: hoisted, they spill
   }
 }
 

@@ -738,9 +738,10 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
   // whole wave tiles take the direct row-per-lane epilogue (registers -> permlane32 half swap -> 16-byte stores); tiles cut by N
   // or n_split, the transposed V^T part, GroupNorm-statistics producers and unaligned outputs keep the LDS-staged one.  The
   // choice depends on N / alignment only (never on the batch), and every wave makes it for itself (staging regions are private).
-  // (GEGLU projections keep the staged epilogue: measured per shape in the step, tools/launch_ab.py, the direct form is 1 - 5 us
-  // faster on every plain shape and 23 - 50 us SLOWER on the 256x320 GEGLU kernel, whose 160 accumulator registers leave no
-  // room for the per-column vectors -- profiles/r03_epilogue_ab.txt)
+  // (GEGLU projections keep the staged epilogue in THIS kernel.  The general direct form, igemm_epilogue_rows<.., true>, was 23 - 50 us
+  // slower on the 256x320 GEGLU kernel -- its residual / ebias / statistics arrays spilled next to 160 accumulator registers,
+  // profiles/r03_epilogue_ab.txt; igemm_wide_kernel now has a GEGLU-only direct form of its own, igemm_epilogue_geglu_rows, one tile
+  // at a time with the column vectors in LDS: 215 registers, no scratch, profiles/geglu_epilogue_ab.txt)
   if constexpr (TSW) {
     if (tsw_swapped) {
       igemm_epilogue_swapped<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, ln_coop ? ln_coef + (wm * WM) * 2 : nullptr, zeros);
@@ -776,7 +777,9 @@ __global__ __launch_bounds__(64 * NW) void igemm_pipe_kernel(const IgemmParams p
 // LDS rows are 64 bytes (32 halfs): a 1-KiB DMA piece covers 16 rows, source chunk = slot ^ ((row>>2)&3), which makes the
 // 16-lane ds_read_b128 service groups hit 16 distinct 16-byte slots of the 256-byte bank row.
 // Per k-tile: {frags kk=0 -> 10 MFMA} {frags kk=1 -> wait own pieces of tile kt+1 -> barrier -> 10 MFMA with the pieces of
-// tile kt+NS (slot just freed) issued between them}.  GEGLU epilogue only (staged through LDS in two 32-row passes).
+// tile kt+NS (slot just freed) issued between them}.  GEGLU epilogue only, in two 32-row passes: DIRECT = from the registers to 16-byte f16
+// stores with the tile's column vectors in 2.5 KiB of static LDS (launch_wide: aligned f16 output, nothing but bias and the folded LayerNorm --
+// every GEGLU projection of the UNet; tail 12.1 k cycles against 17.2 k, profiles/geglu_epilogue_timeline.txt), else staged through LDS.
 #ifdef SDXL_MEASURE
 // coarse s_memtime stamps of the wide kernel (tools/wide_timeline.py): [workgroup][wave][16], words 0..7 = entry, ring fill issued, tile 0 landed
 // (first barrier passed), k-loop done, ring dead (barrier), first / second epilogue pass issued, stores drained
@@ -792,7 +795,7 @@ void igemm_set_wide_timeline(void* buf) {
 // DB (round 5): fragments of the NEXT kk-step are requested before the MFMAs of the current one (two register sets, counted lgkmcnt, the pipe
 // kernels' scheme): the rolled form above waits for its seven ds_read_b128 in front of every 10-MFMA burst with nothing of its own to issue
 // meanwhile -- 1.85 - 1.97 k cycles per 32-deep k-tile for 1.28 k cycles of matrix-pipe work (profiles/r04_wide_geglu_timeline.txt).
-template <int NS, bool DB = false>
+template <int NS, bool DB = false, bool DIRECT = false>
 __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, const void* zeros) {
 #ifdef SDXL_MEASURE
   unsigned wtl[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -908,6 +911,19 @@ __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, co
   float* ln_coef = reinterpret_cast<float*>(smem + NS * STAGE);
   LnC lnc;
   lnc.load(p, m0, tid);
+  // the tile's 320 columns of bias and ln_cs (value and gate halves interleaved by 16, as packed), once per workgroup: threads 0..79 /
+  // 80..159 request 16 bytes each -- an absent vector reads the zero page -- BEFORE the first DMA piece like the statistics above (oldest
+  // entries of the vmcnt queue: the ring's counted waits cover them), and park them in LDS behind the prologue's barrier.  The direct
+  // epilogue reads them there in the accumulator layout instead of five dependent global round trips per pass.  (DIRECT only: the staged
+  // instantiation has no such corner and loads nothing.)
+  __shared__ __attribute__((aligned(16))) float cvec[2][DIRECT ? BN : 4];
+  f32x4 cvv = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (DIRECT) {
+    const bool cv_ln = tid >= BN / 4;
+    const float* cv_src = cv_ln ? (p.ln_stat ? p.ln_cs : nullptr) : p.bias;
+    cvv = *((cv_src && tid < BN / 2) ? reinterpret_cast<const f32x4*>(cv_src + n0 + 4 * (cv_ln ? tid - BN / 4 : tid))
+                                      : reinterpret_cast<const f32x4*>(zeros));
+  }
   __builtin_amdgcn_sched_barrier(0);
   // ---- prologue: NS - 1 tiles in flight, wait for tile 0 only.  The last ring slot is filled from inside k-tile 0 (its first kk-step
   // carries the pieces of tile NS - 1): the first MFMA does not wait behind the issue of a whole ring (every wave's VMEM issue queues
@@ -919,6 +935,9 @@ __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, co
   float lnA[TM], lnC[TM];
   const bool ln_coop = p.ln_slots <= 24;
   lnc.finish(p, m0, ln_coef);
+  if constexpr (DIRECT) {
+    if (tid < BN / 2) *reinterpret_cast<f32x4*>(&cvec[0][0] + 4 * tid) = cvv;
+  }
   if (!ln_coop) ln_prologue<TM>(p, m0 + wm * WM, fr, lnA, lnC);
   if (NS - 1 <= nk) wait_tiles(std::integral_constant<int, NS - 2>{}); else wait_vmcnt<0>();
   wait_lgkmcnt<0>();                             // the coefficients' ds_write has landed (raw s_barrier waits for nothing)
@@ -987,7 +1006,14 @@ __global__ __launch_bounds__(512) void igemm_wide_kernel(const IgemmParams p, co
   __builtin_amdgcn_s_barrier();                  // ring dead -> staging area
   asm volatile("" ::: "memory");
   WIDE_STAMP(4);
-  if (p.act == 1) {
+  if constexpr (DIRECT) {
+    // aligned f16 output without residual, ebias or statistics (launch_wide checks: every GEGLU projection of the UNet): registers ->
+    // 16-byte stores, one 32-row half at a time like the staged passes; rows past M are computed on zero-page operands and not stored
+    const int mw = m0 + wm * WM, nwo = (n0 + wn * WN) >> 1;
+    igemm_epilogue_geglu_rows<TN>(p, acc0, mw, nwo, lane, lnA[0], lnC[0], &cvec[0][wn * WN], &cvec[1][wn * WN]);
+    WIDE_STAMP(5);
+    igemm_epilogue_geglu_rows<TN>(p, acc1, mw + 32, nwo, lane, lnA[1], lnC[1], &cvec[0][wn * WN], &cvec[1][wn * WN]);
+  } else if (p.act == 1) {
     // two passes of 32 rows: a full 64 x 80 fp32 staging region per wave would not fit next to seven others
     char* region = smem + wave * (32 * (WN / 2) * 4);
     {
@@ -1062,6 +1088,17 @@ static void launch_wide(const IgemmParams& p, const IgemmChoice& c, hipStream_t 
     return;
   }
 #endif
+  // the direct epilogue's case -- an aligned f16 output of whole column tiles that takes nothing but bias and the folded LayerNorm: every GEGLU
+  // projection of the UNet -- has an instantiation of its own (both forms in one kernel spill next to the 160 accumulator registers).  Everything
+  // else (the fp32 / HL16 outputs of the op entries and the mixed modes, an unaligned C) and igemm_epilogue_staged = 1, the A/B and identity
+  // partner, run the staged instantiation.  Properties of the launch alone: never of M or the batch.
+  const bool direct = !p.epi_staged && p.act == 1 && !p.R && !p.stat_out && !p.gn_part && !p.ebias && p.c_dt == DT_F16 && p.N % 320 == 0 &&
+                      (p.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+  if (direct) {
+    set_max_dynamic_lds<&igemm_wide_kernel<3, false, true>>(c.lds, dev);
+    hipLaunchKernelGGL((igemm_wide_kernel<3, false, true>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
+    return;
+  }
   set_max_dynamic_lds<&igemm_wide_kernel<3, false>>(c.lds, dev);
   hipLaunchKernelGGL((igemm_wide_kernel<3, false>), dim3(c.grid), dim3(c.block), c.lds, s, p, g_zero_pages[dev]);
 }
