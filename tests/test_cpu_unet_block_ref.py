@@ -6,9 +6,11 @@ import torch
 import unet_block_ref as R
 from oracle import model as OM
 
-CASE_NAMES = [c[0] for c in R.CASES]
-# fp32 against fp64: a GEMM of depth K leaves about sqrt(K) 2^-24 relative (random-walk accumulation; K <= 23040: 9e-6), a chain has at most 22 of them
-# (middle block: 4 convolutions + 2 x 8 projections + proj_in / proj_out) adding in quadrature: 4.3e-5
+CASE_NAMES = [c[0] for c in R.CASES + R.RF_CASES]
+# fp32 against fp64: a GEMM of depth K leaves about sqrt(K) 2^-24 relative (random-walk accumulation; K <= 27648, the refiner's 3072-wide convolutions:
+# sqrt(27648) 2^-24 = 9.9e-6; the base's K <= 23040: 9e-6), a chain has at most 22 of them (either middle block at depth 2: 4 convolutions + 2 x 8
+# projections + proj_in / proj_out) adding in quadrature: sqrt(22) 9.9e-6 = 4.7e-5 if every one of them had the longest K (the deepest chain with a
+# K = 27648 member has four GEMMs) -- the constant that K <= 23040 gave (4.3e-5 -> 5e-5) still holds
 FP32_TOL = 5e-5
 
 
@@ -57,7 +59,11 @@ def test_mode_5_classes_follow_the_mix_bits():
     assert R.mode_of(5).classes == {"attn", "geglu", "qkv", "ff", "out1", "out2", "q2"}
     assert R.mode_of(5, 1 | 2 | 1024).classes == {"attn", "geglu"}      # the fallback classes are another arithmetic: the GPU test asserts the bits
     assert set(R.DEFECTS) == {"emb_slice_neighbour", "emb_other_entry", "skip_dropped", "one_scale", "norm_out_stats_in", "stale_ln_stats",
-                              "ctx_other_entry", "ctx_pad_live", "vt_pad_nonzero", "geglu_swapped", "proj_out_no_residual", "dst_col0"}
+                              "ctx_other_entry", "ctx_pad_live", "vt_pad_nonzero", "geglu_swapped", "proj_out_no_residual", "dst_col0",
+                              "rf/emb_slice_neighbour", "rf/stale_ln_stats", "rf/ctx_pad_live", "rf/vt_pad_nonzero", "rf/skip_dropped", "rf/dst_col0",
+                              "rf/one_scale", "rf/splitk_slice_lost", "rf/splitk_tail_rows", "rf/head_width_128"}
+    # a defect of the refiner plan is planted on a refiner case, and only there
+    assert all((R.CONFIG_OF[name] == "refiner") == d.startswith("rf/") for d, (name, _) in R.DEFECTS.items())
 
 
 @pytest.mark.parametrize("defect", list(R.DEFECTS))

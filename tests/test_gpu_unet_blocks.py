@@ -4,7 +4,13 @@ level's transformer depth cut to 2, seeded synthetic weights, B = 2, 77 context 
 tests/unet_block_ref.py (bound = margin x the error of the mode's CPU emulation on the same operands, never a GPU result);
 tests/test_cpu_unet_block_ref.py shows that the planted defects leave those bounds.
 
-Every assertion prints error / bound / ratio first (pytest -s; recorded in profiles/unet_block_tests.txt)."""
+The same tests over the refiner configuration (transformer depths cut to 2; R.RF_CASES: 12 / 24 heads, eight-slice split-K on whole, ragged and 64-row
+tiles, ResU entries with either upsample form, K up to 27648) stand at the end of the file: the base handles are released before the first refiner
+handle is made.  A refiner handle's arena is printed next to its creation time; the six hold 30.7 GiB together (3.5 ... 6.6 GiB each) and stay alive to
+the end of the module, case-major like the base runs.  Above REFINER_HANDLE_BYTES together the runs would have to be ordered dtype-major with one
+handle alive at a time: _unet asserts the sum.
+
+Every assertion prints error / bound / ratio first (pytest -s; recorded in profiles/unet_block_tests.txt and profiles/refiner_block_tests.txt)."""
 import ctypes
 import time
 
@@ -18,25 +24,35 @@ from util import to_pkg_cfg, unet_weights
 pytestmark = pytest.mark.gpu
 
 RUNS = [(c[0], dt) for c in R.CASES for dt in R.case_dtypes(c[0])]
+RF_RUNS = [(c[0], dt) for c in R.RF_CASES for dt in R.case_dtypes(c[0])]
+REFINER_HANDLE_BYTES = 64 << 30      # what the six refiner handles may hold together on a shared machine
 
 
 @pytest.fixture(scope="module")
 def handles():
-    """one handle per dtype for the whole module (created on first use, released with the module)"""
+    """one handle per (configuration, dtype) for the whole module (created on first use, released with the module)"""
     d = {}
     yield d
     d.clear()
 
 
-def _unet(pkg, ctx, handles, dtype):
-    if dtype not in handles:
+def _unet(pkg, ctx, handles, dtype, model="base"):
+    if (model, dtype) not in handles:
+        if model == "refiner":      # the base handles go before the first refiner handle is made
+            for k in [k for k in handles if k[0] != "refiner"]:
+                del handles[k]
         t0 = time.perf_counter()
-        u = pkg.UNet(ctx, to_pkg_cfg(pkg, R.CFG), dtype, seed=pkg.SEED_F16_WEIGHTS if R.mode_of(dtype).f16w else 0)
+        u = pkg.UNet(ctx, to_pkg_cfg(pkg, R.CONFIGS[model]), dtype, seed=pkg.SEED_F16_WEIGHTS if R.mode_of(dtype).f16w else 0)
         torch.cuda.synchronize()
-        print(f"unet_block handle dtype {dtype}: created in {time.perf_counter() - t0:.2f} s")
-        assert u.mix_classes() == R.MIX_EXPECTED.get(dtype, 0), "the mode fell back to other classes"
-        handles[dtype] = u
-    return handles[dtype]
+        if model == "base":
+            print(f"unet_block handle dtype {dtype}: created in {time.perf_counter() - t0:.2f} s")
+        else:
+            print(f"unet_block refiner handle dtype {dtype}: created in {time.perf_counter() - t0:.2f} s, weight arena {u.weight_arena()[1] / 2 ** 30:.2f} GiB")
+        assert u.mix_classes() == R.MIX_EXPECTED.get(dtype, 0), "the mode fell back to other classes"      # (mix_of: the bits do not depend on the configuration)
+        handles[(model, dtype)] = u
+        held = sum(h.weight_arena()[1] for k, h in handles.items() if k[0] == "refiner")
+        assert held <= REFINER_HANDLE_BYTES, f"the refiner handles hold {held / 2 ** 30:.1f} GiB together: run dtype-major, one alive at a time"
+    return handles[(model, dtype)]
 
 
 def _run(u, name, entries=slice(None)):
@@ -56,7 +72,11 @@ def _check_bound(out, name, dtype, what=""):
 
 @pytest.mark.parametrize("name,dtype", RUNS)
 def test_block_within_emulation_bound(pkg, ctx, handles, name, dtype):
-    out = _run(_unet(pkg, ctx, handles, dtype), name)
+    _within_emulation_bound(pkg, ctx, handles, name, dtype)
+
+
+def _within_emulation_bound(pkg, ctx, handles, name, dtype):
+    out = _run(_unet(pkg, ctx, handles, dtype, R.CONFIG_OF[name]), name)
     assert tuple(out.shape) == tuple(R.ref64(name, f16w=R.mode_of(dtype).f16w).shape)
     _check_bound(out, name, dtype)
 
@@ -65,7 +85,11 @@ def test_block_within_emulation_bound(pkg, ctx, handles, name, dtype):
 def test_block_entries_are_independent(pkg, ctx, handles, name, dtype):
     if name == "rest_640_skip" and dtype == 3:
         name = "rest_640_skip_mag"      # one operand scale per entry: entry 1 (2^10 x) next to entry 0 gets the bits it gets alone
-    u = _unet(pkg, ctx, handles, dtype)
+    _entries_are_independent(pkg, ctx, handles, name, dtype)
+
+
+def _entries_are_independent(pkg, ctx, handles, name, dtype):
+    u = _unet(pkg, ctx, handles, dtype, R.CONFIG_OF[name])
     pair, alone = _run(u, name), _run(u, name, slice(1, 2))
     assert torch.equal(pair[1:2], alone), f"{name} dtype {dtype}: entry 1 alone differs from entry 1 inside the pair by {(pair[1:2] - alone).abs().max().item():.3e}"
 
@@ -73,32 +97,39 @@ def test_block_entries_are_independent(pkg, ctx, handles, name, dtype):
 @pytest.mark.parametrize("dtype", [0, 1, 2, 3, 5, 7])
 def test_block_keeps_no_state_between_calls(pkg, ctx, handles, dtype):
     # ping-pong statistics buffers, tickets, split-K counters and the zero-filled V^T are per call: another entry at another size in between changes nothing
-    u = _unet(pkg, ctx, handles, dtype)
-    first = _run(u, "rest_1280_bucket")
-    other = _run(u, "rest_640_skip")
-    assert torch.equal(first, _run(u, "rest_1280_bucket"))
-    assert torch.equal(other, _run(u, "rest_640_skip"))
-    assert torch.equal(first, _run(u, "rest_1280_bucket"))
+    _keeps_no_state(_unet(pkg, ctx, handles, dtype), "rest_1280_bucket", "rest_640_skip")
+
+
+def _keeps_no_state(u, a, b):
+    first = _run(u, a)
+    other = _run(u, b)
+    assert torch.equal(first, _run(u, a))
+    assert torch.equal(other, _run(u, b))
+    assert torch.equal(first, _run(u, a))
 
 
 @pytest.mark.parametrize("option,dtype", [("set_gn_from_producer", 1), ("set_gn_from_producer", 2), ("set_fused_cross_attention", 1), ("set_fused_cross_attention", 5)])
 def test_block_kernel_paths(pkg, ctx, handles, option, dtype):
-    u = _unet(pkg, ctx, handles, dtype)
+    _kernel_paths(_unet(pkg, ctx, handles, dtype), "rest_1280", option, dtype)
+
+
+def _kernel_paths(u, name, option, dtype):
     try:
         for on in (False, True):
             getattr(u, option)(on)
-            out = _run(u, "rest_1280")
-            _check_bound(out, "rest_1280", dtype, f" {option}({on})")
-            assert torch.equal(out, _run(u, "rest_1280")), f"{option}({on}): the replay differs"
+            out = _run(u, name)
+            _check_bound(out, name, dtype, f" {option}({on})")
+            assert torch.equal(out, _run(u, name)), f"{option}({on}): the replay differs"
     finally:
         getattr(u, option)(True)
 
 
-@pytest.mark.parametrize("dtype", [0, 1, 3, 7])
-def test_chained_blocks_reproduce_forward(pkg, ctx, dtype):
+@pytest.mark.parametrize("dtype,model", [pytest.param(dt, m, id=pre + str(dt)) for m, pre in (("tiny", ""), ("tiny_refiner", "refiner-")) for dt in (0, 1, 3, 7)])
+def test_chained_blocks_reproduce_forward(pkg, ctx, dtype, model):
     # run_block over the whole plan of the tiny model, the skip concatenations on this side: the bits of forward -- the entry runs forward's code with
-    # forward's strides.  emb through the kernels forward's embedding chain launches (timestep_embedding, gemv).
-    ocfg = OC.tiny_config()
+    # forward's strides.  emb through the kernels forward's embedding chain launches (timestep_embedding, gemv).  The tiny refiner: the four-level plan
+    # with ResU entries, a deepest level of ResBlocks alone and y of its own width.
+    ocfg = OC.tiny_config() if model == "tiny" else OC.tiny_refiner_config()
     f16w = dtype == 7
     W = {k: (v.half().float() if f16w and not k.endswith(".eps") else v).cuda() for k, v in unet_weights(ocfg).items()}
     u = pkg.UNet(ctx, to_pkg_cfg(pkg, ocfg), dtype, seed=pkg.SEED_F16_WEIGHTS if f16w else 0)
@@ -162,3 +193,29 @@ def test_block_refuses_bad_arguments(pkg, ctx, handles):
         assert raw(**kw) == 1, (kw, pkg.lib().sdxl_last_error().decode())
     assert raw() == 0 and torch.equal(out, good)
     assert torch.equal(u.run_block("input", 1, x, emb, context), good), "the handle is not usable after a refused call"
+
+
+# ------------------------------------------------------------------------------------------------------------------ the refiner configuration
+@pytest.mark.parametrize("name,dtype", RF_RUNS)
+def test_refiner_block_within_emulation_bound(pkg, ctx, handles, name, dtype):
+    _within_emulation_bound(pkg, ctx, handles, name, dtype)
+
+
+@pytest.mark.parametrize("name,dtype", [(n, dt) for n in ("rf_rest_768_skip", "rf_rest_1536_bucket", "rf_res_1536_deep_bucket", "rf_out_3072_up_bucket")
+                                        for dt in R.case_dtypes(n)])
+def test_refiner_block_entries_are_independent(pkg, ctx, handles, name, dtype):
+    # the two 18 x 14 cases: 252 rows per entry, so the second 256-row tile of the pair holds rows of both entries and goes through the eight-slice
+    # counters and workspace; alone, entry 1 starts a tile
+    if name == "rf_rest_768_skip" and dtype == 3:
+        name = "rf_rest_768_skip_mag"
+    _entries_are_independent(pkg, ctx, handles, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", [0, 1, 2, 3, 5, 7])
+def test_refiner_block_keeps_no_state_between_calls(pkg, ctx, handles, dtype):
+    _keeps_no_state(_unet(pkg, ctx, handles, dtype, "refiner"), "rf_middle_1536_bucket", "rf_rest_768_skip")
+
+
+@pytest.mark.parametrize("option,dtype", [("set_gn_from_producer", 1), ("set_gn_from_producer", 2), ("set_fused_cross_attention", 1), ("set_fused_cross_attention", 5)])
+def test_refiner_block_kernel_paths(pkg, ctx, handles, option, dtype):
+    _kernel_paths(_unet(pkg, ctx, handles, dtype, "refiner"), "rf_rest_1536", option, dtype)

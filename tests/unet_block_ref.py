@@ -3,15 +3,22 @@ sdxl_unet_block (UNet::run_block -> run_entry, res_block, spatial_transformer of
 no GPU, no engine.  tests/test_gpu_unet_blocks.py sends the operands built here to the GPU; tests/test_cpu_unet_block_ref.py shows on the same operands
 that each planted defect leaves the bounds.
 
-Model: the base configuration with the deepest level's transformer depth cut from 10 to 2 (every entry has the base model's widths, embedding width and
-emb_off order).  The engine holds seeded synthetic weights; this module generates only the entry's own tensors (oracle.config.synth_values is keyed by
-tensor name) and every *.lin_embed tensor.
+Models (CONFIGS; every case names its own through CONFIG_OF): "base", the base configuration with the deepest level's transformer depth cut from 10 to
+2, and "refiner", the refiner configuration with every transformer depth cut from 4 to 2 (widths 384 / 768 / 1536 / 1536 on four levels, a 1280-wide
+context, 6 / 12 / 24 heads, the deepest level without a transformer, ResU entries in the decoder).  Either way every entry has its model's widths,
+embedding width and emb_off order.  The engine holds seeded synthetic weights; this module generates only the entry's own tensors
+(oracle.config.synth_values is keyed by tensor name) and every *.lin_embed tensor of the case's model.
 
 Reference: oracle.model._unet_block / res_block / spatial_transformer on float64 tensors, NUM in its default mode (nothing in those functions casts).
 
 Emulations (fp32 on the CPU, roundings where the engine stores rounded values -- read from res_block / spatial_transformer of csrc/unet.cpp):
   dtype 1  f16: both operands of every GEMM and q, k, v, P of both attentions rounded to f16 (the oracle's `operands` emulation with every class on), the
            conv_in output h (stored in the compute dtype) and every write of the residual stream rounded to f16; x, emb-bias and statistics fp32.
+           A ResBlock with a 1x1 skip writes the stream twice: the skip convolution stores skip(x) into the destination and conv_out adds it back as
+           its residual operand (UNet::res_block of csrc/unet.cpp: run_conv(w.skip, ..., out, es); e2.R = out), two f16 roundings where a ResBlock
+           without a skip has one.  The emulation first rounded x + h once in either kind; the refiner's rf_out_3072 (a ResBlock with a skip and
+           nothing behind it, 64 rows) then sat at 1.10 of its bound on one entry, and the base's out_960_res, the same kind of entry, had been
+           the file's worst line at 0.81.  No kernel at fault: the second rounding went into the emulation, for every case of both models.
   dtype 2  the same with an fp32 stream (h is still stored f16: Act h of res_block carries the compute dtype).
   dtype 0, 3, 7  fp32 arithmetic.  The GEMMs (convolutions as the implicit GEMM over C k k) accumulate as the MFMA k-loop does: one fp32 accumulator per
            output, rounded after every step of the chain, k ascending -- dtype 0: steps of 2 (v_mfma_f32_32x32x2_f32: PipeElem<float>::mma of
@@ -36,7 +43,13 @@ What the bounds are not.  (a) Fixed numbers: inside one accumulation step the or
 bound, moves by some 20 % from one test machine to another (res_320 in dtype 0: 1.66e-6 / 1.61e-6 on one, 1.41e-6 / 1.71e-6 on another).  (b) Tight in
 the split modes on long K: the chain is emulated over the whole K, where the engine's in-launch split-K (K = 11520 / 23040) sums shorter chains; the
 emulation over-estimates the engine's rounding there and the 1280-wide cases sit at 0.15 ... 0.25 of their bound in dtypes 3 and 7.  The planted defects
-are three to six orders of magnitude outside those bounds (tests/test_cpu_unet_block_ref.py)."""
+are three to six orders of magnitude outside those bounds (tests/test_cpu_unet_block_ref.py).
+
+What the refiner cases (RF_CASES) reach that no base case does -- tests/test_cpu_unet_block_ref.py asserts it on the selection (csrc/select.cpp) itself:
+self-attention with 12 / 24 heads (never the mixed-block kernel: the key-split kernel at 256 / 1024 queries, the 128-query kernel at 252 / 1008);
+eight-slice split-K (igemm_splitk_slices: one entry has at most 256 rows) on whole tiles with the statistics from the epilogue (rf_rest_1536), on a
+ragged 252-row tile (rf_res_1536_deep_bucket, rf_middle_1536_bucket) and on 64 rows (rf_out_3072, rf_down_1536), three slices at N = 1536 on whole and
+ragged rows; ResU entries with the folded (16 x 16) and the gather (18 x 14: phase_shape_ok refuses it) upsample; K = 3456 ... 27648, N = 384 / 768 / 1536."""
 import math
 import zlib
 
@@ -47,6 +60,8 @@ import torch.nn.functional as F
 from oracle import config as OC, model as OM
 
 CFG = OC.UNetConfig(2816, 320, [1, 2, 4], 64, [0, 2, 2], 2048)
+RF_CFG = OC.UNetConfig(2560, 384, [1, 2, 4, 4], 64, [0, 2, 2, 2], 1280, is_refiner=True)
+CONFIGS = {"base": CFG, "refiner": RF_CFG}
 N_CTX = 77
 B = 2
 F16W_CLASSES = 1 | 2 | 4 | 8 | 16 | 32 | 128 | 256 | 512      # what a SDXL_DTYPE_F32_SPLIT_MIX_F16W model reports (tests/test_gpu_models.py)
@@ -85,6 +100,26 @@ CASES = (
     ("out_960_res", "output", 6, 16, 16, False),       # widest skip ratio, no transformer
     ("head", "head", 0, 16, 16, False),                # N = 4
 )
+# the refiner configuration's cases (rows of one entry decide split-K: <= 256 rows eight slices, <= 1024 three; statistics from the epilogue on whole 256-row tiles)
+RF_CASES = (
+    ("rf_res_384", "input", 1, 16, 16, False),               # N = 384: 12 channels per GroupNorm group, K = 3456
+    ("rf_rest_768_skip", "input", 4, 16, 16, False),         # 384 -> 768 with the 1x1 skip, 12 heads
+    ("rf_rest_768_skip_mag", "input", 4, 16, 16, True),      # entry 1 at 2^10 x (not in dtype 1, as in the base)
+    ("rf_rest_1536_skip", "input", 7, 32, 32, False),        # 768 -> 1536, 24 heads at 1024 queries, three-slice split-K + producer statistics at N = 1536
+    ("rf_rest_1536", "input", 8, 16, 16, False),             # eight slices + producer statistics, 24 heads at 256 queries
+    ("rf_rest_1536_bucket", "input", 8, 36, 28, False),      # HW = 1008: padded V^T, three slices on ragged rows, the statistics pass
+    ("rf_down_1536", "input", 9, 16, 16, False),             # stride-2 convolution, K = 13824, M = 128
+    ("rf_res_1536_deep", "input", 10, 16, 16, False),        # level 3 (no transformer) at its 1024^2 size
+    ("rf_res_1536_deep_bucket", "input", 11, 18, 14, False),  # 252 rows: eight slices on one ragged tile that spans both entries
+    ("rf_middle_1536_bucket", "middle", 0, 18, 14, False),   # 252 queries / keys, 24 heads, both ResBlocks ragged
+    ("rf_out_3072", "output", 0, 8, 8, False),               # K = 27648, 64 rows per entry (statistics-buffer quotient h w / 256 = 0)
+    ("rf_out_3072_up", "output", 2, 16, 16, False),          # ResU: the folded phase upsample
+    ("rf_out_3072_up_bucket", "output", 2, 18, 14, False),   # ResU: the gather upsample (Hin Win % 128 != 0)
+    ("rf_out_2304", "output", 6, 16, 16, False),             # 2304 -> 768 + transformer, K = 20736
+    ("rf_out_1152_res", "output", 9, 16, 16, False),         # 1152 -> 384
+    ("rf_head", "head", 0, 16, 16, False),                   # K = 3456, N = 4
+)
+CONFIG_OF = {**{c[0]: "base" for c in CASES}, **{c[0]: "refiner" for c in RF_CASES}}      # case name -> key of CONFIGS
 ALL_DTYPES = (0, 1, 3)
 TRANSFORMER_DTYPES = (2, 5, 7)
 
@@ -102,11 +137,28 @@ DEFECTS = {
     "geglu_swapped": ("rest_640_skip", 0),
     "proj_out_no_residual": ("rest_640_skip", 0),
     "dst_col0": ("down_320", 0),                    # written at column 0 of the concat buffer: the slice that is read back was never written
+    # the refiner plan: the layout defects where four levels move the offsets ("rf/": the same defect, planted on a refiner case) ...
+    "rf/emb_slice_neighbour": ("rf_res_1536_deep", 0),
+    "rf/stale_ln_stats": ("rf_rest_1536", 1),
+    "rf/ctx_pad_live": ("rf_rest_768_skip", 0),
+    "rf/vt_pad_nonzero": ("rf_middle_1536_bucket", 1),      # 252 keys: 4 padded columns
+    "rf/skip_dropped": ("rf_out_1152_res", 0),
+    "rf/dst_col0": ("rf_down_1536", 0),
+    "rf/one_scale": ("rf_rest_768_skip_mag", 3),
+    # ... and three that only its shapes can show (dtype 1: the widest bounds of the case)
+    "rf/splitk_slice_lost": ("rf_res_1536_deep_bucket", 1),  # the last of eight K slices missing from conv_out
+    "rf/splitk_tail_rows": ("rf_res_1536_deep_bucket", 1),   # rows 248 ... 251 of each entry (the ragged end of its tile) get slice 0 of conv_out only
+    "rf/head_width_128": ("rf_rest_1536", 1),                # self-attention over 1536 channels as 12 heads of 128
 }
 
 
 def case(name):
-    return next(c for c in CASES if c[0] == name)
+    return next(c for c in CASES + RF_CASES if c[0] == name)
+
+
+def config(name):
+    """the UNetConfig of the case's model"""
+    return CONFIGS[CONFIG_OF[name]]
 
 
 def has_transformer(name):
@@ -118,17 +170,18 @@ def case_dtypes(name):
     return tuple(d for d in sorted(dts) if not (case(name)[5] and d == 1))
 
 
-_plan = OC.unet_block_plan(CFG)
+_plan = {k: OC.unet_block_plan(c) for k, c in CONFIGS.items()}
 
 
 def block_of(name):
     _, section, index, _, _, _ = case(name)
+    cfg, plan = config(name), _plan[CONFIG_OF[name]]
     if section == "head":
-        return dict(kind="Head", c_in=CFG.model_channels, c_out=CFG.out_channels)
+        return dict(kind="Head", c_in=cfg.model_channels, c_out=cfg.out_channels)
     if section == "middle":
-        m = _plan[1]
+        m = plan[1]
         return dict(m, c_in=m["c"], c_out=m["c"])
-    b = _plan[0 if section == "input" else 2][index]
+    b = plan[0 if section == "input" else 2][index]
     return dict(b, c_in=b.get("c_in", b.get("c")), c_out=b.get("c_out", b.get("c")))
 
 
@@ -138,7 +191,7 @@ def prefix(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ operands
-_specs = OC.unet_param_specs(CFG)
+_specs = {k: OC.unet_param_specs(c) for k, c in CONFIGS.items()}
 _weights = {}
 
 
@@ -146,17 +199,25 @@ def _own(spec_name, p):
     return spec_name.startswith(p + ".") if p else (spec_name.startswith("norm_out.") or spec_name.startswith("conv_out."))
 
 
+def _tensors(cfg_key, f16w, pick):
+    W = {}
+    for s in _specs[cfg_key]:
+        if pick(s.name):
+            v = torch.from_numpy(OC.synth_values(s.name, s.numel, s.scale, s.mean, 0).reshape(s.shape))
+            W[s.name] = v.half().float() if f16w and not s.name.endswith(".eps") else v
+    return W
+
+
 def weights(name, f16w=False):
-    """fp32 tensors of the case's own parameters + every lin_embed (seed 0; f16w: rounded to f16 values, what SEED_F16_WEIGHTS gives the engine)"""
-    key = (prefix(name), f16w)
-    if key not in _weights:
-        W = {}
-        for s in _specs:
-            if _own(s.name, key[0]) or ".lin_embed." in s.name:
-                v = torch.from_numpy(OC.synth_values(s.name, s.numel, s.scale, s.mean, 0).reshape(s.shape))
-                W[s.name] = v.half().float() if f16w and not s.name.endswith(".eps") else v
-        _weights[key] = W
-    return _weights[key]
+    """fp32 tensors of the case's own parameters + every lin_embed of its model, the latter in emb_off order and shared between the model's cases (seed
+    0; f16w: rounded to f16 values, what SEED_F16_WEIGHTS gives the engine)"""
+    k, p = CONFIG_OF[name], prefix(name)
+    if (k, None, f16w) not in _weights:
+        _weights[(k, None, f16w)] = _tensors(k, f16w, lambda n: ".lin_embed." in n)
+    if (k, p, f16w) not in _weights:
+        own = _tensors(k, f16w, lambda n: _own(n, p) and ".lin_embed." not in n)
+        _weights[(k, p, f16w)] = {**own, **_weights[(k, None, f16w)]}
+    return _weights[(k, p, f16w)]
 
 
 _inputs = {}
@@ -171,7 +232,7 @@ def inputs(name, seed=0):
         r = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
         c_in = block_of(name)["c_in"]
         x = r(B, c_in, h, w) + 0.5 * r(1, c_in, 1, 1)
-        emb, ctx = 0.5 * r(B, 4 * CFG.model_channels), r(B, N_CTX, CFG.context_dim)
+        emb, ctx = 0.5 * r(B, 4 * config(name).model_channels), r(B, N_CTX, config(name).context_dim)
         if mag:
             x[1] *= 2.0 ** 10
         _inputs[(name, seed)] = (x.contiguous(), emb.contiguous(), ctx.contiguous())
@@ -329,7 +390,7 @@ def _res_block(m, x, emb, W, p, defect=None):
     Bn = x.shape[0]
     le = p + ".lin_embed"
     if defect == "emb_slice_neighbour":      # the slice of the ResBlock that follows in emb_off order with the same width
-        names = [s.name[:-len(".weight")] for s in _specs if s.name.endswith(".lin_embed.weight")]
+        names = [n[:-len(".weight")] for n in W if n.endswith(".lin_embed.weight")]      # (weights(): every lin_embed of the model, in emb_off order)
         c_out = W[le + ".weight"].shape[1]
         le = next(n for n in names[names.index(le) + 1:] + names[:names.index(le)] if W[n + ".weight"].shape[1] == c_out)
     e = F.silu(emb.flip(0) if defect == "emb_other_entry" else emb) @ W[le + ".weight"] + W[le + ".bias"]      # the fp32 GEMV over all ResBlocks
@@ -337,7 +398,17 @@ def _res_block(m, x, emb, W, p, defect=None):
     h = _conv(m, _gn(x, W, p + ".norm_in", True, st_in), W, p + ".conv_in", "conv_res", padding=1) + e[:, :, None, None]
     if m.h16:
         h = f16(h)
-    h = _conv(m, _gn(h, W, p + ".norm_out", True, st_in if defect == "norm_out_stats_in" else None), W, p + ".conv_out", "conv_res", padding=1)
+    g = _gn(h, W, p + ".norm_out", True, st_in if defect == "norm_out_stats_in" else None)
+    h = _conv(m, g, W, p + ".conv_out", "conv_res", padding=1)
+    if defect in ("splitk_slice_lost", "splitk_tail_rows"):      # conv_out in eight K slices (K ordered C k k: a slice is an eighth of the channels)
+        w, c8 = W[p + ".conv_out.weight"], h.shape[1] // 8
+        part = lambda lo, hi: _conv(m, g[:, lo:hi], {"w.weight": w[:, lo:hi].contiguous(), "w.bias": W[p + ".conv_out.bias"]}, "w", "conv_res", padding=1)      # noqa: E731
+        if defect == "splitk_slice_lost":
+            h = part(0, 7 * c8)
+        else:      # the last rows of each entry's (ragged) tile: only slice 0 arrived
+            rows = h.flatten(2).clone()
+            rows[:, :, -4:] = part(0, c8).flatten(2)[:, :, -4:]
+            h = rows.reshape(h.shape)
     if p + ".skip_connection.weight" not in W:
         return _stream(m, x + h)
     if defect == "skip_dropped":
@@ -347,7 +418,9 @@ def _res_block(m, x, emb, W, p, defect=None):
     if m.split:      # hl_operand: the (hi, lo) halves are those of x times one power of two per batch entry
         sc = [_pow2_scale(float(x[0 if defect == "one_scale" else b].abs().max())) for b in range(Bn)]
         sc = torch.tensor(sc, dtype=torch.float32).reshape(Bn, 1, 1, 1)
-    return _stream(m, _conv(m, x, W, p + ".skip_connection", "conv_skip", a_scale=sc) + h)
+    # (the skip convolution writes the destination, conv_out reads it back as its residual operand -- UNet::res_block: run_conv(w.skip, ..., out, es);
+    #  e2.R = out -- so an f16 stream rounds skip(x) on its own before the sum is rounded)
+    return _stream(m, _stream(m, _conv(m, x, W, p + ".skip_connection", "conv_skip", a_scale=sc)) + h)
 
 
 def _transformer(m, x, ctx, W, p, n_head, depth, defect=None):
@@ -361,7 +434,7 @@ def _transformer(m, x, ctx, W, p, n_head, depth, defect=None):
     for j in range(depth):
         q = f"{p}.blocks.{j}"
         a = _ln(t, W, q + ".norm1", stale if defect == "stale_ln_stats" and j == 1 else None)
-        a = _attention(m, *(_lin(m, a, W, f"{q}.attn1.{n}", "qkv") for n in ("query", "key", "value")), n_head, "attn", defect)
+        a = _attention(m, *(_lin(m, a, W, f"{q}.attn1.{n}", "qkv") for n in ("query", "key", "value")), n_head // 2 if defect == "head_width_128" else n_head, "attn", defect)
         t = _stream(m, t + _lin(m, a, W, q + ".attn1.out", "out1"))
         a = _attention(m, _lin(m, _ln(t, W, q + ".norm2"), W, q + ".attn2.query", "q2"), _lin(m, ctx, W, q + ".attn2.key", "xkv"),
                        _lin(m, ctx, W, q + ".attn2.value", "xkv"), n_head, "xattn", pad_keys=96 - N_CTX if defect == "ctx_pad_live" else 0)
@@ -376,7 +449,8 @@ def _transformer(m, x, ctx, W, p, n_head, depth, defect=None):
 
 
 def emulate(name, dtype, defect=None, seed=0, mix=None):
-    """the entry's output [B,c_out,h_out,w_out] (fp32) in the arithmetic of `dtype`"""
+    """the entry's output [B,c_out,h_out,w_out] (fp32) in the arithmetic of `dtype`; defect: a key of DEFECTS ("rf/x" plants x)"""
+    defect = defect and defect.rpartition("/")[2]
     m = mode_of(dtype, mix)
     _, section, _, _, _, _ = case(name)
     b, p, W = block_of(name), prefix(name), weights(name, m.f16w)
