@@ -664,8 +664,8 @@ int sdxl_skip_residual_add_steps(sdxl_ctx* ctx, void* stream, int n_segments, vo
 /* ---- Control options: how a control net's residuals enter a trajectory, as the scale of every iteration i (timestep t_i) and batch entry b
  *   s(i, b) = (t_lo <= t_i <= t_hi) ? (n_scales ? scales[b mod n] : scale) : 0,     and 0 for the unconditional entries b >= n where cond_only is set
  * (entries 0 .. n-1 are the conditional ones, n .. 2n-1 the unconditional ones of the CFG pair; t_lo / t_hi are diffusers' control_guidance_start /
- * _end as timesteps) -- rows of the table sdxl_skip_residual_add_steps reads.  The Diffuser's trajectories do not take a control net yet
- * (DESIGN.md 3.8): nothing reads these options so far. */
+ * _end as timesteps) -- rows of the table sdxl_skip_residual_add_steps reads.  sdxl_control_scale_table builds such a table from them.  The
+ * Diffuser's trajectories do not take a control net yet. */
 typedef struct {
   float   scale;       /* conditioning scale of every entry (default 1) */
   int32_t n_scales;    /* 0, or cond.n */
@@ -677,6 +677,22 @@ void sdxl_control_default(sdxl_control* c);
 /* host logic only (no device).  SDXL_ERR_INVALID with the reason in sdxl_last_error: a non-finite scale; n_scales outside 0..8; t_lo < 0 or
  * t_lo > t_hi; cond_only with single_branch != 0 (one branch, as under SDXL_GUIDANCE_OFF, has no unconditional entries). */
 int sdxl_control_check(const sdxl_control* c, int single_branch);
+/* host logic only (no device): the scales of one control net over a trajectory.  timesteps: the iters timesteps t_i of the schedule, in order; n: cond.n;
+ * out: [iters + 1][8] floats,  out[i][b] = s(i, b)  for the entries b of the batch (n with single_branch != 0, else 2 n) and 0 behind them; row `iters`
+ * is all zeros (the row a trajectory's step index rests on after its last iteration).
+ * SDXL_ERR_INVALID, out untouched: what sdxl_control_check refuses; n < 1 or a batch above 8; n_scales neither 0 nor n; iters < 0; a null pointer. */
+int sdxl_control_scale_table(const sdxl_control* c, int n, int single_branch, const int32_t* timesteps, int iters, float* out);
+/* The per-step add with K sources per destination (K control nets on one UNet), in ONE launch with one rounding: src holds n_segments x K pointers,
+ * src[i * K + k] the dense [rows[i]][C[i]] source k of segment i; scales_dev is a device table of rows of K x 8 floats, and source k of element (r, c)
+ * of segment i has the scale  s_k = scales_dev[(*step_idx_dev * K + k) * 8 + b],  b = r / (rows[i] / B).  Per element, in fp32:
+ *   v = dst;  for k = 0 .. K-1 in order, where s_k != 0:  v = fma(s_k, src_k, v);   dst = round(v) where any s_k != 0.
+ * A source whose own scale is 0 is not read, whatever the others' scales: it may hold NaN, or end before row r (a control net that ran on the
+ * conditional entries alone holds the first rows[i] / B * n rows).  An element all of whose scales are 0 is not written.  K == 1 gives the bits of
+ * sdxl_skip_residual_add_steps.
+ * SDXL_ERR_INVALID, nothing launched: what sdxl_skip_residual_add_steps refuses (for every one of the K sources), K outside 1 .. SDXL_MAX_CONTROLS. */
+#define SDXL_MAX_CONTROLS 4
+int sdxl_skip_residual_add_steps_multi(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src, int K,
+                                       const int64_t* rows, const int32_t* C, int B, const float* scales_dev, const int32_t* step_idx_dev, int dtype);
 /* LayerNorm::forward (layernorm/mod.rs:34-49) followed by nn::Linear, as TransformerBlock::forward pairs them
  * (unet/mod.rs:885-891): y = LN(x[M,K]; gamma, beta, eps) @ W[K,N] + b (bias may be NULL), optional GEGLU.  Runs the path
  * the UNet runs in that dtype: SDXL_DTYPE_F16 = LayerNorm folded into the GEMM (row statistics from the producer's

@@ -15,4 +15,5 @@ _Static_assert(offsetof(sdxl_guidance, mode) == 0 && offsetof(sdxl_guidance, res
 _Static_assert(offsetof(sdxl_control, scale) == 0 && offsetof(sdxl_control, n_scales) == 4 && offsetof(sdxl_control, scales) == 8 &&
                offsetof(sdxl_control, t_lo) == 40 && offsetof(sdxl_control, t_hi) == 44 && offsetof(sdxl_control, cond_only) == 48 &&
                sizeof(sdxl_control) == 52, "sdxl_control layout");
+_Static_assert(SDXL_MAX_CONTROLS == 4, "control nets per handle");
 int sdxl_mi355_abi_check(void) { return SDXL_OK; }

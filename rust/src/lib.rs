@@ -444,8 +444,10 @@ impl Guidance {
         g
     }
 }
+/// `SDXL_MAX_CONTROLS`: sources of one `sdxl_skip_residual_add_steps_multi` launch
+pub const MAX_CONTROLS: usize = ffi::SDXL_MAX_CONTROLS as usize;
 /// how a control net's residuals enter a trajectory, as a scale per iteration and batch entry (`sdxl_control`).  `Control::default()` is scale 1
-/// for every entry on every iteration.  The `Diffuser` does not take a control net yet: nothing reads these options so far.
+/// for every entry on every iteration.  `Control::scale_table` is the table they describe; the `Diffuser` does not take a control net yet.
 #[derive(Clone, Debug, PartialEq)]
 pub struct Control {
     /// the conditioning scale of every entry
@@ -477,6 +479,16 @@ impl Control {
         }
         c.cond_only = self.cond_only as i32;
         c
+    }
+    /// `sdxl_control_scale_table` (host logic only): the scales of one control net over a trajectory, `timesteps.len() + 1` rows of 8 -- row `i` for the
+    /// iteration at `timesteps[i]`, column `b` for batch entry `b` (`n` entries with `single_branch`, else the `2 n` of the CFG pair), the last row zeros
+    pub fn scale_table(&self, n: usize, single_branch: bool, timesteps: &[i32]) -> Result<Vec<[f32; 8]>, Box<dyn std::error::Error>> {
+        let c = self.to_c();
+        let mut out = vec![[0f32; 8]; timesteps.len() + 1];
+        try_check(unsafe {
+            ffi::sdxl_control_scale_table(&c, n as c_int, single_branch as c_int, timesteps.as_ptr(), timesteps.len() as c_int, out.as_mut_ptr() as *mut f32)
+        })?;
+        Ok(out)
     }
     /// `sdxl_control_check` (host logic only): what the engine refuses about these options, for one branch or the CFG pair
     pub fn check(&self, single_branch: bool) -> Result<(), Box<dyn std::error::Error>> {

@@ -102,6 +102,9 @@ class Control(ctypes.Structure):
                 f"cond_only={bool(self.cond_only)})")
 
 
+MAX_CONTROLS = 4     # SDXL_MAX_CONTROLS
+
+
 GUIDANCE_CFG = 0     # SDXL_GUIDANCE_CFG: classifier-free guidance (default)
 GUIDANCE_OFF = 1     # SDXL_GUIDANCE_OFF: the conditional branch alone (distilled checkpoints); unconditional tensors may be None
 _GUIDANCE_MODES = {"cfg": GUIDANCE_CFG, "off": GUIDANCE_OFF}
@@ -133,6 +136,7 @@ ABI_SYMBOLS = [
     "sdxl_transformer_projection",
     "sdxl_unet_skip_count", "sdxl_unet_skip_shape", "sdxl_unet_forward_residuals", "sdxl_skip_residual_add",
     "sdxl_skip_residual_add_steps", "sdxl_control_default", "sdxl_control_check",
+    "sdxl_skip_residual_add_steps_multi", "sdxl_control_scale_table",
     "sdxl_controlnet_config_default", "sdxl_controlnet_param_count", "sdxl_controlnet_param_spec", "sdxl_controlnet_create", "sdxl_controlnet_create_f16",
     "sdxl_controlnet_create_synthetic", "sdxl_controlnet_destroy", "sdxl_controlnet_embed_hint", "sdxl_controlnet_forward",
     "sdxl_lora_check", "sdxl_lora_merge", "sdxl_unet_create_lora", "sdxl_diffuser_create_lora",
@@ -205,6 +209,10 @@ def lib() -> ctypes.CDLL:
             l.sdxl_control_default.restype = None
             l.sdxl_control_default.argtypes = [ctypes.POINTER(Control)]
             l.sdxl_control_check.argtypes = [ctypes.POINTER(Control), ctypes.c_int]
+        if hasattr(l, "sdxl_skip_residual_add_steps_multi"):
+            l.sdxl_skip_residual_add_steps_multi.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] + \
+                [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_control_scale_table.argtypes = [ctypes.POINTER(Control), ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         _lib = l
     return _lib
 
@@ -1070,6 +1078,18 @@ def control_check(c: Control, single_branch: bool = False):
     _check_invalid(lib().sdxl_control_check(ctypes.byref(c), int(single_branch)))
 
 
+def control_scale_table(c: Control, n: int, timesteps, single_branch: bool = False):
+    """sdxl_control_scale_table (host logic, no GPU needed): the scales of one control net over a trajectory as a float32 numpy array
+    [len(timesteps) + 1, 8] -- row i for the iteration at timesteps[i], column b for batch entry b (n entries with single_branch, else the 2 n of the
+    CFG pair), the last row zeros.  InvalidArgument: what control_check refuses, a batch above 8, n_scales neither 0 nor n."""
+    import numpy as np
+    ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int32).reshape(-1))
+    out = np.full((ts.size + 1, 8), np.nan, dtype=np.float32)
+    _check_invalid(lib().sdxl_control_scale_table(ctypes.byref(c), int(n), int(single_branch), ts.ctypes.data_as(ctypes.c_void_p), int(ts.size),
+                                                  out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
 def guidance_check(g: Guidance, is_refiner: bool = False):
     """sdxl_guidance_check (host logic, no GPU needed): raises InvalidArgument with the first complaint"""
     _check_invalid(lib().sdxl_guidance_check(ctypes.byref(g), int(is_refiner)))
@@ -1630,6 +1650,57 @@ def skip_residual_add_steps(ctx: Context, segments, B: int, scales, step_idx):
     cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
     _check_invalid(lib().sdxl_skip_residual_add_steps(ctx.h, _stream(), n, dst, ld, src, rows, cols, int(B), ctypes.c_void_p(scales.data_ptr()), pi,
                                                       DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
+
+
+def skip_residual_add_steps_multi(ctx: Context, segments, B: int, scales, step_idx):
+    """sdxl_skip_residual_add_steps_multi, the ControlNet add of K nets in one launch: segments = [(dst, [src_0 .. src_K-1]), ...], scales a float32
+    CUDA tensor [steps, K, 8]; source k of row r has the scale scales[step_idx, k, r // (rows // B)], the sum runs in fp32 over the sources in order and
+    is rounded once.  A source at scale 0 is not read.  A source may hold fewer rows than dst (whole batch entries: a net run on the conditional
+    entries alone) where every entry behind its end is at scale 0 in the row step_idx names -- checked here, by reading that row.
+    InvalidArgument (nothing written): what skip_residual_add_steps refuses, K outside 1..4."""
+    torch = _torch()
+    segments = [(d, list(ss)) for d, ss in segments]
+    n = len(segments)
+    if n < 1:
+        raise InvalidArgument("skip_residual_add_steps_multi: at least one segment")
+    K = len(segments[0][1])
+    if not 1 <= K <= 4 or any(len(ss) != K for _, ss in segments):
+        raise InvalidArgument("skip_residual_add_steps_multi: the number of sources K must be in 1..4, the same for every segment")
+    dt = segments[0][0].dtype
+    if dt not in (torch.float32, torch.float16):
+        raise InvalidArgument("skip_residual_add_steps_multi: float32 or float16 tensors")
+    if not (torch.is_tensor(scales) and scales.is_cuda and scales.dtype == torch.float32 and scales.dim() == 3 and tuple(scales.shape[1:]) == (K, 8)
+            and scales.is_contiguous()):
+        raise InvalidArgument("skip_residual_add_steps_multi: scales must be a contiguous float32 CUDA tensor [steps, K, 8]")
+    if not torch.is_tensor(step_idx):
+        if not 0 <= int(step_idx) < scales.shape[0]:
+            raise InvalidArgument("skip_residual_add_steps_multi: step_idx outside the scale table")
+        step_idx = torch.tensor([int(step_idx)], dtype=torch.int32, device=scales.device)
+    step_idx, pi = _dev(step_idx, torch.int32)
+    row = None
+    for d, ss in segments:
+        if not d.is_cuda or d.dim() != 2 or (d.shape[1] > 1 and d.stride(1) != 1) or d.stride(0) < d.shape[1]:
+            raise InvalidArgument("skip_residual_add_steps_multi: dst must be a [rows, C] view with contiguous columns, on the GPU")
+        for k, s in enumerate(ss):
+            if not s.is_cuda or s.dtype != dt or d.dtype != dt or s.dim() != 2 or s.shape[1] != d.shape[1] or s.shape[0] > d.shape[0] or not s.is_contiguous():
+                raise InvalidArgument("skip_residual_add_steps_multi: every src must be a dense [rows, C] tensor of dst's dtype and width, on the GPU")
+            if s.shape[0] < d.shape[0]:
+                if not 1 <= int(B) <= 8 or d.shape[0] % int(B) != 0 or s.shape[0] % (d.shape[0] // int(B)) != 0:
+                    raise InvalidArgument("skip_residual_add_steps_multi: a short source must hold whole batch entries (rows a multiple of B)")
+                if row is None:
+                    i = int(step_idx.item())
+                    if not 0 <= i < scales.shape[0]:
+                        raise InvalidArgument("skip_residual_add_steps_multi: step_idx outside the scale table")
+                    row = scales[i].cpu()
+                if bool((row[k, s.shape[0] // (d.shape[0] // int(B)):int(B)] != 0).any()):
+                    raise InvalidArgument("skip_residual_add_steps_multi: a short source needs scale 0 for every entry behind its end")
+    dst = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in segments])
+    src = (ctypes.c_void_p * (n * K))(*[s.data_ptr() for _, ss in segments for s in ss])
+    ld = (ctypes.c_int64 * n)(*[int(d.stride(0)) for d, _ in segments])
+    rows = (ctypes.c_int64 * n)(*[int(d.shape[0]) for d, _ in segments])
+    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
+    _check_invalid(lib().sdxl_skip_residual_add_steps_multi(ctx.h, _stream(), n, dst, ld, src, K, rows, cols, int(B), ctypes.c_void_p(scales.data_ptr()), pi,
+                                                            DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
 
 
 def _opt(t):

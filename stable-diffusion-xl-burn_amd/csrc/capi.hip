@@ -904,6 +904,11 @@ int sdxl_control_check(const sdxl_control* c, int single_branch) {
   if (const char* m = control_error(to_control(c), single_branch != 0)) return fail(SDXL_ERR_INVALID, m);
   return SDXL_OK;
 }
+int sdxl_control_scale_table(const sdxl_control* c, int n, int single_branch, const int32_t* timesteps, int iters, float* out) {
+  if (!c) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = control_scale_table(to_control(c), n, single_branch != 0, timesteps, iters, out)) return fail(SDXL_ERR_INVALID, m);
+  return SDXL_OK;
+}
 int sdxl_cfg_rescale_factors(sdxl_ctx* ctx, void* stream, const float* eps, int n, int HW, const float* scales, float rescale,
                              float* factors_out) {
   if (!ctx || !eps || !scales || !factors_out) return fail(SDXL_ERR_INVALID, "null argument");

@@ -918,6 +918,68 @@ __global__ __launch_bounds__(256) void skip_residual_add_steps_kernel(const Skip
     *d = v;
   }
 }
+// K sources per destination (kernels.h SkipSegN: several control nets on one UNet).  The walk is the kernel's above; the K x 8 scales of the table row
+// [*step_idx][K][8] sit in registers (32 at K = 4), every source's scale is picked by the same compares (k and j are unrolled: no dynamic index, no
+// scratch).  The running sum stays in fp32 across the sources and is rounded once.  A source at scale 0 is not read -- it may hold NaN, or be shorter
+// than the segment (a net that ran on the conditional entries alone) -- and a chunk whose scales are all 0 is not written.  K = 1 is the
+// kernel above bit for bit: (T)fmaf(s, (float)a, (float)d).
+template <typename T, int K>
+__global__ __launch_bounds__(256) void skip_residual_add_steps_multi_kernel(const SkipSegN* __restrict__ table, int n_seg, unsigned long long total,
+                                                                            const float* __restrict__ scales, const int* __restrict__ step_idx, unsigned B) {
+  constexpr int E = 16 / (int)sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(E)));
+  float sv[K][kSkipScaleEntries];
+  {
+    const float* row = scales + (size_t)*step_idx * (K * kSkipScaleEntries);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int j = 0; j < kSkipScaleEntries; ++j) sv[k][j] = row[k * kSkipScaleEntries + j];
+  }
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  int si = 0;
+  SkipSegN g = table[0];
+  unsigned long long end = n_seg > 1 ? table[1].first : total;
+  unsigned rpe = (unsigned)g.rows / B;      // rows per batch entry (skip_table_check_entries: rows % B == 0)
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    while (i >= end) {      // (i < total = the last segment's end: si stays inside the table)
+      ++si;
+      g = table[si];
+      end = si + 1 < n_seg ? table[si + 1].first : total;
+      rpe = (unsigned)g.rows / B;
+    }
+    const unsigned l = (unsigned)(i - g.first);      // (skip_table_check: a segment has fewer than 2^32 chunks -- 32-bit divisions)
+    const unsigned cpr = (unsigned)g.C / E;
+    const unsigned row = l / cpr;
+    const unsigned cc = l - row * cpr;
+    const unsigned b = row / rpe;      // (a segment that holds a chunk has rows >= B: rpe >= 1, and b < B)
+    float sc[K];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      sc[k] = sv[k][0];
+#pragma unroll
+      for (int j = 1; j < kSkipScaleEntries; ++j) sc[k] = b == (unsigned)j ? sv[k][j] : sc[k];
+      any = any || sc[k] != 0.f;
+    }
+    if (!any) continue;
+    vec_t* d = reinterpret_cast<vec_t*>(reinterpret_cast<T*>(g.dst) + (unsigned long long)row * (unsigned long long)g.dst_ld) + cc;
+    vec_t v = *d;
+    float f[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) f[j] = (float)v[j];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (sc[k] == 0.f) continue;
+      const vec_t a = reinterpret_cast<const vec_t*>(g.src[k])[l];
+#pragma unroll
+      for (int j = 0; j < E; ++j) f[j] = fmaf(sc[k], (float)a[j], f[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < E; ++j) v[j] = (T)f[j];
+    *d = v;
+  }
+}
 // SiLU in place over a dense tensor (a control net's hint embedder, once per hint: off the per-step path and left plain)
 __global__ void silu_inplace_kernel(void* p, int dt, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -964,6 +1026,42 @@ void launch_skip_residual_add_steps(const SkipSeg* table_dev, int n_seg, unsigne
   const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
   if (dt == DT_F16) hipLaunchKernelGGL(skip_residual_add_steps_kernel<half_t>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
   else hipLaunchKernelGGL(skip_residual_add_steps_kernel<float>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
+}
+const char* skip_table_check_sources(SkipSegN* t, int n_seg, int K, int B, int dt, unsigned long long* total_chunks) {
+  if (K < 1 || K > kSkipMaxSources) return "skip residual add: the number of sources K must be in 1..4";
+  if (n_seg < 1 || !t) return "skip residual add: at least one segment";
+  constexpr int kMaxSegs = 64;      // (the C entry takes 16; a UNet's table has one segment per input entry + 1)
+  if (n_seg > kMaxSegs) return "skip residual add: at most 64 segments";
+  SkipSeg one[kMaxSegs];
+  for (int i = 0; i < n_seg; ++i) one[i] = SkipSeg{t[i].dst, t[i].src[0], t[i].dst_ld, t[i].rows, t[i].C, 0ull};
+  if (const char* bad = skip_table_check(one, n_seg, dt, total_chunks)) return bad;
+  if (const char* bad = skip_table_check_entries(one, n_seg, B)) return bad;
+  for (int i = 0; i < n_seg; ++i) {
+    t[i].first = one[i].first;
+    for (int k = 1; k < K; ++k) {
+      if (!t[i].src[k]) return "skip residual add: null segment pointer";
+      if ((uintptr_t)t[i].src[k] & 15) return "skip residual add: dst, src and the row pitch of dst must be 16-byte aligned";
+    }
+  }
+  return nullptr;
+}
+template <typename T>
+static void launch_multi_t(int K, unsigned grid, hipStream_t s, const SkipSegN* table_dev, int n_seg, unsigned long long total, const float* scales_dev,
+                           const int* step_idx_dev, unsigned B) {
+  switch (K) {
+    case 1: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 1>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
+    case 2: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 2>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
+    case 3: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 3>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
+    default: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 4>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
+  }
+}
+void launch_skip_residual_add_steps_multi(const SkipSegN* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev,
+                                          const int* step_idx_dev, int B, int dt, hipStream_t s) {
+  if (!total_chunks) return;
+  if (K < 1 || K > kSkipMaxSources) throw std::runtime_error("skip residual add: the number of sources K must be in 1..4");      // (skip_table_check_sources)
+  const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
+  if (dt == DT_F16) launch_multi_t<half_t>(K, grid, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
+  else launch_multi_t<float>(K, grid, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -574,7 +574,8 @@ class UNet {
   ControlCfg ccfg_;
   Lin hint_conv_[8]; std::vector<Lin> zero_; Lin mid_out_;
   void run_control(Exec& ex, int B, int H, int W, void* in);
-  std::vector<void*> ctl_res_;             // persistent residual buffers of the plan (dense NHWC, stream dtype), skip_shapes order
+  std::vector<void*> ctl_res_;             // persistent residual buffers of the plan (dense NHWC, stream dtype), skip_shapes order; zero-filled with the plan
+  std::vector<size_t> ctl_res_bytes_;
   DeviceArena hint_arena_;
   void* hint_g_ = nullptr; int hint_n_ = 0, hint_B_ = 0, hint_H_ = 0, hint_W_ = 0;
   const void* graph_hint_ = nullptr;
@@ -719,6 +720,10 @@ struct Control {
 };
 // host logic only: the first complaint about `c` (`single`: one branch, no CFG pair), nullptr where it is valid
 const char* control_error(const Control& c, bool single);
+// host logic only: the scales of one control net over a trajectory, out[iters + 1][8]:  out[i][b] = s(i, b) of the public header for the iteration at
+// timesteps[i] and batch entry b of B = n (single) or 2 n, 0 for b >= B; row `iters` is zeros (where a device step index rests after the last
+// iteration).  nullptr, or the complaint: control_error, n outside the batch, n_scales neither 0 nor n, a null pointer.
+const char* control_scale_table(const Control& c, int n, bool single, const int* timesteps, int iters, float* out);
 
 // The trajectory minus the UNet: the coefficient table, the guidance interval and the launches between two UNet forwards.  Diffuser::diffuse
 // drives one with the UNet's output; sdxl_sampler_step_replay (the op-level test seam) drives one with given noise predictions.

@@ -423,6 +423,18 @@ constexpr int kSkipScaleEntries = 8;
 const char* skip_table_check_entries(const SkipSeg* table_host, int n_seg, int B);
 void launch_skip_residual_add_steps(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scales_dev, const int* step_idx_dev,
                                     int B, int dt, hipStream_t s);
+// The per-step add with K sources per destination (several control nets on one UNet; sdxl_skip_residual_add_steps_multi): one launch, one read and one
+// write of every destination, one rounding.  Source k of a chunk has the scale scales_dev[(*step_idx_dev * K + k) * 8 + b] -- a device table
+// [iterations + 1][K][8].  Per element: v = (float)dst; for k = 0 .. K-1 in order, where s_k != 0: v = fmaf(s_k, (float)src_k, v); dst = round_to_dt(v) where
+// any s_k != 0.  A source whose own scale is 0 is not read (it may hold NaN, or end before the chunk: a control net run on the conditional entries
+// alone); a chunk all of whose scales are 0 is not written.  K = 1 gives the bits of launch_skip_residual_add_steps.  src[k >= K] are not looked at.
+constexpr int kSkipMaxSources = 4;
+struct SkipSegN { void* dst; const void* src[kSkipMaxSources]; long long dst_ld; int rows; int C; unsigned long long first; };
+// host logic only: skip_table_check and skip_table_check_entries over (dst, src[0]), K in 1..kSkipMaxSources, and every src[k < K] non-null and
+// 16-byte aligned; nullptr where the table can run, else the complaint; fills SkipSegN::first and *total_chunks
+const char* skip_table_check_sources(SkipSegN* table_host, int n_seg, int K, int B, int dt, unsigned long long* total_chunks);
+void launch_skip_residual_add_steps_multi(const SkipSegN* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev,
+                                          const int* step_idx_dev, int B, int dt, hipStream_t s);
 void launch_silu_inplace(void* p, int dt, size_t n, hipStream_t s);      // p[i] = silu(p[i]), dense, DT_F32 / DT_F16
 // image post-process (stablediffusion/mod.rs:210-230): u8 = trunc(clamp(((x+1)/2)*255, 0, 255)), NHWC rows of 3
 void launch_to_u8_image(const void* src, int dt, int lds, unsigned char* dst, size_t pixels, hipStream_t s);

@@ -88,6 +88,21 @@ const char* control_error(const Control& c, bool single) {
   return nullptr;
 }
 
+const char* control_scale_table(const Control& c, int n, bool single, const int* timesteps, int iters, float* out) {
+  if (const char* m = control_error(c, single)) return m;
+  if (n < 1 || (single ? n : 2 * n) > kMaxSeeds) return "control: batch out of range (n in 1..8, 1..4 with the CFG pair)";
+  if (c.n_scales != 0 && c.n_scales != n) return "control: n_scales differs from the batch (cond.n)";
+  if (iters < 0 || (iters > 0 && !timesteps) || !out) return "control: null argument";
+  const int B = single ? n : 2 * n;
+  for (int i = 0; i <= iters; ++i) {
+    float* row = out + (size_t)i * kMaxSeeds;
+    const bool on = i < iters && timesteps[i] >= c.t_lo && timesteps[i] <= c.t_hi;      // row `iters`: the sentinel a step index rests on
+    for (int b = 0; b < kMaxSeeds; ++b)
+      row[b] = on && b < B && !(c.cond_only && b >= n) ? (c.n_scales ? c.scales[b % n] : c.scale) : 0.f;
+  }
+  return nullptr;
+}
+
 void Diffuser::set_prediction(int prediction) {
   SDXL_REQUIRE(prediction == kPredictionEpsilon || prediction == kPredictionV, "unknown prediction");
   prediction_ = prediction;

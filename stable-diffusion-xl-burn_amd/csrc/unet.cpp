@@ -867,8 +867,11 @@ void UNet::ensure_plan(int B, int H, int W) {
     gn_partial_ = (float*)act_.alloc(groupnorm_workspace_floats(B, 32) * sizeof(float));
     tconv_ = (float*)act_.alloc(8 * sizeof(float));
     if (control_) {      // the residual tensors: fixed addresses for the plan (the controlled UNet's segment table and both graphs hold them)
-      ctl_res_.clear();
-      for (const SkipShape& k : skip_shapes(cfg_, H, W)) ctl_res_.push_back(act_.alloc((size_t)B * k.C * k.h * k.w * dt_size(sdt_)));
+      ctl_res_.clear(); ctl_res_bytes_.clear();
+      for (const SkipShape& k : skip_shapes(cfg_, H, W)) {
+        ctl_res_bytes_.push_back((size_t)B * k.C * k.h * k.w * dt_size(sdt_));
+        ctl_res_.push_back(act_.alloc(ctl_res_bytes_.back()));
+      }
     }
     if (attn16_) {   // cross-workgroup key split of the (f16) self-attention: workspace + tickets per chain, sized for the largest level
       size_t wsb = 0, cnt = 0;
@@ -933,6 +936,8 @@ void UNet::ensure_plan(int B, int H, int W) {
   persist();
   for (int c = 0; c < 2; ++c) if (skcnt_[c]) SDXL_HIP(hipMemset(skcnt_[c], 0, kSplitkCounters * sizeof(unsigned)));   // armed once
   for (int c = 0; c < (split ? 2 : 1); ++c) if (attn_xcnt_[c] && attn16_) SDXL_HIP(hipMemset(attn_xcnt_[c], 0, attn_xcnt_bytes_));
+  // a control net's residual buffers start as zeros, not as what the allocation held: a reader in front of the first forward sees numbers
+  for (size_t i = 0; i < ctl_res_.size() && control_; ++i) SDXL_HIP(hipMemset(ctl_res_[i], 0, ctl_res_bytes_[i]));
 }
 
 void* UNet::unet_in(int B, int H, int W) { ensure_plan(B, H, W); return in_; }
@@ -1239,6 +1244,7 @@ void UNet::set_hint(const float* hint, int n, int B, int H, int W, hipStream_t s
   // the eight convolutions with a SiLU launch between them, every layer's output kept: once over a dry arena for the size, then for real
   auto pass = [&](Exec& ex) {
     void* g = ex.act->alloc((B / n) * g_bytes);
+    if (!ex.dry) SDXL_HIP(hipMemsetAsync(g, 0, (B / n) * g_bytes, s));      // (zeros under the convolutions' writes, not what the allocation held)
     Act x = ex.alloc((size_t)n * H8 * W8, ch[0], input_dt());
     if (!ex.dry) launch_nchw_to_nhwc(hint, ch[0] * H8 * W8, x.p, x.dt, n, ch[0], H8 * W8, ch[0], 1.0f, s);
     int h = H8, w = W8;
