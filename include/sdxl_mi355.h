@@ -272,7 +272,7 @@ int sdxl_step_count(int n_steps, int step_start, int n_train_steps);
  * (0, 1, 0, 0), the iteration returns x0); second order everywhere else.  At eta = 0 a first-order row equals DDIM's.  The
  * draw numbers do not change: SDXL_DRAW_SIGMA(i) is the z of iteration i for both solvers, drawn where c_z != 0; with explicit
  * noise eta is 0.  Inpainting keeps its blend in front of every iteration; x0p is the x0 computed from the blended state. */
-enum { SDXL_SOLVER_DDIM = 0, SDXL_SOLVER_DPMPP_2M = 1 };
+enum { SDXL_SOLVER_DDIM = 0, SDXL_SOLVER_DPMPP_2M = 1, SDXL_SOLVER_LCM = 3, SDXL_SOLVER_TCD = 4 };   /* 2 is not a solver: it stays refused */
 /* unknown value: SDXL_ERR_INVALID ("solver" in sdxl_last_error), the handle keeps its solver */
 int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver);
 int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out);
@@ -312,6 +312,63 @@ int sdxl_rescale_zero_terminal_snr(const float* alphas_cumprod_in, int n_train_s
  * entry with SDXL_PREDICTION_EPSILON. */
 int sdxl_solver_coefficients_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver,
                                   int prediction, double eta, double* out, int capacity_steps);
+/* ---- few-step sampling: timestep lists and the consistency solvers (distilled checkpoints: LCM / TCD / Hyper-SD LoRAs through
+ * sdxl_diffuser_create_lora, Turbo, Lightning; usually with SDXL_GUIDANCE_OFF or a guidance scale near 1).
+ *
+ * Timestep list.  A trajectory is one UNet evaluation per entry of a strictly decreasing list t_0 > t_1 > ... > t_{n-1} of training
+ * timesteps, and the list is the only source of an iteration's numbers: a = alphas[t_i], ap = alphas[t_{i+1}], ap = 1 behind the last
+ * entry; the guidance interval (t_lo..t_hi), the trace, the step timing and the t fed to the UNet read it too.  Without a list the handle
+ * runs the reference's rule, sdxl_step_count's list, for which alphas[t_{i+1}] is the alphas[t_i - step] it always read: a handle that never
+ * calls the setter runs exactly what it ran before.  DDIM (with eta) and 2M (ODE and SDE; r = h_prev / h copes with uneven spacing) run on
+ * a list through the formulas above.
+ * sdxl_diffuser_set_timesteps sets a per-handle list for all six trajectory calls; n == 0 or NULL goes back to the reference's rule.
+ * SDXL_ERR_INVALID ("timesteps" in sdxl_last_error), the handle keeping what it had: n outside 1..n_train_steps, a value outside
+ * 0..n_train_steps-1, values not strictly decreasing.  With a list set, a trajectory call returns SDXL_ERR_INVALID before anything is
+ * launched where its n_steps differs from the list's length (it is not ignored); sampling and inpainting have step_start = 0;
+ * sdxl_refine_latent* keeps step_start's meaning for the re-noise level alphas[n_train_steps - step_start] and requires
+ * t_0 == n_train_steps - step_start - 1, the reference's own relation between the two.
+ * sdxl_diffuser_get_timesteps returns the count written to out, 0 for the reference's rule; capacity too small: SDXL_ERR_INVALID. */
+int sdxl_diffuser_set_timesteps(sdxl_diffuser* d, const int32_t* timesteps, int n);
+int sdxl_diffuser_get_timesteps(sdxl_diffuser* d, int32_t* out, int capacity);
+/* host logic only: the published spacings as lists.  Returns the count written, or SDXL_ERR_INVALID with out untouched (NULL, n_steps
+ * outside 1..n_train_steps, capacity smaller than the count, an unknown kind, and what each kind refuses).  Integer arithmetic (C division)
+ * except where stated; i = 0 .. count-1:
+ *   SDXL_SCHEDULE_REFERENCE  t_i = n_train - 1 - i (n_train / n_steps) while >= 0; count = sdxl_step_count(n_steps, 0, n_train): 30 -> 31
+ *   SDXL_SCHEDULE_TRAILING   t_i = rint(n_train - i q) - 1 in f64, q = n_train / n_steps in f64, ties to even (diffusers "trailing", numpy's
+ *                            round); count n_steps; 4 -> 999, 749, 499, 249 (Lightning, Turbo)
+ *   SDXL_SCHEDULE_LEADING    t_i = (n_steps - 1 - i) (n_train / n_steps) + param, param = diffusers' steps_offset (1 for SDXL); refused where
+ *                            param < 0 or t_0 >= n_train; count n_steps; 4, offset 1 -> 751, 501, 251, 1
+ *   SDXL_SCHEDULE_LCM        O = param origin steps (50 for the published LCM / TCD / Hyper-SD checkpoints), k = n_train / O,
+ *                            r_j = (O - j) k - 1, t_i = r_floor(i O / n_steps); refused where O < 1, O > n_train or n_steps > O; count n_steps;
+ *                            O = 50: 4 -> 999, 759, 499, 259;  8 -> 999, 879, 759, 639, 499, 379, 259, 139
+ * A count of 1 and SDXL_ERR_INVALID are the same number (here and in sdxl_diffuser_get_timesteps): a refusal leaves out untouched and no list
+ * holds a negative value, so a caller that may get either pre-fills out[0] with -1. */
+enum { SDXL_SCHEDULE_REFERENCE = 0, SDXL_SCHEDULE_TRAILING = 1, SDXL_SCHEDULE_LEADING = 2, SDXL_SCHEDULE_LCM = 3 };
+int sdxl_timestep_schedule(int kind, int n_steps, int n_train_steps, int param, int32_t* out, int capacity);
+/* Consistency solvers.  SDXL_SOLVER_LCM (Luo et al. 2023, multistep consistency sampling) and SDXL_SOLVER_TCD (Zheng et al. 2024,
+ * gamma-sampling; what Hyper-SD ships with) jump to a data prediction and re-noise it with fresh noise every iteration.  Both are
+ * first-order rows (c_x, c_0, 0, c_z) of x' = c_x x + c_0 x0 + c_z z above, with or without a list (without: on the reference's rule);
+ * x0 comes from the epsilon or v lines, z is the SDXL_DRAW_SIGMA(i) tensor, alpha = sqrt(a), sigma = sqrt(1-a), primes for ap.  In the
+ * per-step kernel:  acc = x0 c_0 (one rounding);  x = fma(x, c_x, acc);  x = fma(z, c_z, x) where c_z != 0.  No history is kept.
+ *   SDXL_SOLVER_LCM  diffusers' LCMScheduler.step with sigma_data = 0.5, timestep_scaling = 10:  s = 10 t,  c_skip = 0.25 / (s^2 + 0.25),
+ *                    c_out = s / sqrt(s^2 + 0.25);  row (alpha' c_skip, alpha' c_out, 0, sigma');  behind the last entry ap = 1: (c_skip, c_out,
+ *                    0, 0).  eta is not a parameter: the seeded calls, the replay and the coefficient entries return SDXL_ERR_INVALID for
+ *                    eta != 0 under this solver.
+ *   SDXL_SOLVER_TCD  diffusers' TCDScheduler.step with the seeded calls' eta in [0, 1] read as gamma (as diffusers passes it): with t' the
+ *                    next list entry, s = floor((1.0 - gamma) t') in f64, a_s = alphas[s], alpha_s, sigma_s, r = sqrt(ap / a_s):
+ *                    row (r sigma_s / sigma,  r (alpha_s - sigma_s alpha / sigma),  0,  sqrt(1 - ap / a_s)).  At gamma = 0, s = t': DDIM's row at
+ *                    eta 0, c_z = 0.  Behind the last entry the row is (0, 1, 0, 0), the engine's convention as 2M has it: the trajectory
+ *                    returns x0.  (diffusers returns sqrt(a_0) x0 + sqrt(1 - a_0) e there, a latent still at the noise level of timestep 0.)
+ * Under SDXL_PREDICTION_V a == 0 at an iteration's own timestep is admitted as above, both rows being finite there as written; under
+ * SDXL_PREDICTION_EPSILON it is refused with the message above.  The inpainting blend in front of the next iteration and the draw numbers
+ * do not change.  No seeds, no noise: an explicit-noise trajectory call, or a replay without seeds, whose table (at eta = 0) has any
+ * c_z != 0 returns SDXL_ERR_INVALID before anything is launched (the message says the solver needs the seeded calls).  Still running on
+ * explicit noise: a one-entry LCM list, TCD (gamma = 0 there), and explicit-noise inpainting with every c_z == 0, which keeps its blend. */
+/* sdxl_solver_coefficients_pred on a list: n rows for the n entries of timesteps.  SDXL_ERR_INVALID, out untouched: what that entry refuses,
+ * a list sdxl_diffuser_set_timesteps refuses, capacity_steps < n, eta != 0 under SDXL_SOLVER_LCM.  The two entries above are this one on the
+ * reference's list. */
+int sdxl_solver_coefficients_ts(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver,
+                                int prediction, double eta, double* out, int capacity_steps);
 /* ---- guidance: how the two UNet branches of an iteration become the noise prediction e, a per-handle option all six trajectory
  * calls above honour, with both solvers, explicit and seeded noise, and inpainting.  The default is the reference's line (:539-540),
  * e = eu + (ec - eu) s with the call's scalar s on every iteration, and a handle with default options runs exactly what it ran before
@@ -373,6 +430,12 @@ int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay
 /* the same replay with eps read under `prediction` (SDXL_PREDICTION_V: the rows are v); sdxl_sampler_step_replay is this entry with
  * SDXL_PREDICTION_EPSILON.  The struct is shared.  Refuses what sdxl_solver_coefficients_pred refuses. */
 int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args, int prediction);
+/* the same replay on a list: iterations = n, and the struct's n_steps and step_start are ignored (timesteps == NULL or n == 0: they are
+ * read, and this is sdxl_sampler_step_replay_pred).  The struct's layout is shared.  Refuses, before anything is launched, what that entry
+ * refuses, a list sdxl_diffuser_set_timesteps refuses, eta != 0 under SDXL_SOLVER_LCM, and seeds == NULL with any c_z != 0 in the table.
+ * hist_out stays untouched under SDXL_SOLVER_LCM and SDXL_SOLVER_TCD: they keep no history. */
+int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args, int prediction, const int32_t* timesteps,
+                                int n);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

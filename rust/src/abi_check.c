@@ -15,5 +15,7 @@ _Static_assert(offsetof(sdxl_guidance, mode) == 0 && offsetof(sdxl_guidance, res
 _Static_assert(offsetof(sdxl_control, scale) == 0 && offsetof(sdxl_control, n_scales) == 4 && offsetof(sdxl_control, scales) == 8 &&
                offsetof(sdxl_control, t_lo) == 40 && offsetof(sdxl_control, t_hi) == 44 && offsetof(sdxl_control, cond_only) == 48 &&
                sizeof(sdxl_control) == 52, "sdxl_control layout");
+_Static_assert(SDXL_SOLVER_DDIM == 0 && SDXL_SOLVER_DPMPP_2M == 1 && SDXL_SOLVER_LCM == 3 && SDXL_SOLVER_TCD == 4, "solver codes");
+_Static_assert(SDXL_SCHEDULE_REFERENCE == 0 && SDXL_SCHEDULE_TRAILING == 1 && SDXL_SCHEDULE_LEADING == 2 && SDXL_SCHEDULE_LCM == 3, "timestep schedule kinds");
 _Static_assert(SDXL_MAX_CONTROLS == 4, "control nets per handle");
 int sdxl_mi355_abi_check(void) { return SDXL_OK; }

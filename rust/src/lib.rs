@@ -391,6 +391,34 @@ pub enum Solver {
     Ddim = ffi::SDXL_SOLVER_DDIM as isize,
     /// DPM-Solver++(2M) on the same schedule, with `eta > 0` its SDE form: second order at one UNet evaluation per iteration
     Dpmpp2M = ffi::SDXL_SOLVER_DPMPP_2M as isize,
+    /// LCM multistep consistency sampling (Luo et al. 2023): jumps to the data prediction and re-noises it with fresh noise every iteration.
+    /// Takes no `eta` (it must be 0) and needs a seed (`set_seed`) beyond a one-entry list
+    Lcm = ffi::SDXL_SOLVER_LCM as isize,
+    /// TCD gamma-sampling (Zheng et al. 2024; what Hyper-SD ships with): `eta` of `set_seed` is read as gamma
+    Tcd = ffi::SDXL_SOLVER_TCD as isize,
+}
+/// a published timestep spacing (`SDXL_SCHEDULE_*`) for `timestep_schedule`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Schedule {
+    /// the reference's rule as a list: `sdxl_step_count` entries
+    Reference = ffi::SDXL_SCHEDULE_REFERENCE as isize,
+    /// diffusers' "trailing" spacing (Lightning, Turbo)
+    Trailing = ffi::SDXL_SCHEDULE_TRAILING as isize,
+    /// diffusers' "leading" spacing; `param` is `steps_offset` (1 for SDXL)
+    Leading = ffi::SDXL_SCHEDULE_LEADING as isize,
+    /// the LCM / TCD / Hyper-SD schedule; `param` is the number of origin steps (50 for the published checkpoints)
+    Lcm = ffi::SDXL_SCHEDULE_LCM as isize,
+}
+/// `sdxl_timestep_schedule` (host logic, no device): the list of `kind` for `Diffuser::set_timesteps`.  What the engine refuses is an `Err`
+/// with its message.
+pub fn timestep_schedule(kind: Schedule, n_steps: usize, n_train_steps: usize, param: i32) -> Result<Vec<i32>, Box<dyn std::error::Error>> {
+    let mut out = vec![-1i32; n_train_steps.max(1)];      // a refusal leaves `out` untouched: SDXL_ERR_INVALID (1) is also a valid count
+    let n = unsafe { ffi::sdxl_timestep_schedule(kind as c_int, n_steps as c_int, n_train_steps as c_int, param as c_int, out.as_mut_ptr(), out.len() as c_int) };
+    if n < 1 || out[0] < 0 {
+        return Err(last_error().into());
+    }
+    out.truncate(n as usize);
+    Ok(out)
 }
 /// what the UNet's output means (`SDXL_PREDICTION_*`): a per-handle option all trajectory methods honour
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -675,7 +703,32 @@ impl<B: BurnBackend> Diffuser<B> {
     pub fn solver(&self) -> Solver {
         let mut v: c_int = 0;
         check(unsafe { ffi::sdxl_diffuser_get_solver(self.raw, &mut v) });
-        if v == Solver::Dpmpp2M as c_int { Solver::Dpmpp2M } else { Solver::Ddim }
+        match v {
+            x if x == Solver::Dpmpp2M as c_int => Solver::Dpmpp2M,
+            x if x == Solver::Lcm as c_int => Solver::Lcm,
+            x if x == Solver::Tcd as c_int => Solver::Tcd,
+            _ => Solver::Ddim,
+        }
+    }
+    /// every following trajectory of this handle runs one UNet evaluation per entry of `timesteps`, a strictly decreasing list of training
+    /// timesteps, and its `n_steps` must equal the list's length (`sdxl_diffuser_set_timesteps`); `None` goes back to the reference's rule.
+    /// A list the engine refuses is an `Err` with its message, and the handle keeps what it had.
+    pub fn set_timesteps(&self, timesteps: Option<&[i32]>) -> Result<(), Box<dyn std::error::Error>> {
+        let (p, n) = match timesteps {
+            Some(t) if !t.is_empty() => (t.as_ptr(), t.len() as c_int),
+            _ => (ptr::null(), 0),
+        };
+        try_check(unsafe { ffi::sdxl_diffuser_set_timesteps(self.raw, p, n) })
+    }
+    /// the handle's list, `None` for the reference's rule (`sdxl_diffuser_get_timesteps`)
+    pub fn timesteps(&self) -> Option<Vec<i32>> {
+        let mut out = vec![-1i32; 4096];
+        let n = unsafe { ffi::sdxl_diffuser_get_timesteps(self.raw, out.as_mut_ptr(), out.len() as c_int) };
+        if n < 1 || out[0] < 0 {
+            return None;
+        }
+        out.truncate(n as usize);
+        Some(out)
     }
     /// every following trajectory of this handle reads the UNet's output as `prediction` (`sdxl_diffuser_set_prediction`)
     pub fn set_prediction(&self, prediction: Prediction) {

@@ -128,6 +128,8 @@ ABI_SYMBOLS = [
     "sdxl_sampler_step_replay",
     "sdxl_diffuser_set_prediction", "sdxl_diffuser_get_prediction", "sdxl_rescale_zero_terminal_snr", "sdxl_solver_coefficients_pred",
     "sdxl_sampler_step_replay_pred",
+    "sdxl_diffuser_set_timesteps", "sdxl_diffuser_get_timesteps", "sdxl_timestep_schedule", "sdxl_solver_coefficients_ts",
+    "sdxl_sampler_step_replay_ts",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -196,6 +198,13 @@ def lib() -> ctypes.CDLL:
             l.sdxl_solver_coefficients_pred.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
             l.sdxl_sampler_step_replay_pred.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(l, "sdxl_solver_coefficients_ts"):
+            l.sdxl_diffuser_set_timesteps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_diffuser_get_timesteps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_timestep_schedule.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_solver_coefficients_ts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_sampler_step_replay_ts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         if hasattr(l, "sdxl_unet_forward_residuals"):
             l.sdxl_unet_skip_shape.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
             l.sdxl_unet_forward_residuals.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
@@ -971,7 +980,36 @@ def draw_sigma(i: int) -> int:
 
 SOLVER_DDIM = 0         # SDXL_SOLVER_DDIM: the reference's loop (default)
 SOLVER_DPMPP_2M = 1     # SDXL_SOLVER_DPMPP_2M: DPM-Solver++(2M), with eta > 0 its SDE form
-_SOLVER_NAMES = {"ddim": SOLVER_DDIM, "dpmpp_2m": SOLVER_DPMPP_2M}
+SOLVER_LCM = 3          # SDXL_SOLVER_LCM: LCM multistep consistency sampling (takes no eta; needs the seeded calls beyond one iteration)
+SOLVER_TCD = 4          # SDXL_SOLVER_TCD: TCD gamma-sampling, the seeded calls' eta read as gamma
+_SOLVER_NAMES = {"ddim": SOLVER_DDIM, "dpmpp_2m": SOLVER_DPMPP_2M, "lcm": SOLVER_LCM, "tcd": SOLVER_TCD}
+
+SCHEDULE_REFERENCE, SCHEDULE_TRAILING, SCHEDULE_LEADING, SCHEDULE_LCM = 0, 1, 2, 3      # SDXL_SCHEDULE_*
+_SCHEDULE_KINDS = {"reference": SCHEDULE_REFERENCE, "trailing": SCHEDULE_TRAILING, "leading": SCHEDULE_LEADING, "lcm": SCHEDULE_LCM}
+
+
+def timestep_schedule(kind, n_steps: int, n_train: int = 1000, offset: int = 1, origin_steps: int = 50) -> List[int]:
+    """sdxl_timestep_schedule (host logic: no GPU needed): a published spacing as a list for Diffuser.set_timesteps.  kind "reference" (the
+    default rule: sdxl_step_count entries), "trailing" (Lightning, Turbo), "leading" (diffusers' default with steps_offset = offset) or
+    "lcm" (LCM / TCD / Hyper-SD on origin_steps), or the SCHEDULE_* value; what the engine refuses raises InvalidArgument"""
+    if isinstance(kind, str):
+        if kind not in _SCHEDULE_KINDS:
+            raise InvalidArgument(f"unknown schedule kind {kind!r}: one of {sorted(_SCHEDULE_KINDS)}")
+        kind = _SCHEDULE_KINDS[kind]
+    param = {SCHEDULE_LEADING: int(offset), SCHEDULE_LCM: int(origin_steps)}.get(int(kind), 0)
+    cap = max(int(n_train), 1)
+    out = np.full((cap,), -1, dtype=np.int32)      # a refusal leaves out untouched: that tells SDXL_ERR_INVALID (1) from a count of 1
+    n = lib().sdxl_timestep_schedule(int(kind), int(n_steps), int(n_train), param, out.ctypes.data_as(ctypes.c_void_p), cap)
+    if n < 1 or out[0] < 0:
+        raise InvalidArgument(lib().sdxl_last_error().decode())
+    return [int(v) for v in out[:n]]
+
+
+def _timesteps(timesteps):
+    """int32 array of a list (None stays None)"""
+    if timesteps is None:
+        return None
+    return np.ascontiguousarray(np.asarray(list(timesteps), dtype=np.int64).astype(np.int32).reshape(-1))
 
 
 def _solver(solver) -> int:
@@ -1006,10 +1044,19 @@ def rescale_zero_terminal_snr(alphas) -> np.ndarray:
     return out
 
 
-def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp_2m", eta: float = 0.0, prediction="epsilon") -> np.ndarray:
+def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp_2m", eta: float = 0.0, prediction="epsilon",
+                        timesteps=None) -> np.ndarray:
     """sdxl_solver_coefficients: float64 [iterations, 4] rows (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z, the
-    table the sampler runs (host logic: no GPU needed).  prediction "v" (sdxl_solver_coefficients_pred) admits a zero-terminal-SNR table."""
+    table the sampler runs (host logic: no GPU needed).  prediction "v" (sdxl_solver_coefficients_pred) admits a zero-terminal-SNR table.
+    timesteps (sdxl_solver_coefficients_ts): one row per entry of the list; n_steps and step_start are not read."""
     a = np.ascontiguousarray(alphas, dtype=np.float32)
+    ts = _timesteps(timesteps)
+    if ts is not None:
+        out = np.zeros((int(ts.size), 4), dtype=np.float64)
+        _check_invalid(lib().sdxl_solver_coefficients_ts(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), ts.ctypes.data_as(ctypes.c_void_p),
+                                                         int(ts.size), _solver(solver), _prediction(prediction), float(eta),
+                                                         out.ctypes.data_as(ctypes.c_void_p), int(ts.size)))
+        return out
     iters = max(step_count(n_steps, step_start, int(a.shape[0])), 0) if n_steps >= 1 else 0
     out = np.zeros((iters, 4), dtype=np.float64)
     if _prediction(prediction) == PREDICTION_EPSILON:      # the entry every build has
@@ -1123,21 +1170,22 @@ class _StepReplayArgsC(ctypes.Structure):
 
 def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps, latent0, solver="ddim", eta: float = 0.0,
                         cfg_scale: float = 7.5, guidance: Optional[Guidance] = None, single: bool = False, input_f16: bool = False,
-                        reference=None, mask=None, step_noise=None, seeds=None, prediction="epsilon"):
+                        reference=None, mask=None, step_noise=None, seeds=None, prediction="epsilon", timesteps=None):
     """sdxl_sampler_step_replay, the trajectory without the UNet (a test seam): eps [iterations, B, h*w, 4] and latent0 [n, 4, h, w] float32
     CUDA tensors, B = n where single (or guidance mode "off"), else 2n.  Returns float32 CUDA tensors (latents [iterations + 1, n, 4, h, w],
     hist [n, 4, h, w] -- zeros under DDIM --, unet_in [B, h*w, 4], timesteps [iterations + 1]).  Nothing is checked here but the shapes the
     outputs are sized by: the engine reports what it refuses (InvalidArgument).  prediction "v" (sdxl_sampler_step_replay_pred): the rows
-    of eps are v."""
+    of eps are v.  timesteps (sdxl_sampler_step_replay_ts): one iteration per entry of the list; n_steps and step_start are not read."""
     torch = _torch()
     pred = _prediction(prediction)
+    ts = _timesteps(timesteps)
     a = np.ascontiguousarray(alphas, dtype=np.float32)
     eps, pe = _dev(eps)
     latent0, pl = _dev(latent0)
     n, h, w = int(latent0.shape[0]), int(latent0.shape[2]), int(latent0.shape[3])
     iters = int(eps.shape[0])
     B = n if single or (guidance is not None and guidance.mode == GUIDANCE_OFF) else 2 * n
-    want = step_count(n_steps, step_start, int(a.shape[0])) if n_steps >= 1 else -1
+    want = int(ts.size) if ts is not None else step_count(n_steps, step_start, int(a.shape[0])) if n_steps >= 1 else -1
     if (want >= 0 and iters != want) or tuple(eps.shape[1:]) != (B, h * w, 4) or latent0.shape[1] != 4:
         raise InvalidArgument(f"eps must be [{want}, {B}, {h * w}, 4] and latent0 [n, 4, h, w]")
     for t, lead in ((reference, ()), (mask, ()), (step_noise, (iters,))):
@@ -1151,7 +1199,9 @@ def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps
                             ctypes.pointer(guidance) if guidance is not None else None, int(single), n, h, w, int(input_f16),
                             pe, pl, keep[0][1], keep[1][1], keep[2][1], ctypes.cast(sd, _c_p) if sd is not None else None,
                             *[ctypes.c_void_p(t.data_ptr()) for t in out])
-    if pred == PREDICTION_EPSILON:      # the entry every build has
+    if ts is not None:
+        _check_invalid(lib().sdxl_sampler_step_replay_ts(ctx.h, _stream(), ctypes.byref(args), pred, ts.ctypes.data_as(ctypes.c_void_p), int(ts.size)))
+    elif pred == PREDICTION_EPSILON:      # the entry every build has
         _check_invalid(lib().sdxl_sampler_step_replay(ctx.h, _stream(), ctypes.byref(args)))
     else:
         _check_invalid(lib().sdxl_sampler_step_replay_pred(ctx.h, _stream(), ctypes.byref(args), pred))
@@ -1288,8 +1338,29 @@ class Diffuser:
         return out
 
     def set_solver(self, solver):
-        """"ddim" (default) or "dpmpp_2m" (or the SOLVER_* value): the update every following trajectory of this handle runs"""
+        """"ddim" (default), "dpmpp_2m", "lcm" or "tcd" (or the SOLVER_* value): the update every following trajectory of this handle runs"""
         _check(lib().sdxl_diffuser_set_solver(self.h, _solver(solver)))
+
+    def set_timesteps(self, timesteps=None):
+        """sdxl_diffuser_set_timesteps: a strictly decreasing list of training timesteps, one UNet evaluation each, for every following
+        trajectory of this handle (its n_steps must equal the list's length); None or an empty list: back to the reference's rule.  A list
+        the engine refuses raises InvalidArgument and the handle keeps what it had."""
+        ts = _timesteps(timesteps)
+        if ts is None or ts.size == 0:
+            _check_invalid(lib().sdxl_diffuser_set_timesteps(self.h, None, 0))
+        else:
+            _check_invalid(lib().sdxl_diffuser_set_timesteps(self.h, ts.ctypes.data_as(ctypes.c_void_p), int(ts.size)))
+
+    @property
+    def timesteps(self) -> Optional[List[int]]:
+        """the handle's list (sdxl_diffuser_get_timesteps), None for the reference's rule"""
+        out = np.full((4096,), -1, dtype=np.int32)
+        n = lib().sdxl_diffuser_get_timesteps(self.h, out.ctypes.data_as(ctypes.c_void_p), int(out.size))
+        if n == 0:
+            return None
+        if out[0] < 0:      # a refusal leaves out untouched (SDXL_ERR_INVALID and a count of 1 are the same number)
+            raise InvalidArgument(lib().sdxl_last_error().decode())
+        return [int(v) for v in out[:n]]
 
     @property
     def solver(self) -> str:

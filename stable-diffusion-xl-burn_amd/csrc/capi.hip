@@ -682,10 +682,14 @@ int sdxl_step_count(int n_steps, int step_start, int n_train) {
   try { return (int)Diffuser::step_schedule(n_steps, step_start, n_train).size(); }
   catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+static bool known_solver(int solver) {
+  return solver == SDXL_SOLVER_DDIM || solver == SDXL_SOLVER_DPMPP_2M || solver == SDXL_SOLVER_LCM || solver == SDXL_SOLVER_TCD;
+}
+static const char* const kUnknownSolver = "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M, SDXL_SOLVER_LCM, SDXL_SOLVER_TCD)";
 // solver: a per-handle option; an unknown value is an argument error and leaves the handle as it was
 int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver) {
   if (!d) return fail(SDXL_ERR_INVALID, "null argument");
-  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return fail(SDXL_ERR_INVALID, "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)");
+  if (!known_solver(solver)) return fail(SDXL_ERR_INVALID, kUnknownSolver);
   API_BEGIN
   d->d->set_solver(solver);
   API_END
@@ -695,13 +699,78 @@ int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out) {
   *solver_out = d->d->solver();
   return SDXL_OK;
 }
-// host logic of the sampler's coefficient table -- no device needed; the function Diffuser::diffuse fills its DPM-Solver++(2M) table from
-static const char* schedule_args_error(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta) {
+// timestep list: a per-handle option; a list the check refuses is an argument error and leaves the handle as it was
+int sdxl_diffuser_set_timesteps(sdxl_diffuser* d, const int32_t* timesteps, int n) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  static_assert(sizeof(int32_t) == sizeof(int), "lists travel as int");
+  API_BEGIN
+  if (timesteps && n < 0) throw InvalidArgumentError("timesteps: the list needs 1..n_train_steps entries");
+  d->d->set_timesteps((const int*)timesteps, n);
+  API_END
+}
+int sdxl_diffuser_get_timesteps(sdxl_diffuser* d, int32_t* out, int capacity) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  const std::vector<int>& ts = d->d->timesteps();
+  if (ts.empty()) return 0;
+  if (!out || capacity < (int)ts.size()) return fail(SDXL_ERR_INVALID, "timesteps: capacity is smaller than the handle's list");
+  std::copy(ts.begin(), ts.end(), out);
+  return (int)ts.size();
+}
+// host logic only: the published spacings as lists (integer arithmetic but for the one rint of SDXL_SCHEDULE_TRAILING)
+int sdxl_timestep_schedule(int kind, int n_steps, int n_train_steps, int param, int32_t* out, int capacity) {
+  if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (n_train_steps < 1 || n_steps < 1 || n_steps > n_train_steps) return fail(SDXL_ERR_INVALID, "n_steps out of range (1..n_train_steps)");
+  std::vector<int> ts;
+  switch (kind) {
+    case SDXL_SCHEDULE_REFERENCE:
+      ts = Diffuser::step_schedule(n_steps, 0, n_train_steps);
+      break;
+    case SDXL_SCHEDULE_TRAILING: {
+      const double step = (double)n_train_steps / (double)n_steps;
+      for (int i = 0; i < n_steps; ++i) ts.push_back((int)std::nearbyint((double)n_train_steps - (double)i * step) - 1);     // ties to even
+      break;
+    }
+    case SDXL_SCHEDULE_LEADING: {
+      const int step = n_train_steps / n_steps;
+      if (param < 0 || (int64_t)(n_steps - 1) * step + param >= n_train_steps)
+        return fail(SDXL_ERR_INVALID, "timestep_schedule: the offset puts the first timestep outside 0..n_train_steps-1");
+      for (int i = 0; i < n_steps; ++i) ts.push_back((n_steps - 1 - i) * step + param);
+      break;
+    }
+    case SDXL_SCHEDULE_LCM: {
+      const int O = param;
+      if (O < 1 || O > n_train_steps) return fail(SDXL_ERR_INVALID, "timestep_schedule: origin steps out of range (1..n_train_steps)");
+      if (n_steps > O) return fail(SDXL_ERR_INVALID, "timestep_schedule: n_steps exceeds the origin steps");
+      const int k = n_train_steps / O;
+      for (int i = 0; i < n_steps; ++i) ts.push_back((O - (int)((int64_t)i * O / n_steps)) * k - 1);
+      break;
+    }
+    default:
+      return fail(SDXL_ERR_INVALID, "timestep_schedule: unknown kind (SDXL_SCHEDULE_REFERENCE, _TRAILING, _LEADING, _LCM)");
+  }
+  if (capacity < (int)ts.size()) return fail(SDXL_ERR_INVALID, "timestep_schedule: capacity is smaller than the list");
+  std::copy(ts.begin(), ts.end(), out);
+  return (int)ts.size();
+}
+// host logic of the sampler's coefficient table -- no device needed; the function Diffuser::diffuse fills its row tables from.
+// The checks of a table call in their order: the scalars, then (where there is no list) the reference rule's two numbers
+static const char* solver_args_error(const float* alphas_cumprod_host, int n_train_steps, int solver, double eta) {
   if (!alphas_cumprod_host) return "null argument";
-  if (solver != SDXL_SOLVER_DDIM && solver != SDXL_SOLVER_DPMPP_2M) return "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M)";
+  if (!known_solver(solver)) return kUnknownSolver;
   if (!(eta >= 0.0 && eta <= 1.0)) return "eta must be a finite value in [0, 1]";
+  return nullptr;
+}
+static const char* schedule_args_error(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta) {
+  if (const char* m = solver_args_error(alphas_cumprod_host, n_train_steps, solver, eta)) return m;
   if (n_train_steps < 1 || n_steps < 1 || n_steps > n_train_steps) return "n_steps out of range (1..n_train_steps)";
   if (step_start < 0 || step_start >= n_train_steps) return "step_start out of range (0..n_train_steps-1)";
+  return nullptr;
+}
+static const char* list_args_error(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver, double eta) {
+  if (const char* m = solver_args_error(alphas_cumprod_host, n_train_steps, solver, eta)) return m;
+  if (n_train_steps < 1) return "n_train_steps out of range";
+  if (const char* m = Diffuser::timesteps_error((const int*)timesteps, n, n_train_steps)) return m;
+  if (solver == SDXL_SOLVER_LCM && eta != 0.0) return "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)";
   return nullptr;
 }
 static const char* alphas_error(const float* alphas_cumprod_host, int n_train_steps) {
@@ -709,29 +778,36 @@ static const char* alphas_error(const float* alphas_cumprod_host, int n_train_st
     if (!(alphas_cumprod_host[i] > 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
   return nullptr;
 }
-// the table under a prediction type (valid schedule arguments): SDXL_PREDICTION_V admits 0 in it, and the schedule decides where it may stand;
+// the table under a prediction type (a valid list): SDXL_PREDICTION_V admits 0 in it, and the schedule decides where it may stand;
 // under SDXL_PREDICTION_EPSILON a 0 at a sampled timestep gets the message that names the remedy, any other value outside (0, 1) the old one
-static const char* alphas_error_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int prediction) {
+static const char* alphas_error_pred(const float* alphas_cumprod_host, int n_train_steps, const std::vector<int>& ts, int prediction) {
   if (prediction != SDXL_PREDICTION_EPSILON && prediction != SDXL_PREDICTION_V) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
   for (int i = 0; i < n_train_steps; ++i)
     if (!(alphas_cumprod_host[i] >= 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
   const std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);
-  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train_steps, n_steps, step_start, prediction)) return m;
+  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train_steps, ts, prediction)) return m;
   return prediction == SDXL_PREDICTION_EPSILON ? alphas_error(alphas_cumprod_host, n_train_steps) : nullptr;
+}
+int sdxl_solver_coefficients_ts(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver, int prediction,
+                                double eta, double* out, int capacity_steps) {
+  if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = list_args_error(alphas_cumprod_host, n_train_steps, timesteps, n, solver, eta)) return fail(SDXL_ERR_INVALID, m);
+  if (capacity_steps < n) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than the list (sdxl_step_count for the reference's rule)");
+  const std::vector<int> ts(timesteps, timesteps + n);
+  if (const char* m = alphas_error_pred(alphas_cumprod_host, n_train_steps, ts, prediction)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
+  std::vector<double> rows((size_t)4 * n);
+  Diffuser::solver_coefficients(alphas.data(), n_train_steps, ts, solver, eta, rows.data(), prediction);
+  std::copy(rows.begin(), rows.end(), out);
+  API_END
 }
 int sdxl_solver_coefficients_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, int prediction,
                                   double eta, double* out, int capacity_steps) {
   if (!out) return fail(SDXL_ERR_INVALID, "null argument");
   if (const char* m = schedule_args_error(alphas_cumprod_host, n_train_steps, n_steps, step_start, solver, eta)) return fail(SDXL_ERR_INVALID, m);
-  const int iters = (int)Diffuser::step_schedule(n_steps, step_start, n_train_steps).size();
-  if (capacity_steps < iters) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than sdxl_step_count");
-  if (const char* m = alphas_error_pred(alphas_cumprod_host, n_train_steps, n_steps, step_start, prediction)) return fail(SDXL_ERR_INVALID, m);
-  API_BEGIN
-  std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
-  std::vector<double> rows((size_t)4 * iters);
-  Diffuser::solver_coefficients(alphas.data(), n_train_steps, n_steps, step_start, solver, eta, rows.data(), prediction);
-  std::copy(rows.begin(), rows.end(), out);
-  API_END
+  const std::vector<int> ts = Diffuser::step_schedule(n_steps, step_start, n_train_steps);     // the reference's rule as a list
+  return sdxl_solver_coefficients_ts(alphas_cumprod_host, n_train_steps, ts.data(), (int)ts.size(), solver, prediction, eta, out, capacity_steps);
 }
 int sdxl_solver_coefficients(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, double eta,
                              double* out, int capacity_steps) {
@@ -930,11 +1006,23 @@ int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay
   return sdxl_sampler_step_replay_pred(ctx, stream, a, SDXL_PREDICTION_EPSILON);
 }
 int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction) {
+  return sdxl_sampler_step_replay_ts(ctx, stream, a, prediction, nullptr, 0);
+}
+int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction, const int32_t* timesteps, int n_ts) {
   if (!ctx || !a || !a->eps || !a->latent0 || !a->latents_out || !a->unet_in_out || !a->timesteps_out) return fail(SDXL_ERR_INVALID, "null argument");
   if (a->n < 1 || a->n > kMaxSeeds || a->h < 1 || a->w < 1 || (int64_t)a->h * a->w > 1 << 22)
     return fail(SDXL_ERR_INVALID, "step_replay: n (1..8) or h * w (1..2^22) out of range");
-  if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
-  if (const char* m = alphas_error_pred(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, prediction)) return fail(SDXL_ERR_INVALID, m);
+  const bool listed = timesteps != nullptr && n_ts != 0;      // else the reference's rule on the struct's n_steps and step_start
+  std::vector<int> ts;
+  if (listed) {
+    if (const char* m = list_args_error(a->alphas_cumprod_host, a->n_train_steps, timesteps, n_ts, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
+    ts.assign(timesteps, timesteps + n_ts);
+  } else {
+    if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
+    if (a->solver == SDXL_SOLVER_LCM && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
+    ts = Diffuser::step_schedule(a->n_steps, a->step_start, a->n_train_steps);
+  }
+  if (const char* m = alphas_error_pred(a->alphas_cumprod_host, a->n_train_steps, ts, prediction)) return fail(SDXL_ERR_INVALID, m);
   if ((a->mask != nullptr) != (a->reference != nullptr)) return fail(SDXL_ERR_INVALID, "inpainting needs reference and mask");
   if (a->mask && !a->seeds && !a->step_noise) return fail(SDXL_ERR_INVALID, "inpainting with explicit noise needs step_noise");
   if (!a->seeds && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "eta needs seeds: explicit noise carries none for the sigma term");
@@ -942,13 +1030,15 @@ int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_r
   if (const char* m = Diffuser::guidance_error(g, a->single != 0)) return fail(SDXL_ERR_INVALID, m);
   if (g.n_scales != 0 && g.n_scales != a->n) return fail(SDXL_ERR_INVALID, "guidance: n_scales differs from the batch (n)");
   API_BEGIN
+  const std::vector<double> alphas(a->alphas_cumprod_host, a->alphas_cumprod_host + a->n_train_steps);   // elem -> f64 as the Diffuser holds them
+  if (!a->seeds)      // a table that re-noises (c_z != 0) has no noise to take: refused here, before the device is touched
+    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), a->n_train_steps, ts, a->solver, prediction)) throw InvalidArgumentError(m);
   use(ctx);
   hipStream_t s = pick(ctx, stream);
   const bool single = a->single != 0 || g.mode == kGuidanceOff;
   const int n = a->n, HW = a->h * a->w, B = single ? n : 2 * n;
   const size_t elems = (size_t)n * 4 * HW, bytes = elems * sizeof(float);
   const int in_dt = a->input_f16 ? DT_F16 : DT_F32;
-  const std::vector<double> alphas(a->alphas_cumprod_host, a->alphas_cumprod_host + a->n_train_steps);   // elem -> f64 as the Diffuser holds them
   Tmp tmp;
   StepIo io{};
   io.latent = (float*)tmp.get(bytes);
@@ -956,7 +1046,7 @@ int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_r
   io.reference = a->reference; io.mask = a->mask; io.step_noise = a->step_noise; io.seeds = a->seeds;
   SDXL_HIP(hipMemcpyAsync(io.latent, a->latent0, bytes, hipMemcpyDeviceToDevice, s));
   StepLoop loop;
-  const int iters = loop.begin(alphas, a->n_steps, a->step_start, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s, prediction);
+  const int iters = loop.begin(alphas, ts, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s, prediction);
   for (int i = 0; i <= iters; ++i) {
     if (i > 0) loop.after_forward(i - 1, a->eps + (size_t)(i - 1) * B * HW * 4, s);
     SDXL_HIP(hipMemcpyAsync(a->latents_out + (size_t)i * elems, io.latent, bytes, hipMemcpyDeviceToDevice, s));

@@ -621,6 +621,8 @@ void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n
 //   kSolverDpmpp2M:  acc = c_1 * x0p      (p.hist, read only where c_1 != 0: a first-order row never looks at the history, whatever it holds)
 //                    acc = fma(x0, c_0, acc);  x = fma(x, c_x, acc);  p.hist = x0 -- with inpainting the one computed from the blended state.
 //                    The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.
+//   kSolverRow1:     acc = x0 * c_0;  x = fma(x, c_x, acc): a first-order row of the 2M layout (the LCM and TCD tables).  No history:
+//                    p.hist is neither read nor written.
 //     x   = fma(z, sigma or c_z, x)       (SEEDED, coefficient != 0; z = seeded_normal4(seed, hw, draw_sigma(idx)))
 //   the blend rounds both products.
 // PRED = kPredictionV: the network's rows are v = alpha e - sigma x0.  The two guidance lines above combine them as they combine e (v = vc;
@@ -679,13 +681,16 @@ __global__ void step_kernel(const StepParams p, int do_update) {
         float acc = k.c_1 * x0p[c];
         acc = __builtin_fmaf(x0, k.c_0, acc);
         x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+      } else if constexpr (SOLVER == kSolverRow1) {
+        const float acc = x0 * k.c_0;
+        x[c] = __builtin_fmaf(x[c], k.c_x, acc);
       } else {
         const float en = e * k.sqrt_1map;
         x[c] = c < 2 ? x0 * k.sqrt_ap + en : __builtin_fmaf(x0, k.sqrt_ap, en);
       }
     }
     if constexpr (SEEDED) {
-      const float cz = SOLVER == kSolverDpmpp2M ? k.c_z : k.sigma;
+      const float cz = SOLVER == kSolverDdim ? k.sigma : k.c_z;
       if (cz != 0.f) {
         float z[4];
         seeded_normal4(p.seeds.v[b], (uint32_t)hw, draw_sigma((uint32_t)idx), z);
@@ -724,6 +729,9 @@ static void launch_step_pred(const StepParams& p, int do_update, dim3 grid, dim3
   if (p.solver == kSolverDpmpp2M) {
     if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, true, PRED>), grid, block, 0, s, p, do_update);
     else hipLaunchKernelGGL((step_kernel<kSolverDpmpp2M, false, PRED>), grid, block, 0, s, p, do_update);
+  } else if (p.solver == kSolverRow1) {
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverRow1, true, PRED>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverRow1, false, PRED>), grid, block, 0, s, p, do_update);
   } else {
     if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDdim, true, PRED>), grid, block, 0, s, p, do_update);
     else hipLaunchKernelGGL((step_kernel<kSolverDdim, false, PRED>), grid, block, 0, s, p, do_update);

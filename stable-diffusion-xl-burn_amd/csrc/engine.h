@@ -742,10 +742,12 @@ class StepLoop {
   StepLoop& operator=(const StepLoop&) = delete;
   // Builds the StepCoef table (host f64 -> f32) and the active-iteration array of one trajectory, uploads them and runs the do_update = 0
   // launch: *step_idx = 0, the step-0 inpainting blend, the first UNet input and timestep.  `single`: one branch, no CFG (B = n).  Returns the
-  // number of iterations.  alphas: the n_train alphas_cumprod values as f64.
+  // number of iterations.  alphas: the n_train alphas_cumprod values as f64.  ts: the timestep of every iteration, strictly decreasing -- the
+  // only source of (t, a, ap): a = alphas[ts[i]], ap = alphas[ts[i + 1]], 1 behind the last entry (Diffuser::step_schedule for the reference's rule).
   // prediction: kPredictionEpsilon or kPredictionV, what the rows handed to after_forward mean.  A schedule Diffuser::schedule_error refuses
-  // (alphas_cumprod == 0 at an iteration's timestep under kPredictionEpsilon) throws InvalidArgumentError before anything is launched.
-  int begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale, const Guidance& g,
+  // (alphas_cumprod == 0 at an iteration's timestep under kPredictionEpsilon) throws InvalidArgumentError before anything is launched, and so
+  // does a table with c_z != 0 where io.seeds == nullptr (Diffuser::explicit_noise_error).  kSolverLcm / kSolverTcd allocate no history.
+  int begin(const std::vector<double>& alphas, const std::vector<int>& ts, int solver, double eta, double cfg_scale, const Guidance& g,
             bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction = kPredictionEpsilon);
   // behind the UNet forward of iteration i: eps [B][HW][eps_ld] fp32 (cond entries first) -> the CFG rescale factors where rescale is on and
   // the iteration active, then the update + advance launches
@@ -791,21 +793,33 @@ class Diffuser {
   void refine_latent_seeded(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                             const uint64_t* seeds, double eta, float* out, hipStream_t s);
   static std::vector<int> step_schedule(int n_steps, int step_start, int n_train);
-  // (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z per iteration of step_schedule, f64, out[4 * i ..] (host logic only;
+  // host logic only: the first complaint about a caller's list (n outside 1..n_train, a value outside 0..n_train-1, not strictly decreasing;
+  // every message names "timesteps"), nullptr where it is valid
+  static const char* timesteps_error(const int* ts, int n, int n_train);
+  // a per-handle list that replaces step_schedule in all six trajectory calls (n == 0 or nullptr: back to the reference's rule).  A list
+  // timesteps_error refuses throws InvalidArgumentError and the handle keeps what it had.  With a list the calls' n_steps must equal its length,
+  // step_start must be 0 for sampling and inpainting, and refine_latent needs ts[0] == n_train - step_start - 1 (InvalidArgumentError otherwise).
+  void set_timesteps(const int* ts, int n);
+  const std::vector<int>& timesteps() const { return timesteps_; }     // empty: the reference's rule
+  // (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z per entry of the list ts, f64, out[4 * i ..] (host logic only;
   // formulas in include/sdxl_mi355.h, sdxl_solver_coefficients).  kSolverDpmpp2M: what diffuse() rounds into its table.  kSolverDdim: the
   // DDIM update folded into the same four numbers.  alphas: n_train values in (0, 1).  The rows do not depend on the prediction type; it
   // decides only whether a == 0 at an iteration's timestep (zero terminal SNR) is admitted: kPredictionV writes that row as the limit
-  // lambda -> -inf, kPredictionEpsilon throws InvalidArgumentError.
-  static void solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out,
+  // lambda -> -inf, kPredictionEpsilon throws InvalidArgumentError.  kSolverLcm (eta must be 0) and kSolverTcd (eta is gamma):
+  // the first-order rows (c_x, c_0, 0, c_z) of include/sdxl_mi355.h, finite at a == 0 as written.
+  static void solver_coefficients(const double* alphas, int n_train, const std::vector<int>& ts, int solver, double eta, double* out,
                                   int prediction = kPredictionEpsilon);
-  // host logic only: the first complaint about the (a, ap) pairs of step_schedule under `prediction`, nullptr where the trajectory can run.
+  // host logic only: why a trajectory of `solver` on ts cannot run on explicit noise (its eta == 0 table has a c_z != 0, and explicit noise
+  // carries no tensor for that term), nullptr where it can: DDIM, 2M, TCD (gamma = 0 there) and a one-entry LCM list
+  static const char* explicit_noise_error(const double* alphas, int n_train, const std::vector<int>& ts, int solver, int prediction);
+  // host logic only: the first complaint about the (a, ap) pairs of the list ts under `prediction`, nullptr where the trajectory can run.
   // kPredictionEpsilon: a == 0 on an iteration (x0 would divide by it) -- the message names v-prediction.  kPredictionV: a outside [0, 1)
   // or ap outside (0, 1].
-  static const char* schedule_error(const double* alphas, int n_train, int n_steps, int step_start, int prediction);
+  static const char* schedule_error(const double* alphas, int n_train, const std::vector<int>& ts, int prediction);
   // kPredictionEpsilon (default) or kPredictionV: what the UNet's output means to every following trajectory of this handle
   void set_prediction(int prediction);
   int prediction() const { return prediction_; }
-  // kSolverDdim (default) or kSolverDpmpp2M: the update every following trajectory of this handle runs
+  // kSolverDdim (default), kSolverDpmpp2M, kSolverLcm or kSolverTcd: the update every following trajectory of this handle runs
   void set_solver(int solver);
   int solver() const { return solver_; }
   // guidance options, a per-handle choice like the solver.  guidance_error: host logic only -- the first complaint about `g` (for a refiner
@@ -831,7 +845,9 @@ class Diffuser {
   };
   void trajectory(const Conditioning& c, double cfg_scale, int n_steps, const Trajectory& t, float* out, hipStream_t s);
   // context setup, then StepLoop::begin and one UNet forward + StepLoop::after_forward per iteration
-  void diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale, const float* reference,
+  // the list of this call: the handle's own (checked against n_steps and step_start as set_timesteps documents) or step_schedule
+  std::vector<int> call_schedule(int n_steps, int step_start, bool renoise) const;
+  void diffuse(float* latent, const Conditioning& c, const std::vector<int>& ts, double cfg_scale, const float* reference,
                const unsigned char* mask, const float* step_noise, hipStream_t s, const uint64_t* seeds = nullptr, double eta = 0.0);
   std::unique_ptr<UNet> unet_;
   std::vector<double> alphas_;
@@ -841,6 +857,7 @@ class Diffuser {
   float* latent_ = nullptr; size_t latent_cap_ = 0;
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
   int solver_ = kSolverDdim;
+  std::vector<int> timesteps_;                        // empty: step_schedule
   int prediction_ = kPredictionEpsilon;
   Guidance guidance_;
   StepLoop loop_;

@@ -349,6 +349,11 @@ struct StepCoef {
 };
 static_assert(sizeof(StepCoef) == 32, "one table entry is eight floats in both layouts");
 constexpr int kSolverDdim = 0, kSolverDpmpp2M = 1;   // SDXL_SOLVER_* of the public header
+// the consistency solvers of the public header (few-step sampling): two host tables of first-order rows (c_x, c_0, 0, c_z) in the 2M
+// layout, and one update text for both in the per-step kernel, StepParams::solver == kSolverRow1
+constexpr int kSolverLcm = 3, kSolverTcd = 4;     // SDXL_SOLVER_LCM, SDXL_SOLVER_TCD (2 is no public solver)
+constexpr int kSolverRow1 = 2;                     // kernel level only: never a handle's solver
+constexpr bool solver_is_row1(int solver) { return solver == kSolverLcm || solver == kSolverTcd; }
 constexpr int kPredictionEpsilon = 0, kPredictionV = 1;   // SDXL_PREDICTION_* of the public header: what the UNet's output rows mean
 // draw numbers of the seeded noise (counter word 1 of the generator); the public header carries the same values as SDXL_DRAW_*
 constexpr uint32_t kDrawInitial = 0;
@@ -361,6 +366,7 @@ struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, pas
 //   e  = ec                                  where !use_cfg, or on an inactive iteration (active != nullptr && !active[*step_idx]); eu is not read
 //   e  = fma(ec - eu, scales[b], eu)         otherwise; times factors[b] where factors != nullptr (CFG rescale)
 //   x0 = (x - e sqrt_1ma) / sqrt_a;  x = x0 sqrt_ap + e sqrt_1map (+ z sigma)   or, kSolverDpmpp2M,   x = c_x x + c_0 x0 + c_1 x0p (+ c_z z)
+//   or, kSolverRow1,   x = c_x x + c_0 x0 (+ c_z z): the 2M line without its history term
 // kPredictionV: the rows are v = alpha e - sigma x0, combined by the same two guidance lines (v, vc, vu for e, ec, eu), and then
 //   x0 = x sqrt_a - v sqrt_1ma               no division: finite at sqrt_a == 0 (zero terminal SNR), where x0 = -v
 //   e  = v sqrt_a + x sqrt_1ma               kSolverDdim only; the update lines behind x0 and e are those above
@@ -383,7 +389,7 @@ struct StepParams {
   void* unet_in; int in_dt; int in_ld; int in_rep;   // next UNet input NHWC [in_rep*n][HW][4]
   float* t_out;              // device scalar(s): timestep for the next UNet call
   // kSolverDpmpp2M: table holds the 2M layout and hist [n][4][HW] fp32 the x0 of the previous iteration (read where c_1 != 0, written by
-  // every update); kSolverDdim reads neither
+  // every update); kSolverDdim reads neither.  kSolverRow1: the 2M layout with c_1 == 0; hist is neither read nor written (nullptr)
   // prediction: kPredictionEpsilon or kPredictionV (sits in the padding between solver and hist: no other member moves)
   int solver; int prediction; float* hist;
 };

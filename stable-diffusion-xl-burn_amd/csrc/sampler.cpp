@@ -18,6 +18,10 @@
 //   * what the UNet's output means is a per-handle choice as well (set_prediction): the noise e, or v = alpha e - sigma x0, in further instantiations
 //     of the same kernel (x0 = alpha x - sigma v, no division).  With v a schedule may hold alphas_cumprod == 0 at an iteration's timestep (zero
 //     terminal SNR); the table's row there is written as the limit lambda -> -inf, and under e such a schedule is refused before anything is launched.
+//   * which timesteps a trajectory visits is a per-handle choice (set_timesteps): the reference's rule by default, or any strictly decreasing list.
+//     The list is the only source of an iteration's (t, a, ap) -- ap is the alpha of the next entry, 1 behind the last -- for the table, the guidance
+//     interval, the trace and the t fed to the UNet.  On it run DDIM and 2M as before and the consistency solvers of distilled checkpoints (LCM, TCD):
+//     first-order rows of the same table that re-noise with the seeded z every iteration, in one more instantiation of the same kernel.
 // StepLoop is everything between two UNet forwards; Diffuser::diffuse is context setup and the loop around UNet::forward.
 #include "engine.h"
 
@@ -55,8 +59,33 @@ static void ddim_terms(double a, double ap, double eta, double& sqrt_ap, double&
 }
 
 void Diffuser::set_solver(int solver) {
-  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver_is_row1(solver), "unknown solver");
   solver_ = solver;
+}
+
+const char* Diffuser::timesteps_error(const int* ts, int n, int n_train) {
+  if (!ts || n < 1 || n > n_train) return "timesteps: the list needs 1..n_train_steps entries";
+  for (int i = 0; i < n; ++i) {
+    if (ts[i] < 0 || ts[i] >= n_train) return "timesteps: a value outside 0..n_train_steps-1";
+    if (i > 0 && ts[i] >= ts[i - 1]) return "timesteps: the list must be strictly decreasing";
+  }
+  return nullptr;
+}
+void Diffuser::set_timesteps(const int* ts, int n) {
+  if (!ts || n == 0) { timesteps_.clear(); return; }
+  if (const char* m = timesteps_error(ts, n, n_train_)) throw InvalidArgumentError(m);
+  timesteps_.assign(ts, ts + n);
+}
+
+std::vector<int> Diffuser::call_schedule(int n_steps, int step_start, bool renoise) const {
+  if (timesteps_.empty()) return step_schedule(n_steps, step_start, n_train_);
+  if (n_steps != (int)timesteps_.size())
+    throw InvalidArgumentError("timesteps: n_steps (" + std::to_string(n_steps) + ") differs from the length of the handle's list (" +
+                               std::to_string(timesteps_.size()) + ")");
+  if (!renoise && step_start != 0) throw InvalidArgumentError("timesteps: step_start must be 0 where a list is set");
+  if (renoise && timesteps_[0] != n_train_ - step_start - 1)
+    throw InvalidArgumentError("timesteps: refine_latent re-noises to n_train_steps - step_start, so the list must start at n_train_steps - step_start - 1");
+  return timesteps_;
 }
 
 const char* Diffuser::guidance_error(const Guidance& g, bool is_refiner) {
@@ -108,13 +137,13 @@ void Diffuser::set_prediction(int prediction) {
   prediction_ = prediction;
 }
 
-const char* Diffuser::schedule_error(const double* alphas, int n_train, int n_steps, int step_start, int prediction) {
+const char* Diffuser::schedule_error(const double* alphas, int n_train, const std::vector<int>& ts, int prediction) {
   if (prediction != kPredictionEpsilon && prediction != kPredictionV) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
-  const std::vector<int> ts = step_schedule(n_steps, step_start, n_train);
-  const int step_size = n_train / n_steps;
-  for (int t : ts) {
-    const double a = alphas[t];
-    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+  if (!ts.empty())             // (refine_latent at step_start == n_train: no iteration, nothing to complain about)
+    if (const char* m = timesteps_error(ts.data(), (int)ts.size(), n_train)) return m;
+  for (size_t i = 0; i < ts.size(); ++i) {
+    const double a = alphas[ts[i]];
+    const double ap = i + 1 < ts.size() ? alphas[ts[i + 1]] : 1.0;
     if (prediction == kPredictionEpsilon) {
       if (a == 0.0)
         return "alphas_cumprod is 0 at a sampled timestep (zero terminal SNR): x0 = (x - sigma e) / alpha has no value there under the "
@@ -126,18 +155,17 @@ const char* Diffuser::schedule_error(const double* alphas, int n_train, int n_st
   return nullptr;
 }
 
-void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_steps, int step_start, int solver, double eta, double* out,
+void Diffuser::solver_coefficients(const double* alphas, int n_train, const std::vector<int>& ts, int solver, double eta, double* out,
                                    int prediction) {
-  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M, "unknown solver");
-  if (const char* m = schedule_error(alphas, n_train, n_steps, step_start, prediction)) throw InvalidArgumentError(m);
-  const std::vector<int> ts = step_schedule(n_steps, step_start, n_train);
-  const int step_size = n_train / n_steps;
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver_is_row1(solver), "unknown solver");
+  if (const char* m = schedule_error(alphas, n_train, ts, prediction)) throw InvalidArgumentError(m);
+  if (solver == kSolverLcm && eta != 0.0) throw InvalidArgumentError("solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
   double h_prev = 0.0;
   bool have_prev = false;       // false on iteration 0: no history, first order
   for (size_t i = 0; i < ts.size(); ++i) {
     const int t = ts[i];
     const double a = alphas[t];
-    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+    const double ap = i + 1 < ts.size() ? alphas[ts[i + 1]] : 1.0;      // the next entry of the list; behind the last one the data itself
     SDXL_REQUIRE((a > 0.0 || (a == 0.0 && prediction == kPredictionV)) && a < 1.0 && ap > 0.0 && ap <= 1.0, "alphas_cumprod outside (0, 1)");
     const double alpha = std::sqrt(a), sigma = std::sqrt(1.0 - a);
     double* c = out + 4 * i;     // c_x, c_0, c_1, c_z
@@ -145,6 +173,27 @@ void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_step
       double sqrt_ap, sqrt_1map, sigma_t;
       ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma_t);
       c[0] = sqrt_1map / sigma; c[1] = sqrt_ap - sqrt_1map * alpha / sigma; c[2] = 0.0; c[3] = sigma_t;
+      continue;
+    }
+    if (solver == kSolverLcm) {  // diffusers' LCMScheduler.step: sigma_data = 0.5, timestep_scaling = 10; the boundary-condition pair of x0, then
+                                 // re-noised to the next level with fresh noise.  ap == 1 behind the last entry: (c_skip, c_out, 0, 0)
+      const double st = 10.0 * (double)t, d = st * st + 0.25;
+      const double c_skip = 0.25 / d, c_out = st / std::sqrt(d);
+      const double alpha_p = std::sqrt(ap);
+      c[0] = alpha_p * c_skip; c[1] = alpha_p * c_out; c[2] = 0.0; c[3] = std::sqrt(1.0 - ap);
+      continue;
+    }
+    if (solver == kSolverTcd) {  // TCDScheduler.step, eta read as gamma: the DDIM step to s = floor((1 - gamma) t'), re-noised from s to t'
+      if (ap == 1.0) {           // the engine's last row, as 2M has it: the iteration returns x0
+        c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[3] = 0.0;
+        continue;
+      }
+      const int ts_s = (int)std::floor((1.0 - eta) * (double)ts[i + 1]);
+      const double a_s = alphas[ts_s];
+      if (!(a_s > 0.0 && a_s <= 1.0)) throw InvalidArgumentError("solver TCD: alphas_cumprod outside (0, 1] at the timestep floor((1 - gamma) t')");
+      const double alpha_s = std::sqrt(a_s), sigma_s = std::sqrt(1.0 - a_s), r = std::sqrt(ap / a_s);
+      c[0] = r * sigma_s / sigma; c[1] = r * (alpha_s - sigma_s * alpha / sigma); c[2] = 0.0;
+      c[3] = std::sqrt(std::max(1.0 - ap / a_s, 0.0));
       continue;
     }
     if (ap == 1.0) {             // h is infinite: the step lands on the data prediction
@@ -176,6 +225,16 @@ void Diffuser::solver_coefficients(const double* alphas, int n_train, int n_step
   }
 }
 
+const char* Diffuser::explicit_noise_error(const double* alphas, int n_train, const std::vector<int>& ts, int solver, int prediction) {
+  if (!solver_is_row1(solver)) return nullptr;      // DDIM and 2M at eta == 0 draw nothing
+  std::vector<double> rows((size_t)4 * ts.size());
+  solver_coefficients(alphas, n_train, ts, solver, 0.0, rows.data(), prediction);
+  for (size_t i = 0; i < ts.size(); ++i)
+    if (rows[4 * i + 3] != 0.0)
+      return "this solver re-noises with fresh noise every iteration (c_z != 0): it needs the seeded calls (explicit noise carries none for that term)";
+  return nullptr;
+}
+
 #ifdef SDXL_MEASURE
 bool g_debug_no_cfg = false;
 #else
@@ -202,33 +261,34 @@ StepLoop::~StepLoop() {
     if (p) (void)hipFree(p);
 }
 
-int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_start, int solver, double eta, double cfg_scale,
+int StepLoop::begin(const std::vector<double>& alphas, const std::vector<int>& ts, int solver, double eta, double cfg_scale,
                     const Guidance& go, bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction) {
   const int n_train = (int)alphas.size();
   SDXL_REQUIRE(n >= 1 && n <= kMaxSeeds, "batch out of range");
   // a == 0 on an iteration: x0 = -v under kPredictionV; under kPredictionEpsilon the first update would divide by sqrt_a == 0
-  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train, n_steps, step_start, prediction)) throw InvalidArgumentError(m);
+  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train, ts, prediction)) throw InvalidArgumentError(m);
   SDXL_REQUIRE(single || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
+  const bool rows = solver != kSolverDdim;             // the 2M layout of the table: 2M itself and the first-order rows of LCM / TCD
+  if (!io.seeds)
+    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), n_train, ts, solver, prediction)) throw InvalidArgumentError(m);
   // --- coefficient table (host f64, exactly the reference's scalar arithmetic :407-414, :423-426)
-  const std::vector<int> ts = Diffuser::step_schedule(n_steps, step_start, n_train);
   const int iters = (int)ts.size();
-  const int step_size = n_train / n_steps;
   std::vector<StepCoef> tab(iters + 1);
   act_.assign(iters, 1);                               // guidance interval: iteration i is active where t_lo <= t_i <= t_hi
   std::vector<double> c2m;
-  if (solver == kSolverDpmpp2M) {
+  if (rows) {
     c2m.resize((size_t)4 * iters);
-    Diffuser::solver_coefficients(alphas.data(), n_train, n_steps, step_start, solver, eta, c2m.data(), prediction);
+    Diffuser::solver_coefficients(alphas.data(), n_train, ts, solver, eta, c2m.data(), prediction);
   }
   for (int i = 0; i < iters; ++i) {
     const int t = ts[i];
     const double a = alphas[t];
-    const double ap = t >= step_size ? alphas[t - step_size] : 1.0;
+    const double ap = i + 1 < iters ? alphas[ts[i + 1]] : 1.0;
     StepCoef k{};
     k.t = (float)t;
     k.sqrt_a = (float)std::sqrt(a);
     k.sqrt_1ma = (float)std::sqrt(1.0 - a);
-    if (solver == kSolverDpmpp2M) {
+    if (rows) {
       k.c_x = (float)c2m[4 * i]; k.c_0 = (float)c2m[4 * i + 1]; k.c_1 = (float)c2m[4 * i + 2]; k.c_z = (float)c2m[4 * i + 3];
     } else {
       double sqrt_ap, sqrt_1map, sigma;
@@ -257,7 +317,7 @@ int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_sta
     if (!factors_) SDXL_HIP(hipMalloc((void**)&factors_, kMaxSeeds * sizeof(float)));
     p_.factors = factors_;
   }
-  if (solver == kSolverDpmpp2M) ensure_device(hist_, hist_cap_, (size_t)n * 4 * HW);
+  if (solver == kSolverDpmpp2M) ensure_device(hist_, hist_cap_, (size_t)n * 4 * HW);      // kSolverRow1 keeps no history: nothing is allocated
   SDXL_HIP(hipStreamSynchronize(s));   // tab is a stack-owned host buffer
 
   p_.latent = io.latent;
@@ -267,7 +327,8 @@ int StepLoop::begin(const std::vector<double>& alphas, int n_steps, int step_sta
   p_.ref = io.reference; p_.mask = io.mask; p_.step_noise = io.step_noise; p_.n_steps_total = iters;
   p_.unet_in = io.unet_in; p_.in_dt = io.in_dt; p_.in_ld = io.in_ld; p_.in_rep = single ? 1 : 2;
   p_.t_out = t_dev_;
-  p_.solver = solver; p_.prediction = prediction; p_.hist = hist_;
+  p_.solver = solver_is_row1(solver) ? kSolverRow1 : solver; p_.prediction = prediction;
+  p_.hist = solver_is_row1(solver) ? nullptr : hist_;
   if (io.seeds) {
     p_.seeded = 1;
     for (int b = 0; b < n; ++b) p_.seeds.v[b] = io.seeds[b];
@@ -284,7 +345,7 @@ void StepLoop::after_forward(int i, const float* eps, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------ Diffuser
-void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int n_steps, double cfg_scale,
+void Diffuser::diffuse(float* latent, const Conditioning& c, const std::vector<int>& ts, double cfg_scale,
                        const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s,
                        const uint64_t* seeds, double eta) {
   // diffuse_latent :390-432 / diffuse_latent_with_inpainting :434-483
@@ -321,7 +382,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, int step_start, int
   io.reference = reference; io.mask = mask; io.step_noise = step_noise; io.seeds = seeds;
   u.set_context(ctx_buf_, c.n_ctx, y_buf_, B, s);
 
-  const int iters = loop_.begin(alphas_, n_steps, step_start, solver_, eta, cfg_scale, go, single, n, HW, io, s, prediction_);
+  const int iters = loop_.begin(alphas_, ts, solver_, eta, cfg_scale, go, single, n, HW, io, s, prediction_);
   std::vector<hipEvent_t> ev;
   if (time_steps) {
     ev.resize(iters + 1);
@@ -349,7 +410,11 @@ void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, 
   SDXL_REQUIRE(!t.renoise || (t.step_start >= 1 && t.step_start <= n_train_), "step_start out of range");
   SDXL_REQUIRE(!t.seeds || c.n <= kMaxSeeds, "batch out of range");
   // what StepLoop::begin refuses, before the start latent is written: nothing is launched
-  if (const char* m = schedule_error(alphas_.data(), n_train_, n_steps, t.step_start, prediction_)) throw InvalidArgumentError(m);
+  const std::vector<int> ts = call_schedule(n_steps, t.step_start, t.renoise != nullptr);
+  if (const char* m = schedule_error(alphas_.data(), n_train_, ts, prediction_)) throw InvalidArgumentError(m);
+  if (solver_ == kSolverLcm && t.eta != 0.0) throw InvalidArgumentError("solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
+  if (!t.seeds)
+    if (const char* m = explicit_noise_error(alphas_.data(), n_train_, ts, solver_, prediction_)) throw InvalidArgumentError(m);
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
   ensure_device(latent_, latent_cap_, elems);
@@ -367,7 +432,7 @@ void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, 
   } else {
     SDXL_HIP(hipMemcpyAsync(latent_, t.noise, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-  diffuse(latent_, c, t.step_start, n_steps, cfg_scale, t.reference, t.mask, t.step_noise, s, t.seeds, t.eta);
+  diffuse(latent_, c, ts, cfg_scale, t.reference, t.mask, t.step_noise, s, t.seeds, t.eta);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
