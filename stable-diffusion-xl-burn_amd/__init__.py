@@ -1658,34 +1658,62 @@ def unet_skip_shapes(cfg: UNetConfig, H: int, W: int) -> List[Tuple[int, int, in
     return out
 
 
+def _skip_segments(name: str, segments, multi: bool = False):
+    """the segment checks and the ctypes arrays behind skip_residual_add* (`name` heads the messages): segments = [(dst, src), ...], or with
+    `multi` [(dst, [src_0 .. src_K-1]), ...], whose sources may hold fewer rows than dst (the caller checks what that needs).
+    -> ([(dst, [srcs])], K, the arguments n_segments .. C of the C entry, its dtype code)"""
+    torch = _torch()
+    segments = [(d, list(ss) if multi else [ss]) for d, ss in segments]
+    n = len(segments)
+    if n < 1:
+        raise InvalidArgument(f"{name}: at least one segment")
+    K = len(segments[0][1])
+    if not 1 <= K <= 4 or any(len(ss) != K for _, ss in segments):
+        raise InvalidArgument(f"{name}: the number of sources K must be in 1..4, the same for every segment")
+    dt = segments[0][0].dtype
+    if dt not in (torch.float32, torch.float16):
+        raise InvalidArgument(f"{name}: float32 or float16 tensors")
+    for d, ss in segments:
+        dst_ok = d.is_cuda and d.dim() == 2 and (d.shape[1] <= 1 or d.stride(1) == 1) and d.stride(0) >= d.shape[1]
+        src_ok = dst_ok and d.dtype == dt and all(s.is_cuda and s.dtype == dt and s.dim() == 2 and s.is_contiguous() and s.shape[1] == d.shape[1]
+                                                  and (s.shape[0] <= d.shape[0] if multi else s.shape[0] == d.shape[0]) for s in ss)
+        if not multi and not src_ok:
+            raise InvalidArgument(f"{name}: dst must be a [rows, C] view with contiguous columns and src a dense [rows, C] tensor, one dtype, on the GPU")
+        if not dst_ok:
+            raise InvalidArgument(f"{name}: dst must be a [rows, C] view with contiguous columns, on the GPU")
+        if not src_ok:
+            raise InvalidArgument(f"{name}: every src must be a dense [rows, C] tensor of dst's dtype and width, on the GPU")
+    dst = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in segments])
+    src = (ctypes.c_void_p * (n * K))(*[s.data_ptr() for _, ss in segments for s in ss])
+    ld = (ctypes.c_int64 * n)(*[int(d.stride(0)) for d, _ in segments])
+    rows = (ctypes.c_int64 * n)(*[int(d.shape[0]) for d, _ in segments])
+    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
+    return segments, K, (n, dst, ld, src, rows, cols), DTYPE_F16 if dt == torch.float16 else DTYPE_F32
+
+
+def _skip_scales(name: str, scales, shape: str, tail, step_idx):
+    """the scale table [steps, *tail] and the step index of the trajectory forms -> (step_idx kept alive, its device pointer)"""
+    torch = _torch()
+    if not (torch.is_tensor(scales) and scales.is_cuda and scales.dtype == torch.float32 and tuple(scales.shape[1:]) == tail and scales.is_contiguous()):
+        raise InvalidArgument(f"{name}: scales must be a contiguous float32 CUDA tensor {shape}")
+    if not torch.is_tensor(step_idx):
+        if not 0 <= int(step_idx) < scales.shape[0]:
+            raise InvalidArgument(f"{name}: step_idx outside the scale table")
+        step_idx = torch.tensor([int(step_idx)], dtype=torch.int32, device=scales.device)
+    return _dev(step_idx, torch.int32)
+
+
 def skip_residual_add(ctx: Context, segments, scale):
     """sdxl_skip_residual_add, the UNet's per-step ControlNet add on caller tensors, in place and in ONE launch: for every (dst, src) of `segments`
     (at most 16), dst[r, c] = round(fma(scale, src[r, c], dst[r, c])).  dst: a [rows, C] CUDA view whose columns are contiguous (a column slice of a
     wider row-major buffer), src: a dense [rows, C] tensor; all float32 or all float16.  scale: a float or a one-element fp32 CUDA tensor.
     InvalidArgument (nothing written): C % 8 != 0, a slice or a row pitch that is not 16-byte aligned."""
     torch = _torch()
-    segments = list(segments)
-    n = len(segments)
-    if n < 1:
-        raise InvalidArgument("skip_residual_add: at least one segment")
-    dt = segments[0][0].dtype
-    if dt not in (torch.float32, torch.float16):
-        raise InvalidArgument("skip_residual_add: float32 or float16 tensors")
-    for d, s in segments:
-        if not (d.is_cuda and s.is_cuda) or d.dtype != dt or s.dtype != dt or d.dim() != 2 or tuple(s.shape) != tuple(d.shape) or not s.is_contiguous() \
-                or (d.shape[1] > 1 and d.stride(1) != 1) or d.stride(0) < d.shape[1]:
-            raise InvalidArgument("skip_residual_add: dst must be a [rows, C] view with contiguous columns and src a dense [rows, C] tensor, one dtype, on the GPU")
+    segments, _, (n, dst, ld, src, rows, cols), dtype = _skip_segments("skip_residual_add", segments)
     if not torch.is_tensor(scale):
         scale = torch.tensor([float(scale)], dtype=torch.float32, device=segments[0][0].device)
     scale, ps = _dev(scale)
-    ptrs = ctypes.c_void_p * n
-    i64 = ctypes.c_int64 * n
-    dst = ptrs(*[d.data_ptr() for d, _ in segments])
-    src = ptrs(*[s.data_ptr() for _, s in segments])
-    ld = i64(*[int(d.stride(0)) for d, _ in segments])
-    rows = i64(*[int(d.shape[0]) for d, _ in segments])
-    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
-    _check_invalid(lib().sdxl_skip_residual_add(ctx.h, _stream(), n, dst, ld, src, rows, cols, ps, DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
+    _check_invalid(lib().sdxl_skip_residual_add(ctx.h, _stream(), n, dst, ld, src, rows, cols, ps, dtype))
 
 
 def skip_residual_add_steps(ctx: Context, segments, B: int, scales, step_idx):
@@ -1693,34 +1721,9 @@ def skip_residual_add_steps(ctx: Context, segments, B: int, scales, step_idx):
     segment read from scales[step_idx, r // (rows // B)] -- scales: a float32 CUDA tensor [steps, 8], step_idx: an int or a one-element int32 CUDA
     tensor.  Rows whose scale is 0 are neither read nor written.  InvalidArgument (nothing written): what skip_residual_add refuses, B outside
     1..8, rows that are no multiple of B."""
-    torch = _torch()
-    segments = list(segments)
-    n = len(segments)
-    if n < 1:
-        raise InvalidArgument("skip_residual_add_steps: at least one segment")
-    dt = segments[0][0].dtype
-    if dt not in (torch.float32, torch.float16):
-        raise InvalidArgument("skip_residual_add_steps: float32 or float16 tensors")
-    for d, s in segments:
-        if not (d.is_cuda and s.is_cuda) or d.dtype != dt or s.dtype != dt or d.dim() != 2 or tuple(s.shape) != tuple(d.shape) or not s.is_contiguous() \
-                or (d.shape[1] > 1 and d.stride(1) != 1) or d.stride(0) < d.shape[1]:
-            raise InvalidArgument("skip_residual_add_steps: dst must be a [rows, C] view with contiguous columns and src a dense [rows, C] tensor, one dtype, on the GPU")
-    if not (torch.is_tensor(scales) and scales.is_cuda and scales.dtype == torch.float32 and scales.dim() == 2 and scales.shape[1] == 8 and scales.is_contiguous()):
-        raise InvalidArgument("skip_residual_add_steps: scales must be a contiguous float32 CUDA tensor [steps, 8]")
-    if not torch.is_tensor(step_idx):
-        if not 0 <= int(step_idx) < scales.shape[0]:
-            raise InvalidArgument("skip_residual_add_steps: step_idx outside the scale table")
-        step_idx = torch.tensor([int(step_idx)], dtype=torch.int32, device=scales.device)
-    step_idx, pi = _dev(step_idx, torch.int32)
-    ptrs = ctypes.c_void_p * n
-    i64 = ctypes.c_int64 * n
-    dst = ptrs(*[d.data_ptr() for d, _ in segments])
-    src = ptrs(*[s.data_ptr() for _, s in segments])
-    ld = i64(*[int(d.stride(0)) for d, _ in segments])
-    rows = i64(*[int(d.shape[0]) for d, _ in segments])
-    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
-    _check_invalid(lib().sdxl_skip_residual_add_steps(ctx.h, _stream(), n, dst, ld, src, rows, cols, int(B), ctypes.c_void_p(scales.data_ptr()), pi,
-                                                      DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
+    _, _, (n, dst, ld, src, rows, cols), dtype = _skip_segments("skip_residual_add_steps", segments)
+    step_idx, pi = _skip_scales("skip_residual_add_steps", scales, "[steps, 8]", (8,), step_idx)
+    _check_invalid(lib().sdxl_skip_residual_add_steps(ctx.h, _stream(), n, dst, ld, src, rows, cols, int(B), ctypes.c_void_p(scales.data_ptr()), pi, dtype))
 
 
 def skip_residual_add_steps_multi(ctx: Context, segments, B: int, scales, step_idx):
@@ -1729,49 +1732,24 @@ def skip_residual_add_steps_multi(ctx: Context, segments, B: int, scales, step_i
     is rounded once.  A source at scale 0 is not read.  A source may hold fewer rows than dst (whole batch entries: a net run on the conditional
     entries alone) where every entry behind its end is at scale 0 in the row step_idx names -- checked here, by reading that row.
     InvalidArgument (nothing written): what skip_residual_add_steps refuses, K outside 1..4."""
-    torch = _torch()
-    segments = [(d, list(ss)) for d, ss in segments]
-    n = len(segments)
-    if n < 1:
-        raise InvalidArgument("skip_residual_add_steps_multi: at least one segment")
-    K = len(segments[0][1])
-    if not 1 <= K <= 4 or any(len(ss) != K for _, ss in segments):
-        raise InvalidArgument("skip_residual_add_steps_multi: the number of sources K must be in 1..4, the same for every segment")
-    dt = segments[0][0].dtype
-    if dt not in (torch.float32, torch.float16):
-        raise InvalidArgument("skip_residual_add_steps_multi: float32 or float16 tensors")
-    if not (torch.is_tensor(scales) and scales.is_cuda and scales.dtype == torch.float32 and scales.dim() == 3 and tuple(scales.shape[1:]) == (K, 8)
-            and scales.is_contiguous()):
-        raise InvalidArgument("skip_residual_add_steps_multi: scales must be a contiguous float32 CUDA tensor [steps, K, 8]")
-    if not torch.is_tensor(step_idx):
-        if not 0 <= int(step_idx) < scales.shape[0]:
-            raise InvalidArgument("skip_residual_add_steps_multi: step_idx outside the scale table")
-        step_idx = torch.tensor([int(step_idx)], dtype=torch.int32, device=scales.device)
-    step_idx, pi = _dev(step_idx, torch.int32)
+    name = "skip_residual_add_steps_multi"
+    segments, K, (n, dst, ld, src, rows, cols), dtype = _skip_segments(name, segments, multi=True)
+    step_idx, pi = _skip_scales(name, scales, "[steps, K, 8]", (K, 8), step_idx)
     row = None
     for d, ss in segments:
-        if not d.is_cuda or d.dim() != 2 or (d.shape[1] > 1 and d.stride(1) != 1) or d.stride(0) < d.shape[1]:
-            raise InvalidArgument("skip_residual_add_steps_multi: dst must be a [rows, C] view with contiguous columns, on the GPU")
         for k, s in enumerate(ss):
-            if not s.is_cuda or s.dtype != dt or d.dtype != dt or s.dim() != 2 or s.shape[1] != d.shape[1] or s.shape[0] > d.shape[0] or not s.is_contiguous():
-                raise InvalidArgument("skip_residual_add_steps_multi: every src must be a dense [rows, C] tensor of dst's dtype and width, on the GPU")
             if s.shape[0] < d.shape[0]:
                 if not 1 <= int(B) <= 8 or d.shape[0] % int(B) != 0 or s.shape[0] % (d.shape[0] // int(B)) != 0:
-                    raise InvalidArgument("skip_residual_add_steps_multi: a short source must hold whole batch entries (rows a multiple of B)")
+                    raise InvalidArgument(f"{name}: a short source must hold whole batch entries (rows a multiple of B)")
                 if row is None:
                     i = int(step_idx.item())
                     if not 0 <= i < scales.shape[0]:
-                        raise InvalidArgument("skip_residual_add_steps_multi: step_idx outside the scale table")
+                        raise InvalidArgument(f"{name}: step_idx outside the scale table")
                     row = scales[i].cpu()
                 if bool((row[k, s.shape[0] // (d.shape[0] // int(B)):int(B)] != 0).any()):
-                    raise InvalidArgument("skip_residual_add_steps_multi: a short source needs scale 0 for every entry behind its end")
-    dst = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in segments])
-    src = (ctypes.c_void_p * (n * K))(*[s.data_ptr() for _, ss in segments for s in ss])
-    ld = (ctypes.c_int64 * n)(*[int(d.stride(0)) for d, _ in segments])
-    rows = (ctypes.c_int64 * n)(*[int(d.shape[0]) for d, _ in segments])
-    cols = (ctypes.c_int32 * n)(*[int(d.shape[1]) for d, _ in segments])
+                    raise InvalidArgument(f"{name}: a short source needs scale 0 for every entry behind its end")
     _check_invalid(lib().sdxl_skip_residual_add_steps_multi(ctx.h, _stream(), n, dst, ld, src, K, rows, cols, int(B), ctypes.c_void_p(scales.data_ptr()), pi,
-                                                            DTYPE_F16 if dt == torch.float16 else DTYPE_F32))
+                                                            dtype))
 
 
 def _opt(t):

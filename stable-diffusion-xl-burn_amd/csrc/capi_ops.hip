@@ -507,74 +507,50 @@ int sdxl_timestep_embedding(sdxl_ctx* ctx, void* stream, const float* t, int n, 
   API_END
 }
 // the per-step add of the ControlNet skip residuals (UNet::run behind the middle block) on caller buffers: the table is checked on the host, uploaded,
-// and the one launch walks it.  scales_dev == nullptr: one device scalar (scale_dev); else the trajectory form, scales_dev[*step_idx_dev * 8 + entry of the row]
-static void skip_residual_add_impl(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src,
-                                   const int64_t* rows, const int32_t* C, const float* scale_dev, int B, const float* scales_dev, const int* step_idx_dev,
-                                   int dtype) {
-  if (!ctx || !dst || !dst_ld || !src || !rows || !C || (scales_dev ? !step_idx_dev : !scale_dev)) throw InvalidArgumentError("skip residual add: null argument");
+// and the one launch walks it.  src[i * K + k]; step_idx_dev == nullptr: scales_dev is one device scalar (B == 0, K == 1); else the trajectory form,
+// scales_dev[(*step_idx_dev * K + k) * 8 + entry of the row]
+static void skip_add_impl(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src, int K,
+                          const int64_t* rows, const int32_t* C, int B, const float* scales_dev, const int32_t* step_idx_dev, int dtype) {
+  static_assert(SDXL_MAX_CONTROLS == kSkipMaxSources, "one source per control net");
+  if (!ctx || !dst || !dst_ld || !src || !rows || !C || !scales_dev) throw InvalidArgumentError("skip residual add: null argument");
   if (n_segments < 1 || n_segments > 16) throw InvalidArgumentError("skip residual add: n_segments must be in 1..16");
+  if (K < 1 || K > SDXL_MAX_CONTROLS) throw InvalidArgumentError("skip residual add: the number of sources K must be in 1..4");
+  if (step_idx_dev && B < 1) throw InvalidArgumentError("skip residual add: B must be in 1..8");      // (0 would name the one-scalar form to skip_table_check)
   if (dtype != SDXL_DTYPE_F32 && dtype != SDXL_DTYPE_F16) throw InvalidArgumentError("skip residual add: the dtype must be SDXL_DTYPE_F32 or SDXL_DTYPE_F16");
   const int dt = dtype == SDXL_DTYPE_F16 ? DT_F16 : DT_F32;
   SkipSeg table[16];
   for (int i = 0; i < n_segments; ++i) {
     if (rows[i] < 0 || rows[i] > 0x7fffffff || dst_ld[i] < 0) throw InvalidArgumentError("skip residual add: rows must be in 0..2^31-1 and dst_ld >= C");
-    table[i] = SkipSeg{dst[i], src[i], (long long)dst_ld[i], (int)rows[i], (int)C[i], 0ull};
+    table[i] = SkipSeg{dst[i], {nullptr, nullptr, nullptr, nullptr}, (long long)dst_ld[i], (int)rows[i], (int)C[i], 0ull};
+    for (int k = 0; k < K; ++k) table[i].src[k] = src[(size_t)i * K + k];
   }
   unsigned long long total = 0;
-  if (const char* bad = skip_table_check(table, n_segments, dt, &total)) throw InvalidArgumentError(bad);
-  if (scales_dev)
-    if (const char* bad = skip_table_check_entries(table, n_segments, B)) throw InvalidArgumentError(bad);
+  if (const char* bad = skip_table_check(table, n_segments, K, B, dt, &total)) throw InvalidArgumentError(bad);
   use(ctx);
   hipStream_t s = pick(ctx, stream);
   Tmp tmp;
   SkipSeg* table_dev = (SkipSeg*)tmp.get(sizeof(table));
   SDXL_HIP(hipMemcpyAsync(table_dev, table, n_segments * sizeof(SkipSeg), hipMemcpyHostToDevice, s));
   (void)hipGetLastError();
-  if (scales_dev) launch_skip_residual_add_steps(table_dev, n_segments, total, scales_dev, step_idx_dev, B, dt, s);
-  else launch_skip_residual_add(table_dev, n_segments, total, scale_dev, dt, s);
+  launch_skip_add(table_dev, n_segments, K, total, scales_dev, step_idx_dev, B, dt, s);
   SDXL_HIP(hipGetLastError());
   SDXL_HIP(hipStreamSynchronize(s));
 }
 int sdxl_skip_residual_add(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src,
                            const int64_t* rows, const int32_t* C, const float* scale_dev, int dtype) {
   API_BEGIN
-  skip_residual_add_impl(ctx, stream, n_segments, dst, dst_ld, src, rows, C, scale_dev, 0, nullptr, nullptr, dtype);
+  skip_add_impl(ctx, stream, n_segments, dst, dst_ld, src, 1, rows, C, 0, scale_dev, nullptr, dtype);
   API_END
 }
 int sdxl_skip_residual_add_steps(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src,
                                  const int64_t* rows, const int32_t* C, int B, const float* scales_dev, const int32_t* step_idx_dev, int dtype) {
-  API_BEGIN
-  if (!scales_dev) throw InvalidArgumentError("skip residual add: null argument");
-  skip_residual_add_impl(ctx, stream, n_segments, dst, dst_ld, src, rows, C, nullptr, B, scales_dev, step_idx_dev, dtype);
-  API_END
+  return sdxl_skip_residual_add_steps_multi(ctx, stream, n_segments, dst, dst_ld, src, 1, rows, C, B, scales_dev, step_idx_dev, dtype);
 }
-// the same add with K sources per destination (several control nets): src[i * K + k], scales_dev[(*step_idx_dev * K + k) * 8 + entry of the row]
 int sdxl_skip_residual_add_steps_multi(sdxl_ctx* ctx, void* stream, int n_segments, void* const* dst, const int64_t* dst_ld, const void* const* src, int K,
                                        const int64_t* rows, const int32_t* C, int B, const float* scales_dev, const int32_t* step_idx_dev, int dtype) {
   API_BEGIN
-  if (!ctx || !dst || !dst_ld || !src || !rows || !C || !scales_dev || !step_idx_dev) throw InvalidArgumentError("skip residual add: null argument");
-  if (n_segments < 1 || n_segments > 16) throw InvalidArgumentError("skip residual add: n_segments must be in 1..16");
-  if (K < 1 || K > SDXL_MAX_CONTROLS) throw InvalidArgumentError("skip residual add: the number of sources K must be in 1..4");
-  if (dtype != SDXL_DTYPE_F32 && dtype != SDXL_DTYPE_F16) throw InvalidArgumentError("skip residual add: the dtype must be SDXL_DTYPE_F32 or SDXL_DTYPE_F16");
-  static_assert(SDXL_MAX_CONTROLS == kSkipMaxSources, "one source per control net");
-  const int dt = dtype == SDXL_DTYPE_F16 ? DT_F16 : DT_F32;
-  SkipSegN table[16];
-  for (int i = 0; i < n_segments; ++i) {
-    if (rows[i] < 0 || rows[i] > 0x7fffffff || dst_ld[i] < 0) throw InvalidArgumentError("skip residual add: rows must be in 0..2^31-1 and dst_ld >= C");
-    table[i] = SkipSegN{dst[i], {nullptr, nullptr, nullptr, nullptr}, (long long)dst_ld[i], (int)rows[i], (int)C[i], 0ull};
-    for (int k = 0; k < K; ++k) table[i].src[k] = src[(size_t)i * K + k];
-  }
-  unsigned long long total = 0;
-  if (const char* bad = skip_table_check_sources(table, n_segments, K, B, dt, &total)) throw InvalidArgumentError(bad);
-  use(ctx);
-  hipStream_t s = pick(ctx, stream);
-  Tmp tmp;
-  SkipSegN* table_dev = (SkipSegN*)tmp.get(sizeof(table));
-  SDXL_HIP(hipMemcpyAsync(table_dev, table, n_segments * sizeof(SkipSegN), hipMemcpyHostToDevice, s));
-  (void)hipGetLastError();
-  launch_skip_residual_add_steps_multi(table_dev, n_segments, K, total, scales_dev, step_idx_dev, B, dt, s);
-  SDXL_HIP(hipGetLastError());
-  SDXL_HIP(hipStreamSynchronize(s));
+  if (!step_idx_dev) throw InvalidArgumentError("skip residual add: null argument");
+  skip_add_impl(ctx, stream, n_segments, dst, dst_ld, src, K, rows, C, B, scales_dev, step_idx_dev, dtype);
   API_END
 }
 int sdxl_layer_norm_linear(sdxl_ctx* ctx, void* stream, const float* x, const float* gamma, const float* beta, float eps,

@@ -852,125 +852,65 @@ void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb
 // ---------------------------------------------------------------------------------------------------------
 // ControlNet skip residuals: every segment of the table in one launch (kernels.h SkipSeg).  HBM-bound: one 16-byte chunk per lane and trip (8 halfs /
 // 4 floats), consecutive lanes on consecutive chunks of the flattened segment list, a grid capped at 2048 workgroups striding over the rest.  A lane's
-// chunk index only grows, so it walks the table forwards (a handful of uniform loads per segment change); one fp32 fma and one rounding per element.
-template <typename T>
-__global__ __launch_bounds__(256) void skip_residual_add_kernel(const SkipSeg* __restrict__ table, int n_seg, unsigned long long total,
-                                                                const float* __restrict__ scale_dev) {
+// chunk index only grows, so it walks the table forwards (a handful of uniform loads per segment change).  TABLE == false is the one-scalar form
+// (K == 1, the scale is *scales, the plain fma at every scale); TABLE == true reads the K x 8 scales of the table row [*step_idx][K][8].
+//  * Divisions are 32-bit: skip_table_check keeps a segment under 2^32 chunks, so chunk -> (row, chunk of the row) -> batch entry never takes the
+//    64-bit division, which is a long instruction sequence here.
+//  * The scales of the row sit in registers (32 at K = 4) and a chunk's are picked by compares, k and j unrolled: a dynamic index into a register
+//    array would go through scratch.  A 16-byte chunk lies in one row and a row in one entry (C % 8 == 0, rows % B == 0).
+//  * TABLE: a source at scale 0 is not read, and a chunk whose scales are all 0 is not written.  fma(0, r, dst) is NaN for a non-finite r, and the
+//    sources of an iteration without a control forward are whatever the last one -- or nobody -- left there; a net that ran on the conditional
+//    entries alone has a source that ends before the segment does.
+//  * The sum stays in fp32 across the sources, one fma per live source in the order k = 0 .. K-1, and is rounded to T once: K nets cost a channel
+//    one rounding, as one net does.
+template <typename T, int K, bool TABLE>
+__global__ __launch_bounds__(256) void skip_add_kernel(const SkipSeg* __restrict__ table, int n_seg, unsigned long long total,
+                                                       const float* __restrict__ scales, const int* __restrict__ step_idx, unsigned B) {
+  static_assert(TABLE || K == 1, "one scalar scales one source");
   constexpr int E = 16 / (int)sizeof(T);
+  constexpr int NS = TABLE ? kSkipScaleEntries : 1;
   typedef T vec_t __attribute__((ext_vector_type(E)));
-  const float sc = *scale_dev;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  int si = 0;
-  SkipSeg g = table[0];
-  unsigned long long end = n_seg > 1 ? table[1].first : total;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    while (i >= end) {      // (i < total = the last segment's end: si stays inside the table)
-      ++si;
-      g = table[si];
-      end = si + 1 < n_seg ? table[si + 1].first : total;
-    }
-    const unsigned l = (unsigned)(i - g.first);      // (skip_table_check: a segment has fewer than 2^32 chunks -- a 32-bit division)
-    const unsigned cpr = (unsigned)g.C / E;
-    const unsigned row = l / cpr;
-    const unsigned cc = l - row * cpr;
-    vec_t* d = reinterpret_cast<vec_t*>(reinterpret_cast<T*>(g.dst) + (unsigned long long)row * (unsigned long long)g.dst_ld) + cc;
-    const vec_t a = reinterpret_cast<const vec_t*>(g.src)[l];
-    vec_t v = *d;
-#pragma unroll
-    for (int j = 0; j < E; ++j) v[j] = (T)fmaf(sc, (float)a[j], (float)v[j]);
-    *d = v;
-  }
-}
-// The same add as a trajectory needs it (sdxl_skip_residual_add_steps; the kernel above stays as it is): the scale of a chunk is the entry of its row
-// in the row of a [iterations + 1][8] table that a loop's device step index names.  Same walk, same 16 bytes per lane and trip, same fma and rounding.
-// A chunk whose scale is 0 reads no source and writes nothing: fma(0, r, dst) is NaN for a non-finite r, and the sources of an iteration without a
-// control forward are whatever the last one -- or nobody -- left there.  The eight scales sit in registers and are picked by compares (a dynamic index
-// would go through scratch); a 16-byte chunk lies in one row and a row in one entry (C % 8 == 0, rows % B == 0: skip_table_check_entries).
-template <typename T>
-__global__ __launch_bounds__(256) void skip_residual_add_steps_kernel(const SkipSeg* __restrict__ table, int n_seg, unsigned long long total,
-                                                                      const float* __restrict__ scales, const int* __restrict__ step_idx, unsigned B) {
-  constexpr int E = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(E)));
-  float sv[kSkipScaleEntries];
+  float sv[K][NS];
   {
-    const float* row = scales + (size_t)*step_idx * kSkipScaleEntries;
-#pragma unroll
-    for (int j = 0; j < kSkipScaleEntries; ++j) sv[j] = row[j];
-  }
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  int si = 0;
-  SkipSeg g = table[0];
-  unsigned long long end = n_seg > 1 ? table[1].first : total;
-  unsigned rpe = (unsigned)g.rows / B;      // rows per batch entry (skip_table_check_entries: rows % B == 0)
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    while (i >= end) {      // (i < total = the last segment's end: si stays inside the table)
-      ++si;
-      g = table[si];
-      end = si + 1 < n_seg ? table[si + 1].first : total;
-      rpe = (unsigned)g.rows / B;
-    }
-    const unsigned l = (unsigned)(i - g.first);      // (skip_table_check: a segment has fewer than 2^32 chunks -- 32-bit divisions)
-    const unsigned cpr = (unsigned)g.C / E;
-    const unsigned row = l / cpr;
-    const unsigned cc = l - row * cpr;
-    const unsigned b = row / rpe;      // (a segment that holds a chunk has rows >= B: rpe >= 1, and b < B)
-    float sc = sv[0];
-#pragma unroll
-    for (int j = 1; j < kSkipScaleEntries; ++j) sc = b == (unsigned)j ? sv[j] : sc;
-    if (sc == 0.f) continue;
-    vec_t* d = reinterpret_cast<vec_t*>(reinterpret_cast<T*>(g.dst) + (unsigned long long)row * (unsigned long long)g.dst_ld) + cc;
-    const vec_t a = reinterpret_cast<const vec_t*>(g.src)[l];
-    vec_t v = *d;
-#pragma unroll
-    for (int j = 0; j < E; ++j) v[j] = (T)fmaf(sc, (float)a[j], (float)v[j]);
-    *d = v;
-  }
-}
-// K sources per destination (kernels.h SkipSegN: several control nets on one UNet).  The walk is the kernel's above; the K x 8 scales of the table row
-// [*step_idx][K][8] sit in registers (32 at K = 4), every source's scale is picked by the same compares (k and j are unrolled: no dynamic index, no
-// scratch).  The running sum stays in fp32 across the sources and is rounded once.  A source at scale 0 is not read -- it may hold NaN, or be shorter
-// than the segment (a net that ran on the conditional entries alone) -- and a chunk whose scales are all 0 is not written.  K = 1 is the
-// kernel above bit for bit: (T)fmaf(s, (float)a, (float)d).
-template <typename T, int K>
-__global__ __launch_bounds__(256) void skip_residual_add_steps_multi_kernel(const SkipSegN* __restrict__ table, int n_seg, unsigned long long total,
-                                                                            const float* __restrict__ scales, const int* __restrict__ step_idx, unsigned B) {
-  constexpr int E = 16 / (int)sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(E)));
-  float sv[K][kSkipScaleEntries];
-  {
-    const float* row = scales + (size_t)*step_idx * (K * kSkipScaleEntries);
+    const float* row = scales;
+    if constexpr (TABLE) row += (size_t)*step_idx * (K * NS);
 #pragma unroll
     for (int k = 0; k < K; ++k)
 #pragma unroll
-      for (int j = 0; j < kSkipScaleEntries; ++j) sv[k][j] = row[k * kSkipScaleEntries + j];
+      for (int j = 0; j < NS; ++j) sv[k][j] = row[k * NS + j];
   }
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   int si = 0;
-  SkipSegN g = table[0];
+  SkipSeg g = table[0];
   unsigned long long end = n_seg > 1 ? table[1].first : total;
-  unsigned rpe = (unsigned)g.rows / B;      // rows per batch entry (skip_table_check_entries: rows % B == 0)
+  unsigned rpe = 1;      // rows per batch entry
+  if constexpr (TABLE) rpe = (unsigned)g.rows / B;
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     while (i >= end) {      // (i < total = the last segment's end: si stays inside the table)
       ++si;
       g = table[si];
       end = si + 1 < n_seg ? table[si + 1].first : total;
-      rpe = (unsigned)g.rows / B;
+      if constexpr (TABLE) rpe = (unsigned)g.rows / B;
     }
-    const unsigned l = (unsigned)(i - g.first);      // (skip_table_check: a segment has fewer than 2^32 chunks -- 32-bit divisions)
+    const unsigned l = (unsigned)(i - g.first);
     const unsigned cpr = (unsigned)g.C / E;
     const unsigned row = l / cpr;
     const unsigned cc = l - row * cpr;
-    const unsigned b = row / rpe;      // (a segment that holds a chunk has rows >= B: rpe >= 1, and b < B)
     float sc[K];
-    bool any = false;
+    if constexpr (TABLE) {
+      const unsigned b = row / rpe;      // (a segment that holds a chunk has rows >= B: rpe >= 1, and b < B)
+      bool any = false;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      sc[k] = sv[k][0];
+      for (int k = 0; k < K; ++k) {
+        sc[k] = sv[k][0];
 #pragma unroll
-      for (int j = 1; j < kSkipScaleEntries; ++j) sc[k] = b == (unsigned)j ? sv[k][j] : sc[k];
-      any = any || sc[k] != 0.f;
+        for (int j = 1; j < NS; ++j) sc[k] = b == (unsigned)j ? sv[k][j] : sc[k];
+        any = any || sc[k] != 0.f;
+      }
+      if (!any) continue;
+    } else {
+      sc[0] = sv[0][0];
     }
-    if (!any) continue;
     vec_t* d = reinterpret_cast<vec_t*>(reinterpret_cast<T*>(g.dst) + (unsigned long long)row * (unsigned long long)g.dst_ld) + cc;
     vec_t v = *d;
     float f[E];
@@ -978,7 +918,7 @@ __global__ __launch_bounds__(256) void skip_residual_add_steps_multi_kernel(cons
     for (int j = 0; j < E; ++j) f[j] = (float)v[j];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      if (sc[k] == 0.f) continue;
+      if (TABLE && sc[k] == 0.f) continue;
       const vec_t a = reinterpret_cast<const vec_t*>(g.src[k])[l];
 #pragma unroll
       for (int j = 0; j < E; ++j) f[j] = fmaf(sc[k], (float)a[j], f[j]);
@@ -996,80 +936,43 @@ __global__ void silu_inplace_kernel(void* p, int dt, size_t n) {
 void launch_silu_inplace(void* p, int dt, size_t n, hipStream_t s) {
   if (n) hipLaunchKernelGGL(silu_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, dt, n);
 }
-const char* skip_table_check(SkipSeg* t, int n_seg, int dt, unsigned long long* total_chunks) {
+const char* skip_table_check(SkipSeg* t, int n_seg, int K, int B, int dt, unsigned long long* total_chunks) {
   if (dt != DT_F32 && dt != DT_F16) return "skip residual add: the dtype must be fp32 or f16 (the stream dtype of the UNet)";
   if (n_seg < 1 || !t) return "skip residual add: at least one segment";
+  if (K < 1 || K > kSkipMaxSources) return "skip residual add: the number of sources K must be in 1..4";
+  if (B < 0 || B > kSkipScaleEntries) return "skip residual add: B must be in 1..8";
   const size_t es = dt_size(dt);
   unsigned long long total = 0;
   for (int i = 0; i < n_seg; ++i) {
     if (t[i].rows < 0 || t[i].C <= 0) return "skip residual add: rows must be >= 0 and C > 0";
     if (t[i].C % 8 != 0) return "skip residual add: C must be a multiple of 8";
     if (t[i].dst_ld < t[i].C) return "skip residual add: dst_ld must be >= C";
-    if (!t[i].dst || !t[i].src) return "skip residual add: null segment pointer";
-    if (((uintptr_t)t[i].dst | (uintptr_t)t[i].src | (uintptr_t)((size_t)t[i].dst_ld * es)) & 15) return "skip residual add: dst, src and the row pitch of dst must be 16-byte aligned";
+    uintptr_t bits = (uintptr_t)t[i].dst | (uintptr_t)((size_t)t[i].dst_ld * es);
+    bool null = !t[i].dst;
+    for (int k = 0; k < K; ++k) { null = null || !t[i].src[k]; bits |= (uintptr_t)t[i].src[k]; }
+    if (null) return "skip residual add: null segment pointer";
+    if (bits & 15) return "skip residual add: dst, src and the row pitch of dst must be 16-byte aligned";
     const unsigned long long chunks = (unsigned long long)t[i].rows * (unsigned long long)((size_t)t[i].C * es / 16);
     if (chunks >> 32) return "skip residual add: a segment must be smaller than 2^32 16-byte chunks";
+    if (B && t[i].rows % B != 0) return "skip residual add: every segment's rows must be a multiple of B (equal rows per batch entry)";
     t[i].first = total;
     total += chunks;
   }
   if (total_chunks) *total_chunks = total;
   return nullptr;
 }
-void launch_skip_residual_add(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scale_dev, int dt, hipStream_t s) {
+using SkipAddKernel = void (*)(const SkipSeg*, int, unsigned long long, const float*, const int*, unsigned);
+template <typename T>      // [0]: one scalar; [K]: the table form with K sources
+static constexpr SkipAddKernel kSkipAdd[1 + kSkipMaxSources] = {skip_add_kernel<T, 1, false>, skip_add_kernel<T, 1, true>, skip_add_kernel<T, 2, true>,
+                                                                skip_add_kernel<T, 3, true>, skip_add_kernel<T, 4, true>};
+void launch_skip_add(const SkipSeg* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev, const int* step_idx_dev, int B,
+                     int dt, hipStream_t s) {
   if (!total_chunks) return;
+  if (K < 1 || K > kSkipMaxSources || (!step_idx_dev && K != 1)) throw std::runtime_error("skip residual add: the number of sources K must be in 1..4, 1 under one scalar");      // (skip_table_check)
   const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
-  if (dt == DT_F16) hipLaunchKernelGGL(skip_residual_add_kernel<half_t>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scale_dev);
-  else hipLaunchKernelGGL(skip_residual_add_kernel<float>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scale_dev);
-}
-
-const char* skip_table_check_entries(const SkipSeg* t, int n_seg, int B) {
-  if (B < 1 || B > kSkipScaleEntries) return "skip residual add: B must be in 1..8";
-  for (int i = 0; i < n_seg; ++i)
-    if (t[i].rows % B != 0) return "skip residual add: every segment's rows must be a multiple of B (equal rows per batch entry)";
-  return nullptr;
-}
-void launch_skip_residual_add_steps(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scales_dev, const int* step_idx_dev,
-                                    int B, int dt, hipStream_t s) {
-  if (!total_chunks) return;
-  const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
-  if (dt == DT_F16) hipLaunchKernelGGL(skip_residual_add_steps_kernel<half_t>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
-  else hipLaunchKernelGGL(skip_residual_add_steps_kernel<float>, dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
-}
-const char* skip_table_check_sources(SkipSegN* t, int n_seg, int K, int B, int dt, unsigned long long* total_chunks) {
-  if (K < 1 || K > kSkipMaxSources) return "skip residual add: the number of sources K must be in 1..4";
-  if (n_seg < 1 || !t) return "skip residual add: at least one segment";
-  constexpr int kMaxSegs = 64;      // (the C entry takes 16; a UNet's table has one segment per input entry + 1)
-  if (n_seg > kMaxSegs) return "skip residual add: at most 64 segments";
-  SkipSeg one[kMaxSegs];
-  for (int i = 0; i < n_seg; ++i) one[i] = SkipSeg{t[i].dst, t[i].src[0], t[i].dst_ld, t[i].rows, t[i].C, 0ull};
-  if (const char* bad = skip_table_check(one, n_seg, dt, total_chunks)) return bad;
-  if (const char* bad = skip_table_check_entries(one, n_seg, B)) return bad;
-  for (int i = 0; i < n_seg; ++i) {
-    t[i].first = one[i].first;
-    for (int k = 1; k < K; ++k) {
-      if (!t[i].src[k]) return "skip residual add: null segment pointer";
-      if ((uintptr_t)t[i].src[k] & 15) return "skip residual add: dst, src and the row pitch of dst must be 16-byte aligned";
-    }
-  }
-  return nullptr;
-}
-template <typename T>
-static void launch_multi_t(int K, unsigned grid, hipStream_t s, const SkipSegN* table_dev, int n_seg, unsigned long long total, const float* scales_dev,
-                           const int* step_idx_dev, unsigned B) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 1>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
-    case 2: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 2>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
-    case 3: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 3>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
-    default: hipLaunchKernelGGL((skip_residual_add_steps_multi_kernel<T, 4>), dim3(grid), dim3(256), 0, s, table_dev, n_seg, total, scales_dev, step_idx_dev, B); break;
-  }
-}
-void launch_skip_residual_add_steps_multi(const SkipSegN* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev,
-                                          const int* step_idx_dev, int B, int dt, hipStream_t s) {
-  if (!total_chunks) return;
-  if (K < 1 || K > kSkipMaxSources) throw std::runtime_error("skip residual add: the number of sources K must be in 1..4");      // (skip_table_check_sources)
-  const unsigned grid = (unsigned)std::min<unsigned long long>((total_chunks + 255) / 256, 2048);
-  if (dt == DT_F16) launch_multi_t<half_t>(K, grid, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
-  else launch_multi_t<float>(K, grid, s, table_dev, n_seg, total_chunks, scales_dev, step_idx_dev, (unsigned)B);
+  const int form = step_idx_dev ? K : 0;
+  hipLaunchKernelGGL(dt == DT_F16 ? kSkipAdd<half_t>[form] : kSkipAdd<float>[form], dim3(grid), dim3(256), 0, s, table_dev, n_seg, total_chunks, scales_dev,
+                     step_idx_dev, (unsigned)B);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -412,35 +412,25 @@ void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n
 // noised = latent*sa + noise*sb   (refine_latent :363-367)
 void launch_axpby(float* dst, const float* a, float sa, const float* b, float sb, size_t n, hipStream_t s);
 // ControlNet skip residuals: ONE launch adds every residual tensor of a step into the tensor the decoder reads -- the skip halves of the
-// concat buffers and the middle block's output.  A segment is `rows` rows of C channels: src dense [rows][C], dst rows of dst_ld elements, both in the
-// dtype `dt` (DT_F32 / DT_F16) of the launch;  dst = round_to_dt(fma(*scale_dev, (float)src, (float)dst)).  The table lives in device memory (fixed
-// address: a captured graph keeps it), the scale too (changing it re-captures nothing).  `first` = 16-byte chunks of the segments before this one
-// (filled by skip_table_check).  Segments must not overlap; the result does not depend on the grid.
-struct SkipSeg { void* dst; const void* src; long long dst_ld; int rows; int C; unsigned long long first; };
-// host logic only: nullptr where every segment can run -- rows >= 0, C > 0, C % 8 == 0, dst_ld >= C, dst / src / row pitch 16-byte aligned, fewer
-// than 2^32 chunks, dt is DT_F32 or DT_F16 --, else the complaint; fills SkipSeg::first and *total_chunks
-const char* skip_table_check(SkipSeg* table_host, int n_seg, int dt, unsigned long long* total_chunks);
-void launch_skip_residual_add(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scale_dev, int dt, hipStream_t s);
-// The same add as a trajectory needs it (sdxl_skip_residual_add_steps): the scale of a chunk is scales_dev[*step_idx_dev * 8 + b], b = row / (rows / B) the batch
-// entry of its row -- a device table [iterations + 1][8] and the loop's device step index, so one captured launch serves every iteration.  A chunk whose
-// scale is 0 reads no source and writes nothing (its source may hold anything, NaN included).  skip_table_check_entries (host logic only): B in 1..8 and
-// every segment's rows a multiple of B, else the complaint.
+// concat buffers and the middle block's output.  A segment is `rows` rows of C channels: every src[k < K] dense [rows][C], dst rows of dst_ld elements,
+// all in the dtype `dt` (DT_F32 / DT_F16) of the launch.  The table lives in device memory (fixed address: a captured graph keeps it), the scales too
+// (changing them re-captures nothing).  `first` = 16-byte chunks of the segments before this one (filled by skip_table_check).  Segments must not
+// overlap; the result does not depend on the grid.  Two ways to name the scales:
+//   one scalar (step_idx_dev == nullptr, K == 1):  dst = round_to_dt(fma(*scales_dev, (float)src[0], (float)dst)), at every scale, 0 included;
+//   a table (step_idx_dev != nullptr):  source k of a row has the scale s_k = scales_dev[(*step_idx_dev * K + k) * 8 + b], b = row / (rows / B) the
+//     batch entry of the row -- a device table [iterations + 1][K][8] and the loop's device step index, so one captured launch serves every iteration.
+//     Per element: v = (float)dst; for k = 0 .. K-1 in order, where s_k != 0: v = fmaf(s_k, (float)src[k], v); dst = round_to_dt(v) where any s_k != 0.
+//     A source whose own scale is 0 is not read (it may hold NaN, or end before the chunk: a control net run on the conditional entries alone); a
+//     chunk all of whose scales are 0 is not written.
 constexpr int kSkipScaleEntries = 8;
-const char* skip_table_check_entries(const SkipSeg* table_host, int n_seg, int B);
-void launch_skip_residual_add_steps(const SkipSeg* table_dev, int n_seg, unsigned long long total_chunks, const float* scales_dev, const int* step_idx_dev,
-                                    int B, int dt, hipStream_t s);
-// The per-step add with K sources per destination (several control nets on one UNet; sdxl_skip_residual_add_steps_multi): one launch, one read and one
-// write of every destination, one rounding.  Source k of a chunk has the scale scales_dev[(*step_idx_dev * K + k) * 8 + b] -- a device table
-// [iterations + 1][K][8].  Per element: v = (float)dst; for k = 0 .. K-1 in order, where s_k != 0: v = fmaf(s_k, (float)src_k, v); dst = round_to_dt(v) where
-// any s_k != 0.  A source whose own scale is 0 is not read (it may hold NaN, or end before the chunk: a control net run on the conditional entries
-// alone); a chunk all of whose scales are 0 is not written.  K = 1 gives the bits of launch_skip_residual_add_steps.  src[k >= K] are not looked at.
 constexpr int kSkipMaxSources = 4;
-struct SkipSegN { void* dst; const void* src[kSkipMaxSources]; long long dst_ld; int rows; int C; unsigned long long first; };
-// host logic only: skip_table_check and skip_table_check_entries over (dst, src[0]), K in 1..kSkipMaxSources, and every src[k < K] non-null and
-// 16-byte aligned; nullptr where the table can run, else the complaint; fills SkipSegN::first and *total_chunks
-const char* skip_table_check_sources(SkipSegN* table_host, int n_seg, int K, int B, int dt, unsigned long long* total_chunks);
-void launch_skip_residual_add_steps_multi(const SkipSegN* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev,
-                                          const int* step_idx_dev, int B, int dt, hipStream_t s);
+struct SkipSeg { void* dst; const void* src[kSkipMaxSources]; long long dst_ld; int rows; int C; unsigned long long first; };      // (src[k >= K] are not looked at)
+// host logic only: nullptr where every segment can run -- dt is DT_F32 or DT_F16, K in 1..kSkipMaxSources, rows >= 0, C > 0, C % 8 == 0, dst_ld >= C,
+// dst / every src[k < K] / the row pitch 16-byte aligned, fewer than 2^32 chunks; B == 0 is the one-scalar form, else B in 1..8 and every segment's
+// rows a multiple of B --, else the complaint; fills SkipSeg::first and *total_chunks
+const char* skip_table_check(SkipSeg* table_host, int n_seg, int K, int B, int dt, unsigned long long* total_chunks);
+void launch_skip_add(const SkipSeg* table_dev, int n_seg, int K, unsigned long long total_chunks, const float* scales_dev, const int* step_idx_dev, int B,
+                     int dt, hipStream_t s);
 void launch_silu_inplace(void* p, int dt, size_t n, hipStream_t s);      // p[i] = silu(p[i]), dense, DT_F32 / DT_F16
 // image post-process (stablediffusion/mod.rs:210-230): u8 = trunc(clamp(((x+1)/2)*255, 0, 255)), NHWC rows of 3
 void launch_to_u8_image(const void* src, int dt, int lds, unsigned char* dst, size_t pixels, hipStream_t s);

@@ -828,7 +828,7 @@ void UNet::run(Exec& ex, const float* t_dev, int t_stride, int b0, int nb) {
   if (res_key_ && !ex.dry) {
     SDXL_REQUIRE(res_table_ok_ && b0 == 0 && nb == pB_ && cat[0].p == res_dst_mid_, "skip residuals: the segment table does not describe this run");
     if (ex.prof) ex.prof->begin(Profiler::OTHER, 0.0, ex.s);
-    launch_skip_residual_add(res_table_, res_segs_, res_chunks_, res_scale_, sdt_, ex.s);
+    launch_skip_add(res_table_, res_segs_, 1, res_chunks_, res_scale_, nullptr, 0, sdt_, ex.s);
     if (ex.prof) ex.prof->end(ex.s);
   }
   // --- output blocks (:483-486)
@@ -1179,10 +1179,10 @@ void UNet::prepare_residuals() {
   for (int i = 0; i < n_in; ++i) {
     const int j = n_in - 1 - i;
     const Act d = k.cat[j].cols(k.cx[j]);
-    t[i] = SkipSeg{d.p, res_src_[i], (long long)d.ld, pB_ * k.hs_h[i] * k.hs_w[i], inp_[i].d.c_out, 0ull};
+    t[i] = SkipSeg{d.p, {res_src_[i]}, (long long)d.ld, pB_ * k.hs_h[i] * k.hs_w[i], inp_[i].d.c_out, 0ull};
   }
-  t[n_in] = SkipSeg{k.cat[0].p, res_src_[n_in], (long long)k.cat[0].ld, pB_ * k.hs_h[n_in - 1] * k.hs_w[n_in - 1], mid_res1_.d.c_out, 0ull};
-  if (const char* bad = skip_table_check(t.data(), n_in + 1, sdt_, &res_chunks_)) throw InvalidArgumentError(bad);
+  t[n_in] = SkipSeg{k.cat[0].p, {res_src_[n_in]}, (long long)k.cat[0].ld, pB_ * k.hs_h[n_in - 1] * k.hs_w[n_in - 1], mid_res1_.d.c_out, 0ull};
+  if (const char* bad = skip_table_check(t.data(), n_in + 1, 1, 0, sdt_, &res_chunks_)) throw InvalidArgumentError(bad);
   SDXL_HIP(hipMemcpy(res_table_, t.data(), t.size() * sizeof(SkipSeg), hipMemcpyHostToDevice));
   res_segs_ = n_in + 1;
   res_dst_mid_ = k.cat[0].p;

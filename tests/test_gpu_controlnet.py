@@ -9,6 +9,7 @@ from oracle import config as OC, model as OM
 from util import rel_err, rounding_slack, seeded, to_pkg_cfg, unet_weights
 from test_gpu_models import FWD_TOL
 import controlnet_ref as CR
+from skip_add_ref import skip_add_expected
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +29,10 @@ TABLES = {
 
 def _spacing32(v):
     return torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126))) - 23.0)
+
+
+def _bits(t):
+    return t.view(torch.int16 if t.dtype == torch.float16 else torch.int32)
 
 
 def _table(n, tdt):
@@ -68,11 +73,34 @@ def test_add_op_against_fp64(pkg, ctx, tdt, n_seg, scale):
             bound, err = slack, (got - h).abs()
         assert bool((err <= bound).all()), f"segment {(rows, C, ld, off)}: max err {err.max():.3e}"
         worst = max(worst, (got - ref).abs().max().item())
+        # the bits: one correctly rounded fp32 fma and one rounding to the type, computed on the CPU (the one-scalar form does not skip at scale 0)
+        old = buf[:, off:off + C].numpy()
+        want = torch.from_numpy(skip_add_expected(old, [src.numpy()], [scale], old.dtype, skip_zero=False))
+        differ = int((_bits(out[:, off:off + C]) != _bits(want)).sum())
+        print(f"segment {(rows, C, ld, off)}: {differ} of {want.numel()} elements differ from the expected bits")
+        assert differ == 0
         if scale == 0.0:
             assert torch.equal(out, buf), "scale 0 changed the destination"
         else:
             assert not torch.equal(out[:, off:off + C], buf[:, off:off + C])
     print(f"skip_residual_add {n_seg} segments {tdt} scale {scale}: max |out - fp64| {worst:.3e}")
+
+
+def test_add_op_scale_zero_is_still_the_fma(pkg, ctx):
+    """dst = round(fma(scale, src, dst)) at every scale: the one-scalar entry has no rule for scale 0 (the table forms do), so a NaN source
+    reaches its rows of the destination and all other rows keep their bits"""
+    rows, C, ld, off = SEGS[1]
+    buf, src = seeded(rows, ld, seed=5).half(), seeded(rows, C, seed=6).half()
+    src[11] = float("nan")
+    d = buf.cuda()
+    pkg.skip_residual_add(ctx, [(d[:, off:off + C], src.cuda())], 0.0)
+    out = d.cpu()
+    assert bool(torch.isnan(out[11, off:off + C]).all()), "0 * NaN + dst must be NaN"
+    want = buf.clone()
+    want[:, off:off + C] = torch.from_numpy(skip_add_expected(buf[:, off:off + C].numpy(), [src.numpy()], [0.0], np.float16, skip_zero=False))
+    live = torch.arange(rows) != 11
+    assert torch.equal(_bits(out[live]), _bits(want[live])) and torch.equal(_bits(out[live]), _bits(buf[live]))
+    assert torch.equal(_bits(out[11, :off]), _bits(buf[11, :off])) and torch.equal(_bits(out[11, off + C:]), _bits(buf[11, off + C:]))
 
 
 @pytest.mark.parametrize("tdt", [torch.float32, torch.float16], ids=["f32", "f16"])

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from skip_add_ref import skip_add_expected
 from util import rounding_slack, seeded
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +72,10 @@ def test_step_add_op_against_fp64(pkg, ctx, tdt, B, step):
             assert bool((err <= bound).all()), f"segment {(r, C, ld, off)} entry {b}: max err {err.max():.3e}"
             assert not torch.equal(got, old)
             worst = max(worst, (got.double() - ref).abs().max().item())
+            want = torch.from_numpy(skip_add_expected(old.numpy(), [src[rows].numpy()], [scales[b]], old.numpy().dtype))
+            differ = int((_bits(got) != _bits(want)).sum())
+            print(f"segment {(r, C, ld, off)} entry {b}: {differ} of {want.numel()} elements differ from the expected bits")
+            assert differ == 0
     print(f"skip_residual_add_steps B {B} {tdt} step {step} scales {scales}: max |out - fp64| {worst:.3e}")
 
 
@@ -89,6 +94,19 @@ def test_step_add_op_cond_only_is_the_second_half_at_zero(pkg, ctx):
         one = buf[b * r:(b + 1) * r].cuda()
         pkg.skip_residual_add(ctx, [(one, src[b * r:(b + 1) * r].cuda())], s)
         assert torch.equal(_bits(d[b * r:(b + 1) * r].cpu()), _bits(one.cpu()))
+
+
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float16], ids=["f32", "f16"])
+def test_step_add_op_one_scale_for_every_entry_is_the_one_scalar_add(pkg, ctx, tdt):
+    """a table row whose B entries hold the same non-zero scale gives the bits of the one-scalar entry at that scale"""
+    B, (r, C, ld, off) = 3, OP_SEGS[1]
+    buf, src = seeded(B * r, ld, seed=21).to(tdt), seeded(B * r, C, seed=22).to(tdt)
+    table = torch.tensor([[NAN] * 8, [-0.37] * B + [NAN] * (8 - B)], dtype=torch.float32).cuda()
+    steps, one = buf.cuda(), buf.cuda()
+    pkg.skip_residual_add_steps(ctx, [(steps[:, off:off + C], src.cuda())], B, table, 1)
+    pkg.skip_residual_add(ctx, [(one[:, off:off + C], src.cuda())], -0.37)
+    assert torch.equal(_bits(steps.cpu()), _bits(one.cpu()))
+    assert not torch.equal(_bits(steps.cpu()), _bits(buf))
 
 
 def test_step_add_op_refusals_write_nothing(pkg, ctx):

@@ -3,7 +3,7 @@
 
     --add N      N launches of the one-launch skip-residual add (sdxl_skip_residual_add) over the ten segments a UNet's table has there: the skip
                  halves of the concat buffers (column slices, row pitch = the concat width) and the middle block's output.  Run it under
-                 rocprofv3 --kernel-trace --stats and read skip_residual_add_kernel's row: the entry itself allocates and synchronises.
+                 rocprofv3 --kernel-trace --stats and read the row of skip_add_kernel<_Float16, 1, false>: the entry itself allocates and synchronises.
     --convs      the ten 1x1 convolutions of a control net, shape by shape through sdxl_bench_igemm (event-timed mean of 20 launches each, in
                  isolation: no graph, no neighbours in the cache -- not the cost inside a step)
 """

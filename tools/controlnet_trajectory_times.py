@@ -1,9 +1,10 @@
 """The per-step add of several control nets on its own (profiles/controlnet_trajectory_times.txt), at the base model's shapes on a
 128 x 128 latent, B = 2, f16:
 
-    --add N      N launches each of the per-step add with one and with two sources (sdxl_skip_residual_add_steps_multi) and of the one-source kernel
-                 it extends (sdxl_skip_residual_add_steps) over the ten segments a UNet's table has there.  Run it under
-                 rocprofv3 --kernel-trace --stats and read the kernels' rows: the entries themselves allocate and synchronise.
+    --add N      N launches each of the per-step add with one and with two sources (sdxl_skip_residual_add_steps_multi) and of the one-source
+                 entry (sdxl_skip_residual_add_steps) over the ten segments a UNet's table has there.  Run it under
+                 rocprofv3 --kernel-trace --stats and read the rows of skip_add_kernel<_Float16, 1, true> (2 N launches: both one-source entries
+                 run it) and skip_add_kernel<_Float16, 2, true>: the entries themselves allocate and synchronise.
 """
 import argparse
 import json
