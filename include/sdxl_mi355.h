@@ -272,7 +272,8 @@ int sdxl_step_count(int n_steps, int step_start, int n_train_steps);
  * (0, 1, 0, 0), the iteration returns x0); second order everywhere else.  At eta = 0 a first-order row equals DDIM's.  The
  * draw numbers do not change: SDXL_DRAW_SIGMA(i) is the z of iteration i for both solvers, drawn where c_z != 0; with explicit
  * noise eta is 0.  Inpainting keeps its blend in front of every iteration; x0p is the x0 computed from the blended state. */
-enum { SDXL_SOLVER_DDIM = 0, SDXL_SOLVER_DPMPP_2M = 1, SDXL_SOLVER_LCM = 3, SDXL_SOLVER_TCD = 4 };   /* 2 is not a solver: it stays refused */
+enum { SDXL_SOLVER_DDIM = 0, SDXL_SOLVER_DPMPP_2M = 1, SDXL_SOLVER_LCM = 3, SDXL_SOLVER_TCD = 4,
+       SDXL_SOLVER_DPMPP_3M = 5 };   /* 2 is not a solver: it stays refused.  DPMPP_3M: the noise-level section below */
 /* unknown value: SDXL_ERR_INVALID ("solver" in sdxl_last_error), the handle keeps its solver */
 int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver);
 int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out);
@@ -369,6 +370,92 @@ int sdxl_timestep_schedule(int kind, int n_steps, int n_train_steps, int param, 
  * reference's list. */
 int sdxl_solver_coefficients_ts(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver,
                                 int prediction, double eta, double* out, int capacity_steps);
+/* ---- noise-level schedules: sigma lists, partial trajectories, DPM++ 3M SDE.
+ *
+ * A trajectory is a list of noise levels with an end level: iteration i runs at alphas_cumprod a_i and lands on ap = a_{i+1}, behind the last
+ * entry on the end level (1 = the data itself: the complete trajectory).  A timestep list is the special case a_i = alphas[t_i].
+ *
+ * Sigma list.  k-diffusion's sigma = sqrt((1 - a) / a), strictly decreasing, finite and > 0; a_i = 1 / (1 + sigma_i^2) in f64 -- a level
+ * between two training timesteps.  The timestep of such a level -- what the UNet is fed as a float, what the guidance interval compares
+ * (t_lo <= t <= t_hi on the f64 value) and what LCM scales (s = 10 t) -- is k-diffusion's sigma_to_t in f64: with
+ * L_j = 0.5 ln((1 - alphas[j]) / alphas[j]), low the largest j <= n_train_steps - 2 with L_j <= ln sigma (0 if there is none), high = low + 1,
+ *     w = clamp((L_low - ln sigma) / (L_low - L_high), 0, 1),    t = (1 - w) low + w high.
+ * SDXL_SIGMAS_ROUND_T rounds that t to the nearest integer, ties to even (diffusers' use_karras_sigmas convention); a stays the sigma's own.
+ * DDIM (Euler-ancestral is DDIM at eta = 1 on the same list), 2M, 3M and LCM run on a sigma list.  TCD reads alphas at floor((1 - gamma) t'),
+ * a training timestep: on a sigma list it is refused (SDXL_ERR_INVALID, "sigmas" in sdxl_last_error).
+ * The start latent of sampling and inpainting stays the unit-normal tensor it is on a timestep list (noise0, or the SDXL_DRAW_INITIAL draw):
+ * it is NOT scaled by sqrt(1 - a_0) or by sigma_0.  A list that starts at the table's sigma_max (14.6 for SDXL, sqrt(1 - a) = 0.998) is the
+ * usual case; k-diffusion's x = noise * sigma_max is this tensor in its variance-exploding variables.
+ * sdxl_diffuser_set_sigmas: the list of every following trajectory call of the handle, whose n_steps must equal n and whose step_start is 0.
+ * sigma_end in [0, sigmas[n-1]) is the level behind the last entry, 0 the complete trajectory.  While a sigma list is set it is the one list
+ * in force (sdxl_diffuser_get_timesteps reports none); n == 0 or NULL drops it and the handle is back on the timestep list or rule it had
+ * before; sdxl_diffuser_set_timesteps* drops it too.  SDXL_ERR_INVALID ("sigmas" in sdxl_last_error), the handle keeping what it had: n
+ * outside 1..n_train_steps, a value that is not finite and > 0, values not strictly decreasing, sigma_end outside its range, unknown flags.
+ * sdxl_refine_latent* on a handle with a sigma list is refused: its re-noise level is tied to step_start; the message names sdxl_continue_latent.
+ * sdxl_diffuser_get_sigmas returns the count written to out (0: no sigma list; sigma_end_out / flags_out, optional, are then left alone). */
+enum { SDXL_SIGMAS_ROUND_T = 1 };
+int sdxl_diffuser_set_sigmas(sdxl_diffuser* d, const double* sigmas, int n, double sigma_end, int flags);
+int sdxl_diffuser_get_sigmas(sdxl_diffuser* d, double* out, int capacity, double* sigma_end_out, int* flags_out);
+/* sdxl_diffuser_set_timesteps with an end level: the last iteration lands on ap = alphas[t_end], -1 <= t_end < timesteps[n-1]; -1 gives ap = 1,
+ * and sdxl_diffuser_set_timesteps is this entry with -1.  A t_end outside its range: SDXL_ERR_INVALID ("timesteps"), the handle keeps what it
+ * had.  sdxl_diffuser_get_timesteps_end: the handle's t_end, -1 without a list. */
+int sdxl_diffuser_set_timesteps_end(sdxl_diffuser* d, const int32_t* timesteps, int n, int t_end);
+int sdxl_diffuser_get_timesteps_end(sdxl_diffuser* d, int* t_end_out);
+/* host logic only: the published sigma spacings, f64, i = 0 .. count-1.  Returns the count written (the terminal 0 is not part of a list), or
+ * SDXL_ERR_INVALID with out untouched.  sigma_min / sigma_max <= 0 take the table's own ends sqrt((1 - a) / a) at timestep 0 and n_train_steps - 1
+ * (0.02917 and 14.6146 on SDXL's table).
+ *   SDXL_SIGMAS_KARRAS        (smax^(1/rho) + i / (n-1) (smin^(1/rho) - smax^(1/rho)))^rho  (Karras et al. 2022, eq. 5; rho = 7); count n_steps
+ *   SDXL_SIGMAS_EXPONENTIAL   exp(ln smax + i / (n-1) (ln smin - ln smax)); count n_steps
+ *   SDXL_SIGMAS_OF_TIMESTEPS  the sigma of every entry of SDXL_SCHEDULE_REFERENCE's list; count sdxl_step_count(n_steps, 0, n_train_steps);
+ *                             sigma_min, sigma_max and rho are not read
+ * n_steps == 1 gives smax.  Refused: NULL, a table of fewer than two entries or with a value outside [0, 1), n_steps outside 1..n_train_steps,
+ * not 0 < smin < smax, rho not finite and > 0, an unknown kind, a sigma that is not finite (a == 0 in the table), capacity < count. */
+enum { SDXL_SIGMAS_KARRAS = 0, SDXL_SIGMAS_EXPONENTIAL = 1, SDXL_SIGMAS_OF_TIMESTEPS = 2 };
+int sdxl_sigma_schedule(int kind, int n_steps, const float* alphas_cumprod_host, int n_train_steps, double sigma_min, double sigma_max,
+                        double rho, double* out, int capacity);
+/* host logic only: the mapping above as an entry of its own; flags: 0 or SDXL_SIGMAS_ROUND_T.  A sigma that is not finite and > 0, unknown
+ * flags, NULL, a table as above: SDXL_ERR_INVALID, t_out untouched. */
+int sdxl_sigma_to_timestep(const float* alphas_cumprod_host, int n_train_steps, double sigma, int flags, double* t_out);
+/* Continuing a trajectory: the SDXL base -> refiner handoff ("ensemble of expert denoisers") and any other split.  A handle whose list ends on
+ * a level (sigma_end > 0, t_end >= 0) returns the latent AT that level; sdxl_continue_latent runs the handle's list -- sigma or timestep; a
+ * handle without one is refused, and n_steps must equal its length -- from a given latent [n,4,h/8,w/8]:
+ *   renoise == 0   the latent is used as it is: the handoff.  noise is ignored; seeds may be NULL if and only if the table has no c_z != 0
+ *                  (eta == 0 under DDIM, 2M and 3M: the explicit-noise rule above).
+ *   renoise != 0   the start is sqrt(a_0) latent + sqrt(1 - a_0) z with a_0 the list's first level and z the noise tensor or the
+ *                  SDXL_DRAW_INITIAL draw of seeds: exactly one of the two is given.
+ * It honours solver, prediction, guidance and eta (in [0, 1], seeds needed where != 0) like the six calls above; there is no inpainting
+ * through it.  A multistep solver starts first order here, as on iteration 0 of any trajectory: a 4 + 2 split of a 6-entry list equals the
+ * one 6-entry run bit for bit under DDIM at eta 0 and restarts the order under 2M and 3M.  Draw numbers restart too (SDXL_DRAW_SIGMA(i), i
+ * counted from the continued list's first entry).  Refusals: SDXL_ERR_INVALID before anything is launched, out untouched. */
+int sdxl_continue_latent(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond,
+                         double unconditional_guidance_scale, int n_steps, const float* noise, const uint64_t* seeds, double eta, int renoise,
+                         float* out_latent);
+/* SDXL_SOLVER_DPMPP_3M: k-diffusion's sample_dpmpp_3m_sde in alpha / sigma terms, the 2M update with one more history term,
+ *     x' = c_x x + c_0 x0 + c_1 x0p + c_2 x0pp + c_z z
+ * with eta in [0, 1] of the seeded calls (0: the ODE form).  lambda = ln(alpha / sigma), h = lambda' - lambda, h_eta = (1 + eta) h, h1 and h2
+ * the previous two h, r0 = h1 / h, r1 = h2 / h:
+ *     A = -expm1(-h_eta)     phi2 = expm1(-h_eta) / h_eta + 1     phi3 = phi2 / h_eta - 1/2
+ *     c_x = (sigma' / sigma) exp(-eta h)     c_z = sigma' sqrt(-expm1(-2 eta h))
+ *     third order (two histories):  P = phi2 (1 + r0 / (r0 + r1)) - phi3 / (r0 + r1),   Q = (phi3 - phi2 r0) / (r0 + r1)
+ *         c_0 = alpha' (A + P / r0)     c_1 = alpha' (-P / r0 + Q / r1)     c_2 = -alpha' Q / r1
+ *     second order (one history):   c_0 = alpha' (A + phi2 / r0)     c_1 = -alpha' phi2 / r0     c_2 = 0
+ *     first order (iteration 0):    c_0 = alpha' A,  c_1 = c_2 = 0
+ *     ap == 1:  (0, 1, 0, 0, 0)
+ * The order starts at one wherever a trajectory starts (sdxl_continue_latent included) and, under SDXL_PREDICTION_V, behind a row with a == 0
+ * (h = +inf), which is 2M's limit row.  In the per-step kernel: acc = c_2 x0pp; acc = fma(x0p, c_1, acc); acc = fma(x0, c_0, acc);
+ * x = fma(x, c_x, acc); x = fma(z, c_z, x) where c_z != 0; a history is read only where its coefficient != 0.
+ * sdxl_solver_rows: host logic only, (c_x, c_0, c_1, c_2, c_z) as f64 per iteration, out[5*i ..], for any solver on any schedule.  For the
+ * solvers above columns 0, 1, 2 and 4 are the numbers of sdxl_solver_coefficients_ts and column 3 is 0.  The four-column entries and
+ * sdxl_sampler_step_replay* refuse SDXL_SOLVER_DPMPP_3M; the message names sdxl_solver_rows / sdxl_sampler_step_replay_levels.
+ * sdxl_schedule_desc: a schedule as plain data, exactly one of timesteps and sigmas non-NULL, n entries; t_end as in
+ * sdxl_diffuser_set_timesteps_end (read with timesteps), sigma_end and flags as in sdxl_diffuser_set_sigmas (read with sigmas).
+ * SDXL_ERR_INVALID, out untouched: what the list setters and sdxl_solver_coefficients_ts refuse, TCD on sigmas, capacity_rows < n. */
+typedef struct {
+  const float* alphas_cumprod_host; int32_t n_train_steps;
+  const int32_t* timesteps; const double* sigmas; int32_t n;
+  int32_t t_end; double sigma_end; int32_t flags;
+} sdxl_schedule_desc;
+int sdxl_solver_rows(const sdxl_schedule_desc* schedule, int solver, int prediction, double eta, double* out, int capacity_rows);
 /* ---- guidance: how the two UNet branches of an iteration become the noise prediction e, a per-handle option all six trajectory
  * calls above honour, with both solvers, explicit and seeded noise, and inpainting.  The default is the reference's line (:539-540),
  * e = eu + (ec - eu) s with the call's scalar s on every iteration, and a handle with default options runs exactly what it ran before
@@ -436,6 +523,14 @@ int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_r
  * hist_out stays untouched under SDXL_SOLVER_LCM and SDXL_SOLVER_TCD: they keep no history. */
 int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args, int prediction, const int32_t* timesteps,
                                 int n);
+/* the same replay on any schedule and with any solver: iterations = schedule->n; the struct's alphas_cumprod_host, n_train_steps, n_steps and
+ * step_start are ignored (the schedule carries the table).  timesteps_out holds (float)t of every entry, fractional on a sigma list, and 0
+ * behind the last.  hist_out / hist2_out [n,4,h,w], both optional: the x0 histories after the last update -- hist_out the last x0 under
+ * SDXL_SOLVER_DPMPP_2M and _3M; hist2_out, under _3M and with at least two iterations, the x0p of the last update that read one (the x0 in
+ * front of hist_out's unless the last row is the ap == 1 row or restarts the order).  They stay untouched where the solver keeps none.
+ * An integer list with t_end = -1 gives the bits of sdxl_sampler_step_replay_ts.  Refuses what sdxl_solver_rows and that entry refuse. */
+int sdxl_sampler_step_replay_levels(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* args, int prediction,
+                                    const sdxl_schedule_desc* schedule, float* hist2_out);
 /* per-iteration GPU milliseconds of the last trajectory (enable first); returns the number written */
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled);
 int sdxl_diffuser_step_times(sdxl_diffuser* d, float* out_ms, int capacity);

@@ -18,4 +18,11 @@ _Static_assert(offsetof(sdxl_control, scale) == 0 && offsetof(sdxl_control, n_sc
 _Static_assert(SDXL_SOLVER_DDIM == 0 && SDXL_SOLVER_DPMPP_2M == 1 && SDXL_SOLVER_LCM == 3 && SDXL_SOLVER_TCD == 4, "solver codes");
 _Static_assert(SDXL_SCHEDULE_REFERENCE == 0 && SDXL_SCHEDULE_TRAILING == 1 && SDXL_SCHEDULE_LEADING == 2 && SDXL_SCHEDULE_LCM == 3, "timestep schedule kinds");
 _Static_assert(SDXL_MAX_CONTROLS == 4, "control nets per handle");
+_Static_assert(SDXL_SOLVER_DPMPP_3M == 5 && SDXL_SIGMAS_ROUND_T == 1 && SDXL_SIGMAS_KARRAS == 0 && SDXL_SIGMAS_EXPONENTIAL == 1 && SDXL_SIGMAS_OF_TIMESTEPS == 2,
+               "noise-level codes");
+_Static_assert(offsetof(sdxl_schedule_desc, alphas_cumprod_host) == 0 && offsetof(sdxl_schedule_desc, n_train_steps) == sizeof(void*) &&
+               offsetof(sdxl_schedule_desc, timesteps) == 2 * sizeof(void*) && offsetof(sdxl_schedule_desc, sigmas) == 3 * sizeof(void*) &&
+               offsetof(sdxl_schedule_desc, n) == 4 * sizeof(void*) && offsetof(sdxl_schedule_desc, t_end) == 4 * sizeof(void*) + 4 &&
+               offsetof(sdxl_schedule_desc, sigma_end) == 4 * sizeof(void*) + 8 && offsetof(sdxl_schedule_desc, flags) == 4 * sizeof(void*) + 16 &&
+               sizeof(sdxl_schedule_desc) == 4 * sizeof(void*) + 24, "sdxl_schedule_desc layout (LP64)");
 int sdxl_mi355_abi_check(void) { return SDXL_OK; }

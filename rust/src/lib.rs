@@ -396,6 +396,34 @@ pub enum Solver {
     Lcm = ffi::SDXL_SOLVER_LCM as isize,
     /// TCD gamma-sampling (Zheng et al. 2024; what Hyper-SD ships with): `eta` of `set_seed` is read as gamma
     Tcd = ffi::SDXL_SOLVER_TCD as isize,
+    /// DPM++ 3M SDE (k-diffusion's `sample_dpmpp_3m_sde`; `eta = 0` its ODE form): the 2M update with a second history term, the usual
+    /// companion of the Karras and exponential sigma spacings at 20-40 steps
+    Dpmpp3M = ffi::SDXL_SOLVER_DPMPP_3M as isize,
+}
+/// a published sigma spacing (`SDXL_SIGMAS_*`) for `sigma_schedule`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum SigmaSchedule {
+    /// Karras et al. 2022, eq. 5 with exponent `rho` (7)
+    Karras = ffi::SDXL_SIGMAS_KARRAS as isize,
+    /// log-linear between sigma_max and sigma_min
+    Exponential = ffi::SDXL_SIGMAS_EXPONENTIAL as isize,
+    /// the sigmas of the reference rule's timestep list
+    OfTimesteps = ffi::SDXL_SIGMAS_OF_TIMESTEPS as isize,
+}
+/// `sdxl_sigma_schedule` (host logic, no device): the list of `kind` for `Diffuser::set_sigmas`; `sigma_min` / `sigma_max` <= 0 take the ends of
+/// the `alphas_cumprod` table.  What the engine refuses is an `Err` with its message.
+pub fn sigma_schedule(kind: SigmaSchedule, n_steps: usize, alphas_cumprod: &[f32], sigma_min: f64, sigma_max: f64, rho: f64)
+                      -> Result<Vec<f64>, Box<dyn std::error::Error>> {
+    let mut out = vec![-1f64; alphas_cumprod.len().max(1)];      // a refusal leaves `out` untouched: SDXL_ERR_INVALID (1) is also a valid count
+    let n = unsafe {
+        ffi::sdxl_sigma_schedule(kind as c_int, n_steps as c_int, alphas_cumprod.as_ptr(), alphas_cumprod.len() as c_int, sigma_min, sigma_max, rho,
+                                 out.as_mut_ptr(), out.len() as c_int)
+    };
+    if n < 1 || out[0] < 0.0 {
+        return Err(last_error().into());
+    }
+    out.truncate(n as usize);
+    Ok(out)
 }
 /// a published timestep spacing (`SDXL_SCHEDULE_*`) for `timestep_schedule`
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -707,6 +735,7 @@ impl<B: BurnBackend> Diffuser<B> {
             x if x == Solver::Dpmpp2M as c_int => Solver::Dpmpp2M,
             x if x == Solver::Lcm as c_int => Solver::Lcm,
             x if x == Solver::Tcd as c_int => Solver::Tcd,
+            x if x == Solver::Dpmpp3M as c_int => Solver::Dpmpp3M,
             _ => Solver::Ddim,
         }
     }
@@ -719,6 +748,32 @@ impl<B: BurnBackend> Diffuser<B> {
             _ => (ptr::null(), 0),
         };
         try_check(unsafe { ffi::sdxl_diffuser_set_timesteps(self.raw, p, n) })
+    }
+    /// `set_timesteps` with an end level: the last iteration lands on `alphas[t_end]` instead of the data (`sdxl_diffuser_set_timesteps_end`;
+    /// `t_end` below the last entry, -1: the complete trajectory).  The latent it returns is the one `continue_latent` of another handle takes.
+    pub fn set_timesteps_end(&self, timesteps: &[i32], t_end: i32) -> Result<(), Box<dyn std::error::Error>> {
+        try_check(unsafe { ffi::sdxl_diffuser_set_timesteps_end(self.raw, timesteps.as_ptr(), timesteps.len() as c_int, t_end as c_int) })
+    }
+    /// every following trajectory of this handle runs one UNet evaluation per entry of `sigmas`, a strictly decreasing list of noise levels
+    /// sigma = sqrt((1 - a) / a) (`sigma_schedule`), and ends on `sigma_end` (0: the complete trajectory); `round_t` feeds the UNet integer
+    /// timesteps (`SDXL_SIGMAS_ROUND_T`).  `None` drops the list: the handle is back on its timestep list or rule (`sdxl_diffuser_set_sigmas`).
+    pub fn set_sigmas(&self, sigmas: Option<&[f64]>, sigma_end: f64, round_t: bool) -> Result<(), Box<dyn std::error::Error>> {
+        let (p, n) = match sigmas {
+            Some(s) if !s.is_empty() => (s.as_ptr(), s.len() as c_int),
+            _ => (ptr::null(), 0),
+        };
+        try_check(unsafe { ffi::sdxl_diffuser_set_sigmas(self.raw, p, n, sigma_end, if round_t { ffi::SDXL_SIGMAS_ROUND_T as c_int } else { 0 }) })
+    }
+    /// the handle's sigma list with its end level, `None` without one (`sdxl_diffuser_get_sigmas`)
+    pub fn sigmas(&self) -> Option<(Vec<f64>, f64)> {
+        let mut out = vec![-1f64; 4096];
+        let mut end = 0f64;
+        let n = unsafe { ffi::sdxl_diffuser_get_sigmas(self.raw, out.as_mut_ptr(), out.len() as c_int, &mut end, ptr::null_mut()) };
+        if n < 1 || out[0] < 0.0 {
+            return None;
+        }
+        out.truncate(n as usize);
+        Some((out, end))
     }
     /// the handle's list, `None` for the reference's rule (`sdxl_diffuser_get_timesteps`)
     pub fn timesteps(&self) -> Option<Vec<i32>> {
@@ -806,6 +861,25 @@ impl<B: BurnBackend> Diffuser<B> {
                                            n_steps as c_int, seeds.as_ptr(), eta, out.f32_mut())
         });
         bridge::download(&out, dims, &device)
+    }
+    /// `sdxl_continue_latent` with `renoise = 0`: the handle's list (`set_sigmas`, `set_timesteps`) from `latent` as it is -- the SDXL
+    /// base -> refiner handoff, the latent being what a handle whose list ends on a level returned.  `seeds` (one per batch entry) feed the
+    /// `eta` noise; `None` needs `eta == 0`.  What the engine refuses is an `Err` with its message.
+    pub fn continue_latent(&self, latent: Tensor<B, 4>, conditioning: Conditioning<B>, unconditional_guidance_scale: f64, n_steps: usize,
+                           seeds: Option<&[u64]>, eta: f64) -> Result<Tensor<B, 4>, Box<dyn std::error::Error>> {
+        let device = conditioning.context_full.device();
+        let dims = latent.dims();
+        if let Some(s) = seeds {
+            assert_eq!(s.len(), dims[0], "one seed per batch entry");
+        }
+        let dc = to_c_conditioning(&conditioning);
+        let d_lat = bridge::upload(latent);
+        let out = DeviceBuf::new(dims.iter().product::<usize>() * 4);
+        try_check(unsafe {
+            ffi::sdxl_continue_latent(self.raw, ptr::null_mut(), d_lat.f32_ptr(), &dc.c, unconditional_guidance_scale, n_steps as c_int, ptr::null(),
+                                      seeds.map_or(ptr::null(), |s| s.as_ptr()), eta, 0, out.f32_mut())
+        })?;
+        Ok(bridge::download(&out, dims, &device))
     }
     /// `gen_noise` (`:378-388`)
     fn gen_noise(conditioning: &Conditioning<B>) -> Tensor<B, 4> {

@@ -130,6 +130,8 @@ ABI_SYMBOLS = [
     "sdxl_sampler_step_replay_pred",
     "sdxl_diffuser_set_timesteps", "sdxl_diffuser_get_timesteps", "sdxl_timestep_schedule", "sdxl_solver_coefficients_ts",
     "sdxl_sampler_step_replay_ts",
+    "sdxl_diffuser_set_sigmas", "sdxl_diffuser_get_sigmas", "sdxl_diffuser_set_timesteps_end", "sdxl_diffuser_get_timesteps_end", "sdxl_sigma_schedule",
+    "sdxl_sigma_to_timestep", "sdxl_continue_latent", "sdxl_solver_rows", "sdxl_sampler_step_replay_levels",
     "sdxl_vae_create", "sdxl_vae_create_synthetic", "sdxl_vae_destroy", "sdxl_vae_decode_latent",
     "sdxl_latent_to_image", "sdxl_vae_encode_image", "sdxl_image_to_latent",
     "sdxl_unet_weight_arena", "sdxl_vae_weight_arena", "sdxl_diffuser_create_empty", "sdxl_vae_create_empty",
@@ -205,6 +207,18 @@ def lib() -> ctypes.CDLL:
             l.sdxl_solver_coefficients_ts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
             l.sdxl_sampler_step_replay_ts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(l, "sdxl_solver_rows"):
+            l.sdxl_diffuser_set_sigmas.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
+            l.sdxl_diffuser_get_sigmas.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+            l.sdxl_diffuser_set_timesteps_end.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+            l.sdxl_diffuser_get_timesteps_end.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+            l.sdxl_sigma_schedule.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_sigma_to_timestep.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
+            l.sdxl_continue_latent.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
+            l.sdxl_solver_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int]
+            l.sdxl_sampler_step_replay_levels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         if hasattr(l, "sdxl_unet_forward_residuals"):
             l.sdxl_unet_skip_shape.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
             l.sdxl_unet_forward_residuals.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
@@ -982,7 +996,8 @@ SOLVER_DDIM = 0         # SDXL_SOLVER_DDIM: the reference's loop (default)
 SOLVER_DPMPP_2M = 1     # SDXL_SOLVER_DPMPP_2M: DPM-Solver++(2M), with eta > 0 its SDE form
 SOLVER_LCM = 3          # SDXL_SOLVER_LCM: LCM multistep consistency sampling (takes no eta; needs the seeded calls beyond one iteration)
 SOLVER_TCD = 4          # SDXL_SOLVER_TCD: TCD gamma-sampling, the seeded calls' eta read as gamma
-_SOLVER_NAMES = {"ddim": SOLVER_DDIM, "dpmpp_2m": SOLVER_DPMPP_2M, "lcm": SOLVER_LCM, "tcd": SOLVER_TCD}
+SOLVER_DPMPP_3M = 5     # SDXL_SOLVER_DPMPP_3M: DPM++ 3M SDE (eta = 0: its ODE form), two x0 histories
+_SOLVER_NAMES = {"ddim": SOLVER_DDIM, "dpmpp_2m": SOLVER_DPMPP_2M, "lcm": SOLVER_LCM, "tcd": SOLVER_TCD, "dpmpp_3m": SOLVER_DPMPP_3M}
 
 SCHEDULE_REFERENCE, SCHEDULE_TRAILING, SCHEDULE_LEADING, SCHEDULE_LCM = 0, 1, 2, 3      # SDXL_SCHEDULE_*
 _SCHEDULE_KINDS = {"reference": SCHEDULE_REFERENCE, "trailing": SCHEDULE_TRAILING, "leading": SCHEDULE_LEADING, "lcm": SCHEDULE_LCM}
@@ -1066,6 +1081,71 @@ def solver_coefficients(alphas, n_steps: int, step_start: int = 0, solver="dpmpp
         _check_invalid(lib().sdxl_solver_coefficients_pred(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), n_steps, step_start,
                                                            _solver(solver), _prediction(prediction), float(eta),
                                                            out.ctypes.data_as(ctypes.c_void_p), iters))
+    return out
+
+
+SIGMAS_ROUND_T = 1      # SDXL_SIGMAS_ROUND_T: the timestep of a sigma rounded to the nearest integer (diffusers' use_karras_sigmas convention)
+SIGMAS_KARRAS, SIGMAS_EXPONENTIAL, SIGMAS_OF_TIMESTEPS = 0, 1, 2      # SDXL_SIGMAS_*
+_SIGMA_KINDS = {"karras": SIGMAS_KARRAS, "exponential": SIGMAS_EXPONENTIAL, "of_timesteps": SIGMAS_OF_TIMESTEPS}
+
+
+def _sigmas(sigmas):
+    """float64 array of a list (None stays None)"""
+    if sigmas is None:
+        return None
+    return np.ascontiguousarray(np.asarray(list(sigmas), dtype=np.float64).reshape(-1))
+
+
+def sigma_schedule(kind, n_steps: int, alphas=None, sigma_min: float = 0.0, sigma_max: float = 0.0, rho: float = 7.0) -> List[float]:
+    """sdxl_sigma_schedule (host logic: no GPU needed): a published sigma spacing as a list for Diffuser.set_sigmas.  kind "karras",
+    "exponential" or "of_timesteps" (the sigmas of the reference rule's list), or the SIGMAS_* value; sigma_min / sigma_max <= 0 take the
+    ends of the table (alphas, default the SDXL table); what the engine refuses raises InvalidArgument"""
+    if isinstance(kind, str):
+        if kind not in _SIGMA_KINDS:
+            raise InvalidArgument(f"unknown sigma schedule kind {kind!r}: one of {sorted(_SIGMA_KINDS)}")
+        kind = _SIGMA_KINDS[kind]
+    a = np.ascontiguousarray(default_alphas_cumprod() if alphas is None else alphas, dtype=np.float32)
+    cap = max(int(a.shape[0]), 1)
+    out = np.full((cap,), -1.0, dtype=np.float64)      # a refusal leaves out untouched: that tells SDXL_ERR_INVALID (1) from a count of 1
+    n = lib().sdxl_sigma_schedule(int(kind), int(n_steps), a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), float(sigma_min), float(sigma_max),
+                                  float(rho), out.ctypes.data_as(ctypes.c_void_p), cap)
+    if n < 1 or out[0] < 0:
+        raise InvalidArgument(lib().sdxl_last_error().decode())
+    return [float(v) for v in out[:n]]
+
+
+def sigma_to_timestep(sigma: float, alphas=None, round_t: bool = False) -> float:
+    """sdxl_sigma_to_timestep (host logic: no GPU needed): k-diffusion's sigma_to_t in f64, the timestep a sigma list feeds the UNet"""
+    a = np.ascontiguousarray(default_alphas_cumprod() if alphas is None else alphas, dtype=np.float32)
+    t = ctypes.c_double(-1.0)
+    _check_invalid(lib().sdxl_sigma_to_timestep(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), float(sigma), SIGMAS_ROUND_T if round_t else 0,
+                                                ctypes.byref(t)))
+    return t.value
+
+
+class _ScheduleDescC(ctypes.Structure):
+    _fields_ = [("alphas_cumprod_host", ctypes.c_void_p), ("n_train_steps", ctypes.c_int32), ("timesteps", ctypes.c_void_p), ("sigmas", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("t_end", ctypes.c_int32), ("sigma_end", ctypes.c_double), ("flags", ctypes.c_int32)]
+
+
+def _schedule_desc(alphas, timesteps=None, sigmas=None, t_end: int = -1, sigma_end: float = 0.0, flags: int = 0):
+    """(sdxl_schedule_desc, the arrays it points into, the number of entries)"""
+    a = np.ascontiguousarray(alphas, dtype=np.float32)
+    ts, sg = _timesteps(timesteps), _sigmas(sigmas)
+    n = int(ts.size) if ts is not None else int(sg.size) if sg is not None else 0
+    desc = _ScheduleDescC(a.ctypes.data_as(ctypes.c_void_p), int(a.shape[0]), ts.ctypes.data_as(ctypes.c_void_p) if ts is not None else None,
+                          sg.ctypes.data_as(ctypes.c_void_p) if sg is not None else None, n, int(t_end), float(sigma_end), int(flags))
+    return desc, (a, ts, sg), n
+
+
+def solver_rows(alphas, solver="dpmpp_3m", eta: float = 0.0, prediction="epsilon", timesteps=None, sigmas=None, t_end: int = -1,
+                sigma_end: float = 0.0, flags: int = 0) -> np.ndarray:
+    """sdxl_solver_rows (host logic: no GPU needed): float64 [n, 5] rows (c_x, c_0, c_1, c_2, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_2 x0pp
+    + c_z z for any solver on a timestep list (with t_end) or a sigma list (with sigma_end and flags): exactly one of the two lists"""
+    desc, keep, n = _schedule_desc(alphas, timesteps, sigmas, t_end, sigma_end, flags)
+    out = np.zeros((n, 5), dtype=np.float64)
+    _check_invalid(lib().sdxl_solver_rows(ctypes.byref(desc), _solver(solver), _prediction(prediction), float(eta),
+                                          out.ctypes.data_as(ctypes.c_void_p), n))
     return out
 
 
@@ -1208,6 +1288,39 @@ def sampler_step_replay(ctx: Context, alphas, n_steps: int, step_start: int, eps
     return out
 
 
+def sampler_step_replay_levels(ctx: Context, alphas, eps, latent0, solver="dpmpp_3m", eta: float = 0.0, cfg_scale: float = 7.5,
+                               guidance: Optional[Guidance] = None, single: bool = False, input_f16: bool = False, reference=None, mask=None,
+                               step_noise=None, seeds=None, prediction="epsilon", timesteps=None, sigmas=None, t_end: int = -1,
+                               sigma_end: float = 0.0, flags: int = 0, hist_fill: Optional[float] = None):
+    """sdxl_sampler_step_replay_levels: sampler_step_replay on any schedule (a timestep list with t_end or a sigma list with sigma_end and
+    flags) and any solver.  Returns float32 CUDA tensors (latents [n_entries + 1, n, 4, h, w], hist, hist2 [n, 4, h, w], unet_in [B, h*w, 4],
+    timesteps [n_entries + 1]); hist and hist2 start from hist_fill (default 0) and keep it where the solver writes none."""
+    torch = _torch()
+    desc, keep_desc, iters = _schedule_desc(alphas, timesteps, sigmas, t_end, sigma_end, flags)
+    eps, pe = _dev(eps)
+    latent0, pl = _dev(latent0)
+    n, h, w = int(latent0.shape[0]), int(latent0.shape[2]), int(latent0.shape[3])
+    B = n if single or (guidance is not None and guidance.mode == GUIDANCE_OFF) else 2 * n
+    if tuple(eps.shape) != (iters, B, h * w, 4) or latent0.shape[1] != 4:
+        raise InvalidArgument(f"eps must be [{iters}, {B}, {h * w}, 4] and latent0 [n, 4, h, w]")
+    for t, lead in ((reference, ()), (mask, ()), (step_noise, (iters,))):
+        if t is not None and tuple(t.shape) != lead + (n, 4, h, w):
+            raise InvalidArgument(f"reference / mask must be [{n}, 4, {h}, {w}], step_noise [{iters}, {n}, 4, {h}, {w}]")
+    keep = [_dev(t, torch.uint8 if t is mask else None) if t is not None else (None, None) for t in (reference, mask, step_noise)]
+    fill = 0.0 if hist_fill is None else hist_fill
+    latents, hist, hist2 = torch.zeros((iters + 1, n, 4, h, w), device="cuda"), torch.full((n, 4, h, w), fill, device="cuda"), torch.full((n, 4, h, w), fill, device="cuda")
+    unet_in, ts_out = torch.zeros((B, h * w, 4), device="cuda"), torch.zeros((iters + 1,), device="cuda")
+    sd = _seeds(seeds, n)
+    a = keep_desc[0]
+    args = _StepReplayArgsC(a.ctypes.data_as(_c_p), int(a.shape[0]), 0, 0, _solver(solver), float(eta), float(cfg_scale),
+                            ctypes.pointer(guidance) if guidance is not None else None, int(single), n, h, w, int(input_f16),
+                            pe, pl, keep[0][1], keep[1][1], keep[2][1], ctypes.cast(sd, _c_p) if sd is not None else None,
+                            *[ctypes.c_void_p(t.data_ptr()) for t in (latents, hist, unet_in, ts_out)])
+    _check_invalid(lib().sdxl_sampler_step_replay_levels(ctx.h, _stream(), ctypes.byref(args), _prediction(prediction), ctypes.byref(desc),
+                                                         ctypes.c_void_p(hist2.data_ptr())))
+    return latents, hist, hist2, unet_in, ts_out
+
+
 def _seeds(seeds, n: int):
     """host uint64 array [n] (None stays NULL: the engine reports it)"""
     if seeds is None:
@@ -1337,11 +1450,53 @@ class Diffuser:
                                        step_start, n_steps, pn, ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def continue_latent(self, latent, conditioning, unconditional_guidance_scale, n_steps, noise=None, *, seeds=None, eta: float = 0.0,
+                        renoise: bool = False):
+        """sdxl_continue_latent: the handle's list (set_sigmas / set_timesteps) from a given latent.  renoise False: the latent as it is -- the
+        base -> refiner handoff --; True: re-noised to the list's first level with `noise` or the DRAW_INITIAL draw of seeds (exactly one).
+        seeds also feed the eta noise.  What the engine refuses raises InvalidArgument."""
+        torch = _torch()
+        c, keep = conditioning.to_c()
+        latent, pl = _dev(latent)
+        pn = None
+        if noise is not None:
+            noise, pn = _dev(noise)
+        out = torch.empty_like(latent)
+        sd = _seeds(seeds, out.shape[0])
+        _check_invalid(lib().sdxl_continue_latent(self.h, _stream(), pl, ctypes.byref(c), ctypes.c_double(unconditional_guidance_scale), int(n_steps),
+                                                  pn, ctypes.cast(sd, ctypes.c_void_p) if sd is not None else None, ctypes.c_double(eta), int(renoise),
+                                                  ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def set_sigmas(self, sigmas=None, sigma_end: float = 0.0, round_t: bool = False):
+        """sdxl_diffuser_set_sigmas: a strictly decreasing list of noise levels sigma = sqrt((1 - a) / a) (sigma_schedule writes the Karras and
+        exponential spacings), one UNet evaluation each, with sigma_end behind the last entry (0: the complete trajectory); None or an empty
+        list drops it (the handle is back on its timestep list or rule).  A list the engine refuses raises InvalidArgument and the handle
+        keeps what it had."""
+        sg = _sigmas(sigmas)
+        if sg is None or sg.size == 0:
+            _check_invalid(lib().sdxl_diffuser_set_sigmas(self.h, None, 0, 0.0, 0))
+        else:
+            _check_invalid(lib().sdxl_diffuser_set_sigmas(self.h, sg.ctypes.data_as(ctypes.c_void_p), int(sg.size), float(sigma_end),
+                                                          SIGMAS_ROUND_T if round_t else 0))
+
+    @property
+    def sigmas(self) -> Optional[Tuple[List[float], float, bool]]:
+        """(the handle's sigma list, sigma_end, round_t) (sdxl_diffuser_get_sigmas), None without one"""
+        out = np.full((4096,), -1.0, dtype=np.float64)
+        end, flags = ctypes.c_double(0.0), ctypes.c_int(0)
+        n = lib().sdxl_diffuser_get_sigmas(self.h, out.ctypes.data_as(ctypes.c_void_p), int(out.size), ctypes.byref(end), ctypes.byref(flags))
+        if n == 0:
+            return None
+        if out[0] < 0:
+            raise InvalidArgument(lib().sdxl_last_error().decode())
+        return [float(v) for v in out[:n]], end.value, bool(flags.value & SIGMAS_ROUND_T)
+
     def set_solver(self, solver):
-        """"ddim" (default), "dpmpp_2m", "lcm" or "tcd" (or the SOLVER_* value): the update every following trajectory of this handle runs"""
+        """"ddim" (default), "dpmpp_2m", "dpmpp_3m", "lcm" or "tcd" (or the SOLVER_* value): the update every following trajectory of this handle runs"""
         _check(lib().sdxl_diffuser_set_solver(self.h, _solver(solver)))
 
-    def set_timesteps(self, timesteps=None):
+    def set_timesteps(self, timesteps=None, t_end: int = -1):
         """sdxl_diffuser_set_timesteps: a strictly decreasing list of training timesteps, one UNet evaluation each, for every following
         trajectory of this handle (its n_steps must equal the list's length); None or an empty list: back to the reference's rule.  A list
         the engine refuses raises InvalidArgument and the handle keeps what it had."""
@@ -1349,6 +1504,9 @@ class Diffuser:
         if ts is None or ts.size == 0:
             _check_invalid(lib().sdxl_diffuser_set_timesteps(self.h, None, 0))
         else:
+            if t_end != -1:      # sdxl_diffuser_set_timesteps_end: the last iteration lands on alphas[t_end], not on the data
+                _check_invalid(lib().sdxl_diffuser_set_timesteps_end(self.h, ts.ctypes.data_as(ctypes.c_void_p), int(ts.size), int(t_end)))
+                return
             _check_invalid(lib().sdxl_diffuser_set_timesteps(self.h, ts.ctypes.data_as(ctypes.c_void_p), int(ts.size)))
 
     @property
@@ -1361,6 +1519,13 @@ class Diffuser:
         if out[0] < 0:      # a refusal leaves out untouched (SDXL_ERR_INVALID and a count of 1 are the same number)
             raise InvalidArgument(lib().sdxl_last_error().decode())
         return [int(v) for v in out[:n]]
+
+    @property
+    def timesteps_end(self) -> int:
+        """t_end of the handle's timestep list (sdxl_diffuser_get_timesteps_end), -1: the complete trajectory"""
+        v = ctypes.c_int(-1)
+        _check(lib().sdxl_diffuser_get_timesteps_end(self.h, ctypes.byref(v)))
+        return v.value
 
     @property
     def solver(self) -> str:

@@ -678,14 +678,29 @@ int sdxl_refine_latent_seeded(sdxl_diffuser* d, void* stream, const float* laten
   d->d->refine_latent_seeded(latent, to_cond(cond), cfg, step_start, n_steps, seeds, eta, out, pick(d->ctx, stream));
   API_END
 }
+int sdxl_continue_latent(sdxl_diffuser* d, void* stream, const float* latent, const sdxl_conditioning* cond, double cfg, int n_steps,
+                         const float* noise, const uint64_t* seeds, double eta, int renoise, float* out) {
+  if (!(eta >= 0.0 && eta <= 1.0)) return fail(SDXL_ERR_INVALID, "eta must be a finite value in [0, 1]");
+  if (const char* m = guidance_call_error(d, cond)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  if (!d || !latent || !out) throw InvalidArgumentError("null argument");
+  use(d->ctx);
+  d->d->continue_latent(latent, to_cond(cond), cfg, n_steps, noise, seeds, eta, renoise != 0, out, pick(d->ctx, stream));
+  API_END
+}
 int sdxl_step_count(int n_steps, int step_start, int n_train) {
   try { return (int)Diffuser::step_schedule(n_steps, step_start, n_train).size(); }
   catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 static bool known_solver(int solver) {
-  return solver == SDXL_SOLVER_DDIM || solver == SDXL_SOLVER_DPMPP_2M || solver == SDXL_SOLVER_LCM || solver == SDXL_SOLVER_TCD;
+  return solver == SDXL_SOLVER_DDIM || solver == SDXL_SOLVER_DPMPP_2M || solver == SDXL_SOLVER_LCM || solver == SDXL_SOLVER_TCD ||
+         solver == SDXL_SOLVER_DPMPP_3M;
 }
-static const char* const kUnknownSolver = "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M, SDXL_SOLVER_LCM, SDXL_SOLVER_TCD)";
+static const char* const kUnknownSolver =
+    "unknown solver (SDXL_SOLVER_DDIM, SDXL_SOLVER_DPMPP_2M, SDXL_SOLVER_DPMPP_3M, SDXL_SOLVER_LCM, SDXL_SOLVER_TCD)";
+// the entries with four-column rows and one history output cannot carry the 3M solver's c_2 and second history
+static const char* const kSolver3MEntry =
+    "solver DPMPP_3M has five-column rows and two histories: use sdxl_solver_rows / sdxl_sampler_step_replay_levels";
 // solver: a per-handle option; an unknown value is an argument error and leaves the handle as it was
 int sdxl_diffuser_set_solver(sdxl_diffuser* d, int solver) {
   if (!d) return fail(SDXL_ERR_INVALID, "null argument");
@@ -700,13 +715,86 @@ int sdxl_diffuser_get_solver(sdxl_diffuser* d, int* solver_out) {
   return SDXL_OK;
 }
 // timestep list: a per-handle option; a list the check refuses is an argument error and leaves the handle as it was
-int sdxl_diffuser_set_timesteps(sdxl_diffuser* d, const int32_t* timesteps, int n) {
+int sdxl_diffuser_set_timesteps(sdxl_diffuser* d, const int32_t* timesteps, int n) { return sdxl_diffuser_set_timesteps_end(d, timesteps, n, -1); }
+int sdxl_diffuser_set_timesteps_end(sdxl_diffuser* d, const int32_t* timesteps, int n, int t_end) {
   if (!d) return fail(SDXL_ERR_INVALID, "null argument");
   static_assert(sizeof(int32_t) == sizeof(int), "lists travel as int");
   API_BEGIN
   if (timesteps && n < 0) throw InvalidArgumentError("timesteps: the list needs 1..n_train_steps entries");
-  d->d->set_timesteps((const int*)timesteps, n);
+  d->d->set_timesteps((const int*)timesteps, n, t_end);
   API_END
+}
+int sdxl_diffuser_get_timesteps_end(sdxl_diffuser* d, int* t_end_out) {
+  if (!d || !t_end_out) return fail(SDXL_ERR_INVALID, "null argument");
+  *t_end_out = d->d->timesteps().empty() ? -1 : d->d->timesteps_end();
+  return SDXL_OK;
+}
+// sigma list: a per-handle option like the timestep list; a list the check refuses is an argument error and leaves the handle as it was
+int sdxl_diffuser_set_sigmas(sdxl_diffuser* d, const double* sigmas, int n, double sigma_end, int flags) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  API_BEGIN
+  if (sigmas && n < 0) throw InvalidArgumentError("sigmas: the list needs 1..n_train_steps entries");
+  d->d->set_sigmas(sigmas, n, sigma_end, flags);
+  API_END
+}
+int sdxl_diffuser_get_sigmas(sdxl_diffuser* d, double* out, int capacity, double* sigma_end_out, int* flags_out) {
+  if (!d) return fail(SDXL_ERR_INVALID, "null argument");
+  const std::vector<double>& sg = d->d->sigmas();
+  if (sg.empty()) return 0;
+  if (!out || capacity < (int)sg.size()) return fail(SDXL_ERR_INVALID, "sigmas: capacity is smaller than the handle's list");
+  std::copy(sg.begin(), sg.end(), out);
+  if (sigma_end_out) *sigma_end_out = d->d->sigma_end();
+  if (flags_out) *flags_out = d->d->sigma_flags();
+  return (int)sg.size();
+}
+static const char* table_error(const float* alphas_cumprod_host, int n_train_steps) {      // a table a sigma entry can read
+  if (!alphas_cumprod_host) return "null argument";
+  if (n_train_steps < 2) return "sigmas: the alphas_cumprod table needs at least two entries";
+  for (int i = 0; i < n_train_steps; ++i)
+    if (!(alphas_cumprod_host[i] >= 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
+  return nullptr;
+}
+int sdxl_sigma_to_timestep(const float* alphas_cumprod_host, int n_train_steps, double sigma, int flags, double* t_out) {
+  if (!t_out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = table_error(alphas_cumprod_host, n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  if (const char* m = Diffuser::sigmas_error(&sigma, 1, 0.0, flags, n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  API_BEGIN
+  const std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);
+  *t_out = Diffuser::sigma_to_t(alphas.data(), n_train_steps, sigma, flags);
+  API_END
+}
+// host logic only: the published sigma spacings
+int sdxl_sigma_schedule(int kind, int n_steps, const float* alphas_cumprod_host, int n_train_steps, double sigma_min, double sigma_max, double rho,
+                        double* out, int capacity) {
+  if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (const char* m = table_error(alphas_cumprod_host, n_train_steps)) return fail(SDXL_ERR_INVALID, m);
+  if (n_steps < 1 || n_steps > n_train_steps) return fail(SDXL_ERR_INVALID, "n_steps out of range (1..n_train_steps)");
+  const auto sigma_of = [&](int j) { const double a = (double)alphas_cumprod_host[j]; return std::sqrt((1.0 - a) / a); };
+  std::vector<double> sg;
+  if (kind == SDXL_SIGMAS_OF_TIMESTEPS) {
+    for (int t : Diffuser::step_schedule(n_steps, 0, n_train_steps)) sg.push_back(sigma_of(t));
+  } else if (kind == SDXL_SIGMAS_KARRAS || kind == SDXL_SIGMAS_EXPONENTIAL) {
+    const double lo = sigma_min > 0.0 ? sigma_min : sigma_of(0), hi = sigma_max > 0.0 ? sigma_max : sigma_of(n_train_steps - 1);
+    if (!(std::isfinite(lo) && std::isfinite(hi) && lo > 0.0 && lo < hi)) return fail(SDXL_ERR_INVALID, "sigmas: needs finite 0 < sigma_min < sigma_max");
+    if (kind == SDXL_SIGMAS_KARRAS && !(std::isfinite(rho) && rho > 0.0)) return fail(SDXL_ERR_INVALID, "sigmas: rho must be finite and > 0 (Karras et al. use 7)");
+    for (int i = 0; i < n_steps; ++i) {
+      const double ramp = n_steps == 1 ? 0.0 : (double)i / (double)(n_steps - 1);
+      if (kind == SDXL_SIGMAS_KARRAS) {
+        const double hi_r = std::pow(hi, 1.0 / rho), lo_r = std::pow(lo, 1.0 / rho);
+        sg.push_back(std::pow(hi_r + ramp * (lo_r - hi_r), rho));
+      } else {
+        const double lh = std::log(hi), ll = std::log(lo);
+        sg.push_back(std::exp(lh + ramp * (ll - lh)));
+      }
+    }
+  } else {
+    return fail(SDXL_ERR_INVALID, "sigmas: unknown kind (SDXL_SIGMAS_KARRAS, _EXPONENTIAL, _OF_TIMESTEPS)");
+  }
+  for (double v : sg)
+    if (!(std::isfinite(v) && v > 0.0)) return fail(SDXL_ERR_INVALID, "sigmas: the table gives a sigma that is not finite and > 0 (alphas_cumprod == 0 at a timestep)");
+  if (capacity < (int)sg.size()) return fail(SDXL_ERR_INVALID, "sigmas: capacity is smaller than the list");
+  std::copy(sg.begin(), sg.end(), out);
+  return (int)sg.size();
 }
 int sdxl_diffuser_get_timesteps(sdxl_diffuser* d, int32_t* out, int capacity) {
   if (!d) return fail(SDXL_ERR_INVALID, "null argument");
@@ -766,10 +854,11 @@ static const char* schedule_args_error(const float* alphas_cumprod_host, int n_t
   if (step_start < 0 || step_start >= n_train_steps) return "step_start out of range (0..n_train_steps-1)";
   return nullptr;
 }
-static const char* list_args_error(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver, double eta) {
+static const char* list_args_error(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver, double eta,
+                                   int t_end = -1) {
   if (const char* m = solver_args_error(alphas_cumprod_host, n_train_steps, solver, eta)) return m;
   if (n_train_steps < 1) return "n_train_steps out of range";
-  if (const char* m = Diffuser::timesteps_error((const int*)timesteps, n, n_train_steps)) return m;
+  if (const char* m = Diffuser::timesteps_end_error((const int*)timesteps, n, t_end, n_train_steps)) return m;
   if (solver == SDXL_SOLVER_LCM && eta != 0.0) return "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)";
   return nullptr;
 }
@@ -780,31 +869,74 @@ static const char* alphas_error(const float* alphas_cumprod_host, int n_train_st
 }
 // the table under a prediction type (a valid list): SDXL_PREDICTION_V admits 0 in it, and the schedule decides where it may stand;
 // under SDXL_PREDICTION_EPSILON a 0 at a sampled timestep gets the message that names the remedy, any other value outside (0, 1) the old one
-static const char* alphas_error_pred(const float* alphas_cumprod_host, int n_train_steps, const std::vector<int>& ts, int prediction) {
+// ts: a list Diffuser::timesteps_end_error accepts
+static const char* alphas_error_pred(const float* alphas_cumprod_host, int n_train_steps, const std::vector<int>& ts, int prediction, int t_end = -1) {
   if (prediction != SDXL_PREDICTION_EPSILON && prediction != SDXL_PREDICTION_V) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
   for (int i = 0; i < n_train_steps; ++i)
     if (!(alphas_cumprod_host[i] >= 0.f && alphas_cumprod_host[i] < 1.f)) return "alphas_cumprod outside (0, 1)";
   const std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);
-  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train_steps, ts, prediction)) return m;
+  const Schedule sc = Diffuser::schedule_of_timesteps(alphas.data(), n_train_steps, ts.data(), (int)ts.size(), t_end);
+  if (const char* m = Diffuser::schedule_error(sc, prediction)) return m;
   return prediction == SDXL_PREDICTION_EPSILON ? alphas_error(alphas_cumprod_host, n_train_steps) : nullptr;
+}
+// the schedule a sdxl_schedule_desc describes, with every check of the list entries: nullptr and (alphas, sc) filled, or the complaint
+static const char* desc_schedule(const sdxl_schedule_desc* k, int solver, double eta, int prediction, std::vector<double>& alphas, Schedule& sc) {
+  if (!k) return "null argument";
+  if ((k->timesteps != nullptr) == (k->sigmas != nullptr)) return "schedule: give exactly one of timesteps and sigmas";
+  if (k->timesteps) {
+    if (const char* m = list_args_error(k->alphas_cumprod_host, k->n_train_steps, k->timesteps, k->n, solver, eta, k->t_end)) return m;
+    const std::vector<int> ts(k->timesteps, k->timesteps + k->n);
+    if (const char* m = alphas_error_pred(k->alphas_cumprod_host, k->n_train_steps, ts, prediction, k->t_end)) return m;
+    alphas.assign(k->alphas_cumprod_host, k->alphas_cumprod_host + k->n_train_steps);
+    sc = Diffuser::schedule_of_timesteps(alphas.data(), k->n_train_steps, ts.data(), k->n, k->t_end);
+    return nullptr;
+  }
+  if (const char* m = solver_args_error(k->alphas_cumprod_host, k->n_train_steps, solver, eta)) return m;
+  if (const char* m = table_error(k->alphas_cumprod_host, k->n_train_steps)) return m;
+  if (const char* m = Diffuser::sigmas_error(k->sigmas, k->n, k->sigma_end, k->flags, k->n_train_steps)) return m;
+  if (solver == SDXL_SOLVER_LCM && eta != 0.0) return "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)";
+  if (solver == SDXL_SOLVER_TCD)
+    return "solver TCD reads alphas_cumprod at floor((1 - gamma) t'), a training timestep: it does not run on sigmas (use a timestep list)";
+  if (prediction != SDXL_PREDICTION_EPSILON && prediction != SDXL_PREDICTION_V) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
+  alphas.assign(k->alphas_cumprod_host, k->alphas_cumprod_host + k->n_train_steps);
+  sc = Diffuser::schedule_of_sigmas(alphas.data(), k->n_train_steps, k->sigmas, k->n, k->sigma_end, k->flags);
+  return Diffuser::schedule_error(sc, prediction);
+}
+int sdxl_solver_rows(const sdxl_schedule_desc* schedule, int solver, int prediction, double eta, double* out, int capacity_rows) {
+  if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  std::vector<double> alphas;
+  Schedule sc;
+  if (const char* m = desc_schedule(schedule, solver, eta, prediction, alphas, sc)) return fail(SDXL_ERR_INVALID, m);
+  if (capacity_rows < (int)sc.size()) return fail(SDXL_ERR_INVALID, "capacity_rows is smaller than the list");
+  API_BEGIN
+  std::vector<double> rows((size_t)kRowCols * sc.size());
+  Diffuser::solver_coefficients(alphas.data(), (int)alphas.size(), sc, solver, eta, rows.data(), prediction);
+  std::copy(rows.begin(), rows.end(), out);
+  API_END
 }
 int sdxl_solver_coefficients_ts(const float* alphas_cumprod_host, int n_train_steps, const int32_t* timesteps, int n, int solver, int prediction,
                                 double eta, double* out, int capacity_steps) {
   if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (solver == SDXL_SOLVER_DPMPP_3M && alphas_cumprod_host) return fail(SDXL_ERR_INVALID, kSolver3MEntry);
   if (const char* m = list_args_error(alphas_cumprod_host, n_train_steps, timesteps, n, solver, eta)) return fail(SDXL_ERR_INVALID, m);
   if (capacity_steps < n) return fail(SDXL_ERR_INVALID, "capacity_steps is smaller than the list (sdxl_step_count for the reference's rule)");
   const std::vector<int> ts(timesteps, timesteps + n);
   if (const char* m = alphas_error_pred(alphas_cumprod_host, n_train_steps, ts, prediction)) return fail(SDXL_ERR_INVALID, m);
   API_BEGIN
   std::vector<double> alphas(alphas_cumprod_host, alphas_cumprod_host + n_train_steps);   // elem -> f64 as the Diffuser holds them
-  std::vector<double> rows((size_t)4 * n);
-  Diffuser::solver_coefficients(alphas.data(), n_train_steps, ts, solver, eta, rows.data(), prediction);
-  std::copy(rows.begin(), rows.end(), out);
+  const Schedule sc = Diffuser::schedule_of_timesteps(alphas.data(), n_train_steps, ts.data(), n);
+  std::vector<double> rows((size_t)kRowCols * n);
+  Diffuser::solver_coefficients(alphas.data(), n_train_steps, sc, solver, eta, rows.data(), prediction);
+  for (int i = 0; i < n; ++i) {      // the four columns these entries have always had: c_2 is 0 for their solvers
+    const double* r = &rows[(size_t)kRowCols * i];
+    out[4 * i] = r[0]; out[4 * i + 1] = r[1]; out[4 * i + 2] = r[2]; out[4 * i + 3] = r[4];
+  }
   API_END
 }
 int sdxl_solver_coefficients_pred(const float* alphas_cumprod_host, int n_train_steps, int n_steps, int step_start, int solver, int prediction,
                                   double eta, double* out, int capacity_steps) {
   if (!out) return fail(SDXL_ERR_INVALID, "null argument");
+  if (solver == SDXL_SOLVER_DPMPP_3M && alphas_cumprod_host) return fail(SDXL_ERR_INVALID, kSolver3MEntry);
   if (const char* m = schedule_args_error(alphas_cumprod_host, n_train_steps, n_steps, step_start, solver, eta)) return fail(SDXL_ERR_INVALID, m);
   const std::vector<int> ts = Diffuser::step_schedule(n_steps, step_start, n_train_steps);     // the reference's rule as a list
   return sdxl_solver_coefficients_ts(alphas_cumprod_host, n_train_steps, ts.data(), (int)ts.size(), solver, prediction, eta, out, capacity_steps);
@@ -1008,21 +1140,15 @@ int sdxl_sampler_step_replay(sdxl_ctx* ctx, void* stream, const sdxl_step_replay
 int sdxl_sampler_step_replay_pred(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction) {
   return sdxl_sampler_step_replay_ts(ctx, stream, a, prediction, nullptr, 0);
 }
-int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction, const int32_t* timesteps, int n_ts) {
-  if (!ctx || !a || !a->eps || !a->latent0 || !a->latents_out || !a->unet_in_out || !a->timesteps_out) return fail(SDXL_ERR_INVALID, "null argument");
-  if (a->n < 1 || a->n > kMaxSeeds || a->h < 1 || a->w < 1 || (int64_t)a->h * a->w > 1 << 22)
-    return fail(SDXL_ERR_INVALID, "step_replay: n (1..8) or h * w (1..2^22) out of range");
-  const bool listed = timesteps != nullptr && n_ts != 0;      // else the reference's rule on the struct's n_steps and step_start
-  std::vector<int> ts;
-  if (listed) {
-    if (const char* m = list_args_error(a->alphas_cumprod_host, a->n_train_steps, timesteps, n_ts, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
-    ts.assign(timesteps, timesteps + n_ts);
-  } else {
-    if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
-    if (a->solver == SDXL_SOLVER_LCM && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
-    ts = Diffuser::step_schedule(a->n_steps, a->step_start, a->n_train_steps);
-  }
-  if (const char* m = alphas_error_pred(a->alphas_cumprod_host, a->n_train_steps, ts, prediction)) return fail(SDXL_ERR_INVALID, m);
+// what every replay entry checks besides its schedule
+static const char* replay_args_error(const sdxl_ctx* ctx, const sdxl_step_replay_args* a) {
+  if (!ctx || !a || !a->eps || !a->latent0 || !a->latents_out || !a->unet_in_out || !a->timesteps_out) return "null argument";
+  if (a->n < 1 || a->n > kMaxSeeds || a->h < 1 || a->w < 1 || (int64_t)a->h * a->w > 1 << 22) return "step_replay: n (1..8) or h * w (1..2^22) out of range";
+  return nullptr;
+}
+// the replay itself on a schedule its entry has checked; hist2_out: kSolverDpmpp3M's second history (may be null)
+static int replay_run(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction, const std::vector<double>& alphas, const Schedule& sc,
+                      float* hist2_out) {
   if ((a->mask != nullptr) != (a->reference != nullptr)) return fail(SDXL_ERR_INVALID, "inpainting needs reference and mask");
   if (a->mask && !a->seeds && !a->step_noise) return fail(SDXL_ERR_INVALID, "inpainting with explicit noise needs step_noise");
   if (!a->seeds && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "eta needs seeds: explicit noise carries none for the sigma term");
@@ -1030,9 +1156,9 @@ int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_rep
   if (const char* m = Diffuser::guidance_error(g, a->single != 0)) return fail(SDXL_ERR_INVALID, m);
   if (g.n_scales != 0 && g.n_scales != a->n) return fail(SDXL_ERR_INVALID, "guidance: n_scales differs from the batch (n)");
   API_BEGIN
-  const std::vector<double> alphas(a->alphas_cumprod_host, a->alphas_cumprod_host + a->n_train_steps);   // elem -> f64 as the Diffuser holds them
+  const int n_train = (int)alphas.size();
   if (!a->seeds)      // a table that re-noises (c_z != 0) has no noise to take: refused here, before the device is touched
-    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), a->n_train_steps, ts, a->solver, prediction)) throw InvalidArgumentError(m);
+    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), n_train, sc, a->solver, prediction)) throw InvalidArgumentError(m);
   use(ctx);
   hipStream_t s = pick(ctx, stream);
   const bool single = a->single != 0 || g.mode == kGuidanceOff;
@@ -1046,16 +1172,47 @@ int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_rep
   io.reference = a->reference; io.mask = a->mask; io.step_noise = a->step_noise; io.seeds = a->seeds;
   SDXL_HIP(hipMemcpyAsync(io.latent, a->latent0, bytes, hipMemcpyDeviceToDevice, s));
   StepLoop loop;
-  const int iters = loop.begin(alphas, ts, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s, prediction);
+  const int iters = loop.begin(alphas, sc, a->solver, a->eta, a->unconditional_guidance_scale, g, single, n, HW, io, s, prediction);
   for (int i = 0; i <= iters; ++i) {
     if (i > 0) loop.after_forward(i - 1, a->eps + (size_t)(i - 1) * B * HW * 4, s);
     SDXL_HIP(hipMemcpyAsync(a->latents_out + (size_t)i * elems, io.latent, bytes, hipMemcpyDeviceToDevice, s));
     SDXL_HIP(hipMemcpyAsync(a->timesteps_out + i, loop.t_dev(), sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-  if (a->solver == SDXL_SOLVER_DPMPP_2M && a->hist_out) SDXL_HIP(hipMemcpyAsync(a->hist_out, loop.hist(), bytes, hipMemcpyDeviceToDevice, s));
+  const bool hist = a->solver == SDXL_SOLVER_DPMPP_2M || a->solver == SDXL_SOLVER_DPMPP_3M;
+  if (hist && a->hist_out && iters > 0) SDXL_HIP(hipMemcpyAsync(a->hist_out, loop.hist(), bytes, hipMemcpyDeviceToDevice, s));
+  // the second history holds a value only once an update has shifted one into it: with fewer than two iterations it was never written
+  if (a->solver == SDXL_SOLVER_DPMPP_3M && hist2_out && iters > 1) SDXL_HIP(hipMemcpyAsync(hist2_out, loop.hist2(), bytes, hipMemcpyDeviceToDevice, s));
   launch_copy_rows(io.unet_in, in_dt, 4, a->unet_in_out, DT_F32, 4, B * HW, 4, s);
   SDXL_HIP(hipStreamSynchronize(s));     // the loop and the scratch go away with this call
   API_END
+}
+int sdxl_sampler_step_replay_ts(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction, const int32_t* timesteps, int n_ts) {
+  if (const char* m = replay_args_error(ctx, a)) return fail(SDXL_ERR_INVALID, m);
+  if (a->solver == SDXL_SOLVER_DPMPP_3M && a->alphas_cumprod_host) return fail(SDXL_ERR_INVALID, kSolver3MEntry);
+  const bool listed = timesteps != nullptr && n_ts != 0;      // else the reference's rule on the struct's n_steps and step_start
+  std::vector<int> ts;
+  if (listed) {
+    if (const char* m = list_args_error(a->alphas_cumprod_host, a->n_train_steps, timesteps, n_ts, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
+    ts.assign(timesteps, timesteps + n_ts);
+  } else {
+    if (const char* m = schedule_args_error(a->alphas_cumprod_host, a->n_train_steps, a->n_steps, a->step_start, a->solver, a->eta)) return fail(SDXL_ERR_INVALID, m);
+    if (a->solver == SDXL_SOLVER_LCM && a->eta != 0.0) return fail(SDXL_ERR_INVALID, "solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
+    ts = Diffuser::step_schedule(a->n_steps, a->step_start, a->n_train_steps);
+  }
+  if (const char* m = alphas_error_pred(a->alphas_cumprod_host, a->n_train_steps, ts, prediction)) return fail(SDXL_ERR_INVALID, m);
+  const std::vector<double> alphas(a->alphas_cumprod_host, a->alphas_cumprod_host + a->n_train_steps);   // elem -> f64 as the Diffuser holds them
+  Schedule sc;
+  try { sc = Diffuser::schedule_of_timesteps(alphas.data(), a->n_train_steps, ts.data(), (int)ts.size()); }
+  catch (const std::exception& e) { return fail(SDXL_ERR_INVALID, e.what()); }
+  return replay_run(ctx, stream, a, prediction, alphas, sc, nullptr);
+}
+int sdxl_sampler_step_replay_levels(sdxl_ctx* ctx, void* stream, const sdxl_step_replay_args* a, int prediction, const sdxl_schedule_desc* schedule,
+                                    float* hist2_out) {
+  if (const char* m = replay_args_error(ctx, a)) return fail(SDXL_ERR_INVALID, m);
+  std::vector<double> alphas;
+  Schedule sc;
+  if (const char* m = desc_schedule(schedule, a->solver, a->eta, prediction, alphas, sc)) return fail(SDXL_ERR_INVALID, m);
+  return replay_run(ctx, stream, a, prediction, alphas, sc, hist2_out);
 }
 int sdxl_diffuser_enable_step_timing(sdxl_diffuser* d, int enabled) {
   API_BEGIN

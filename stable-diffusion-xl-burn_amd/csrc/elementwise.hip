@@ -623,6 +623,9 @@ void launch_seeded_noise(float* out, const uint64_t* seeds, uint32_t draw, int n
 //                    The last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): the result is x0 itself.
 //   kSolverRow1:     acc = x0 * c_0;  x = fma(x, c_x, acc): a first-order row of the 2M layout (the LCM and TCD tables).  No history:
 //                    p.hist is neither read nor written.
+//   kSolverDpmpp3M:  acc = c_2 * x0pp     (p.hist2, read only where c_2 != 0)
+//                    acc = fma(x0p, c_1, acc)   (p.hist, read only where c_1 != 0);  acc = fma(x0, c_0, acc);  x = fma(x, c_x, acc)
+//                    then p.hist2 = x0p where x0p was read and p.hist = x0: the histories shift per element, in place.
 //     x   = fma(z, sigma or c_z, x)       (SEEDED, coefficient != 0; z = seeded_normal4(seed, hw, draw_sigma(idx)))
 //   the blend rounds both products.
 // PRED = kPredictionV: the network's rows are v = alpha e - sigma x0.  The two guidance lines above combine them as they combine e (v = vc;
@@ -659,6 +662,17 @@ __global__ void step_kernel(const StepParams p, int do_update) {
         for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
       }
     }
+    float x0pp[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SOLVER == kSolverDpmpp3M) {
+      if (k.c_2 != 0.f) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x0pp[c] = p.hist2[((size_t)b * 4 + c) * p.HW + hw];
+      }
+      if (k.c_1 != 0.f) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x0p[c] = p.hist[((size_t)b * 4 + c) * p.HW + hw];
+      }
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const float ec = ld_f(p.eps, ((size_t)b * p.HW + hw) * p.eps_ld + c, p.eps_dt);
@@ -681,6 +695,13 @@ __global__ void step_kernel(const StepParams p, int do_update) {
         float acc = k.c_1 * x0p[c];
         acc = __builtin_fmaf(x0, k.c_0, acc);
         x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+      } else if constexpr (SOLVER == kSolverDpmpp3M) {
+        float acc = k.c_2 * x0pp[c];
+        acc = __builtin_fmaf(x0p[c], k.c_1, acc);
+        acc = __builtin_fmaf(x0, k.c_0, acc);
+        x[c] = __builtin_fmaf(x[c], k.c_x, acc);
+        if (k.c_1 != 0.f) p.hist2[((size_t)b * 4 + c) * p.HW + hw] = x0p[c];
+        p.hist[((size_t)b * 4 + c) * p.HW + hw] = x0;
       } else if constexpr (SOLVER == kSolverRow1) {
         const float acc = x0 * k.c_0;
         x[c] = __builtin_fmaf(x[c], k.c_x, acc);
@@ -732,6 +753,9 @@ static void launch_step_pred(const StepParams& p, int do_update, dim3 grid, dim3
   } else if (p.solver == kSolverRow1) {
     if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverRow1, true, PRED>), grid, block, 0, s, p, do_update);
     else hipLaunchKernelGGL((step_kernel<kSolverRow1, false, PRED>), grid, block, 0, s, p, do_update);
+  } else if (p.solver == kSolverDpmpp3M) {
+    if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDpmpp3M, true, PRED>), grid, block, 0, s, p, do_update);
+    else hipLaunchKernelGGL((step_kernel<kSolverDpmpp3M, false, PRED>), grid, block, 0, s, p, do_update);
   } else {
     if (p.seeded) hipLaunchKernelGGL((step_kernel<kSolverDdim, true, PRED>), grid, block, 0, s, p, do_update);
     else hipLaunchKernelGGL((step_kernel<kSolverDdim, false, PRED>), grid, block, 0, s, p, do_update);

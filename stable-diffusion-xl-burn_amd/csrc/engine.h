@@ -725,6 +725,22 @@ const char* control_error(const Control& c, bool single);
 // iteration).  nullptr, or the complaint: control_error, n outside the batch, n_scales neither 0 nor n, a null pointer.
 const char* control_scale_table(const Control& c, int n, bool single, const int* timesteps, int iters, float* out);
 
+// The noise levels of one trajectory: iteration i runs at alphas_cumprod a[i] and lands on ap(i) = a[i + 1], a_end behind the last
+// entry (1: the complete trajectory, the data itself).  t[i] is what the UNet is fed (rounded to float), what the guidance interval compares and
+// what LCM scales; an integer list has t[i] = ts[i], a[i] = alphas[ts[i]]; a sigma list a[i] = 1 / (1 + sigma_i^2) and t[i] = sigma_to_t(sigma_i).
+// t_end: the training timestep behind the last entry of an integer list (-1: none; TCD reads it), meaningless where from_sigmas.
+struct Schedule {
+  std::vector<double> t, a;
+  double a_end = 1.0;
+  int t_end = -1;
+  bool from_sigmas = false;
+  size_t size() const { return a.size(); }
+  bool empty() const { return a.empty(); }
+  double ap(size_t i) const { return i + 1 < a.size() ? a[i + 1] : a_end; }
+};
+constexpr int kSigmasRoundT = 1;      // SDXL_SIGMAS_ROUND_T
+constexpr int kRowCols = 5;           // (c_x, c_0, c_1, c_2, c_z) per iteration
+
 // The trajectory minus the UNet: the coefficient table, the guidance interval and the launches between two UNet forwards.  Diffuser::diffuse
 // drives one with the UNet's output; sdxl_sampler_step_replay (the op-level test seam) drives one with given noise predictions.
 struct StepIo {                       // device buffers of one trajectory (seeds: host array [n], nullptr = explicit noise)
@@ -742,18 +758,20 @@ class StepLoop {
   StepLoop& operator=(const StepLoop&) = delete;
   // Builds the StepCoef table (host f64 -> f32) and the active-iteration array of one trajectory, uploads them and runs the do_update = 0
   // launch: *step_idx = 0, the step-0 inpainting blend, the first UNet input and timestep.  `single`: one branch, no CFG (B = n).  Returns the
-  // number of iterations.  alphas: the n_train alphas_cumprod values as f64.  ts: the timestep of every iteration, strictly decreasing -- the
-  // only source of (t, a, ap): a = alphas[ts[i]], ap = alphas[ts[i + 1]], 1 behind the last entry (Diffuser::step_schedule for the reference's rule).
+  // number of iterations.  alphas: the n_train alphas_cumprod values as f64 (TCD reads them).  sc: the schedule -- the only source of an
+  // iteration's (t, a, ap) (Diffuser::schedule_of_timesteps on Diffuser::step_schedule for the reference's rule).
   // prediction: kPredictionEpsilon or kPredictionV, what the rows handed to after_forward mean.  A schedule Diffuser::schedule_error refuses
   // (alphas_cumprod == 0 at an iteration's timestep under kPredictionEpsilon) throws InvalidArgumentError before anything is launched, and so
-  // does a table with c_z != 0 where io.seeds == nullptr (Diffuser::explicit_noise_error).  kSolverLcm / kSolverTcd allocate no history.
-  int begin(const std::vector<double>& alphas, const std::vector<int>& ts, int solver, double eta, double cfg_scale, const Guidance& g,
+  // does a table with c_z != 0 where io.seeds == nullptr (Diffuser::explicit_noise_error).  kSolverLcm / kSolverTcd allocate no history, kSolverDpmpp2M one,
+  // kSolverDpmpp3M two.  The order of a multistep solver starts at one: whatever the history buffers hold is not read on iteration 0.
+  int begin(const std::vector<double>& alphas, const Schedule& sc, int solver, double eta, double cfg_scale, const Guidance& g,
             bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction = kPredictionEpsilon);
   // behind the UNet forward of iteration i: eps [B][HW][eps_ld] fp32 (cond entries first) -> the CFG rescale factors where rescale is on and
   // the iteration active, then the update + advance launches
   void after_forward(int i, const float* eps, hipStream_t s);
   float* t_dev() const { return t_dev_; }       // device scalar: the timestep of the next UNet call
-  const float* hist() const { return hist_; }   // kSolverDpmpp2M: x0 of the previous iteration [n][4][HW]
+  const float* hist() const { return hist_; }   // kSolverDpmpp2M / kSolverDpmpp3M: x0 of the previous iteration [n][4][HW]
+  const float* hist2() const { return hist2_; } // kSolverDpmpp3M: the x0 before that one
 
  private:
   StepCoef* table_ = nullptr; int table_cap_ = 0;
@@ -763,6 +781,7 @@ class StepLoop {
   float* factors_ = nullptr;
   int* step_idx_ = nullptr; float* t_dev_ = nullptr;
   float* hist_ = nullptr; size_t hist_cap_ = 0;
+  float* hist2_ = nullptr; size_t hist2_cap_ = 0;
   // the trajectory begin() set up
   StepParams p_{};
   float rescale_ = 0.f;
@@ -799,27 +818,54 @@ class Diffuser {
   // a per-handle list that replaces step_schedule in all six trajectory calls (n == 0 or nullptr: back to the reference's rule).  A list
   // timesteps_error refuses throws InvalidArgumentError and the handle keeps what it had.  With a list the calls' n_steps must equal its length,
   // step_start must be 0 for sampling and inpainting, and refine_latent needs ts[0] == n_train - step_start - 1 (InvalidArgumentError otherwise).
-  void set_timesteps(const int* ts, int n);
-  const std::vector<int>& timesteps() const { return timesteps_; }     // empty: the reference's rule
-  // (c_x, c_0, c_1, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_z z per entry of the list ts, f64, out[4 * i ..] (host logic only;
+  // t_end: the training timestep the last iteration lands on, ap = alphas[t_end] there (-1: ap = 1, the complete trajectory); it must lie in
+  // -1 .. ts[n - 1] - 1 (timesteps_end_error names "timesteps").  Setting a timestep list (or clearing it) drops the handle's sigma list.
+  static const char* timesteps_end_error(const int* ts, int n, int t_end, int n_train);
+  void set_timesteps(const int* ts, int n, int t_end = -1);
+  // the handle's timestep list; empty: the reference's rule -- and while a sigma list is set, which is then the list in force
+  const std::vector<int>& timesteps() const { static const std::vector<int> none; return sigmas_.empty() ? timesteps_ : none; }
+  int timesteps_end() const { return timesteps_end_; }
+  // Noise-level (sigma) lists, k-diffusion's sigma = sqrt((1 - a) / a).  sigmas_error: host logic only -- the first complaint (n
+  // outside 1..n_train, a value that is not finite and > 0, not strictly decreasing, sigma_end outside [0, sigmas[n - 1]), unknown flags, a table
+  // of fewer than two entries; every message names "sigmas"), nullptr where the list is valid.  set_sigmas: the list every following
+  // trajectory runs, with sigma_end behind the last entry (0: the complete trajectory); n == 0 or nullptr drops it, and the handle is back on
+  // the timestep list or rule it had before.  While it is set it is the only list in force.
+  static const char* sigmas_error(const double* sigmas, int n, double sigma_end, int flags, int n_train);
+  void set_sigmas(const double* sigmas, int n, double sigma_end, int flags);
+  const std::vector<double>& sigmas() const { return sigmas_; }
+  double sigma_end() const { return sigma_end_; }
+  int sigma_flags() const { return sigma_flags_; }
+  // k-diffusion's sigma_to_t in f64 on L_j = 0.5 ln((1 - alphas[j]) / alphas[j]): low the largest j <= n_train - 2 with L_j <= ln sigma (0 if
+  // none), w = clamp((L_low - ln sigma) / (L_low - L_{low+1}), 0, 1), t = (1 - w) low + w (low + 1); kSigmasRoundT: rint(t), ties to even
+  static double sigma_to_t(const double* alphas, int n_train, double sigma, int flags);
+  // the two ways to a Schedule; both require a list their *_error accepts (InvalidArgumentError otherwise)
+  static Schedule schedule_of_timesteps(const double* alphas, int n_train, const int* ts, int n, int t_end = -1);
+  static Schedule schedule_of_sigmas(const double* alphas, int n_train, const double* sigmas, int n, double sigma_end, int flags);
+  // sdxl_continue_latent: the handle's list from a given latent.  renoise == false: the latent as it is (noise ignored); else the start is
+  // sqrt(a_0) latent + sqrt(1 - a_0) z, z = noise or the kDrawInitial draw of seeds (exactly one of the two).  A multistep solver starts first order.
+  void continue_latent(const float* latent, const Conditioning& c, double cfg_scale, int n_steps, const float* noise, const uint64_t* seeds,
+                       double eta, bool renoise, float* out, hipStream_t s);
+  // (c_x, c_0, c_1, c_2, c_z) of x' = c_x x + c_0 x0 + c_1 x0p + c_2 x0pp + c_z z per entry of the schedule, f64, out[kRowCols * i ..] (host logic only;
   // formulas in include/sdxl_mi355.h, sdxl_solver_coefficients).  kSolverDpmpp2M: what diffuse() rounds into its table.  kSolverDdim: the
   // DDIM update folded into the same four numbers.  alphas: n_train values in (0, 1).  The rows do not depend on the prediction type; it
   // decides only whether a == 0 at an iteration's timestep (zero terminal SNR) is admitted: kPredictionV writes that row as the limit
   // lambda -> -inf, kPredictionEpsilon throws InvalidArgumentError.  kSolverLcm (eta must be 0) and kSolverTcd (eta is gamma):
-  // the first-order rows (c_x, c_0, 0, c_z) of include/sdxl_mi355.h, finite at a == 0 as written.
-  static void solver_coefficients(const double* alphas, int n_train, const std::vector<int>& ts, int solver, double eta, double* out,
+  // the first-order rows (c_x, c_0, 0, 0, c_z) of include/sdxl_mi355.h, finite at a == 0 as written; TCD reads alphas at
+  // floor((1 - gamma) t') and so needs training timesteps: on a sigma list it throws InvalidArgumentError (the message names "sigmas").
+  // kSolverDpmpp3M: the only solver with c_2 != 0.
+  static void solver_coefficients(const double* alphas, int n_train, const Schedule& sc, int solver, double eta, double* out,
                                   int prediction = kPredictionEpsilon);
   // host logic only: why a trajectory of `solver` on ts cannot run on explicit noise (its eta == 0 table has a c_z != 0, and explicit noise
   // carries no tensor for that term), nullptr where it can: DDIM, 2M, TCD (gamma = 0 there) and a one-entry LCM list
-  static const char* explicit_noise_error(const double* alphas, int n_train, const std::vector<int>& ts, int solver, int prediction);
-  // host logic only: the first complaint about the (a, ap) pairs of the list ts under `prediction`, nullptr where the trajectory can run.
+  static const char* explicit_noise_error(const double* alphas, int n_train, const Schedule& sc, int solver, int prediction);
+  // host logic only: the first complaint about the (a, ap) pairs of the schedule under `prediction`, nullptr where the trajectory can run.
   // kPredictionEpsilon: a == 0 on an iteration (x0 would divide by it) -- the message names v-prediction.  kPredictionV: a outside [0, 1)
   // or ap outside (0, 1].
-  static const char* schedule_error(const double* alphas, int n_train, const std::vector<int>& ts, int prediction);
+  static const char* schedule_error(const Schedule& sc, int prediction);
   // kPredictionEpsilon (default) or kPredictionV: what the UNet's output means to every following trajectory of this handle
   void set_prediction(int prediction);
   int prediction() const { return prediction_; }
-  // kSolverDdim (default), kSolverDpmpp2M, kSolverLcm or kSolverTcd: the update every following trajectory of this handle runs
+  // kSolverDdim (default), kSolverDpmpp2M, kSolverDpmpp3M, kSolverLcm or kSolverTcd: the update every following trajectory of this handle runs
   void set_solver(int solver);
   int solver() const { return solver_; }
   // guidance options, a per-handle choice like the solver.  guidance_error: host logic only -- the first complaint about `g` (for a refiner
@@ -840,14 +886,16 @@ class Diffuser {
   struct Trajectory {
     const float* noise = nullptr;                             // explicit start (or re-noise) tensor; nullptr with seeds
     const float* renoise = nullptr; int step_start = 0;       // refine_latent: the finished latent and where to re-noise it to
+    const float* start = nullptr;                             // continue_latent: the start latent as it is; with renoise0: re-noised to the list's a_0
+    bool renoise0 = false;
     const float* reference = nullptr; const unsigned char* mask = nullptr; const float* step_noise = nullptr;      // inpainting
     const uint64_t* seeds = nullptr; double eta = 0.0;        // seeded noise
   };
   void trajectory(const Conditioning& c, double cfg_scale, int n_steps, const Trajectory& t, float* out, hipStream_t s);
   // context setup, then StepLoop::begin and one UNet forward + StepLoop::after_forward per iteration
   // the list of this call: the handle's own (checked against n_steps and step_start as set_timesteps documents) or step_schedule
-  std::vector<int> call_schedule(int n_steps, int step_start, bool renoise) const;
-  void diffuse(float* latent, const Conditioning& c, const std::vector<int>& ts, double cfg_scale, const float* reference,
+  Schedule call_schedule(int n_steps, int step_start, bool renoise, bool listed_only = false) const;
+  void diffuse(float* latent, const Conditioning& c, const Schedule& sc, double cfg_scale, const float* reference,
                const unsigned char* mask, const float* step_noise, hipStream_t s, const uint64_t* seeds = nullptr, double eta = 0.0);
   std::unique_ptr<UNet> unet_;
   std::vector<double> alphas_;
@@ -858,6 +906,9 @@ class Diffuser {
   float* noise_ = nullptr; size_t noise_cap_ = 0;     // re-noise tensor of refine_latent_seeded
   int solver_ = kSolverDdim;
   std::vector<int> timesteps_;                        // empty: step_schedule
+  int timesteps_end_ = -1;
+  std::vector<double> sigmas_;                        // non-empty: the list in force (timesteps_ rests)
+  double sigma_end_ = 0.0; int sigma_flags_ = 0;
   int prediction_ = kPredictionEpsilon;
   Guidance guidance_;
   StepLoop loop_;

@@ -343,7 +343,8 @@ struct StepCoef {
   float t; float sqrt_a; float sqrt_1ma;
   union { float sqrt_ap; float c_0; };
   union { float sqrt_1map; float c_x; };
-  float pad;     // (held the guidance scale until it became StepParams::scales)
+  union { float pad; float c_2; };     // DDIM and 2M layouts: 0 (held the guidance scale until it became StepParams::scales); kSolverDpmpp3M: the
+                                       // coefficient of the second history term
   union { float sigma; float c_z; };
   float c_1;     // padding of the DDIM layout (0)
 };
@@ -353,6 +354,8 @@ constexpr int kSolverDdim = 0, kSolverDpmpp2M = 1;   // SDXL_SOLVER_* of the pub
 // layout, and one update text for both in the per-step kernel, StepParams::solver == kSolverRow1
 constexpr int kSolverLcm = 3, kSolverTcd = 4;     // SDXL_SOLVER_LCM, SDXL_SOLVER_TCD (2 is no public solver)
 constexpr int kSolverRow1 = 2;                     // kernel level only: never a handle's solver
+// DPM++ 3M SDE: the 2M layout with one more history term, x' = c_x x + c_0 x0 + c_1 x0p + c_2 x0pp + c_z z, c_2 in StepCoef::c_2
+constexpr int kSolverDpmpp3M = 5;                  // SDXL_SOLVER_DPMPP_3M
 constexpr bool solver_is_row1(int solver) { return solver == kSolverLcm || solver == kSolverTcd; }
 constexpr int kPredictionEpsilon = 0, kPredictionV = 1;   // SDXL_PREDICTION_* of the public header: what the UNet's output rows mean
 // draw numbers of the seeded noise (counter word 1 of the generator); the public header carries the same values as SDXL_DRAW_*
@@ -367,6 +370,7 @@ struct CfgScales { float v[kMaxSeeds]; };      // per-entry guidance scales, pas
 //   e  = fma(ec - eu, scales[b], eu)         otherwise; times factors[b] where factors != nullptr (CFG rescale)
 //   x0 = (x - e sqrt_1ma) / sqrt_a;  x = x0 sqrt_ap + e sqrt_1map (+ z sigma)   or, kSolverDpmpp2M,   x = c_x x + c_0 x0 + c_1 x0p (+ c_z z)
 //   or, kSolverRow1,   x = c_x x + c_0 x0 (+ c_z z): the 2M line without its history term
+//   or, kSolverDpmpp3M, x = c_x x + c_0 x0 + c_1 x0p + c_2 x0pp (+ c_z z): the 2M line with a second history term
 // kPredictionV: the rows are v = alpha e - sigma x0, combined by the same two guidance lines (v, vc, vu for e, ec, eu), and then
 //   x0 = x sqrt_a - v sqrt_1ma               no division: finite at sqrt_a == 0 (zero terminal SNR), where x0 = -v
 //   e  = v sqrt_a + x sqrt_1ma               kSolverDdim only; the update lines behind x0 and e are those above
@@ -392,6 +396,9 @@ struct StepParams {
   // every update); kSolverDdim reads neither.  kSolverRow1: the 2M layout with c_1 == 0; hist is neither read nor written (nullptr)
   // prediction: kPredictionEpsilon or kPredictionV (sits in the padding between solver and hist: no other member moves)
   int solver; int prediction; float* hist;
+  // kSolverDpmpp3M: hist2 [n][4][HW] fp32 the x0 before hist's (read where c_2 != 0; receives hist's value wherever that was read, i.e. where
+  // c_1 != 0: the shift happens per element inside the update, the two addresses never change).  Every other solver: nullptr, never looked at
+  float* hist2;
 };
 // do_update=0: first call of a trajectory -- sets *step_idx = 0, applies the step-0 inpaint blend, writes the UNet
 // input and timestep.  do_update=1: the update with table[*step_idx], blend for the next step, then advances.

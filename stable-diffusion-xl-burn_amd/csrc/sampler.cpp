@@ -22,6 +22,10 @@
 //     The list is the only source of an iteration's (t, a, ap) -- ap is the alpha of the next entry, 1 behind the last -- for the table, the guidance
 //     interval, the trace and the t fed to the UNet.  On it run DDIM and 2M as before and the consistency solvers of distilled checkpoints (LCM, TCD):
 //     first-order rows of the same table that re-noise with the seeded z every iteration, in one more instantiation of the same kernel.
+//   * the list itself is a Schedule of noise levels: (t, a) per iteration and the level behind the last one.  An integer list fills it
+//     from the table; a sigma list (Karras, exponential, hand-tuned) with a = 1 / (1 + sigma^2) and a fractional t; an end level other than the data
+//     stops a trajectory early, and continue_latent starts one from a given latent: the base -> refiner handoff without re-noising.  DPM++ 3M SDE is
+//     the 2M row with a second history term, in four more instantiations of the same kernel.
 // StepLoop is everything between two UNet forwards; Diffuser::diffuse is context setup and the loop around UNet::forward.
 #include "engine.h"
 
@@ -59,7 +63,7 @@ static void ddim_terms(double a, double ap, double eta, double& sqrt_ap, double&
 }
 
 void Diffuser::set_solver(int solver) {
-  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver_is_row1(solver), "unknown solver");
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver == kSolverDpmpp3M || solver_is_row1(solver), "unknown solver");
   solver_ = solver;
 }
 
@@ -71,21 +75,99 @@ const char* Diffuser::timesteps_error(const int* ts, int n, int n_train) {
   }
   return nullptr;
 }
-void Diffuser::set_timesteps(const int* ts, int n) {
-  if (!ts || n == 0) { timesteps_.clear(); return; }
-  if (const char* m = timesteps_error(ts, n, n_train_)) throw InvalidArgumentError(m);
+const char* Diffuser::timesteps_end_error(const int* ts, int n, int t_end, int n_train) {
+  if (const char* m = timesteps_error(ts, n, n_train)) return m;
+  if (t_end < -1 || t_end >= ts[n - 1]) return "timesteps: t_end must lie below the last entry (-1: the complete trajectory)";
+  return nullptr;
+}
+void Diffuser::set_timesteps(const int* ts, int n, int t_end) {
+  if (!ts || n == 0) { timesteps_.clear(); timesteps_end_ = -1; sigmas_.clear(); return; }
+  if (const char* m = timesteps_end_error(ts, n, t_end, n_train_)) throw InvalidArgumentError(m);
   timesteps_.assign(ts, ts + n);
+  timesteps_end_ = t_end;
+  sigmas_.clear();
 }
 
-std::vector<int> Diffuser::call_schedule(int n_steps, int step_start, bool renoise) const {
-  if (timesteps_.empty()) return step_schedule(n_steps, step_start, n_train_);
+const char* Diffuser::sigmas_error(const double* sigmas, int n, double sigma_end, int flags, int n_train) {
+  if (n_train < 2) return "sigmas: the alphas_cumprod table needs at least two entries";
+  if (!sigmas || n < 1 || n > n_train) return "sigmas: the list needs 1..n_train_steps entries";
+  if ((flags & ~kSigmasRoundT) != 0) return "sigmas: unknown flags (SDXL_SIGMAS_ROUND_T)";
+  for (int i = 0; i < n; ++i) {
+    if (!(std::isfinite(sigmas[i]) && sigmas[i] > 0.0)) return "sigmas: a value that is not finite and > 0";
+    if (i > 0 && !(sigmas[i] < sigmas[i - 1])) return "sigmas: the list must be strictly decreasing";
+  }
+  if (!(sigma_end >= 0.0 && sigma_end < sigmas[n - 1])) return "sigmas: sigma_end must lie in [0, the last entry) (0: the complete trajectory)";
+  return nullptr;
+}
+void Diffuser::set_sigmas(const double* sigmas, int n, double sigma_end, int flags) {
+  if (!sigmas || n == 0) { sigmas_.clear(); return; }
+  if (const char* m = sigmas_error(sigmas, n, sigma_end, flags, n_train_)) throw InvalidArgumentError(m);
+  sigmas_.assign(sigmas, sigmas + n);
+  sigma_end_ = sigma_end;
+  sigma_flags_ = flags;
+}
+
+double Diffuser::sigma_to_t(const double* alphas, int n_train, double sigma, int flags) {
+  SDXL_REQUIRE(n_train >= 2, "sigmas: the alphas_cumprod table needs at least two entries");
+  const auto L = [&](int j) { return 0.5 * std::log((1.0 - alphas[j]) / alphas[j]); };
+  const double ls = std::log(sigma);
+  int low = 0;
+  for (int j = n_train - 2; j >= 0; --j)
+    if (L(j) <= ls) { low = j; break; }
+  const int high = low + 1;
+  const double Ll = L(low), Lh = L(high);
+  double w = (Ll - ls) / (Ll - Lh);
+  w = !(w > 0.0) ? 0.0 : w > 1.0 ? 1.0 : w;      // clamp; a NaN (a table with equal neighbours) counts as 0
+  const double t = (1.0 - w) * (double)low + w * (double)high;
+  return (flags & kSigmasRoundT) ? std::nearbyint(t) : t;     // ties to even in the default rounding mode
+}
+
+Schedule Diffuser::schedule_of_timesteps(const double* alphas, int n_train, const int* ts, int n, int t_end) {
+  Schedule sc;
+  if (n == 0) return sc;        // (refine_latent at step_start == n_train: no iteration)
+  if (const char* m = timesteps_end_error(ts, n, t_end, n_train)) throw InvalidArgumentError(m);
+  sc.t.resize(n); sc.a.resize(n);
+  for (int i = 0; i < n; ++i) { sc.t[i] = (double)ts[i]; sc.a[i] = alphas[ts[i]]; }
+  sc.t_end = t_end;
+  sc.a_end = t_end < 0 ? 1.0 : alphas[t_end];
+  return sc;
+}
+Schedule Diffuser::schedule_of_sigmas(const double* alphas, int n_train, const double* sigmas, int n, double sigma_end, int flags) {
+  if (const char* m = sigmas_error(sigmas, n, sigma_end, flags, n_train)) throw InvalidArgumentError(m);
+  Schedule sc;
+  sc.from_sigmas = true;
+  sc.t.resize(n); sc.a.resize(n);
+  for (int i = 0; i < n; ++i) {
+    sc.a[i] = 1.0 / (1.0 + sigmas[i] * sigmas[i]);
+    sc.t[i] = sigma_to_t(alphas, n_train, sigmas[i], flags);
+  }
+  sc.a_end = sigma_end == 0.0 ? 1.0 : 1.0 / (1.0 + sigma_end * sigma_end);
+  return sc;
+}
+
+Schedule Diffuser::call_schedule(int n_steps, int step_start, bool renoise, bool listed_only) const {
+  if (!sigmas_.empty()) {
+    if (renoise)
+      throw InvalidArgumentError("sigmas: refine_latent ties its re-noise level to step_start, which a sigma list does not have; re-noise to the "
+                                 "list's first level with sdxl_continue_latent");
+    if (n_steps != (int)sigmas_.size())
+      throw InvalidArgumentError("sigmas: n_steps (" + std::to_string(n_steps) + ") differs from the length of the handle's list (" +
+                                 std::to_string(sigmas_.size()) + ")");
+    if (step_start != 0) throw InvalidArgumentError("sigmas: step_start must be 0 where a list is set");
+    return schedule_of_sigmas(alphas_.data(), n_train_, sigmas_.data(), (int)sigmas_.size(), sigma_end_, sigma_flags_);
+  }
+  if (timesteps_.empty()) {
+    if (listed_only) throw InvalidArgumentError("continue_latent runs the handle's list: set one first (sdxl_diffuser_set_sigmas, sdxl_diffuser_set_timesteps)");
+    const std::vector<int> ts = step_schedule(n_steps, step_start, n_train_);
+    return schedule_of_timesteps(alphas_.data(), n_train_, ts.data(), (int)ts.size());
+  }
   if (n_steps != (int)timesteps_.size())
     throw InvalidArgumentError("timesteps: n_steps (" + std::to_string(n_steps) + ") differs from the length of the handle's list (" +
                                std::to_string(timesteps_.size()) + ")");
   if (!renoise && step_start != 0) throw InvalidArgumentError("timesteps: step_start must be 0 where a list is set");
   if (renoise && timesteps_[0] != n_train_ - step_start - 1)
     throw InvalidArgumentError("timesteps: refine_latent re-noises to n_train_steps - step_start, so the list must start at n_train_steps - step_start - 1");
-  return timesteps_;
+  return schedule_of_timesteps(alphas_.data(), n_train_, timesteps_.data(), (int)timesteps_.size(), timesteps_end_);
 }
 
 const char* Diffuser::guidance_error(const Guidance& g, bool is_refiner) {
@@ -137,13 +219,11 @@ void Diffuser::set_prediction(int prediction) {
   prediction_ = prediction;
 }
 
-const char* Diffuser::schedule_error(const double* alphas, int n_train, const std::vector<int>& ts, int prediction) {
+const char* Diffuser::schedule_error(const Schedule& sc, int prediction) {
   if (prediction != kPredictionEpsilon && prediction != kPredictionV) return "unknown prediction (SDXL_PREDICTION_EPSILON, SDXL_PREDICTION_V)";
-  if (!ts.empty())             // (refine_latent at step_start == n_train: no iteration, nothing to complain about)
-    if (const char* m = timesteps_error(ts.data(), (int)ts.size(), n_train)) return m;
-  for (size_t i = 0; i < ts.size(); ++i) {
-    const double a = alphas[ts[i]];
-    const double ap = i + 1 < ts.size() ? alphas[ts[i + 1]] : 1.0;
+  for (size_t i = 0; i < sc.size(); ++i) {
+    const double a = sc.a[i];
+    const double ap = sc.ap(i);
     if (prediction == kPredictionEpsilon) {
       if (a == 0.0)
         return "alphas_cumprod is 0 at a sampled timestep (zero terminal SNR): x0 = (x - sigma e) / alpha has no value there under the "
@@ -155,82 +235,107 @@ const char* Diffuser::schedule_error(const double* alphas, int n_train, const st
   return nullptr;
 }
 
-void Diffuser::solver_coefficients(const double* alphas, int n_train, const std::vector<int>& ts, int solver, double eta, double* out,
-                                   int prediction) {
-  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver_is_row1(solver), "unknown solver");
-  if (const char* m = schedule_error(alphas, n_train, ts, prediction)) throw InvalidArgumentError(m);
+void Diffuser::solver_coefficients(const double* alphas, int n_train, const Schedule& sc, int solver, double eta, double* out, int prediction) {
+  SDXL_REQUIRE(solver == kSolverDdim || solver == kSolverDpmpp2M || solver == kSolverDpmpp3M || solver_is_row1(solver), "unknown solver");
+  if (const char* m = schedule_error(sc, prediction)) throw InvalidArgumentError(m);
   if (solver == kSolverLcm && eta != 0.0) throw InvalidArgumentError("solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
-  double h_prev = 0.0;
-  bool have_prev = false;       // false on iteration 0: no history, first order
-  for (size_t i = 0; i < ts.size(); ++i) {
-    const int t = ts[i];
-    const double a = alphas[t];
-    const double ap = i + 1 < ts.size() ? alphas[ts[i + 1]] : 1.0;      // the next entry of the list; behind the last one the data itself
+  if (solver == kSolverTcd && sc.from_sigmas)
+    throw InvalidArgumentError("solver TCD reads alphas_cumprod at floor((1 - gamma) t'), a training timestep: it does not run on sigmas (use a timestep list)");
+  double h_prev = 0.0, h_prev2 = 0.0;
+  int order = 0;                // history terms at hand: 0 on iteration 0 (first order), at most 1 under 2M and 2 under 3M
+  for (size_t i = 0; i < sc.size(); ++i) {
+    const double t = sc.t[i];
+    const double a = sc.a[i];
+    const double ap = sc.ap(i);      // the next entry of the list; behind the last one the end level (1: the data itself)
     SDXL_REQUIRE((a > 0.0 || (a == 0.0 && prediction == kPredictionV)) && a < 1.0 && ap > 0.0 && ap <= 1.0, "alphas_cumprod outside (0, 1)");
     const double alpha = std::sqrt(a), sigma = std::sqrt(1.0 - a);
-    double* c = out + 4 * i;     // c_x, c_0, c_1, c_z
+    double* c = out + kRowCols * i;     // c_x, c_0, c_1, c_2, c_z
+    c[3] = 0.0;
     if (solver == kSolverDdim) {
       double sqrt_ap, sqrt_1map, sigma_t;
       ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma_t);
-      c[0] = sqrt_1map / sigma; c[1] = sqrt_ap - sqrt_1map * alpha / sigma; c[2] = 0.0; c[3] = sigma_t;
+      c[0] = sqrt_1map / sigma; c[1] = sqrt_ap - sqrt_1map * alpha / sigma; c[2] = 0.0; c[4] = sigma_t;
       continue;
     }
     if (solver == kSolverLcm) {  // diffusers' LCMScheduler.step: sigma_data = 0.5, timestep_scaling = 10; the boundary-condition pair of x0, then
                                  // re-noised to the next level with fresh noise.  ap == 1 behind the last entry: (c_skip, c_out, 0, 0)
-      const double st = 10.0 * (double)t, d = st * st + 0.25;
+      const double st = 10.0 * t, d = st * st + 0.25;
       const double c_skip = 0.25 / d, c_out = st / std::sqrt(d);
       const double alpha_p = std::sqrt(ap);
-      c[0] = alpha_p * c_skip; c[1] = alpha_p * c_out; c[2] = 0.0; c[3] = std::sqrt(1.0 - ap);
+      c[0] = alpha_p * c_skip; c[1] = alpha_p * c_out; c[2] = 0.0; c[4] = std::sqrt(1.0 - ap);
       continue;
     }
     if (solver == kSolverTcd) {  // TCDScheduler.step, eta read as gamma: the DDIM step to s = floor((1 - gamma) t'), re-noised from s to t'
       if (ap == 1.0) {           // the engine's last row, as 2M has it: the iteration returns x0
-        c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[3] = 0.0;
+        c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[4] = 0.0;
         continue;
       }
-      const int ts_s = (int)std::floor((1.0 - eta) * (double)ts[i + 1]);
+      const double t_next = i + 1 < sc.size() ? sc.t[i + 1] : (double)sc.t_end;
+      const int ts_s = (int)std::floor((1.0 - eta) * t_next);
+      SDXL_REQUIRE(ts_s >= 0 && ts_s < n_train, "solver TCD: floor((1 - gamma) t') outside the table");
       const double a_s = alphas[ts_s];
       if (!(a_s > 0.0 && a_s <= 1.0)) throw InvalidArgumentError("solver TCD: alphas_cumprod outside (0, 1] at the timestep floor((1 - gamma) t')");
       const double alpha_s = std::sqrt(a_s), sigma_s = std::sqrt(1.0 - a_s), r = std::sqrt(ap / a_s);
       c[0] = r * sigma_s / sigma; c[1] = r * (alpha_s - sigma_s * alpha / sigma); c[2] = 0.0;
-      c[3] = std::sqrt(std::max(1.0 - ap / a_s, 0.0));
+      c[4] = std::sqrt(std::max(1.0 - ap / a_s, 0.0));
       continue;
     }
     if (ap == 1.0) {             // h is infinite: the step lands on the data prediction
-      c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[3] = 0.0;
-      have_prev = false;
+      c[0] = 0.0; c[1] = 1.0; c[2] = 0.0; c[4] = 0.0;
+      order = 0;
       continue;
     }
     const double alpha_p = std::sqrt(ap), sigma_p = std::sqrt(1.0 - ap);
     if (a == 0.0) {              // alpha = 0, sigma = 1, lambda = -inf, h = +inf: the limits of the first-order row, written out (the formulas
                                  // below would evaluate exp(-0 * inf)).  A -> 1; eta == 0: c_x = sigma'; eta > 0: c_x -> 0, c_z -> sigma'
-      c[0] = eta == 0.0 ? sigma_p : 0.0; c[1] = alpha_p; c[2] = 0.0; c[3] = eta == 0.0 ? 0.0 : sigma_p;
-      have_prev = false;         // the next iteration has r = h_prev / h = inf: first order, as iteration 0
+      c[0] = eta == 0.0 ? sigma_p : 0.0; c[1] = alpha_p; c[2] = 0.0; c[4] = eta == 0.0 ? 0.0 : sigma_p;
+      order = 0;                 // the next iteration has r = h_prev / h = inf: first order, as iteration 0
       continue;
     }
     const double h = std::log(alpha_p / sigma_p) - std::log(alpha / sigma);
     const double A = -std::expm1(-(1.0 + eta) * h);
     c[0] = (sigma_p / sigma) * std::exp(-eta * h);
-    c[3] = sigma_p * std::sqrt(-std::expm1(-2.0 * eta * h));
-    if (have_prev) {
-      const double r = h_prev / h;
-      c[1] = alpha_p * A * (1.0 + 1.0 / (2.0 * r));
-      c[2] = -alpha_p * A / (2.0 * r);
-    } else {
-      c[1] = alpha_p * A;
-      c[2] = 0.0;
+    c[4] = sigma_p * std::sqrt(-std::expm1(-2.0 * eta * h));
+    if (solver == kSolverDpmpp2M) {
+      if (order >= 1) {
+        const double r = h_prev / h;
+        c[1] = alpha_p * A * (1.0 + 1.0 / (2.0 * r));
+        c[2] = -alpha_p * A / (2.0 * r);
+      } else {
+        c[1] = alpha_p * A;
+        c[2] = 0.0;
+      }
+    } else {                     // kSolverDpmpp3M: k-diffusion's sample_dpmpp_3m_sde in alpha / sigma terms
+      const double h_eta = (1.0 + eta) * h;
+      const double phi2 = std::expm1(-h_eta) / h_eta + 1.0;
+      if (order >= 2) {
+        const double phi3 = phi2 / h_eta - 0.5;
+        const double r0 = h_prev / h, r1 = h_prev2 / h;
+        const double P = phi2 * (1.0 + r0 / (r0 + r1)) - phi3 / (r0 + r1), Q = (phi3 - phi2 * r0) / (r0 + r1);
+        c[1] = alpha_p * (A + P / r0);
+        c[2] = alpha_p * (-P / r0 + Q / r1);
+        c[3] = -alpha_p * Q / r1;
+      } else if (order == 1) {
+        const double r0 = h_prev / h;
+        c[1] = alpha_p * (A + phi2 / r0);
+        c[2] = -alpha_p * phi2 / r0;
+      } else {
+        c[1] = alpha_p * A;
+        c[2] = 0.0;
+      }
     }
+    h_prev2 = h_prev;
     h_prev = h;
-    have_prev = true;
+    order = std::min(order + 1, 2);
   }
 }
 
-const char* Diffuser::explicit_noise_error(const double* alphas, int n_train, const std::vector<int>& ts, int solver, int prediction) {
-  if (!solver_is_row1(solver)) return nullptr;      // DDIM and 2M at eta == 0 draw nothing
-  std::vector<double> rows((size_t)4 * ts.size());
-  solver_coefficients(alphas, n_train, ts, solver, 0.0, rows.data(), prediction);
-  for (size_t i = 0; i < ts.size(); ++i)
-    if (rows[4 * i + 3] != 0.0)
+const char* Diffuser::explicit_noise_error(const double* alphas, int n_train, const Schedule& sc, int solver, int prediction) {
+  if (!solver_is_row1(solver)) return nullptr;      // DDIM, 2M and 3M at eta == 0 draw nothing
+  std::vector<double> rows((size_t)kRowCols * sc.size());
+  solver_coefficients(alphas, n_train, sc, solver, 0.0, rows.data(), prediction);
+  for (size_t i = 0; i < sc.size(); ++i)
+    if (rows[kRowCols * i + 4] != 0.0)
       return "this solver re-noises with fresh noise every iteration (c_z != 0): it needs the seeded calls (explicit noise carries none for that term)";
   return nullptr;
 }
@@ -257,39 +362,40 @@ StepLoop::StepLoop() {
   SDXL_HIP(hipMalloc((void**)&t_dev_, 8 * sizeof(float)));
 }
 StepLoop::~StepLoop() {
-  for (void* p : {(void*)table_, (void*)active_, (void*)moments_, (void*)factors_, (void*)step_idx_, (void*)t_dev_, (void*)hist_})
+  for (void* p : {(void*)table_, (void*)active_, (void*)moments_, (void*)factors_, (void*)step_idx_, (void*)t_dev_, (void*)hist_, (void*)hist2_})
     if (p) (void)hipFree(p);
 }
 
-int StepLoop::begin(const std::vector<double>& alphas, const std::vector<int>& ts, int solver, double eta, double cfg_scale,
+int StepLoop::begin(const std::vector<double>& alphas, const Schedule& sc, int solver, double eta, double cfg_scale,
                     const Guidance& go, bool single, int n, int HW, const StepIo& io, hipStream_t s, int prediction) {
   const int n_train = (int)alphas.size();
   SDXL_REQUIRE(n >= 1 && n <= kMaxSeeds, "batch out of range");
   // a == 0 on an iteration: x0 = -v under kPredictionV; under kPredictionEpsilon the first update would divide by sqrt_a == 0
-  if (const char* m = Diffuser::schedule_error(alphas.data(), n_train, ts, prediction)) throw InvalidArgumentError(m);
+  if (const char* m = Diffuser::schedule_error(sc, prediction)) throw InvalidArgumentError(m);
   SDXL_REQUIRE(single || go.n_scales == 0 || go.n_scales == n, "guidance: n_scales differs from the batch (cond.n)");
   const bool rows = solver != kSolverDdim;             // the 2M layout of the table: 2M itself and the first-order rows of LCM / TCD
   if (!io.seeds)
-    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), n_train, ts, solver, prediction)) throw InvalidArgumentError(m);
+    if (const char* m = Diffuser::explicit_noise_error(alphas.data(), n_train, sc, solver, prediction)) throw InvalidArgumentError(m);
   // --- coefficient table (host f64, exactly the reference's scalar arithmetic :407-414, :423-426)
-  const int iters = (int)ts.size();
+  const int iters = (int)sc.size();
   std::vector<StepCoef> tab(iters + 1);
   act_.assign(iters, 1);                               // guidance interval: iteration i is active where t_lo <= t_i <= t_hi
   std::vector<double> c2m;
   if (rows) {
-    c2m.resize((size_t)4 * iters);
-    Diffuser::solver_coefficients(alphas.data(), n_train, ts, solver, eta, c2m.data(), prediction);
+    c2m.resize((size_t)kRowCols * iters);
+    Diffuser::solver_coefficients(alphas.data(), n_train, sc, solver, eta, c2m.data(), prediction);
   }
   for (int i = 0; i < iters; ++i) {
-    const int t = ts[i];
-    const double a = alphas[t];
-    const double ap = i + 1 < iters ? alphas[ts[i + 1]] : 1.0;
+    const double t = sc.t[i];
+    const double a = sc.a[i];
+    const double ap = sc.ap(i);
     StepCoef k{};
     k.t = (float)t;
     k.sqrt_a = (float)std::sqrt(a);
     k.sqrt_1ma = (float)std::sqrt(1.0 - a);
     if (rows) {
-      k.c_x = (float)c2m[4 * i]; k.c_0 = (float)c2m[4 * i + 1]; k.c_1 = (float)c2m[4 * i + 2]; k.c_z = (float)c2m[4 * i + 3];
+      const double* c = &c2m[(size_t)kRowCols * i];
+      k.c_x = (float)c[0]; k.c_0 = (float)c[1]; k.c_1 = (float)c[2]; k.c_2 = (float)c[3]; k.c_z = (float)c[4];
     } else {
       double sqrt_ap, sqrt_1map, sigma;
       ddim_terms(a, ap, eta, sqrt_ap, sqrt_1map, sigma);
@@ -298,7 +404,7 @@ int StepLoop::begin(const std::vector<double>& alphas, const std::vector<int>& t
       k.sigma = (float)sigma;
     }
     tab[i] = k;
-    if (!single) act_[i] = t >= go.t_lo && t <= go.t_hi;
+    if (!single) act_[i] = t >= (double)go.t_lo && t <= (double)go.t_hi;
   }
   tab[iters] = StepCoef{};
   ensure_device(table_, table_cap_, (size_t)iters + 1);
@@ -317,7 +423,8 @@ int StepLoop::begin(const std::vector<double>& alphas, const std::vector<int>& t
     if (!factors_) SDXL_HIP(hipMalloc((void**)&factors_, kMaxSeeds * sizeof(float)));
     p_.factors = factors_;
   }
-  if (solver == kSolverDpmpp2M) ensure_device(hist_, hist_cap_, (size_t)n * 4 * HW);      // kSolverRow1 keeps no history: nothing is allocated
+  if (solver == kSolverDpmpp2M || solver == kSolverDpmpp3M) ensure_device(hist_, hist_cap_, (size_t)n * 4 * HW);      // kSolverRow1 keeps no history: nothing is allocated
+  if (solver == kSolverDpmpp3M) ensure_device(hist2_, hist2_cap_, (size_t)n * 4 * HW);
   SDXL_HIP(hipStreamSynchronize(s));   // tab is a stack-owned host buffer
 
   p_.latent = io.latent;
@@ -329,6 +436,7 @@ int StepLoop::begin(const std::vector<double>& alphas, const std::vector<int>& t
   p_.t_out = t_dev_;
   p_.solver = solver_is_row1(solver) ? kSolverRow1 : solver; p_.prediction = prediction;
   p_.hist = solver_is_row1(solver) ? nullptr : hist_;
+  p_.hist2 = solver == kSolverDpmpp3M ? hist2_ : nullptr;
   if (io.seeds) {
     p_.seeded = 1;
     for (int b = 0; b < n; ++b) p_.seeds.v[b] = io.seeds[b];
@@ -345,7 +453,7 @@ void StepLoop::after_forward(int i, const float* eps, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------ Diffuser
-void Diffuser::diffuse(float* latent, const Conditioning& c, const std::vector<int>& ts, double cfg_scale,
+void Diffuser::diffuse(float* latent, const Conditioning& c, const Schedule& sc, double cfg_scale,
                        const float* reference, const unsigned char* mask, const float* step_noise, hipStream_t s,
                        const uint64_t* seeds, double eta) {
   // diffuse_latent :390-432 / diffuse_latent_with_inpainting :434-483
@@ -382,7 +490,7 @@ void Diffuser::diffuse(float* latent, const Conditioning& c, const std::vector<i
   io.reference = reference; io.mask = mask; io.step_noise = step_noise; io.seeds = seeds;
   u.set_context(ctx_buf_, c.n_ctx, y_buf_, B, s);
 
-  const int iters = loop_.begin(alphas_, ts, solver_, eta, cfg_scale, go, single, n, HW, io, s, prediction_);
+  const int iters = loop_.begin(alphas_, sc, solver_, eta, cfg_scale, go, single, n, HW, io, s, prediction_);
   std::vector<hipEvent_t> ev;
   if (time_steps) {
     ev.resize(iters + 1);
@@ -410,11 +518,13 @@ void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, 
   SDXL_REQUIRE(!t.renoise || (t.step_start >= 1 && t.step_start <= n_train_), "step_start out of range");
   SDXL_REQUIRE(!t.seeds || c.n <= kMaxSeeds, "batch out of range");
   // what StepLoop::begin refuses, before the start latent is written: nothing is launched
-  const std::vector<int> ts = call_schedule(n_steps, t.step_start, t.renoise != nullptr);
-  if (const char* m = schedule_error(alphas_.data(), n_train_, ts, prediction_)) throw InvalidArgumentError(m);
+  const Schedule sc = call_schedule(n_steps, t.step_start, t.renoise != nullptr, t.start != nullptr);
+  if (const char* m = schedule_error(sc, prediction_)) throw InvalidArgumentError(m);
   if (solver_ == kSolverLcm && t.eta != 0.0) throw InvalidArgumentError("solver LCM takes no eta: eta must be 0 (SDXL_SOLVER_LCM)");
+  if (solver_ == kSolverTcd && sc.from_sigmas)
+    throw InvalidArgumentError("solver TCD reads alphas_cumprod at floor((1 - gamma) t'), a training timestep: it does not run on sigmas (use a timestep list)");
   if (!t.seeds)
-    if (const char* m = explicit_noise_error(alphas_.data(), n_train_, ts, solver_, prediction_)) throw InvalidArgumentError(m);
+    if (const char* m = explicit_noise_error(alphas_.data(), n_train_, sc, solver_, prediction_)) throw InvalidArgumentError(m);
   const int HW = (c.height / 8) * (c.width / 8);
   const size_t elems = (size_t)c.n * 4 * HW;
   ensure_device(latent_, latent_cap_, elems);
@@ -427,12 +537,25 @@ void Diffuser::trajectory(const Conditioning& c, double cfg_scale, int n_steps, 
     }
     const double a = alphas_[n_train_ - t.step_start];
     launch_axpby(latent_, t.renoise, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
+  } else if (t.start) {
+    if (t.renoise0) {           // continue_latent with renoise: to the list's own first level
+      const float* noise = t.noise;
+      if (!noise) {
+        ensure_device(noise_, noise_cap_, elems);
+        launch_seeded_noise(noise_, t.seeds, kDrawInitial, c.n, HW, s);
+        noise = noise_;
+      }
+      const double a = sc.a[0];
+      launch_axpby(latent_, t.start, (float)std::sqrt(a), noise, (float)std::sqrt(1.0 - a), elems, s);
+    } else {
+      SDXL_HIP(hipMemcpyAsync(latent_, t.start, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
   } else if (t.seeds) {
     launch_seeded_noise(latent_, t.seeds, kDrawInitial, c.n, HW, s);
   } else {
     SDXL_HIP(hipMemcpyAsync(latent_, t.noise, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-  diffuse(latent_, c, ts, cfg_scale, t.reference, t.mask, t.step_noise, s, t.seeds, t.eta);
+  diffuse(latent_, c, sc, cfg_scale, t.reference, t.mask, t.step_noise, s, t.seeds, t.eta);
   SDXL_HIP(hipMemcpyAsync(out, latent_, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
@@ -453,6 +576,16 @@ void Diffuser::sample_latent_inpaint(const Conditioning& c, double cfg_scale, in
 void Diffuser::refine_latent(const float* latent, const Conditioning& c, double cfg_scale, int step_start, int n_steps,
                              const float* noise, float* out, hipStream_t s) {
   Trajectory t; t.renoise = latent; t.step_start = step_start; t.noise = noise;
+  trajectory(c, cfg_scale, n_steps, t, out, s);
+}
+
+void Diffuser::continue_latent(const float* latent, const Conditioning& c, double cfg_scale, int n_steps, const float* noise, const uint64_t* seeds,
+                               double eta, bool renoise, float* out, hipStream_t s) {
+  SDXL_REQUIRE(latent && out, "null argument");
+  if (renoise && (noise != nullptr) == (seeds != nullptr))
+    throw InvalidArgumentError("continue_latent: renoise takes exactly one of noise (an explicit tensor) and seeds (the SDXL_DRAW_INITIAL draw)");
+  if (!seeds && eta != 0.0) throw InvalidArgumentError("eta needs seeds: explicit noise carries none for the sigma term");
+  Trajectory t; t.start = latent; t.renoise0 = renoise; t.noise = renoise ? noise : nullptr; t.seeds = seeds; t.eta = eta;
   trajectory(c, cfg_scale, n_steps, t, out, s);
 }
 
